@@ -21,7 +21,13 @@ Opt-in modes:
                    all ranks all-gather them over RCCL inside the timed region — the exchange step of configs[3].
 
 Inputs are synthetic: seeded random-playout positions generated on the GPU with the rules kernels,
-Glorot-uniform weights (seed 0).  Nothing here reads /root/reference.
+Glorot-uniform weights (seed 0): with the same arguments they are the same from run to run.  Nothing here reads the
+reference unless CCHESS_REFERENCE names a checkout of it.
+
+  --dump-outputs DIR   after the K timed steps, what the timed path computed (the net's outputs of the last step and the
+                       search state a caller reads: root statistics and per-tree counters) goes to DIR/<name>.npy in
+                       float32, at most 64 MB (a fixed, seeded sample of the trees beyond that), so that two builds can be
+                       compared output for output.
 """
 import argparse
 import json
@@ -48,8 +54,8 @@ MX_KERNEL = "k_trunk_mx_c128"   # what cz_net_trunk_mx launches (csrc/cz_conv.hi
 TRUNK_KERNEL = {"fp16": "k_tower8_c128", "bf16": "k_tower8_c128", "fp16x2": "k_trunk_split_c128", "bf16x2": "k_trunk_split_c128", "mx6": MX_KERNEL}
 TRAFFIC_FILE = {"k_tower8_c128": "pmc_traffic.json", "k_trunk_split_c128": "pmc_traffic_strict.json", "k_trunk_mx_c128": "pmc_traffic_mx.json"}
 
-# The unmodified reference (pure Python) timed in the build container — it cannot run on the GPU box, where
-# /root/reference does not exist; recorded in BASELINE.md and attached to the line as static, labelled fields.
+# The unmodified reference (pure Python) timed on a CPU host with a checkout of it; recorded in BASELINE.md and attached to
+# the line as static, labelled fields.
 REFERENCE_PYTHON = {
     "search_only_sims_per_s_per_core": 405, "end_to_end_2block_sims_per_s": 237, "end_to_end_7block_sims_per_s": 157,
     "where": "build container (8 vCPU), tools/time_reference.py on the unmodified reference, recorded in BASELINE.md; "
@@ -89,9 +95,10 @@ def _cpu_workers(specs):
 
 
 def reference_python_now(timeout=90):
-    """SURVEY 8(d) items 1-2 when the unmodified reference is importable (this container; never on the GPU box): its own
-    MCTS_tree.main with a constant-time forward, 50 and 400 playouts, one core — tools/time_reference.py --json in a subprocess."""
-    if not os.path.exists("/root/reference/main.py"):
+    """SURVEY 8(d) items 1-2 when CCHESS_REFERENCE names a checkout of the unmodified reference: its own MCTS_tree.main
+    with a constant-time forward, 50 and 400 playouts, one core — tools/time_reference.py --json in a subprocess."""
+    ref = os.environ.get("CCHESS_REFERENCE")
+    if not ref or not os.path.exists(os.path.join(ref, "main.py")):
         return None
     try:
         r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "time_reference.py"), "--json"], stdout=subprocess.PIPE,
@@ -105,7 +112,10 @@ def cpu_baseline(blocks, seconds_target=12.0):
     """The CPU port timed on this host, single core and all cores: C oracle search + fp32 torch-CPU
     net, a bounded sample of the same workload family.  Test infrastructure used as the *baseline being measured*, never
     as the product path.  `value` is the all-core figure."""
-    cores = os.cpu_count() or 1
+    try:   # the CPUs this process may run on, not every CPU of the host
+        cores = len(os.sched_getaffinity(0))
+    except (AttributeError, OSError):
+        cores = os.cpu_count() or 1
     out = {"unit": "sims/s", "kind": "port", "reference_python": dict(REFERENCE_PYTHON, measured_in_this_run=False)}
     live = reference_python_now()
     if live and "error" not in live:
@@ -303,6 +313,34 @@ def write_detail(full, tag):
         return "not written: %r" % (e,)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(d, eng, net_out, limit=DUMP_LIMIT_BYTES, seed=20240601):
+    """What the timed path computed, as a caller of it receives it: the net outputs the last step's expansion read (z: the
+    head convolutions' [trees, k, 90, 3] with the policy FC in the expansion, else logits [trees, k, 2086]; value [trees, k];
+    k = simulations in flight per tree; only where rows are trees, not in compact mode or the self-play loop) and the search
+    state after the last step (root children's label / N / Q / P / W, the child count, and per tree status, nodes,
+    simulations and leaf depth).  Every array in float32 (the integers are
+    exact in it).  Trees beyond the byte budget are a fixed, seeded sample; tree_index.npy lists the trees kept, in order."""
+    G = eng.G
+    rs = eng.root_stats()
+    st, nodes, sims, depth = eng.status()
+    per_tree = {"root_label": rs["label"].to(torch.int32) & 0xFFFF, "root_N": rs["N"], "root_Q": rs["Q"], "root_P": rs["P"],
+                "root_W": rs["W"], "root_count": rs["count"].to(torch.int32) & 0xFFFF,
+                "tree_status": st, "tree_nodes": nodes, "tree_sims": sims, "tree_depth": depth}
+    for k, t in net_out.items():
+        per_tree["net_" + k] = t.reshape(G, -1, *t.shape[1:]) if k != "value" else t.reshape(G, -1)
+    tree_bytes = 4 + sum(4 * (v.numel() // G) for v in per_tree.values())
+    keep = min(G, max(1, limit // tree_bytes))
+    idx = np.arange(G) if keep == G else np.sort(np.random.default_rng(seed).choice(G, keep, replace=False))
+    it = torch.from_numpy(idx).to(st.device)
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "tree_index.npy"), idx.astype(np.float32))
+    for k, v in per_tree.items():
+        np.save(os.path.join(d, k + ".npy"), v.index_select(0, it).float().cpu().numpy())
+
+
 def self_launch(n):
     """`python bench.py --gpus N` from a bare shell: start the N ranks through torch.distributed.run."""
     s = socket.socket()
@@ -327,8 +365,8 @@ def main():
     ap.add_argument("--dtype", default="strict", choices=["bf16", "fp16", "fp32", "fp16x2", "bf16x2", "mx6", "strict"],
                     help="engine of the tower (fp32 accumulate).  strict (default since round 6: the engine policy_value_network() and main.py run, so `value` and `roofline` are the product's): the net measures itself against fp32 on its weights and runs the cheapest engine of mx6 -> fp16x2 -> fp32 inside 5e-4 (mx6 on the bench's TF-default weights at 7 and at 19 blocks; fp16x2 on the peaked trained-like set at 19); the fast fp16 engine is then timed as the fast_engine leg.  mx6 = fp16 hi halves + both cross terms of the hi + lo split on one block-scaled fp6 MFMA (k_trunk_mx_c128, 1.5 MFMA-equivalents per product); fp16x2 / bf16x2 = hi + lo halves of that type, three MFMAs per product (k_trunk_split_c128; also 19 blocks); fp16: one fp16 per operand (k_tower8_c128), twice the rate, 1e-3 only relative to the logit scale (see net_error in the output); with fp16 / bf16 the strict engine is the extra leg")
     ap.add_argument("--age-steps", type=int, default=800, help="untimed lock-steps BEFORE --warmup that bring every tree to a representative phase of its search: each tree's first search is cut at its own threshold (uniform in [8, age-steps] simulations), so when the timed region starts the trees are spread over the phases of a playout-long search on subtrees kept from a previous ply — the state of a long run — instead of all standing 25 simulations into a fresh search")
-    ap.add_argument("--steady-steps", type=int, default=2000, help="extra lock-steps timed AFTER the K contract steps (own barrier-bracketed region) for the steady_state block of the output; 0 = off")
-    ap.add_argument("--alt-steps", "--strict-steps", dest="alt_steps", type=int, default=240, help="lock-steps of a third timed region in which the SAME trees are searched with the OTHER engine: the fast fp16 engine (k_tower8_c128; the fast_engine block of the output) when the run's engine is a strict one, the strict engine of this depth (the strict_engine block) when --dtype is fp16 / bf16; 0 = off")
+    ap.add_argument("--steady-steps", type=int, default=0, help="extra lock-steps timed AFTER the K contract steps (own barrier-bracketed region) for the steady_state block of the output, which then gives value and ms_per_step; 0 (default) = off: the K steps are the only timed ones")
+    ap.add_argument("--alt-steps", "--strict-steps", dest="alt_steps", type=int, default=0, help="lock-steps of a third timed region in which the SAME trees are searched with the OTHER engine: the fast fp16 engine (k_tower8_c128; the fast_engine block of the output) when the run's engine is a strict one, the strict engine of this depth (the strict_engine block) when --dtype is fp16 / bf16; 0 (default) = off")
     ap.add_argument("--backend", default="auto", choices=["auto", "hip", "torch"], help="conv backend of the net")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"], help="nccl = RCCL (default); gloo only for single-GPU smoke tests of the N>1 path")
@@ -348,6 +386,7 @@ def main():
     ap.add_argument("--torch-advance", action="store_true", help="A/B only: the round-2 advance of ready trees (status / root statistics / argmax / reload as ~20 torch ops) instead of cz_search_pick_ready + cz_search_advance + cz_search_reload_finished")
     ap.add_argument("--force-dist", action="store_true", help="testing only: initialise the process group and run every collective even with a world of 1 (RCCL API check on one GPU)")
     ap.add_argument("--start-position", action="store_true", help="--selfplay: every game starts from the start position (default: the synthetic positions)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the K timed steps, write what they computed (last step's net outputs, root statistics, per-tree counters) to DIR/<name>.npy, float32, at most 64 MB (rank 0)")
     args = ap.parse_args()
     asked_strict = args.dtype == "strict"
     if asked_strict:   # where the ladder starts; the net's own measurement (strict_check, below) has the last word
@@ -434,6 +473,13 @@ def main():
     step_no = [0]
 
     cur = {"net": net, "conv_ev": conv_ev, "ev": ev}   # the strict leg swaps the engine under the same loop
+    # --dump-outputs: the net outputs the expansion of the latest step read (references to the tensors, no copies); a
+    # replayed HIP graph writes into the tensors its capture saw (graph_net_out)
+    last_net_out, graph_net_out = {}, {}
+
+    def keep_net_out(planes, z_or_logits, value):
+        last_net_out.update({"z" if z_or_logits.dim() == 3 else "logits": z_or_logits, "value": value})
+    keep = keep_net_out if args.dump_outputs else None
 
     def one_step(mode, timed):
         # HIP events around the launches of every 8th timed step (recorded on the stream the kernels are launched on)
@@ -442,11 +488,16 @@ def main():
         n_.conv_events = cur["conv_ev"] if sample else None
         step_no[0] += 1
         if not sample:
-            eng.step(n_.forward_device, mode=mode)
+            eng.step(n_.forward_device, mode=mode, tap=keep)
             return
         e = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
         e[0].record()
-        eng.step(n_.forward_device, mode=mode, pre_net=e[1].record, tap=lambda *a: e[2].record())
+
+        def tap(*a):
+            e[2].record()
+            if keep is not None:
+                keep(*a)
+        eng.step(n_.forward_device, mode=mode, pre_net=e[1].record, tap=tap)
         e[3].record()
         cur["ev"].append(e)
 
@@ -506,6 +557,7 @@ def main():
             if graph[0] is not None and not (timed and step_no[0] % 8 == 0):
                 step_no[0] += 1
                 graph[0].replay()
+                last_net_out.update(graph_net_out)
             else:
                 one_step(1, timed)   # mode 1 also expands the roots of trees that have just advanced
             steps_since_reset[0] += 1
@@ -564,6 +616,7 @@ def main():
             gr = torch.cuda.CUDAGraph()
             with torch.cuda.graph(gr):
                 one_step(1, False)
+            graph_net_out.update(last_net_out)
             step_no[0] -= 1                      # the capture itself executed nothing
             torch.cuda.synchronize()
             graph[0] = gr
@@ -625,6 +678,8 @@ def main():
         return dtm, mine, count_sims() - sims0, rows, rpl
 
     dt, my_dt, my_sims, my_rows, rows_per_launch = timed_region(args.steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng, {} if compact else last_net_out)
     if trace:
         print("per-step GPU ms of the timed region:", " ".join("%.3f" % trace[i].elapsed_time(trace[i + 1]) for i in range(len(trace) - 1)), file=sys.stderr)
         trace = None

@@ -6,6 +6,8 @@ import json
 import os
 import sys
 
+import torch
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
@@ -143,3 +145,49 @@ def test_round6_record_compacts_to_the_committed_line():
     assert ne["meets_1e-3_abs_logit_and_value_as_benchmarked"] and ne["meets_1e-3_abs_logit_and_value_trained_like"] and ne["probe_informative"]
     assert ne["trained_like"]["dvalue"] > 0 and ne["strict_on_trained_like"]["engine"] in ("mx6", "fp16x2")
     assert line["cpu_baseline"]["kind"] == "port" and line["cpu_baseline"]["cores"] >= 1 and line["cpu_baseline"]["reference_python"]["measured_in_this_run"] is False
+
+
+class _FakeEngine:
+    """The three things bench.dump_outputs reads from a SearchEngine, as CPU tensors with a recognisable value per tree."""
+
+    def __init__(self, G):
+        self.G = G
+        g = torch.arange(G, dtype=torch.int32)
+        self._rs = dict(label=(g.unsqueeze(1) * 3 + torch.arange(128, dtype=torch.int32)).to(torch.int16),
+                        N=g.unsqueeze(1).repeat(1, 128), Q=g.float().unsqueeze(1).repeat(1, 128) * 0.5,
+                        P=torch.full((G, 128), 0.25), W=torch.full((G, 128), -1.0), count=torch.full((G,), -1, dtype=torch.int16))
+        self._st = (g % 2, g * 7, g * 11, g % 5)
+
+    def root_stats(self):
+        return self._rs
+
+    def status(self):
+        return self._st
+
+
+
+def test_dump_outputs_float32_budget_and_fixed_sample(tmp_path):
+    """--dump-outputs: every array float32 and exact; all trees when they fit; beyond the budget a sorted, seeded sample that
+    is the same in every run, with tree_index naming the trees kept."""
+    import numpy as np
+    import bench
+    G = 64
+    eng = _FakeEngine(G)
+    net_out = {"z": torch.arange(G * 270, dtype=torch.float32).reshape(G, 90, 3), "value": torch.linspace(-1, 1, G).reshape(G, 1)}
+    bench.dump_outputs(str(tmp_path / "all"), eng, net_out)
+    got = {f[:-4]: np.load(str(tmp_path / "all" / f)) for f in os.listdir(str(tmp_path / "all"))}
+    assert set(got) == {"tree_index", "root_label", "root_N", "root_Q", "root_P", "root_W", "root_count", "tree_status",
+                        "tree_nodes", "tree_sims", "tree_depth", "net_z", "net_value"}
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert np.array_equal(got["tree_index"], np.arange(G))
+    assert got["root_label"].shape == (G, 128) and got["root_label"][1, 2] == 5 and got["root_count"][0] == 0xFFFF
+    assert got["net_z"].shape == (G, 1, 90, 3) and got["net_z"][2, 0, 1, 0] == 2 * 270 + 3
+    assert got["net_value"].shape == (G, 1) and np.array_equal(got["tree_sims"], np.arange(G) * 11.0)
+    # a budget of 10 trees: a sample, the same one twice, the rows of the trees it names
+    tree_bytes = 4 * (1 + 5 * 128 + 5 + 270 + 1)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), eng, net_out, limit=10 * tree_bytes + 100)
+    i1, i2 = (np.load(str(tmp_path / d / "tree_index.npy")) for d in ("s1", "s2"))
+    assert len(i1) == 10 and np.array_equal(i1, i2) and np.all(np.diff(i1) > 0)
+    assert np.array_equal(np.load(str(tmp_path / "s1" / "root_N.npy"))[:, 0], i1)
+    assert sum(os.path.getsize(str(tmp_path / "s1" / f)) for f in os.listdir(str(tmp_path / "s1"))) <= 10 * tree_bytes + 100 + 13 * 256

@@ -281,3 +281,32 @@ def test_schedule_optimisations_leave_full_batch_search_unchanged():
         print("8192 trees x 2 plies x %d playouts, terminal_extra %d, cache %s: %d lock-steps instead of %d; cache hits %d / %d" %
               (playouts, extra, cache, steps, steps0, hits[0], hits[1]))
         assert steps <= steps0
+
+
+def test_bench_times_k_steps_and_dumps_identical_outputs(tmp_path):
+    """`bench.py --steps K --dump-outputs DIR`: the K steps are the only timed region and give ms_per_step; two runs with the
+    same arguments dump the same arrays, bit for bit (float32, the search state and the last step's net outputs)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lines, dumps = [], []
+    for i in range(2):
+        d = str(tmp_path / ("run%d" % i))
+        p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--games", "512", "--playout", "64", "--steps", "24",
+                            "--warmup", "4", "--age-steps", "48", "--no-cpu-baseline", "--dump-outputs", d],
+                           capture_output=True, text=True, cwd=str(tmp_path), timeout=900, stdin=subprocess.DEVNULL)
+        assert p.returncode == 0, p.stderr[-3000:]
+        lines.append(json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1]))
+        dumps.append({f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))})
+    for line in lines:
+        assert line["steps"] == 24 and line["contract_steps"]["steps"] == 24 and line["value_source"] == "contract_steps"
+        assert line["steady_state"] is None and line["fast_engine"] is None and line["strict_engine"] is None
+        assert line["ms_per_step"] == line["contract_steps"]["ms_per_step"] > 0
+    a, b = dumps
+    assert {"root_N", "root_Q", "root_label", "tree_sims", "net_z", "net_value", "tree_index"} <= set(a) and set(a) == set(b)
+    assert all(v.dtype == np.float32 for v in a.values()) and sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert a["root_N"].shape == (512, 128) and a["net_z"].shape == (512, 1, 90, 3) and a["root_N"].sum() > 0
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k

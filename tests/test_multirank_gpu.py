@@ -117,6 +117,15 @@ def test_train_two_ranks_end_with_identical_weights(tmp_path):
     assert "samples:" in p.stdout and "kl:" in p.stdout
 
 
+def _one_gpu_per_rank(n):
+    """The eight-rank shapes run one rank per GPU: eight ranks on one device would be nine processes (with this one) holding
+    it open.  Checked before any work is started."""
+    import torch
+    found = torch.cuda.device_count()
+    if found < n:
+        pytest.skip("needs %d GPUs (one per rank), found %d" % (n, found))
+
+
 def _disjoint(rank_cpus):
     """[first cpu, last cpu, count] per rank -> the slices do not overlap (pin_rank_to_cpus hands out contiguous slices)"""
     spans = sorted((a, b) for a, b, n in rank_cpus)
@@ -125,11 +134,12 @@ def _disjoint(rank_cpus):
 
 @pytest.mark.gpu
 def test_bench_eight_ranks_self_launch_selfplay_with_timed_exchange():
-    """the shape of the driver's 8-GPU launch, on one device — `python bench.py --gpus 8` from a bare shell
-    (bench.py starts its own 8 ranks through torch.distributed.run), self-play with the fixed-capacity record exchange inside
+    """the shape of the driver's 8-GPU launch — `python bench.py --gpus 8` from a bare shell (bench.py
+    starts its own 8 ranks through torch.distributed.run, one per GPU), self-play with the fixed-capacity record exchange inside
     the timed region (configs[3]'s exchange step; policy_value_network_gpus.py:216-250 / main.py:1240 in the reference).  Eight
     per-rank figures, disjoint CPU slices, every record delivered, nothing left in the exchange."""
-    d = _bench(["--gpus", "8", "--all-on-device0", "--dist-backend", "gloo", "--selfplay", "--timed-gather", "--games", "64",
+    _one_gpu_per_rank(8)
+    d = _bench(["--gpus", "8", "--dist-backend", "gloo", "--selfplay", "--timed-gather", "--games", "64",
                 "--playout", "16", "--steps", "128", "--warmup", "8", "--age-steps", "32", "--steady-steps", "0", "--strict-steps", "0",
                 "--no-cpu-baseline"], timeout=1500)
     c = d["config"]
@@ -150,10 +160,11 @@ def test_bench_eight_ranks_self_launch_selfplay_with_timed_exchange():
 
 @pytest.mark.gpu
 def test_train_eight_ranks_end_with_identical_weights(tmp_path):
-    """`main.py --mode train` with eight ranks on one device: eight self-play shards, one all-gather of records, one data-parallel
+    """`main.py --mode train` with eight ranks, one per GPU: eight self-play shards, one all-gather of records, one data-parallel
     policy update — eight identical replicas afterwards."""
-    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    env.update(CCHESS_DIST_BACKEND="gloo", CCHESS_ALL_ON_DEVICE0="1", CCHESS_WEIGHT_DIGEST_DIR=str(tmp_path),
+    _one_gpu_per_rank(8)
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "CCHESS_ALL_ON_DEVICE0")}
+    env.update(CCHESS_DIST_BACKEND="gloo", CCHESS_WEIGHT_DIGEST_DIR=str(tmp_path),
                HSA_ENABLE_IPC_MODE_LEGACY="0", PYTHONPATH=ROOT + os.pathsep + env.get("PYTHONPATH", ""))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
            "--master-port", "29617", os.path.join(ROOT, "main.py"), "--mode", "train", "--games", "32", "--train_playout", "12",

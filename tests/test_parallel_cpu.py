@@ -57,7 +57,7 @@ def _worker(rank, world, port, q):
     PL.allreduce_gradients(lin)
     q.put((rank, games.tolist(), rec.tobytes(), allrec.tobytes(), allrec.shape, empty.shape,
            float(lin.weight[0, 0]), float(lin.weight.grad[0, 0]), float(lin.bias.grad[0])))
-    dist.barrier()
+    dist.monitored_barrier()   # gloo's host barrier: dist.barrier() first probes for a GPU, which opens the device in a CPU-only rank
     dist.destroy_process_group()
 
 
@@ -162,7 +162,7 @@ def _plumbing_worker(rank, world, port, q):
         take(blk)
     want = [[(r, i) for i in range(int(sizes[:, r].sum()))] for r in range(world)]
     q.put((rank, cpus, slowest, tot, pr, ok, ex.pending(), got == want, ex.exchanges))
-    dist.barrier()
+    dist.monitored_barrier()   # gloo's host barrier: dist.barrier() first probes for a GPU, which opens the device in a CPU-only rank
     dist.destroy_process_group()
 
 

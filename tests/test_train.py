@@ -300,7 +300,7 @@ def _update_worker(rank, world, port, q, tmp):
         infos.append((info["steps"], round(info["kl"], 12), lrm))
     flat = torch.cat([p.detach().reshape(-1) for p in net.module.parameters()])
     q.put((rank, infos, flat.numpy().tobytes(), net.saved, net.global_step))
-    dist.barrier()
+    dist.monitored_barrier()   # gloo's host barrier: dist.barrier() first probes for a GPU, which opens the device in a CPU-only rank
     dist.destroy_process_group()
 
 
