@@ -47,6 +47,8 @@ _SIGS = {
     "cz_search_eval_cache_collisions": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong)]),
     "cz_search_debug_eval_cache_key_bits": (C.c_int, [C.c_void_p, C.c_int]),
     "cz_search_debug_advance_in_global_memory": (C.c_int, [C.c_void_p, C.c_int]),
+    "cz_search_debug_xcache_dump": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "cz_search_debug_eval_cache_dump": (C.c_int, [C.c_void_p, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "cz_search_set_xcache": (C.c_int, [C.c_void_p, C.c_int]),
     "cz_search_xcache_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong)]),
     "cz_search_xcache_stats5": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong)]),

@@ -301,7 +301,7 @@ int cz_search_set_eval_cache(cz_ctx *c, int on) {
         // an empty cache: entries of an earlier use would point into trees that no longer exist
         CZ_HIP(hipMemsetAsync(c->ec_block, 0, per * 8, c->stream));
         czk_search_clear_cache_stats(c);
-        if (c->t.xc_base) CZ_HIP(hipMemsetAsync(c->xc_block, 0, ((size_t)1 << c->xc_log2_entries) * 8 + 64, c->stream));   // and the cross-tree level
+        if (c->t.xc_base) CZ_HIP(hipMemsetAsync(c->xc_block, 0, ((size_t)1 << c->xc_log2_entries) * 16 + 64, c->stream));   // and the cross-tree level (keys, values, counts)
     } else {
         c->t.ec_key = nullptr; c->t.ec_node = nullptr; c->t.ec_val = nullptr; c->t.ec_board = nullptr; c->t.pend_board = nullptr;
         if (c->xc_block) return cz_search_set_xcache(c, 0);   // the cross-tree level lives behind the per-tree probe
@@ -327,8 +327,9 @@ int cz_search_set_xcache(cz_ctx *c, int log2_entries) {
         c->t.xc_base = (char *)c->xc_block;
         c->t.xc_mask = (uint32_t)(n / 64 - 1);
     }
-    // an empty table (new weights => remembered evaluations are stale): only the keys and the counters need clearing
-    CZ_HIP(hipMemsetAsync(c->xc_block, 0, n * 8 + 64, c->stream));
+    // an empty table (new weights => remembered evaluations are stale): keys, values and count | ply words (a full bucket's
+    // victim is chosen by the ply of every slot: no slot may carry a ply of an earlier use or uninitialised memory)
+    CZ_HIP(hipMemsetAsync(c->xc_block, 0, n * 16 + 64, c->stream));
     CZ_HIP(hipMemsetAsync(czx_tree_stats(c->t), 0, (size_t)c->max_games * 32, c->stream));
     return CZ_OK;
 }
@@ -349,6 +350,55 @@ int cz_search_xcache_stats(cz_ctx *c, unsigned long long *stats4) {
 int cz_search_xcache_stats5(cz_ctx *c, unsigned long long *stats5) {
     CZ_REQUIRE(c && stats5, "cz_search_xcache_stats5: null argument");
     return xcache_stats5(c, stats5, 5);
+}
+int cz_search_debug_xcache_dump(cz_ctx *c, void *host, size_t bytes) {
+    CZ_REQUIRE(c, "cz_search_debug_xcache_dump: null context");
+    if (!c->t.xc_base) { cz_set_error("cz_search_debug_xcache_dump: the cross-tree table is off"); return CZ_EINVAL; }
+    const size_t n = czx_n(c->t), need = n * 1088 + 64;
+    if (!host) return (int)n;
+    if (bytes < need) { cz_set_error("cz_search_debug_xcache_dump: %zu bytes < %zu", bytes, need); return CZ_EINVAL; }
+    CZ_HIP(hipStreamSynchronize(c->stream));
+    CZ_HIP(hipMemcpy(host, c->t.xc_base, need, hipMemcpyDeviceToHost));
+    return (int)n;
+}
+int cz_search_debug_eval_cache_dump(cz_ctx *c, int g, unsigned long long *key, int32_t *node, float *value, uint32_t *board,
+                                    int32_t *record) {
+    CZ_REQUIRE(c && c->G > 0 && g >= 0 && g < c->G, "cz_search_debug_eval_cache_dump: bad tree index");
+    if (!c->t.ec_key) { cz_set_error("cz_search_debug_eval_cache_dump: the evaluation cache is off"); return CZ_EINVAL; }
+    CZ_HIP(hipStreamSynchronize(c->stream));
+    const size_t e0 = (size_t)g * CZ_EC_ENTRIES;
+    std::vector<unsigned long long> k(CZ_EC_ENTRIES);
+    std::vector<int32_t> nd(CZ_EC_ENTRIES);
+    CZ_HIP(hipMemcpy(k.data(), c->t.ec_key + e0, 8 * (size_t)CZ_EC_ENTRIES, hipMemcpyDeviceToHost));
+    CZ_HIP(hipMemcpy(nd.data(), c->t.ec_node + e0, 4 * (size_t)CZ_EC_ENTRIES, hipMemcpyDeviceToHost));
+    if (key) memcpy(key, k.data(), 8 * (size_t)CZ_EC_ENTRIES);
+    if (node) memcpy(node, nd.data(), 4 * (size_t)CZ_EC_ENTRIES);
+    if (value) CZ_HIP(hipMemcpy(value, c->t.ec_val + e0, 4 * (size_t)CZ_EC_ENTRIES, hipMemcpyDeviceToHost));
+    if (board) CZ_HIP(hipMemcpy(board, c->t.ec_board + e0 * 12, 48 * (size_t)CZ_EC_ENTRIES, hipMemcpyDeviceToHost));
+    if (record) {
+        // the entry's node as cz_search_tree_dump numbers it: the same pre-order walk over the tree's expansion records
+        int32_t root = 0, n = 0;
+        CZ_HIP(hipMemcpy(&root, &c->t.root_node[g], 4, hipMemcpyDeviceToHost));
+        CZ_HIP(hipMemcpy(&n, &c->t.n_nodes[g], 4, hipMemcpyDeviceToHost));
+        const size_t base = (size_t)g * (size_t)c->cap;
+        std::vector<int32_t> cb(n), rec(n, -2);
+        std::vector<uint16_t> cc(n);
+        CZ_HIP(hipMemcpy(cb.data(), c->t.pool.child_begin + base, 4 * (size_t)n, hipMemcpyDeviceToHost));
+        CZ_HIP(hipMemcpy(cc.data(), c->t.pool.child_count + base, 2 * (size_t)n, hipMemcpyDeviceToHost));
+        std::vector<std::pair<int, int>> st;   // (node, next child)
+        int nrec = 0;
+        if (root >= 0 && root < n) { rec[root] = -1; if (cb[root] >= 0) st.push_back({root, 0}); }
+        while (!st.empty()) {
+            auto &f = st.back();
+            if (f.second >= cc[f.first]) { st.pop_back(); continue; }
+            const int ch = cb[f.first] + f.second++;
+            if (ch < 0 || ch >= n) break;   // a broken record: what was numbered so far stands, the rest stays "not in the tree"
+            rec[ch] = nrec++;
+            if (cb[ch] >= 0) st.push_back({ch, 0});
+        }
+        for (int i = 0; i < CZ_EC_ENTRIES; ++i) record[i] = (k[i] && nd[i] >= 0 && nd[i] < n) ? rec[nd[i]] : -2;
+    }
+    return CZ_EC_ENTRIES;
 }
 int cz_search_debug_eval_cache_key_bits(cz_ctx *c, int bits) {
     CZ_REQUIRE(c && (bits == 64 || (bits >= 8 && bits <= 24)), "cz_search_debug_eval_cache_key_bits: bits must be 8..24 or 64");

@@ -64,6 +64,9 @@ struct CzSelfplay {
 };
 
 #define CZ_EC_BUCKETS 128
+// cross-tree table: the bit that marks an entry whose payload is being written (claimed as key | CZ_XC_BUSY, not yet published);
+// no position's key has it (wave_position_key clears it), so a claim still tells the other trees which position it is for
+#define CZ_XC_BUSY (1ull << 63)
 #define CZ_EC_ENTRIES (CZ_EC_BUCKETS * 64)
 #ifndef CZ_EC_BUDGET
 #define CZ_EC_BUDGET 4   // evaluation-cache hits a tree may complete inside one select launch (its own budget, beside terminal_extra)
@@ -137,8 +140,10 @@ struct CzTrees {
     // when the bucket is full (round 6), the entry whose position lies DEEPEST in its game (game ply = re-roots of the filing tree
     // + depth of the leaf, kept in the upper half of the move-count word) if the new position is shallower: the table converges
     // to the shallowest positions ever evaluated — the openings every restarted game walks through again — instead of whatever
-    // arrived first.  k_select (a later launch: the kernel boundary publishes the payload) only reads, and verifies the stored
-    // position on every hit.  Emptied by the host whenever the weights change.
+    // arrived first.  A filing claims its slot by swapping the key to key | CZ_XC_BUSY, writes the payload write-through and only
+    // then stores the real key, so a slot is never claimed twice before its payload is in memory.  k_select (a later launch: the
+    // kernel boundary publishes the payload) only reads, and verifies the stored position on every hit.  Emptied by the host
+    // (keys, values and counts) whenever the weights change.
     // ONE base pointer (the kernels are short of scalar registers): with n = (xc_mask + 1) * 64 entries the block holds
     //   keys u64 [n] | counters u64 [8] | value f32 [n] | move count u32 [n] | position u32 [n][12] | labels u16 [n][128] |
     //   (src, dst) u16 [n][128] | priors f32 [n][128]        (czx_* below)

@@ -99,7 +99,8 @@ __device__ __forceinline__ Cand better(Cand a, Cand b) {
     return a;
 }
 
-// Zobrist key of the position in LDS (the same function as cz_hash; 0 is reserved for "empty" in the evaluation cache)
+// Zobrist key of the position in LDS: cz_hash without its top bit, which marks "being written" in the cross-tree table
+// (CZ_XC_BUSY); 0 is reserved for "empty" in the evaluation cache (a position with key 0 is filed under 1)
 __device__ __forceinline__ unsigned long long wave_position_key(const uint8_t *b, int side, const uint64_t *__restrict__ zob, int lane) {
     unsigned long long h = 0ull;
     const int c0 = b[lane];
@@ -111,7 +112,13 @@ __device__ __forceinline__ unsigned long long wave_position_key(const uint8_t *b
     // the key is wave-uniform: keep it in scalar registers (the select kernel sits exactly at its 64-VGPR budget)
     const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)h), hi = __builtin_amdgcn_readfirstlane((uint32_t)(h >> 32));
     h = ((unsigned long long)hi << 32) | lo;
+    h &= ~CZ_XC_BUSY;
     return h ? h : 1ull;
+}
+// write-through store (agent scope, sc1): reaches memory, not only this XCD's L2 — followed by s_waitcnt vmcnt(0), the value is
+// in memory before anything stored after the wait (the cross-tree table's payload before its key)
+template <typename T> __device__ __forceinline__ void st_through(T *p, T x) {
+    __hip_atomic_store((__attribute__((address_space(1))) T *)p, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 __device__ __forceinline__ int ec_bucket(unsigned long long key) { return (int)((key >> 17) & (CZ_EC_BUCKETS - 1)); }
 __device__ __forceinline__ uint32_t xc_bucket(unsigned long long key) { return (uint32_t)(key >> 24); }   // cross-tree table: other key bits
@@ -630,15 +637,20 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_num_sgpr(80), amdgpu_num_
                 if (lane == slot) { t.ec_key[eb0 + lane] = key; t.ec_node[eb0 + lane] = leaf; t.ec_val[eb0 + lane] = val; }
                 if (lane < 12) t.ec_board[(eb0 + slot) * 12 + lane] = t.pend_board[(size_t)g * 12 + lane];
             }
-            // cross-tree level (cz_search_set_xcache): file the evaluation for the OTHER trees as well — a write-once entry in an
-            // empty slot of the key's bucket, claimed by compare-and-swap on the key (two trees expanding the same position in this
-            // launch: one of them wins the slot, the other finds the key taken or loses the swap and leaves).  Readers are the
-            // select kernels of later launches, so the payload needs no flag: the kernel boundary publishes it.
+            // cross-tree level (cz_search_set_xcache): file the evaluation for the OTHER trees as well — in an empty slot of the key's
+            // bucket, or in place of the entry deepest in its game.  A slot is claimed in two phases: a compare-and-swap takes its key
+            // to key | CZ_XC_BUSY, the payload (ply included) is stored write-through and drained, and only then is the real key stored.
+            // So no two trees of a launch hold one slot at once, and a later claim of the slot (which has to find the real key) writes
+            // after this payload is in memory: the XCDs' L2s are not coherent with each other, and the plain stores of two claimants
+            // could reach memory in either order — a key and board of one position with the labels, priors or count of another.
+            // Two trees expanding the same position in this launch: one files it, the other finds the key, claimed or published (or
+            // loses the swap to it), and leaves.  Readers are the select kernels of later launches (the kernel boundary publishes the
+            // payload); they never match a claimed key, and none is left once this launch has ended.
             if (t.xc_base) {
                 const size_t xb0 = (size_t)(xc_bucket(key) & t.xc_mask) * 64;
                 const unsigned long long xk = czx_key(t)[xb0 + lane];
                 const unsigned long long xm = __ballot(xk == 0ull);
-                if (__ballot(xk == key) == 0ull) {
+                if (__ballot((xk & ~CZ_XC_BUSY) == key) == 0ull) {
                     // this position's game ply: re-roots of the tree + levels below the root (the priority of the entry: low = shared)
                     const uint32_t myply = (uint32_t)min((int)t.root_ply[g] + (int)t.pend_depth[g], 0xFFFF);
                     int slot = 0, won = 0, dup = 0;
@@ -652,15 +664,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_num_sgpr(80), amdgpu_num_
                             slot = (__ffsll((long long)xr) - 1 + rot) & 63;
                             xr &= xr - 1ull;
                             unsigned long long seen = 0ull;
-                            if (lane == 0) seen = atomicCAS(&czx_key(t)[xb0 + slot], 0ull, key);
+                            if (lane == 0) seen = atomicCAS(&czx_key(t)[xb0 + slot], 0ull, key | CZ_XC_BUSY);
                             seen = __shfl(seen, 0, 64);
                             won = seen == 0ull ? 1 : 0;
-                            dup = seen == key ? 1 : 0;
+                            dup = (seen & ~CZ_XC_BUSY) == key ? 1 : 0;
                         }
                     } else {
-                        // full bucket: the entry deepest in its game makes room if this position is shallower.  One attempt: a lost
-                        // swap (another tree of this launch took the victim) drops the filing.
-                        const uint32_t ep = czx_cnt(t)[xb0 + lane] >> 16;
+                        // full bucket: the entry deepest in its game makes room if this position is shallower.  A slot another tree of
+                        // this launch is writing (CZ_XC_BUSY set: its count word is not this key's) is no candidate.  One attempt: a lost swap
+                        // drops the filing.
+                        const uint32_t ep = (xk & CZ_XC_BUSY) ? 0u : czx_cnt(t)[xb0 + lane] >> 16;
                         uint32_t best = (ep << 6) | (uint32_t)lane;
 #pragma unroll
                         for (int o = 32; o >= 1; o >>= 1) best = max(best, (uint32_t)__shfl_xor((int)best, o, 64));
@@ -668,7 +681,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_num_sgpr(80), amdgpu_num_
                             slot = (int)(best & 63u);
                             const unsigned long long old = __shfl(xk, slot, 64);
                             unsigned long long seen = 0ull;
-                            if (lane == 0) seen = atomicCAS(&czx_key(t)[xb0 + slot], old, key);
+                            if (lane == 0) seen = atomicCAS(&czx_key(t)[xb0 + slot], old, key | CZ_XC_BUSY);
                             seen = __shfl(seen, 0, 64);
                             won = seen == old ? 1 : 0;
                             if (won && lane == 0) czx_tree_stats(t)[(size_t)g * 8 + 4] += 1u;
@@ -678,17 +691,22 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_num_sgpr(80), amdgpu_num_
                         const size_t e = xb0 + slot;
                         const int n2 = t.pend_nmoves[g];
                         const int cb2 = begin;   // the children written above: lane l re-reads exactly the elements lane l wrote
-                        if (lane < 12) czx_board(t)[e * 12 + lane] = mine;
+                        if (lane < 12) st_through(&czx_board(t)[e * 12 + lane], mine);
 #pragma unroll
                         for (int r = 0; r < 2; ++r) {
                             const int i = lane + 64 * r;
                             if (i < n2) {
-                                czx_P(t)[e * CZD_MAXMOVES + i] = v.P[cb2 + i];
-                                czx_moves(t)[e * CZD_MAXMOVES + i] = v.move[cb2 + i];
-                                czx_sd(t)[e * CZD_MAXMOVES + i] = v.sd[cb2 + i];
+                                st_through(&czx_P(t)[e * CZD_MAXMOVES + i], v.P[cb2 + i]);
+                                st_through(&czx_moves(t)[e * CZD_MAXMOVES + i], v.move[cb2 + i]);
+                                st_through(&czx_sd(t)[e * CZD_MAXMOVES + i], v.sd[cb2 + i]);
                             }
                         }
-                        if (lane == 0) { czx_val(t)[e] = val; czx_cnt(t)[e] = (uint32_t)n2 | (myply << 16); czx_tree_stats(t)[(size_t)g * 8 + 2] += 1u; }
+                        if (lane == 0) { st_through(&czx_val(t)[e], val); st_through(&czx_cnt(t)[e], (uint32_t)n2 | (myply << 16)); }
+                        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the whole payload is in memory ...
+                        if (lane == 0) {                                    // ... before the slot shows its key
+                            __hip_atomic_store(&czx_key(t)[e], key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                            czx_tree_stats(t)[(size_t)g * 8 + 2] += 1u;
+                        }
                     } else if (!dup && lane == 0) {
                         czx_tree_stats(t)[(size_t)g * 8 + 3] += 1u;     // filings that found no room (deeper than everything in a full bucket, or lost every swap)
                     }

@@ -122,6 +122,39 @@ class SearchEngine:
         check(lib().cz_search_xcache_stats5(self.ctx.h, a), "cz_search_xcache_stats5")
         return dict(hits=int(a[0]), lookups=int(a[1]), written=int(a[2]), lost=int(a[3]), replaced=int(a[4]))
 
+    def xcache_dump(self):
+        """(tests) The cross-tree table as it stands (cz_search_debug_xcache_dump): dict of numpy arrays over its n entries —
+        key u64 [n] (0 = empty), value f32 [n], count u16 [n], ply u16 [n], board u32 [n, 12] (the packed position),
+        label u16 [n, 128], sd u16 [n, 128] (src | dst << 8), P f32 [n, 128]."""
+        self.ctx.bind_stream()
+        n = lib().cz_search_debug_xcache_dump(self.ctx.h, None, 0)
+        check(min(n, 0), "cz_search_debug_xcache_dump")
+        raw = np.zeros(n * 1088 + 64, np.uint8)
+        check(min(lib().cz_search_debug_xcache_dump(self.ctx.h, raw.ctypes.data_as(C.c_void_p), raw.nbytes), 0),
+              "cz_search_debug_xcache_dump")
+
+        def part(off, dt, shape):
+            return raw[off:off + int(np.prod(shape)) * np.dtype(dt).itemsize].view(dt).reshape(shape).copy()
+        cnt = part(n * 12 + 64, np.uint32, (n,))
+        return dict(key=part(0, np.uint64, (n,)), value=part(n * 8 + 64, np.float32, (n,)),
+                    count=(cnt & 0xFFFF).astype(np.uint16), ply=(cnt >> 16).astype(np.uint16),
+                    board=part(n * 16 + 64, np.uint32, (n, 12)), label=part(n * 64 + 64, np.uint16, (n, MAXMOVES)),
+                    sd=part(n * 320 + 64, np.uint16, (n, MAXMOVES)), P=part(n * 576 + 64, np.float32, (n, MAXMOVES)))
+
+    def eval_cache_dump(self, g):
+        """(tests) Tree g's per-tree cache entries (cz_search_debug_eval_cache_dump): dict of numpy arrays over its 8192 entries —
+        key u64 (0 = empty), node i32, value f32, board u32 [8192, 12], record i32 (the node's row in tree_dump(g), -1 = the root,
+        -2 = not in the tree)."""
+        self.ctx.bind_stream()
+        n = 128 * 64
+        out = dict(key=np.zeros(n, np.uint64), node=np.zeros(n, np.int32), value=np.zeros(n, np.float32),
+                   board=np.zeros((n, 12), np.uint32), record=np.zeros(n, np.int32))
+        p = [out[k].ctypes.data_as(C.c_void_p) for k in ("key", "node", "value", "board", "record")]
+        got = lib().cz_search_debug_eval_cache_dump(self.ctx.h, int(g), *p)
+        check(min(got, 0), "cz_search_debug_eval_cache_dump")
+        assert got == n
+        return out
+
     def eval_cache_stats(self):
         """-> (hits, lookups) summed over the trees since the cache was turned on."""
         h, n = C.c_ulonglong(0), C.c_ulonglong(0)

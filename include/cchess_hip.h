@@ -235,7 +235,11 @@ int cz_search_debug_eval_cache_key_bits(cz_ctx *, int bits);
  * on the tree it is asked for).  log2_entries 0 frees the table; calling it again (or cz_search_set_eval_cache(ctx, 1)) empties
  * it — do so whenever the weights change.  Round 6: a FULL bucket is no longer closed — the entry whose position lies deepest in
  * its game (re-roots of the filing tree + depth of the leaf) is replaced when the new position is shallower, so the table converges
- * to the openings every restarted game walks through again.  stats4: hits, lookups, entries written, filings that found no room
+ * to the openings every restarted game walks through again.  A filing claims its slot by swapping in its key with the top bit
+ * set (the bit no position's key has: keys are cz_hash without it), writes the entry through to memory and only then stores
+ * the real key: two trees of one launch never write one entry at once, no entry mixes two positions, and a tree filing a
+ * position another tree is still writing leaves it to that one.  Emptying the
+ * table clears keys, values and counts.  stats4: hits, lookups, entries written, filings that found no room
  * (a full bucket of shallower positions, or every swap lost to another tree of the launch); stats5 adds: entries that replaced
  * a deeper one (included in `written`). */
 int cz_search_set_xcache(cz_ctx *, int log2_entries);
@@ -244,6 +248,17 @@ int cz_search_xcache_stats5(cz_ctx *, unsigned long long *stats5);
 /* tests: cz_search_advance keeps the kept-node bitmap of a tree in LDS when it fits (12 bytes per 64 nodes) and in global memory
  * otherwise; on != 0 forces the global-memory kernel so that it is exercised at test sizes. */
 int cz_search_debug_advance_in_global_memory(cz_ctx *, int on);
+/* tests: read the caches back (synchronise the stream).
+ *   cz_search_debug_xcache_dump: the whole cross-tree block, n * 1088 + 64 bytes for n entries, in the table's own layout:
+ *     key u64 [n] | 64 bytes | value f32 [n] | count | ply << 16 u32 [n] | packed position u32 [n][12] | labels u16 [n][128] |
+ *     (src | dst << 8) u16 [n][128] | priors f32 [n][128].  Key 0 = empty.  host NULL: only returns n.  Returns n, or an error
+ *     when the table is off or `bytes` is short.
+ *   cz_search_debug_eval_cache_dump: tree g's per-tree entries (8192 = 128 buckets x 64): key, node, value, packed position
+ *     [8192][12]; record[i] = the node's index in cz_search_tree_dump's pre-order records, -1 for the root, -2 when the node
+ *     is not in the tree (or the entry is empty).  Any array may be NULL.  Returns 8192. */
+int cz_search_debug_xcache_dump(cz_ctx *, void *host, size_t bytes);
+int cz_search_debug_eval_cache_dump(cz_ctx *, int g, unsigned long long *key, int32_t *node, float *value, uint32_t *board,
+                                    int32_t *record);
 int cz_search_select_k(cz_ctx *, int mode, int k, const uint8_t *active, void *leaf_planes, int dtype,
                        int channels, uint8_t *needs_eval);
 int cz_search_expand_backup_k(cz_ctx *, int k, const void *logits, const void *value, int dtype);
