@@ -12,6 +12,13 @@ cz_search_advance, the update_tree of the reference) at the next check (every 8 
 runs stay in the self-play regime.  Rank 0 prints ONE JSON line.  Metric/config follow
 BASELINE.json: "MCTS simulations/sec (whole node), playout=1600, 7-block net", 8192 games per GPU (configs[2]).
 
+A plain run does only what the headline needs: set-up (positions, net and its strict self-check, node pools, ageing), warm-up,
+the K timed steps, --dump-outputs, and the line, whose roofline / roofline_tree come from HIP events of the timed steps.
+  --full           also everything measured or checked outside those steps: the net-error probes (as benchmarked and on
+                   trained-like weights), the stand-alone rules-kernel roofline, the MFMA ceiling probe, the CPU baseline
+                   (unless --no-cpu-baseline), the record all-gather self-check (N > 1) and, with --selfplay, the 16 extra
+                   sampled steps that give that mode its per-kernel figures.
+
 Opt-in modes:
   --selfplay       the timed region is the whole device-resident self-play loop (cchess_zero_amd/selfplay.py: search,
                    visit-count policy, Dirichlet-noise sampling, records, re-rooting, adjudication, re-seeding of finished
@@ -368,7 +375,8 @@ def main():
     ap.add_argument("--steady-steps", type=int, default=0, help="extra lock-steps timed AFTER the K contract steps (own barrier-bracketed region) for the steady_state block of the output, which then gives value and ms_per_step; 0 (default) = off: the K steps are the only timed ones")
     ap.add_argument("--alt-steps", "--strict-steps", dest="alt_steps", type=int, default=0, help="lock-steps of a third timed region in which the SAME trees are searched with the OTHER engine: the fast fp16 engine (k_tower8_c128; the fast_engine block of the output) when the run's engine is a strict one, the strict engine of this depth (the strict_engine block) when --dtype is fp16 / bf16; 0 (default) = off")
     ap.add_argument("--backend", default="auto", choices=["auto", "hip", "torch"], help="conv backend of the net")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also run what the headline does not need: net-error probes, rules roofline, MFMA ceiling probe, CPU baseline, the N > 1 record all-gather self-check, the --selfplay sampled steps")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"], help="nccl = RCCL (default); gloo only for single-GPU smoke tests of the N>1 path")
     ap.add_argument("--all-on-device0", action="store_true", help="testing only: every rank uses cuda:0")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
@@ -726,7 +734,7 @@ def main():
             leg = timed_region(args.alt_steps)
             strict_leg = (leg, cur["conv_ev"], net_s, alt_key)
             cur.update(net=net, conv_ev=conv_ev, ev=ev)
-    if dist_on:
+    if dist_on and args.full:
         # outside the timed regions: the record exchange of the self-play loop (all-gather of packed (s, pi, z) records,
         # device-resident end to end; both the sized and the fixed-capacity form) on a ragged token batch, so every N>1 run
         # exercises the collective path; a failure is reported in the line, it does not take the throughput number with it
@@ -739,7 +747,7 @@ def main():
     if gathered:
         gather_stats["records"] += int(torch.stack(gathered).contiguous().view(torch.int64).sum().item())
         del gathered[:]
-    if sp:   # the self-play loop launches through SelfPlay.run_async: sample the kernels' durations on 16 extra, uncounted steps
+    if sp and args.full:   # the self-play loop launches through SelfPlay.run_async: sample the kernels' durations on 16 extra, uncounted steps
         eng.set_terminal_extra(TE)
         eng.set_sim_target(playout)
         for _ in range(16):
@@ -856,7 +864,7 @@ def main():
             r["telemetry"] = telemetry_
         return r
     mfma_peak_measured = None
-    if fused and rank == 0:
+    if fused and rank == 0 and args.full:
         try:
             mfma_peak_measured = mfma_probe()
         except Exception as e:
@@ -878,11 +886,13 @@ def main():
                     "achieved": conv_flops / (conv_ms * 1e-3) / 1e12, "peak": peak, "unit": "TFLOP/s",
                     "frac": conv_flops / (conv_ms * 1e-3) / 1e12 / peak, "traffic": traffic, "traffic_source": traffic_src,
                     "us_per_launch": conv_ms * 1e3, "launches_timed": len(conv_ev), "flops_per_launch": conv_flops}
-    else:
+    elif ev:
         achieved = flops / (net_ms * 1e-3) / 1e12
         roof = {"bound": "mfma", "kernel": "net forward via torch/MIOpen (conv tower + heads), all launches of one step",
                 "achieved": achieved, "peak": peak, "unit": "TFLOP/s", "frac": achieved / peak, "traffic": None,
                 "ms_per_launch_group": net_ms, "flops_per_step": flops}
+    else:   # no sampled step: --selfplay without --full
+        roof = None
     # second roofline entry: the HBM-bound tree / rules side of a step (k_select = selection descent + make-move + move
     # generation + plane encoding; k_expand_backup = policy FC at the legal labels + node append + backup).  Algorithmic
     # bytes per tree: select  depth * L * 20 B of sibling statistics + 96 B root board + 2 B * L pending
@@ -988,7 +998,7 @@ def main():
     cfg["lock_steps_per_move"] = head_ms and cfg["ms_per_move"] / head_ms
     cfg["efficiency_vs_min_rank"] = head_val / (world * min(own_rate))
     cfg["efficiency_vs_max_rank"] = head_val / (world * max(own_rate))
-    if rank == 0:
+    if rank == 0 and args.full:
         # precision of the benchmarked engine, measured here: the net exactly as timed (same weights) and a peaked,
         # trained-like weight set, against fp32 on the same inputs (256 of the run's own synthetic positions)
         try:
@@ -1027,7 +1037,7 @@ def main():
         # the CPU baseline runs after every rank has left the timed regions and the process group (N > 1: the other ranks
         # have exited or are exiting; a shorter sample keeps the multi-GPU line quick)
         PL.unpin_cpus()
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.blocks, args.cpu_seconds if world == 1 else min(args.cpu_seconds, 5.0))
         else:
             out["cpu_baseline"] = None

@@ -304,6 +304,10 @@ def test_bench_times_k_steps_and_dumps_identical_outputs(tmp_path):
         assert line["steps"] == 24 and line["contract_steps"]["steps"] == 24 and line["value_source"] == "contract_steps"
         assert line["steady_state"] is None and line["fast_engine"] is None and line["strict_engine"] is None
         assert line["ms_per_step"] == line["contract_steps"]["ms_per_step"] > 0
+        # a plain run (no --full) measures nothing beyond its timed steps
+        assert line["net_error"] is None and line["roofline_rules"] is None and line["cpu_baseline"] is None
+        assert line["roofline"]["kernel"] == "k_trunk_mx_c128" and line["roofline"]["achieved"] > 0 and line["roofline"]["launches_timed"] >= 1
+        assert "mfma_peak_measured_TFLOPs" not in line["roofline"]
     a, b = dumps
     assert {"root_N", "root_Q", "root_label", "tree_sims", "net_z", "net_value", "tree_index"} <= set(a) and set(a) == set(b)
     assert all(v.dtype == np.float32 for v in a.values()) and sum(v.nbytes for v in a.values()) <= 64 << 20

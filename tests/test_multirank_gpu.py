@@ -42,7 +42,7 @@ def _bench(args, timeout=900):
 @pytest.mark.gpu
 def test_bench_two_ranks_selfplay_with_timed_record_exchange():
     d = _bench(["--gpus", "2", "--all-on-device0", "--dist-backend", "gloo", "--selfplay", "--timed-gather", "--games", "512",
-                "--playout", "40", "--steps", "64", "--warmup", "8", "--age-steps", "64", "--steady-steps", "0", "--no-cpu-baseline"])
+                "--playout", "40", "--steps", "64", "--warmup", "8", "--age-steps", "64", "--steady-steps", "0", "--full", "--no-cpu-baseline"])
     c = d["config"]
     assert d["n_gpus"] == 2 and c["world_size"] == 2 and c["dist_backend"] == "gloo" and d["scaling"] == "weak"
     assert len(c["per_rank_sims_per_s"]) == 2 and all(v > 0 for v in c["per_rank_sims_per_s"])
@@ -63,7 +63,7 @@ def test_bench_two_ranks_search_loop_default_engine():
     figures.  Since round 6 the default engine is precision "strict" (what policy_value_network() runs), selected by the net's own
     measurement; the fast fp16 engine is the extra leg."""
     d = _bench(["--gpus", "2", "--all-on-device0", "--dist-backend", "gloo", "--games", "512", "--playout", "64", "--steps", "24",
-                "--warmup", "4", "--age-steps", "48", "--steady-steps", "48", "--alt-steps", "16", "--no-cpu-baseline"])
+                "--warmup", "4", "--age-steps", "48", "--steady-steps", "48", "--alt-steps", "16", "--full", "--no-cpu-baseline"])
     assert d["n_gpus"] == 2 and d["value_source"].startswith("steady_state")
     assert len(d["steady_state"]["per_rank_sims_per_s"]) == 2 and len(d["fast_engine"]["per_rank_sims_per_s"]) == 2
     assert d["contract_steps"]["steps"] == 24 and d["config"]["record_gather"] is True
@@ -81,7 +81,7 @@ def test_bench_two_ranks_search_loop_default_engine():
     assert full["net_error"]["strict_on_trained_like"]["engine"] in ("mx6", "fp16x2") and "telemetry" in json.dumps(full)
     # the fast engine by explicit choice: the strict engine is then the extra leg (round 5's layout)
     d = _bench(["--dtype", "fp16", "--games", "512", "--playout", "64", "--steps", "24", "--warmup", "4", "--age-steps", "48", "--steady-steps", "0",
-                "--strict-steps", "16", "--no-cpu-baseline"])
+                "--strict-steps", "16", "--full", "--no-cpu-baseline"])
     assert d["dtype"] == "fp16" and d["fast_engine"] is None and d["strict_engine"]["kernel"] == "k_trunk_mx_c128"
     assert d["strict_engine"]["meets_1e-3_abs_logit_and_value"] is True and d["strict_check"] is None
 
@@ -90,7 +90,7 @@ def test_bench_two_ranks_search_loop_default_engine():
 def test_bench_rccl_world_of_one():
     """RCCL (backend "nccl") with a world of 1: process-group set-up on the device, the timed all-gather of records, barriers."""
     d = _bench(["--force-dist", "--selfplay", "--timed-gather", "--games", "512", "--playout", "40", "--steps", "64", "--warmup", "8",
-                "--age-steps", "64", "--steady-steps", "0", "--no-cpu-baseline"])
+                "--age-steps", "64", "--steady-steps", "0", "--full", "--no-cpu-baseline"])
     c = d["config"]
     assert d["n_gpus"] == 1 and c["dist_backend"] == "nccl" and c["record_gather"] is True
     assert c["selfplay"]["gathers"] >= 1 and c["selfplay"]["gathered_records"] > 0 and c["trees_with_error_status"] == 0
@@ -141,7 +141,7 @@ def test_bench_eight_ranks_self_launch_selfplay_with_timed_exchange():
     _one_gpu_per_rank(8)
     d = _bench(["--gpus", "8", "--dist-backend", "gloo", "--selfplay", "--timed-gather", "--games", "64",
                 "--playout", "16", "--steps", "128", "--warmup", "8", "--age-steps", "32", "--steady-steps", "0", "--strict-steps", "0",
-                "--no-cpu-baseline"], timeout=1500)
+                "--full", "--no-cpu-baseline"], timeout=1500)
     c = d["config"]
     assert d["n_gpus"] == 8 and c["world_size"] == 8 and c["dist_backend"] == "gloo" and d["scaling"] == "weak"
     assert len(c["per_rank_sims_per_s"]) == 8 and all(v > 0 for v in c["per_rank_sims_per_s"])

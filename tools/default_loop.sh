@@ -6,7 +6,7 @@
 O=gpurun_out/${2:-r06b}; mkdir -p $O
 STEPS=${1:-48000}
 timeout 1500 python bench.py --selfplay --start-position --dtype strict --eval-cache --xcache 24 --steps $STEPS --warmup 16 --age-steps 0 \
-    --steady-steps 0 --alt-steps 0 --no-cpu-baseline > $O/sp_strict_xcache24_${STEPS}.json 2> $O/sp_strict_xcache24_${STEPS}.err
+    --steady-steps 0 --alt-steps 0 --full --no-cpu-baseline > $O/sp_strict_xcache24_${STEPS}.json 2> $O/sp_strict_xcache24_${STEPS}.err
 python tools/jline.py $O/sp_strict_xcache24_${STEPS}.json | head -12
 cp gpurun_out/bench_detail_*.json $O/ 2>/dev/null
 if [ "$3" != "nomain" ]; then

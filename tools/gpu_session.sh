@@ -2,7 +2,7 @@
 # Runs ON THE GPU BOX (gpurun): one parameterised session instead of one script per session (rounds 2-4 kept ~45 of those; they
 # are in git history).  usage: tools/gpu_session.sh <tag> <step> [<step> ...]   — output under gpurun_out/<tag>/
 #   tests[:k-expr]   pytest -m gpu (optionally -k <expr>)        smoke            __graft_entry__.smoke()
-#   bench[:args]     python bench.py <args> (default line + CPU baseline)         bench_nocpu[:args]  the same with --no-cpu-baseline
+#   bench[:args]     python bench.py --full <args> (complete record + CPU baseline)  bench_nocpu[:args]  the same with --no-cpu-baseline
 #   profile[:dtype]  tools/profile_round.sh (rocprofv3 kernel stats + HBM PMC passes of the bench, engine <dtype>)
 #   pmcsq:<engine>   tools/pmc_mx.sh (SQ counters of one trunk engine: fp16 | x3 | mx)
 #   rules            tools/rules_bench.py (stand-alone K1 / K2 / K3 / hash kernels, 1 M positions) + its rocprofv3 kernel stats
@@ -20,8 +20,8 @@ for step in "$@"; do
   case $name in
     tests) ( timeout 1700 python -m pytest tests -m gpu -q -x -p no:cacheprovider ${arg:+-k "$arg"} > $O/pytest_gpu.log 2>&1; echo "pytest rc=$?" >> $O/pytest_gpu.log ); tail -5 $O/pytest_gpu.log;;
     smoke) ( timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1; echo "smoke rc=$?" >> $O/smoke.log ); tail -3 $O/smoke.log;;
-    bench) n=bench_$(echo "${arg:-default}" | tr -c 'A-Za-z0-9\n' '_'); timeout 900 python bench.py $arg > $O/$n.json 2> $O/$n.err; python tools/jline.py $O/$n.json | tee $O/$n.txt; cp gpurun_out/bench_detail_*.json $O/ 2>/dev/null;;
-    bench_nocpu) n=bench_$(echo "${arg:-default}" | tr -c 'A-Za-z0-9\n' '_'); timeout 900 python bench.py --no-cpu-baseline $arg > $O/$n.json 2> $O/$n.err; python tools/jline.py $O/$n.json | tee $O/$n.txt; cp gpurun_out/bench_detail_*.json $O/ 2>/dev/null;;
+    bench) n=bench_$(echo "${arg:-default}" | tr -c 'A-Za-z0-9\n' '_'); timeout 900 python bench.py --full $arg > $O/$n.json 2> $O/$n.err; python tools/jline.py $O/$n.json | tee $O/$n.txt; cp ${O%/*}/bench_detail_*.json $O/ 2>/dev/null;;
+    bench_nocpu) n=bench_$(echo "${arg:-default}" | tr -c 'A-Za-z0-9\n' '_'); timeout 900 python bench.py --full --no-cpu-baseline $arg > $O/$n.json 2> $O/$n.err; python tools/jline.py $O/$n.json | tee $O/$n.txt; cp ${O%/*}/bench_detail_*.json $O/ 2>/dev/null;;
     profile) d=${arg:-fp16}; tools/profile_round.sh $TAG/prof_$d ${arg:+--dtype $arg} > $O/profile_$d.log 2>&1
              # summarised HERE (the raw traces are tens of MB and gpurun merges at most 64 MiB back): profiles_out/ holds what goes to profiles/
              case $d in mx6) k=k_trunk_mx; sfx=_mx;; fp16x2) k=k_trunk_split; sfx=_strict;; *) k=k_tower8; sfx="";; esac
@@ -41,7 +41,7 @@ for step in "$@"; do
                python -c "import json,sys; d=json.loads([x for x in open('$O/$n.json') if x.startswith('{')][-1]); c=d['config']; print('playout $po: %s %.0f sims/s %.3f ms per lock-step %.2f ms per move (%s launches, %.1f lock-steps per move)' % (d['dtype'], d['value'], d['ms_per_step'], c['ms_per_move'], c['launches_per_lock_step'], c['lock_steps_per_move']))"; done;;
     xcache) st=${arg:-160000}
             for v in "nocache" "xcache22 --eval-cache --xcache 22" "xcache24 --eval-cache --xcache 24"; do set -- $v; n=$1; shift
-              timeout 1500 python bench.py --selfplay --start-position --dtype fp16 --steps $st --warmup 16 --age-steps 0 --steady-steps 0 --alt-steps 0 --no-cpu-baseline "$@" > $O/sp_p1600_${st}_$n.json 2> $O/sp_p1600_${st}_$n.err
+              timeout 1500 python bench.py --selfplay --start-position --dtype fp16 --steps $st --warmup 16 --age-steps 0 --steady-steps 0 --alt-steps 0 --full --no-cpu-baseline "$@" > $O/sp_p1600_${st}_$n.json 2> $O/sp_p1600_${st}_$n.err
               python tools/jline.py $O/sp_p1600_${st}_$n.json | head -1; cp gpurun_out/bench_detail_fp16_n1.json $O/detail_$n.json 2>/dev/null; done;;
     loop) tools/default_loop.sh ${arg:-48000} $TAG;;
     *) echo "unknown step $step";;

@@ -12,9 +12,10 @@ if "detail_file" in d:   # the compact line of round 5: the complete record sits
         if os.path.exists(cand):
             d = json.load(open(cand))
             break
-r = d["roofline"]
+r = d.get("roofline") or {}   # none in a --selfplay run without --full (no sampled steps)
 print("%.0f sims/s  %.3f ms/step  n_gpus %d  trunk %.1f us  %.1f TF/s (frac %.3f)  errors %s" % (
-    d["value"], d["ms_per_step"], d["n_gpus"], r.get("us_per_launch", float("nan")), r["achieved"], r["frac"], d["config"].get("trees_with_error_status")))
+    d["value"], d["ms_per_step"], d["n_gpus"], r.get("us_per_launch", float("nan")), r.get("achieved", float("nan")), r.get("frac", float("nan")),
+    d["config"].get("trees_with_error_status")))
 ss = d.get("steady_state")
 if ss:
     print("  steady state: %.0f sims/s over %d steps (%.3f ms/step, %.0f net rows/s, %.3f sims per row)" % (ss["value"], ss["steps"], ss["ms_per_step"], ss["net_rows_per_s"], ss["simulations_per_net_row"]))

@@ -4,9 +4,9 @@
 OUT=$1; ROOT=$(pwd); mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 C="SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY"
-(timeout 200 rocprofv3 --kernel-trace --pmc $C --output-format csv -d $ROOT/$OUT/sq_a -o p -- python $ROOT/bench.py --no-cpu-baseline --steps 24 --warmup 4 --age-steps 200 --steady-steps 0 > $ROOT/$OUT/sq_a.out 2>&1) < /dev/null
+(timeout 200 rocprofv3 --kernel-trace --pmc $C --output-format csv -d $ROOT/$OUT/sq_a -o p -- python $ROOT/bench.py --full --no-cpu-baseline --steps 24 --warmup 4 --age-steps 200 --steady-steps 0 > $ROOT/$OUT/sq_a.out 2>&1) < /dev/null
 C2="SQ_INSTS_LDS SQ_INSTS_VMEM SQ_INSTS_SMEM SQ_INSTS_BRANCH SQ_WAIT_INST_LDS SQ_INST_CYCLES_VMEM GRBM_GUI_ACTIVE"
-(timeout 200 rocprofv3 --kernel-trace --pmc $C2 --output-format csv -d $ROOT/$OUT/sq_b -o p -- python $ROOT/bench.py --no-cpu-baseline --steps 24 --warmup 4 --age-steps 200 --steady-steps 0 > $ROOT/$OUT/sq_b.out 2>&1) < /dev/null
+(timeout 200 rocprofv3 --kernel-trace --pmc $C2 --output-format csv -d $ROOT/$OUT/sq_b -o p -- python $ROOT/bench.py --full --no-cpu-baseline --steps 24 --warmup 4 --age-steps 200 --steady-steps 0 > $ROOT/$OUT/sq_b.out 2>&1) < /dev/null
 cd $ROOT
 python3 - $OUT <<'PY'
 import csv, sys, collections, glob, json
@@ -39,7 +39,7 @@ for key, c in res.items():
                                           "parked in s_waitcnt / barrier (SQ_WAIT_ANY)": c.get("SQ_WAIT_ANY", 0) / wc},
                  "raw": c}
     print(key, json.dumps(summ[key]["per_wave"]), json.dumps(summ[key]["share_of_wave_cycles"]))
-json.dump({"method": "rocprofv3 --kernel-trace --pmc, two separate passes over `python bench.py --no-cpu-baseline --steps 24 --warmup 4` "
+json.dump({"method": "rocprofv3 --kernel-trace --pmc, two separate passes over `python bench.py --full --no-cpu-baseline --steps 24 --warmup 4` "
                      "(tools/pmc_tree.sh); means over the launches of each kernel; SQ_WAVE_CYCLES / SQ_WAIT_* / SQ_ACTIVE_INST_* count quad-cycles",
            "kernels": summ}, open(out + "/pmc_tree_sq.json", "w"), indent=1)
 PY
