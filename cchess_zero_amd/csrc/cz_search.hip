@@ -1022,154 +1022,21 @@ __global__ __launch_bounds__(64) void k_root_stats(CzTrees t, int G, uint16_t *_
 // (a) keeps every sibling group contiguous and in generation order — selection is unchanged —, (b) moves every node
 // to an index <= its old one, so it can be done in place, ascending, with no spare pool (round 1 kept a second pool
 // of the same size as the compaction target: 2 x 59 GB at 8192 trees x 256 320 nodes).
-//   pass 1  kept[i] = (i == played child) || kept[parent[i]], ascending in chunks of 256 nodes; a parent inside the
-//           same chunk is resolved by iterating over the chunk (parent < child bounds the iterations by the chunk's
-//           chain depth); one 64-bit word of the bitmap per wave and chunk (ballot)
-//   rank    exclusive prefix count of the bitmap words: new index of node i = rank[i / 64] + popc(bits below i)
-//   pass 2  ascending: a chunk is read into registers, barrier, written to the new indices with parent /
-//           child_begin remapped through the rank
+//   pass 1  kept[i] = (i == played child) || kept[parent[i]], ascending in chunks of CZ_ADV_T nodes (16 waves); a parent
+//           inside the same chunk is resolved by iterating over the chunk (parent < child bounds the iterations by the
+//           chunk's chain depth); one 64-bit word of the bitmap per wave and chunk (ballot); the next chunk's parents are
+//           in flight while the current one is resolved
+//   rank    exclusive prefix count of the bitmap words (wave shuffles): new index of node i = rank[i / 64] + popc(bits below i)
+//   pass 2  ascending: a chunk, loaded into registers one iteration ahead, is written to the new indices after a barrier,
+//           with parent / child_begin remapped through the rank
 // Board / side / restrict_round follow selfplay's bookkeeping, main.py:1522-1528.  The tree's POOL_EXHAUSTED status
 // is cleared: the compaction has made room again (a tree that stays full is flagged again by the next expansion).
+// One workgroup compacts one tree at a time.  The bitmap and its ranks (12 bytes per 64 nodes) live in the workgroup's dynamic
+// LDS when they fit (k_advance_lds: a chunk then costs LDS round trips only), in global memory otherwise (k_advance_global,
+// t.mark_bits / t.mark_rank: pools of more than 819 200 nodes per tree); the algorithm is the same.
+#define CZ_ADV_T 1024
 __device__ __forceinline__ bool mark_tst(const unsigned long long *bits, int i) { return (bits[i >> 6] >> (i & 63)) & 1ull; }
 __device__ __forceinline__ int mark_rank_of(const unsigned long long *bits, const uint32_t *rank, int i) {
-    const unsigned long long below = (i & 63) ? (bits[i >> 6] & ((1ull << (i & 63)) - 1ull)) : 0ull;
-    return (int)rank[i >> 6] + __popcll(below);
-}
-
-__global__ __launch_bounds__(256) void k_advance_global(CzTrees t, CzTables tab, int G, const uint16_t *__restrict__ played) {
-    __shared__ int s_found, s_total;
-    __shared__ int s_flag[256];
-    const int g = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (g >= G) return;
-    const uint16_t l = played[g];
-    if (l >= CZ_NLABELS) return;
-    const TreeView v = view_of(t, g);
-    unsigned long long *bits = t.mark_bits + (size_t)g * t.words;
-    uint32_t *rank = t.mark_rank + (size_t)g * t.words;
-    const int root = t.root_node[g];
-    const int n = t.n_nodes[g];
-    // find the played child (children are unique; at most 128 of them)
-    const int cb = v.child_begin[root];
-    const int cc = cb < 0 ? 0 : v.child_count[root];
-    if (tid == 0) s_found = -1;
-    __syncthreads();
-    if (tid < cc && v.move[cb + tid] == l) s_found = cb + tid;
-    // board bookkeeping
-    uint8_t *rb = t.root_board + (size_t)g * CZD_BOARD_LDS;
-    if (tid == 0) {
-        const int src = tab.srcdst[l] & 0xFF, dst = tab.srcdst[l] >> 8;
-        const int cap = rb[dst];
-        rb[dst] = rb[src]; rb[src] = 0;
-        t.root_side[g] ^= 1;
-        t.root_rr[g] = cap ? 0 : t.root_rr[g] + 1;
-        t.root_ply[g] = (uint16_t)min((int)t.root_ply[g] + 1, 65535);
-        t.sims[g] = 0;
-    }
-    __syncthreads();
-    const int found = s_found;
-    if (found < 0) {
-        if (tid == 0) {
-            t.status[g] = (t.status[g] & ~CZ_ST_POOL_EXHAUSTED) | CZ_ST_BAD_ADVANCE;
-            init_root(v, 0);
-            t.root_node[g] = 0; t.n_nodes[g] = 1;
-        }
-        ec_clear_tree(t, g, tid, 256);
-        return;
-    }
-    // ---- pass 1: the kept-node bitmap.  Nothing below `found` can be in its subtree.
-    const int w0 = found >> 6, W = (n + 63) >> 6;
-    for (int w = tid; w < w0; w += 256) bits[w] = 0ull;
-    __syncthreads();
-    for (int base = w0 << 6; base < n; base += 256) {
-        const int i = base + tid;
-        int st, p = -1;   // st: 0 unknown, 1 kept, 2 dropped
-        if (i >= n || i < found) st = 2;
-        else if (i == found) st = 1;
-        else {
-            p = v.parent[i];
-            if (p < found) st = 2;
-            else if (p == found) st = 1;
-            else if (p < base) st = mark_tst(bits, p) ? 1 : 2;
-            else st = 0;
-        }
-        s_flag[tid] = st;
-        __syncthreads();
-        for (;;) {
-            int open = 0;
-            if (st == 0) { const int ps = s_flag[p - base]; if (ps) st = ps; else open = 1; }
-            open = __syncthreads_or(open);
-            s_flag[tid] = st;
-            __syncthreads();
-            if (!open) break;
-        }
-        const unsigned long long m = __ballot(st == 1);
-        if (lane == 0 && (base >> 6) + wave < W) bits[(base >> 6) + wave] = m;
-        __syncthreads();
-    }
-    // ---- rank: exclusive prefix count over the bitmap words (W <= cap / 64)
-    {
-        const int per = (W + 255) / 256;
-        const int lo = tid * per, hi = min(W, lo + per);
-        int c = 0;
-        for (int w = lo; w < hi; ++w) c += __popcll(bits[w]);
-        s_flag[tid] = c;
-        __syncthreads();
-        if (tid == 0) {
-            int acc = 0;
-            for (int k = 0; k < 256; ++k) { const int x = s_flag[k]; s_flag[k] = acc; acc += x; }
-            s_total = acc;
-        }
-        __syncthreads();
-        int acc = s_flag[tid];
-        for (int w = lo; w < hi; ++w) { rank[w] = (uint32_t)acc; acc += __popcll(bits[w]); }
-        __syncthreads();
-    }
-    // ---- evaluation cache: entries of kept nodes follow them to their new indices, the others are forgotten
-    if (t.ec_key) {
-        unsigned long long *ek = t.ec_key + (size_t)g * CZ_EC_ENTRIES;
-        int32_t *en = t.ec_node + (size_t)g * CZ_EC_ENTRIES;
-        for (int e = tid; e < CZ_EC_ENTRIES; e += 256) {
-            if (ek[e] == 0ull) continue;
-            const int nd = en[e];
-            if (nd >= found && nd < n && mark_tst(bits, nd)) en[e] = (int)mark_rank_of(bits, rank, nd);
-            else ek[e] = 0ull;
-        }
-    }
-    // ---- pass 2: move the kept nodes down, ascending (new index <= old index)
-    for (int base = w0 << 6; base < n; base += 256) {
-        const int i = base + tid;
-        const bool keep = i < n && mark_tst(bits, i);
-        float nP = 0.f, nW = 0.f, nQ = 0.f;
-        int nN = 0, np = -1, ncb = -1;
-        uint16_t ncc = 0, nmv = 0, nsd = 0;
-        if (keep) {
-            nP = v.P[i]; nW = v.W[i]; nQ = v.Q[i]; nN = v.N[i]; np = v.parent[i]; ncb = v.child_begin[i];
-            ncc = v.child_count[i]; nmv = v.move[i]; nsd = v.sd[i];
-        }
-        __syncthreads();   // the whole chunk is in registers before any of its slots is overwritten
-        if (keep) {
-            const int o = mark_rank_of(bits, rank, i);
-            v.P[o] = nP; v.W[o] = nW; v.Q[o] = nQ; v.N[o] = nN;
-            v.parent[o] = i == found ? -1 : mark_rank_of(bits, rank, np);
-            v.child_begin[o] = ncb >= 0 ? mark_rank_of(bits, rank, ncb) : -1;
-            v.child_count[o] = ncc; v.move[o] = nmv; v.sd[o] = nsd;
-        }
-    }
-    if (tid == 0) {
-        t.root_node[g] = 0; t.n_nodes[g] = s_total;
-        t.status[g] &= ~CZ_ST_POOL_EXHAUSTED;
-    }
-}
-
-// The same compaction with the bitmap and its ranks in LDS, 1024 nodes per chunk (16 waves) and the next chunk's loads in
-// flight while the current one is resolved: a tree of a 1600-playout search has ~62 k nodes — 245 strictly sequential
-// 256-node chunks of the kernel above, each paying two or three dependent global round trips (parent, bitmap word, rank),
-// ~0.6 ms for the handful of trees that move at one check of an asynchronous loop, i.e. ~3 % of the run.  Here a chunk costs
-// LDS round trips only (61 chunks, parent / node fields prefetched one chunk ahead).  Used when the tree's bitmap fits the
-// workgroup's dynamic LDS (12 bytes per 64 nodes); the global-memory variant above remains for larger pools.
-#define CZ_ADV_T 1024
-__device__ __forceinline__ bool lmark_tst(const unsigned long long *bits, int i) { return (bits[i >> 6] >> (i & 63)) & 1ull; }
-__device__ __forceinline__ int lmark_rank_of(const unsigned long long *bits, const uint32_t *rank, int i) {
     const unsigned long long below = (i & 63) ? (bits[i >> 6] & ((1ull << (i & 63)) - 1ull)) : 0ull;
     return (int)rank[i >> 6] + __popcll(below);
 }
@@ -1181,16 +1048,18 @@ __global__ __launch_bounds__(256) void k_advance_list(CzTrees t, int G, const ui
     if (g < G && played[g] < CZ_NLABELS) t.adv_list[atomicAdd(t.adv_cnt, 1)] = g;
 }
 
-__device__ __forceinline__ void advance_tree_lds(const CzTrees &t, const CzTables &tab, int g, unsigned long long *adv_lds,
-                                                 const uint16_t *__restrict__ played) {
+// LDS_BITS: the bitmap and its ranks in adv_lds (the workgroup's dynamic LDS), else in t.mark_bits / t.mark_rank
+template <bool LDS_BITS>
+__device__ __forceinline__ void advance_tree(const CzTrees &t, const CzTables &tab, int g, unsigned long long *adv_lds,
+                                             const uint16_t *__restrict__ played) {
     __shared__ int s_found, s_total;
     __shared__ int s_flag[CZ_ADV_T];
     __shared__ int s_wave[CZ_ADV_T / 64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint16_t l = played[g];
     const TreeView v = view_of(t, g);
-    unsigned long long *bits = adv_lds;                          // [t.words]
-    uint32_t *rank = (uint32_t *)(adv_lds + t.words);            // [t.words]
+    unsigned long long *bits = LDS_BITS ? adv_lds : t.mark_bits + (size_t)g * t.words;                 // [t.words]
+    uint32_t *rank = LDS_BITS ? (uint32_t *)(adv_lds + t.words) : t.mark_rank + (size_t)g * t.words;   // [t.words]
     const int root = t.root_node[g];
     const int n = t.n_nodes[g];
     const int cb = v.child_begin[root];
@@ -1235,7 +1104,7 @@ __device__ __forceinline__ void advance_tree_lds(const CzTrees &t, const CzTable
         else if (i == found) st = 1;
         else if (p < found) st = 2;
         else if (p == found) st = 1;
-        else if (p < base) st = lmark_tst(bits, p) ? 1 : 2;
+        else if (p < base) st = mark_tst(bits, p) ? 1 : 2;
         else st = 0;
         s_flag[tid] = st;
         __syncthreads();
@@ -1281,7 +1150,7 @@ __device__ __forceinline__ void advance_tree_lds(const CzTrees &t, const CzTable
         for (int e = tid; e < CZ_EC_ENTRIES; e += CZ_ADV_T) {
             if (ek[e] == 0ull) continue;
             const int nd = en[e];
-            if (nd >= found && nd < n && lmark_tst(bits, nd)) en[e] = lmark_rank_of(bits, rank, nd);
+            if (nd >= found && nd < n && mark_tst(bits, nd)) en[e] = mark_rank_of(bits, rank, nd);
             else ek[e] = 0ull;
         }
     }
@@ -1290,7 +1159,7 @@ __device__ __forceinline__ void advance_tree_lds(const CzTrees &t, const CzTable
     float nP = 0.f, nW = 0.f, nQ = 0.f;
     int nN = 0, np = -1, ncb = -1;
     uint16_t ncc = 0, nmv = 0, nsd = 0;
-    bool nkeep = first + tid < n && lmark_tst(bits, first + tid);
+    bool nkeep = first + tid < n && mark_tst(bits, first + tid);
     if (nkeep) {
         const int i = first + tid;
         nP = v.P[i]; nW = v.W[i]; nQ = v.Q[i]; nN = v.N[i]; np = v.parent[i]; ncb = v.child_begin[i]; ncc = v.child_count[i]; nmv = v.move[i]; nsd = v.sd[i];
@@ -1302,16 +1171,16 @@ __device__ __forceinline__ void advance_tree_lds(const CzTrees &t, const CzTable
         const int cN = nN, cp = np, ccb = ncb;
         const uint16_t ccc = ncc, cmv = nmv, csd = nsd;
         const int in = i + CZ_ADV_T;
-        nkeep = in < n && lmark_tst(bits, in);
+        nkeep = in < n && mark_tst(bits, in);
         if (nkeep) {
             nP = v.P[in]; nW = v.W[in]; nQ = v.Q[in]; nN = v.N[in]; np = v.parent[in]; ncb = v.child_begin[in]; ncc = v.child_count[in]; nmv = v.move[in]; nsd = v.sd[in];
         }
         __syncthreads();   // every thread holds its node of this chunk (loaded one iteration ago) before any slot of it is overwritten
         if (keep) {
-            const int o = lmark_rank_of(bits, rank, i);
+            const int o = mark_rank_of(bits, rank, i);
             v.P[o] = cP; v.W[o] = cW; v.Q[o] = cQ; v.N[o] = cN;
-            v.parent[o] = i == found ? -1 : lmark_rank_of(bits, rank, cp);
-            v.child_begin[o] = ccb >= 0 ? lmark_rank_of(bits, rank, ccb) : -1;
+            v.parent[o] = i == found ? -1 : mark_rank_of(bits, rank, cp);
+            v.child_begin[o] = ccb >= 0 ? mark_rank_of(bits, rank, ccb) : -1;
             v.child_count[o] = ccc; v.move[o] = cmv; v.sd[o] = csd;
         }
     }
@@ -1325,8 +1194,16 @@ __global__ __launch_bounds__(CZ_ADV_T) void k_advance_lds(CzTrees t, CzTables ta
     extern __shared__ unsigned long long adv_lds[];
     const int cnt = *t.adv_cnt;
     for (int e = blockIdx.x; e < cnt; e += gridDim.x) {
-        advance_tree_lds(t, tab, t.adv_list[e], adv_lds, played);
+        advance_tree<true>(t, tab, t.adv_list[e], adv_lds, played);
         __syncthreads();   // the LDS bitmap and flags are reused by the next tree
+    }
+}
+
+__global__ __launch_bounds__(CZ_ADV_T) void k_advance_global(CzTrees t, CzTables tab, const uint16_t *__restrict__ played) {
+    const int cnt = *t.adv_cnt;
+    for (int e = blockIdx.x; e < cnt; e += gridDim.x) {
+        advance_tree<false>(t, tab, t.adv_list[e], nullptr, played);
+        __syncthreads();   // the flags are reused by the next tree
     }
 }
 
@@ -1434,17 +1311,16 @@ int czk_search_advance(cz_ctx *c, const uint16_t *played) {
     // bitmap + ranks of one tree in LDS: 12 bytes per 64 nodes (38 KB for the bench's 205 056-node pools)
     const size_t lds = (size_t)c->t.words * 12;
     const size_t lds_max = 150 * 1024;   // 160 KB per CU minus the kernel's static LDS; the attribute is per function, so always the maximum
-    if (lds <= lds_max && !c->adv_force_global) {
-        if (!c->adv_attr_set) {
-            CZ_HIP(hipFuncSetAttribute((const void *)k_advance_lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
-            c->adv_attr_set = true;
-        }
-        CZ_HIP(hipMemsetAsync(c->t.adv_cnt, 0, sizeof(int32_t), c->stream));
-        hipLaunchKernelGGL(k_advance_list, dim3((c->G + 255) / 256), dim3(256), 0, c->stream, c->t, c->G, played);
-        hipLaunchKernelGGL(k_advance_lds, dim3(c->G < 512 ? c->G : 512), dim3(CZ_ADV_T), lds, c->stream, c->t, c->tab, played);
-    } else {
-        hipLaunchKernelGGL(k_advance_global, dim3(c->G), dim3(256), 0, c->stream, c->t, c->tab, c->G, played);
+    const bool in_lds = lds <= lds_max && !c->adv_force_global;
+    if (in_lds && !c->adv_attr_set) {
+        CZ_HIP(hipFuncSetAttribute((const void *)k_advance_lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
+        c->adv_attr_set = true;
     }
+    CZ_HIP(hipMemsetAsync(c->t.adv_cnt, 0, sizeof(int32_t), c->stream));
+    hipLaunchKernelGGL(k_advance_list, dim3((c->G + 255) / 256), dim3(256), 0, c->stream, c->t, c->G, played);
+    const dim3 grid(c->G < 512 ? c->G : 512);
+    if (in_lds) hipLaunchKernelGGL(k_advance_lds, grid, dim3(CZ_ADV_T), lds, c->stream, c->t, c->tab, played);
+    else hipLaunchKernelGGL(k_advance_global, grid, dim3(CZ_ADV_T), 0, c->stream, c->t, c->tab, played);
     CZ_HIP(hipGetLastError());
     return CZ_OK;
 }

@@ -245,8 +245,8 @@ int cz_search_debug_eval_cache_key_bits(cz_ctx *, int bits);
 int cz_search_set_xcache(cz_ctx *, int log2_entries);
 int cz_search_xcache_stats(cz_ctx *, unsigned long long *stats4);
 int cz_search_xcache_stats5(cz_ctx *, unsigned long long *stats5);
-/* tests: cz_search_advance keeps the kept-node bitmap of a tree in LDS when it fits (12 bytes per 64 nodes) and in global memory
- * otherwise; on != 0 forces the global-memory kernel so that it is exercised at test sizes. */
+/* tests: cz_search_advance runs one compaction with the kept-node bitmap of a tree in LDS when it fits (12 bytes per 64 nodes)
+ * and in global memory otherwise; on != 0 forces the global-memory home so that it is exercised at test sizes. */
 int cz_search_debug_advance_in_global_memory(cz_ctx *, int on);
 /* tests: read the caches back (synchronise the stream).
  *   cz_search_debug_xcache_dump: the whole cross-tree block, n * 1088 + 64 bytes for n entries, in the table's own layout:

@@ -62,24 +62,28 @@ def test_search_matches_reference_at_depth(mcts_deep_golden):
     assert max(r["max_level"] for res in results for r in res) >= 60
 
 
-@pytest.mark.parametrize("mode,advance", [("pos", "lds"), ("signed", "lds"), ("pos", "global")])
+@pytest.mark.parametrize("mode,advance", [("pos", "lds"), ("signed", "lds"), ("pos", "global"), ("pos", "large_pool")])
 def test_search_vs_oracle_batch(rules_golden, mode, advance):
     """256 trees from corpus positions, 3 plies x 48 playouts, device-resident loop; compared with the
     oracle: needs_eval + planes every step, root stats and whole-tree dumps after each ply.  advance: the in-place
-    compaction of cz_search_advance with the bitmap in LDS (default) or in global memory (pools too large for LDS)."""
+    compaction of cz_search_advance with the bitmap in LDS (default) or in global memory (forced by the debug switch, or
+    large_pool: 2^20 nodes per tree, whose 196 KB bitmap exceeds LDS; every 8th tree keeps the oracle's pools modest)."""
     from oracle import oracle as O
     g = rules_golden
     ok = [(g["boards"][i] == 1).any() and (g["boards"][i] == 8).any() and g["counts"][i] > 0 for i in range(len(g["boards"]))]
     idx = np.nonzero(ok)[0][::11][:256]
+    cap = 20000
+    if advance == "large_pool":
+        idx, cap = idx[::8], 1 << 20
     G = len(idx)
     boards, side = g["boards"][idx], g["side"][idx]
     rr = (np.arange(G) * 7 % 61).astype(np.int32)
     rr[::5] = 57
-    hip = _HipEngine(G, 20000)
+    hip = _HipEngine(G, cap)
     if advance == "global":
         from cchess_zero_amd._lib import check, lib
         check(lib().cz_search_debug_advance_in_global_memory(hip.e.ctx.h, 1), "cz_search_debug_advance_in_global_memory")
-    orc = O.Search(G, 20000)
+    orc = O.Search(G, cap)
     hip.reset(boards, side, rr)
     orc.reset(boards, side, rr)
     fwd = fakenet.make_forward(mode, 99)
