@@ -98,6 +98,58 @@ __device__ __forceinline__ Cand better(Cand a, Cand b) {
     if (b.s > a.s || (b.s == a.s && b.i < a.i)) return b;
     return a;
 }
+// select_new / get_Q_plus_U_new, main.py:108-116,158-159: a child's score Q + 5P * sqrt(parent N) / (1 + N), in float64
+// (`sq` is the square root of the parent's N)
+__device__ __forceinline__ double puct(float P, int N, float Q, double sq) {
+    const float cp = 5.0f * P;
+    const double u = (double)cp * sq / (double)(1 + N);
+    return (double)Q + u;
+}
+// main.py:409-414: the value a king capture backs up from the child (`side`: the player to move there)
+__device__ __forceinline__ float terminal_value(bool Kmiss, bool kmiss, int side) {
+    float value = 0.f;
+    if (Kmiss) value = side ? 1.0f : -1.0f;
+    if (kmiss) value = side ? -1.0f : 1.0f;
+    return value * -1.0f;
+}
+
+// back_up_value on one node of the path, main.py:189-194,426-435.  Width 1: the virtual loss lives only in the arithmetic,
+// (W + -3) + 3 reproduces its float32 rounding.
+__device__ __forceinline__ void backup_level(const TreeView &v, int n, float x) {
+    float w = v.W[n];
+    w = w + -3.0f;
+    w = w + 3.0f;
+    const int cnt = v.N[n] + 1;
+    w = w + x;
+    v.N[n] = cnt; v.W[n] = w; v.Q[n] = w / (float)cnt;
+}
+// Width k: the virtual loss is in the tree (N += 3, W += -3, main.py:403-404).  unwind_path takes it off and backs x up on
+// every node from `from` to below the root (main.py:426-427,190); take_back_vl only takes it off (an abandoned descent).
+__device__ __forceinline__ void unwind_path(const TreeView &v, int from, int root, float x) {
+    for (int n = from; n != root; n = v.parent[n]) {
+        const int cnt = v.N[n] - 3 + 1;
+        float w = v.W[n] + 3.0f;
+        w = w + x;
+        v.N[n] = cnt; v.W[n] = w; v.Q[n] = w / (float)cnt;
+        x = x * -1.0f;
+    }
+}
+__device__ __forceinline__ void take_back_vl(const TreeView &v, int from, int root) {
+    for (int n = from; n != root; n = v.parent[n]) { v.N[n] -= 3; v.W[n] = v.W[n] + 3.0f; }
+}
+
+// the leaf's moves for its expansion (row `row` of pend_moves) and its planes for the net (generate_inputs, main.py:362 /
+// :477); without a leaf to evaluate the planes are zeroed if `zero`
+template <typename T>
+__device__ __forceinline__ void write_leaf(bool eval, const CzTrees &t, size_t row, const uint16_t *mv, int nmoves, const uint8_t *b,
+                                           int side, bool zero, T *pl, int C, T one, int lane) {
+    if (eval) {
+        for (int i = lane; i < nmoves; i += 64) t.pend_moves[row * CZD_MAXMOVES + i] = mv[i];
+        if (pl) czd_wave_encode_planes<T>(b, side, 1, pl, C, one, lane);
+    } else if (zero && pl) {
+        for (int e = lane; e < 90 * C; e += 64) pl[e] = (T)0;
+    }
+}
 
 // Zobrist key of the position in LDS: cz_hash without its top bit, which marks "being written" in the cross-tree table
 // (CZ_XC_BUSY); 0 is reserved for "empty" in the evaluation cache (a position with key 0 is filed under 1)
@@ -225,9 +277,7 @@ __device__ __forceinline__ void select_body(const CzTrees &t, const CzTables &ta
                     for (int r = 0; r < 2; ++r) {
                         const int i = lane + 64 * r;
                         if (i < cc) {
-                            const float cp = 5.0f * cP[r];
-                            const double u = (double)cp * sq / (double)(1 + cN[r]);
-                            double s = (double)cQ[r] + u;
+                            double s = puct(cP[r], cN[r], cQ[r], sq);
                             if (s != s) { if (i == 0) first_nan = true; s = -INFINITY; }
                             Cand c; c.s = s; c.i = i;
                             best = better(best, c);
@@ -260,11 +310,7 @@ __device__ __forceinline__ void select_body(const CzTrees &t, const CzTables &ta
                     if (cap == 1) Kmiss = true;
                     if (cap == 8) kmiss = true;
                     if (Kmiss || kmiss) {
-                        // main.py:409-414; `side` is the player to move at the child
-                        float value = 0.f;
-                        if (Kmiss) value = side ? 1.0f : -1.0f;
-                        if (kmiss) value = side ? -1.0f : 1.0f;
-                        kind = 2; leaf = c; pend = value * -1.0f; break;
+                        kind = 2; leaf = c; pend = terminal_value(Kmiss, kmiss, side); break;
                     } else if (rr >= 60) {      // main.py:415-416
                         kind = 2; leaf = c; pend = 0.f; break;
                     }
@@ -347,18 +393,8 @@ __device__ __forceinline__ void select_body(const CzTrees &t, const CzTables &ta
                         full = true;   // this simulation is still backed up; the tree then stops, as it does after k_expand_backup
                     }
                 } else if (!(kind == 2 && may)) break;
-                // back_up_value along the path (main.py:189-194,426-435), exactly as k_expand_backup does it: lane d owns
-                // the node of level d; (W + -3) + 3 reproduces the float32 rounding of the virtual loss
-                if (lane < depth) {
-                    const int n = path_s[lane];
-                    const float x = ((depth - 1 - lane) & 1) ? pend * -1.0f : pend;
-                    float w = v.W[n];
-                    w = w + -3.0f;
-                    w = w + 3.0f;
-                    const int cnt = v.N[n] + 1;
-                    w = w + x;
-                    v.N[n] = cnt; v.W[n] = w; v.Q[n] = w / (float)cnt;
-                }
+                // back_up_value along the path, exactly as k_expand_backup does it: lane d owns the node of level d
+                if (lane < depth) backup_level(v, path_s[lane], ((depth - 1 - lane) & 1) ? pend * -1.0f : pend);
                 ++done_here;
                 if (CACHE && kind == 1) --cache_left; else --extra_left;
                 if (full) { kind = 0; break; }
@@ -387,12 +423,7 @@ __device__ __forceinline__ void select_body(const CzTrees &t, const CzTables &ta
             if (g == 0) t.evcnt[parity ^ 1] = 0;   // nobody touches the other counter until the next step's select
         }
     }
-    if (kind == 1 || kind == 3) {
-        for (int i = lane; i < nmoves; i += 64) t.pend_moves[(size_t)g * CZD_MAXMOVES + i] = mv[i];
-        if (pl) czd_wave_encode_planes<T>(b, side, 1, pl, C, one, lane);  // generate_inputs, main.py:362 / :477
-    } else if (pl && !COMPACT) {
-        for (int e = lane; e < 90 * C; e += 64) pl[e] = (T)0;
-    }
+    write_leaf<T>(kind == 1 || kind == 3, t, (size_t)g, mv, nmoves, b, side, !COMPACT, pl, C, one, lane);
     if (CACHE && (kind == 1 || kind == 3)) {
         if (kind == 3) {
             key = wave_position_key(b, side, tab.zob, lane) & t.ec_key_mask;
@@ -436,7 +467,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_num_sgpr(80))) void k_sel
     select_body<T, false, true>(t, tab, G, mode, active, planes, C, one, needs_eval, parity, sim_target, extra);
 }
 // ... and with the cross-tree level behind it (cz_search_set_xcache).  Their own instantiations: the extra probe costs registers
-// (65 VGPRs: 7 waves per SIMD) that the plain cache kernels (59) do not pay.
+// (64 VGPRs, the whole budget) that the plain cache kernels (59) do not pay.
 template <typename T>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_num_sgpr(80))) void k_select_xcache(CzTrees t, CzTables tab, int G, int mode,
                                                       const uint8_t *__restrict__ active, T *__restrict__ planes, int C,
@@ -460,6 +491,22 @@ __global__ __launch_bounds__(64) void k_select_compact_cache(CzTrees t, CzTables
 template <typename T> __device__ __forceinline__ float to_f32(T x);
 template <> __device__ __forceinline__ float to_f32<float>(float x) { return x; }
 template <> __device__ __forceinline__ float to_f32<uint16_t>(uint16_t x) { return czd_bf16_bits_to_f32(x); }
+
+// the raw priors of a leaf's n moves (row `row` of pend_moves) from its logits row lg [CZ_NLABELS]: flip_policy's unflip for
+// black, main.py:371-372,1153-1155; lane l keeps the labels of moves l and l + 64
+template <typename T>
+__device__ __forceinline__ void gather_logit_priors(const T *lg, const CzTrees &t, size_t row, int n, int side, const CzTables &tab,
+                                                    float *pr, uint16_t lab[2], int lane) {
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        const int i = lane + 64 * r;
+        lab[r] = 0;
+        if (i < n) {
+            lab[r] = t.pend_moves[row * CZD_MAXMOVES + i];
+            pr[i] = to_f32<T>(lg[side ? tab.unflip[lab[r]] : lab[r]]);
+        }
+    }
+}
 
 // FC = false: the raw prior of a move is read from a full logits row [2086] of type T.
 // FC = true : `logits` is instead the head-conv output z [G][90][3] f32 and the policy FC (policy_value_network.py:62-63,
@@ -582,16 +629,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_num_sgpr(80), amdgpu_num_
                     }
                 }
             } else {
-                const T *lg = logits + (size_t)g * CZ_NLABELS;
-#pragma unroll
-                for (int r = 0; r < 2; ++r) {
-                    const int i = lane + 64 * r;
-                    lab[r] = 0;
-                    if (i < n) {
-                        lab[r] = t.pend_moves[(size_t)g * CZD_MAXMOVES + i];
-                        pr[i] = to_f32<T>(lg[sd ? tab.unflip[lab[r]] : lab[r]]);
-                    }
-                }
+                gather_logit_priors<T>(logits + (size_t)g * CZ_NLABELS, t, (size_t)g, n, sd, tab, pr, lab, lane);
             }
             __syncthreads();
             if (lane == 0) {
@@ -723,28 +761,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_num_sgpr(80), amdgpu_num_
     // the whole path instead of one per level along the parent pointers.
     const int depth = t.pend_depth[g];
     if (depth <= CZ_PATH_MAX) {
-        if (lane < depth) {
-            const int n = t.pend_path[(size_t)g * CZ_PATH_MAX + lane];
-            const float x = ((depth - 1 - lane) & 1) ? val * -1.0f : val;
-            float w = v.W[n];
-            w = w + -3.0f;
-            w = w + 3.0f;
-            const int cnt = v.N[n] + 1;
-            w = w + x;
-            v.N[n] = cnt; v.W[n] = w; v.Q[n] = w / (float)cnt;
-        }
+        if (lane < depth) backup_level(v, t.pend_path[(size_t)g * CZ_PATH_MAX + lane], ((depth - 1 - lane) & 1) ? val * -1.0f : val);
         if (lane == 0) { t.sims[g] += 1; t.pend_kind[g] = 0; }
     } else if (lane == 0) {
         const int root = t.root_node[g];
         int n = leaf;
         float x = val;
         while (n != root) {
-            float w = v.W[n];
-            w = w + -3.0f;
-            w = w + 3.0f;
-            const int cnt = v.N[n] + 1;
-            w = w + x;
-            v.N[n] = cnt; v.W[n] = w; v.Q[n] = w / (float)cnt;
+            backup_level(v, n, x);
             x = x * -1.0f;
             n = v.parent[n];
         }
@@ -762,7 +786,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_num_sgpr(80), amdgpu_num_
 // `while node in now_expanding: await asyncio.sleep`, main.py:354-355) is abandoned: its virtual loss is taken back
 // and the tree issues no further descents in this step.  The net is then evaluated for all pending leaves at once
 // and k_expand_backup_k expands them in descent order and unwinds each path (N -= 3, W += 3, back_up_value).
-// With K = 1 this is arithmetically identical to k_select / k_expand_backup (tested).  The asyncio interleaving of
+// With K = 1 this is arithmetically identical to k_select / k_expand_backup (tested); the score, the terminal value, the prior
+// gather and the leaf's moves and planes are the same helpers.  The asyncio interleaving of
 // the reference for K > 1 depends on wall-clock sleeps, so K > 1 is checked against the C oracle's restatement of
 // THIS schedule and through invariants, not against reference golden trees.
 template <typename T>
@@ -817,8 +842,7 @@ __global__ __launch_bounds__(64) void k_select_k(CzTrees t, CzTables tab, int G,
                     if (cb == -2) abandon = true;                                   // expansion pending in this batch
                     else if (cc == 0) { if (lane == 0) t.status[g] |= CZ_ST_NO_MOVES; abandon = true; }
                     if (abandon) {
-                        if (lane == 0)   // take the virtual loss of this descent back (main.py:426-427 without a backup)
-                            for (int n = node; n != root; n = v.parent[n]) { v.N[n] -= 3; v.W[n] = v.W[n] + 3.0f; }
+                        if (lane == 0) take_back_vl(v, node, root);   // main.py:426-427 without a backup
                         stop = true;
                         break;
                     }
@@ -829,9 +853,7 @@ __global__ __launch_bounds__(64) void k_select_k(CzTrees t, CzTables tab, int G,
                     for (int r = 0; r < 2; ++r) {
                         const int i = lane + 64 * r;
                         if (i < cc) {
-                            const float cp = 5.0f * v.P[cb + i];
-                            const double u = (double)cp * sq / (double)(1 + v.N[cb + i]);
-                            double s = (double)v.Q[cb + i] + u;   // Q is not recomputed under virtual loss (quirk Q6)
+                            double s = puct(v.P[cb + i], v.N[cb + i], v.Q[cb + i], sq);   // Q is not recomputed under virtual loss (quirk Q6)
                             if (s != s) { if (i == 0) first_nan = true; s = -INFINITY; }
                             Cand c; c.s = s; c.i = i;
                             best = better(best, c);
@@ -861,23 +883,8 @@ __global__ __launch_bounds__(64) void k_select_k(CzTrees t, CzTables tab, int G,
                     if (cap == 1) Kmiss = true;
                     if (cap == 8) kmiss = true;
                     const bool term = Kmiss || kmiss;
-                    if (term || rr >= 60) {
-                        float value = 0.f;
-                        if (term) {
-                            if (Kmiss) value = side ? 1.0f : -1.0f;
-                            if (kmiss) value = side ? -1.0f : 1.0f;
-                            value = value * -1.0f;
-                        }
-                        if (lane == 0) {   // unwind immediately: main.py:426-435
-                            float x = value;
-                            for (int n = c; n != root; n = v.parent[n]) {
-                                const int cnt = v.N[n] - 3 + 1;
-                                float w = v.W[n] + 3.0f;
-                                w = w + x;
-                                v.N[n] = cnt; v.W[n] = w; v.Q[n] = w / (float)cnt;
-                                x = x * -1.0f;
-                            }
-                        }
+                    if (term || rr >= 60) {   // unwind immediately: main.py:409-435
+                        if (lane == 0) unwind_path(v, c, root, term ? terminal_value(Kmiss, kmiss, side) : 0.f);
                         __threadfence_block();
                         __syncthreads();
                         ++done_now;
@@ -895,21 +902,13 @@ __global__ __launch_bounds__(64) void k_select_k(CzTrees t, CzTables tab, int G,
             if (nmoves < 0) {   // > 128 moves / unlabeled move: report, give the node and the virtual loss back
                 if (lane == 0) {
                     t.status[g] |= CZ_ST_MOVE_OVERFLOW;
-                    if (kind == 1) {
-                        v.child_begin[leaf] = -1;
-                        for (int n = leaf; n != root; n = v.parent[n]) { v.N[n] -= 3; v.W[n] = v.W[n] + 3.0f; }
-                    }
+                    if (kind == 1) { v.child_begin[leaf] = -1; take_back_vl(v, leaf, root); }
                 }
                 if (kind == 1) --issued;
                 kind = 0; nmoves = 0; stop = true;
             }
         }
-        if (kind == 1 || kind == 3) {
-            for (int i = lane; i < nmoves; i += 64) t.pend_moves[slot * CZD_MAXMOVES + i] = mv[i];
-            if (pl) czd_wave_encode_planes<T>(b, side, 1, pl, C, one, lane);
-        } else if (pl) {
-            for (int e = lane; e < 90 * C; e += 64) pl[e] = (T)0;
-        }
+        write_leaf<T>(kind == 1 || kind == 3, t, slot, mv, nmoves, b, side, true, pl, C, one, lane);
         if (lane == 0) {
             t.pk_kind[slot] = kind; t.pk_leaf[slot] = leaf; t.pk_value[slot] = 0.f;
             t.pk_side[slot] = (uint8_t)side; t.pk_nmoves[slot] = (uint16_t)nmoves;
@@ -942,17 +941,8 @@ __global__ __launch_bounds__(64) void k_expand_backup_k(CzTrees t, CzTables tab,
         const bool fits = begin + n <= t.cap;
         __syncthreads();
         if (fits) {
-            const T *lg = logits + slot * CZ_NLABELS;
             uint16_t lab[2];
-#pragma unroll
-            for (int r = 0; r < 2; ++r) {
-                const int i = lane + 64 * r;
-                lab[r] = 0;
-                if (i < n) {
-                    lab[r] = t.pend_moves[slot * CZD_MAXMOVES + i];
-                    pr[i] = to_f32<T>(lg[sd ? tab.unflip[lab[r]] : lab[r]]);
-                }
-            }
+            gather_logit_priors<T>(logits + slot * CZ_NLABELS, t, slot, n, sd, tab, pr, lab, lane);
             __syncthreads();
             if (lane == 0) {
                 float tot = (float)1e-8;
@@ -977,14 +967,7 @@ __global__ __launch_bounds__(64) void k_expand_backup_k(CzTrees t, CzTables tab,
             v.child_begin[leaf] = -1;   // no longer pending
         }
         if (kind == 1 && lane == 0) {
-            float x = to_f32<T>(value[slot]) * -1.0f;
-            for (int m = leaf; m != root; m = v.parent[m]) {
-                const int cnt = v.N[m] - 3 + 1;   // virtual loss off, visit on (main.py:426-427,190)
-                float w = v.W[m] + 3.0f;
-                w = w + x;
-                v.N[m] = cnt; v.W[m] = w; v.Q[m] = w / (float)cnt;
-                x = x * -1.0f;
-            }
+            unwind_path(v, leaf, root, to_f32<T>(value[slot]) * -1.0f);
             t.sims[g] += 1;
         }
         if (lane == 0) t.pk_kind[slot] = 0;
@@ -1249,34 +1232,33 @@ int czk_search_reset(cz_ctx *c, const uint8_t *boards, const uint8_t *side, cons
     return CZ_OK;
 }
 
+// The element type of planes and logits: CZ_F32 as float, the 16-bit formats as their bits.  f(one) is called with 1.0 in
+// that format (the planes' "piece present" value).
+template <typename F> static void with_dtype(int dtype, F f) {
+    if (dtype == CZ_F32) f(1.0f);
+    else f((uint16_t)(dtype == CZ_F16 ? 0x3C00 : 0x3F80));
+}
+
 int czk_search_select(cz_ctx *c, int mode, const uint8_t *active, void *planes, int dtype, int C, uint8_t *needs_eval, bool compact) {
-    const uint16_t one16 = (uint16_t)(dtype == CZ_F16 ? 0x3C00 : 0x3F80);
-    const int par = c->step_parity;
-#define CZ_LAUNCH_SELECT(KERNEL, TT, ONE)                                                                               \
-    hipLaunchKernelGGL((KERNEL<TT>), dim3(c->G), dim3(64), 0, c->stream, c->t, c->tab, c->G, mode, active, (TT *)planes, C, ONE, needs_eval, par, c->sim_target, c->terminal_extra)
     const bool cache = c->t.ec_key != nullptr, xc = cache && c->t.xc_base != nullptr;
-    if (xc) {
-        if (dtype == CZ_F32) { if (compact) CZ_LAUNCH_SELECT(k_select_compact_xcache, float, 1.0f); else CZ_LAUNCH_SELECT(k_select_xcache, float, 1.0f); }
-        else { if (compact) CZ_LAUNCH_SELECT(k_select_compact_xcache, uint16_t, one16); else CZ_LAUNCH_SELECT(k_select_xcache, uint16_t, one16); }
-    } else if (dtype == CZ_F32) {
-        if (cache) { if (compact) CZ_LAUNCH_SELECT(k_select_compact_cache, float, 1.0f); else CZ_LAUNCH_SELECT(k_select_cache, float, 1.0f); }
-        else { if (compact) CZ_LAUNCH_SELECT(k_select_compact, float, 1.0f); else CZ_LAUNCH_SELECT(k_select, float, 1.0f); }
-    } else {
-        if (cache) { if (compact) CZ_LAUNCH_SELECT(k_select_compact_cache, uint16_t, one16); else CZ_LAUNCH_SELECT(k_select_cache, uint16_t, one16); }
-        else { if (compact) CZ_LAUNCH_SELECT(k_select_compact, uint16_t, one16); else CZ_LAUNCH_SELECT(k_select, uint16_t, one16); }
-    }
-#undef CZ_LAUNCH_SELECT
+    with_dtype(dtype, [&](auto one) {
+        using T = decltype(one);
+        void (*k)(CzTrees, CzTables, int, int, const uint8_t *, T *, int, T, uint8_t *, int, int, int) =
+            compact ? (xc ? k_select_compact_xcache<T> : cache ? k_select_compact_cache<T> : k_select_compact<T>)
+                    : (xc ? k_select_xcache<T> : cache ? k_select_cache<T> : k_select<T>);
+        hipLaunchKernelGGL(k, dim3(c->G), dim3(64), 0, c->stream, c->t, c->tab, c->G, mode, active, (T *)planes, C, one, needs_eval,
+                           c->step_parity, c->sim_target, c->terminal_extra);
+    });
     CZ_HIP(hipGetLastError());
     return CZ_OK;
 }
 
 int czk_search_expand_backup(cz_ctx *c, const void *logits, const void *value, int dtype) {
-    if (dtype == CZ_F32)
-        hipLaunchKernelGGL((k_expand_backup<float, false>), dim3(c->G), dim3(64), 0, c->stream, c->t, c->tab, c->G, (const float *)logits,
-                           (const float *)value, (const float *)nullptr, (const float *)nullptr, -1);
-    else
-        hipLaunchKernelGGL((k_expand_backup<uint16_t, false>), dim3(c->G), dim3(64), 0, c->stream, c->t, c->tab, c->G, (const uint16_t *)logits,
-                           (const uint16_t *)value, (const float *)nullptr, (const float *)nullptr, -1);
+    with_dtype(dtype, [&](auto one) {
+        using T = decltype(one);
+        hipLaunchKernelGGL((k_expand_backup<T, false>), dim3(c->G), dim3(64), 0, c->stream, c->t, c->tab, c->G, (const T *)logits,
+                           (const T *)value, (const float *)nullptr, (const float *)nullptr, -1);
+    });
     CZ_HIP(hipGetLastError());
     return CZ_OK;
 }
@@ -1334,19 +1316,19 @@ int cz_search_root_state(cz_ctx *c, uint8_t *boards, uint8_t *side, int32_t *rr)
 }
 
 int czk_search_select_k(cz_ctx *c, int mode, int K, const uint8_t *active, void *planes, int dtype, int C, uint8_t *needs_eval) {
-    if (dtype == CZ_F32)
-        hipLaunchKernelGGL(k_select_k<float>, dim3(c->G), dim3(64), 0, c->stream, c->t, c->tab, c->G, mode, K, c->sim_target, active, (float *)planes, C, 1.0f, needs_eval);
-    else
-        hipLaunchKernelGGL(k_select_k<uint16_t>, dim3(c->G), dim3(64), 0, c->stream, c->t, c->tab, c->G, mode, K, c->sim_target, active, (uint16_t *)planes, C, (uint16_t)(dtype == CZ_F16 ? 0x3C00 : 0x3F80), needs_eval);
+    with_dtype(dtype, [&](auto one) {
+        using T = decltype(one);
+        hipLaunchKernelGGL(k_select_k<T>, dim3(c->G), dim3(64), 0, c->stream, c->t, c->tab, c->G, mode, K, c->sim_target, active, (T *)planes, C, one, needs_eval);
+    });
     CZ_HIP(hipGetLastError());
     return CZ_OK;
 }
 
 int czk_search_expand_backup_k(cz_ctx *c, int K, const void *logits, const void *value, int dtype) {
-    if (dtype == CZ_F32)
-        hipLaunchKernelGGL(k_expand_backup_k<float>, dim3(c->G), dim3(64), 0, c->stream, c->t, c->tab, c->G, K, (const float *)logits, (const float *)value);
-    else
-        hipLaunchKernelGGL(k_expand_backup_k<uint16_t>, dim3(c->G), dim3(64), 0, c->stream, c->t, c->tab, c->G, K, (const uint16_t *)logits, (const uint16_t *)value);
+    with_dtype(dtype, [&](auto one) {
+        using T = decltype(one);
+        hipLaunchKernelGGL(k_expand_backup_k<T>, dim3(c->G), dim3(64), 0, c->stream, c->t, c->tab, c->G, K, (const T *)logits, (const T *)value);
+    });
     CZ_HIP(hipGetLastError());
     return CZ_OK;
 }

@@ -85,8 +85,12 @@ def test_hot_kernels_use_no_scratch(tmp_path):
     # register budgets that decide occupancy (MI355X_MICROARCH.md: <= 168 VGPRs for 3 waves per SIMD, <= 64 for 8): round 5 lost 26 %
     # of k_movegen_mask to nine registers (163 -> 172) without any test noticing
     budgets = {"k_movegen_mask": 168, "k_movegen_listILb0": 168, "k_movegen_listILb1": 256, "k_trunk_mx_c128": 256, "k_trunk_split_c128": 256, "k_tower8_c128": 256}
+    # the search step of 8192 trees is 32 waves per CU, resident in one round only at <= 64 VGPRs (8 waves per SIMD): the
+    # non-compact select kernels and k_expand_backup (mangled-name prefixes: k_select_k and the compact variants do not match)
+    budgets.update({"8k_selectI": 64, "14k_select_cacheI": 64, "15k_select_xcacheI": 64, "15k_expand_backupI": 64,
+                    "10k_select_kI": 128, "17k_expand_backup_kI": 128})
     seen = set()
-    for src in ("cz_rules.hip", "cz_conv.hip"):
+    for src in ("cz_rules.hip", "cz_conv.hip", "cz_search.hip"):
         for m in re.finditer(r"\.name:\s+(\S+)\n(?:.*\n)*?\s+\.vgpr_count:\s+(\d+)", texts[src]):
             for name, lim in budgets.items():
                 if name in m.group(1):
