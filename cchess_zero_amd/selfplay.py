@@ -178,23 +178,36 @@ class SelfPlay:
         self.overflow_intervals = 0
 
     # -- one ply of every game ------------------------------------------------------------------------
-    def step_ply(self, forward=None, forced=None):
+    def step_ply(self, forward=None, forced=None, rand=None):
         """Search, choose, record, advance, adjudicate, flush — all enqueued, nothing synchronised.
-        forced: int16/uint16 [G] labels overriding the sampled moves (0xFFFF = sample), for replaying recorded games."""
+        forced: int16/uint16 [G] labels overriding the sampled moves (0xFFFF = sample), for replaying recorded games.
+        rand: (gamma [G,128], u [G]) to sample with instead of random_inputs() (replaying a recorded random stream)."""
         eng = self.eng
         fwd = forward or self.net.forward_device
         eng.search(fwd, self.playouts, active=None if self.continuous else self._active_ptr)
-        self._transition(0, forced)
+        self._transition(0, forced, rand)
         self.plies += 1
 
-    def _transition(self, min_sims, forced=None):
-        """choose / advance / adjudicate / flush for every game (min_sims = 0) or for the games whose search has completed
-        min_sims simulations (asynchronous plies)."""
-        eng, h = self.eng, self.eng.ctx.h
+    def random_inputs(self):
+        """The random numbers of one cz_selfplay_choose, drawn from self.gen: (gamma f32 [G,128] Gamma(0.3, 1) variates —
+        normalised over a game's k children they are np.random.dirichlet(0.3 * ones(k)), main.py:1346 — or None when not
+        exploring, u f32 [G] uniforms in [0, 1) for the inverse-CDF pick of np.random.choice)."""
         gamma = None
-        if self.exploration:   # np.random.dirichlet(0.3 * ones(k)) = normalised Gamma(0.3) variates, main.py:1346
+        if self.exploration:
             gamma = torch._standard_gamma(self._alpha, generator=self.gen)
-        u = torch.rand(eng.G, generator=self.gen, device=self.dev, dtype=torch.float32)
+        u = torch.rand(self.eng.G, generator=self.gen, device=self.dev, dtype=torch.float32)
+        return gamma, u
+
+    def _transition(self, min_sims, forced=None, rand=None):
+        """choose / advance / adjudicate / flush for every game (min_sims = 0) or for the games whose search has completed
+        min_sims simulations (asynchronous plies).  rand: (gamma, u) replacing random_inputs() (gamma may be None)."""
+        eng, h = self.eng, self.eng.ctx.h
+        if rand is None:
+            gamma, u = self.random_inputs()
+        else:
+            dev_f32 = lambda t: None if t is None else torch.as_tensor(t, dtype=torch.float32).to(self.dev).contiguous()
+            gamma, u = dev_f32(rand[0]), dev_f32(rand[1])
+            assert (gamma is None or gamma.shape == (eng.G, MAXMOVES)) and u.shape == (eng.G,)
         f = None
         if forced is not None:
             f = torch.as_tensor(np.ascontiguousarray(forced).view(np.int16) if not torch.is_tensor(forced) else forced).to(self.dev).contiguous()
