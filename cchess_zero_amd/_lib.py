@@ -19,6 +19,8 @@ F32, BF16, F16 = 0, 1, 2
 # one packed self-play record (include/cchess_hip.h: CZ_REC_*)
 REC_BYTES, REC_SIDE, REC_COUNT, REC_Z, REC_FLAGS, REC_PLY, REC_LABELS, REC_VISITS = 608, 90, 91, 92, 93, 94, 96, 352
 SP_STATS = ("games", "red_wins", "black_wins", "draws", "plies", "stalled", "dropped", "sims")
+# why a match game ended (include/cchess_hip.h: CZ_MATCH_*); 0 = not finished
+MATCH_KING, MATCH_RR60, MATCH_PLY_CAP, MATCH_ABORTED = 1, 2, 3, 4
 
 _u8p, _u16p, _i32p, _f32p, _vp = C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p
 
@@ -80,6 +82,14 @@ _SIGS = {
     "cz_selfplay_adjudicate": (C.c_int, [C.c_void_p, C.c_int, _u16p, _i32p]),
     "cz_selfplay_flush": (C.c_int, [C.c_void_p, _i32p, _vp, _u8p, C.c_longlong, _vp]),
     "cz_selfplay_stats": (C.c_int, [C.c_void_p, _vp]),
+    "cz_match_create": (C.c_int, [C.c_void_p, C.c_void_p, _u8p, _u8p, _i32p, C.c_int, C.c_longlong, C.c_longlong, C.c_int,
+                                  C.POINTER(C.c_void_p)]),
+    "cz_match_destroy": (None, [C.c_void_p]),
+    "cz_match_active": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
+    "cz_match_choose": (C.c_int, [C.c_void_p, C.c_int, C.c_ulonglong, _u16p]),
+    "cz_match_adjudicate": (C.c_int, [C.c_void_p, _u16p]),
+    "cz_match_results": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_void_p)] * 6),
+    "cz_match_finished": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_ulonglong)]),
     "cz_conv3x3_c128_bf16": (C.c_int, [C.c_void_p, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int]),
     "cz_tower_c128_bf16": (C.c_int, [C.c_void_p, _vp, _vp, _vp, _vp, C.c_int, C.c_int]),
     "cz_net_trunk_bf16": (C.c_int, [C.c_void_p, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int]),

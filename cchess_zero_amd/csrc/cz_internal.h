@@ -2,6 +2,7 @@
 #pragma once
 #include <cstddef>
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <string>
@@ -230,6 +231,83 @@ __device__ __forceinline__ void ec_clear_tree(const CzTrees &t, int g, int tid, 
     if (!t.ec_key) return;
     unsigned long long *k = t.ec_key + (size_t)g * CZ_EC_ENTRIES;
     for (int i = tid; i < CZ_EC_ENTRIES; i += nthreads) k[i] = 0ull;
+}
+
+// ---- move choice at a root (k_pick_ready, k_sp_choose, k_match_choose) ---------------------------
+// get_action in its T -> 0 limit (main.py:1332-1341): the first maximum of N over the root's n children at cb, in
+// generation order (Python max() over root.child.items()); the index is wave-uniform, 0 when n == 0
+__device__ __forceinline__ int wave_most_visited(const TreeView &v, int cb, int n, int lane) {
+    int bn = -1, bi = 0x7fffffff;
+    for (int i = lane; i < n; i += 64) {
+        const int x = v.N[cb + i];
+        if (x > bn) { bn = x; bi = i; }
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const int on = __shfl_xor(bn, d, 64), oi = __shfl_xor(bi, d, 64);
+        if (on > bn || (on == bn && oi < bi)) { bn = on; bi = oi; }
+    }
+    return bi;
+}
+
+__device__ __forceinline__ double wave_sum(double x) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) x += __shfl_xor(x, d, 64);
+    return x;
+}
+__device__ __forceinline__ double wave_max(double x) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) x = fmax(x, __shfl_xor(x, d, 64));
+    return x;
+}
+__device__ __forceinline__ double wave_incl_scan(double v, int lane) {
+    double x = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const double y = __shfl_up(x, d, 64);
+        if (lane >= d) x += y;
+    }
+    return x;
+}
+
+// probs = softmax(1.0 / temperature * np.log(visits)), main.py:1341, over the n <= 128 children of a root: N[r] is the
+// visit count of child lane + 64 r (0 past n).  log(0) = -inf -> probability 0; with no visit at all (zero playouts)
+// the reference's softmax is NaN and np.random.choice raises: every child gets 1 / n.  pi[r] = 0 past n.
+__device__ __forceinline__ void wave_visit_policy(const int N[2], int n, double inv_temp, int lane, double pi[2]) {
+    double x[2], e[2];
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        const int i = lane + 64 * r;
+        x[r] = (i < n && N[r] > 0) ? inv_temp * log((double)N[r]) : -INFINITY;
+    }
+    const double m = wave_max(fmax(x[0], x[1]));
+#pragma unroll
+    for (int r = 0; r < 2; ++r) e[r] = (x[r] == -INFINITY || m == -INFINITY) ? 0.0 : exp(x[r] - m);
+    const double se = wave_sum(e[0] + e[1]);
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        const int i = lane + 64 * r;
+        pi[r] = se > 0.0 ? e[r] / se : (i < n ? 1.0 / (double)n : 0.0);
+    }
+}
+
+// np.random.choice(actions, p = ...) given its uniform u in [0, 1): inverse CDF over the children in generation order
+// (p[r] of child lane + 64 r) -> the child index, wave-uniform
+__device__ __forceinline__ int wave_pick_inverse_cdf(const double p[2], double u, int lane) {
+    const double c0 = wave_incl_scan(p[0], lane);
+    const double t0 = __shfl(c0, 63, 64);
+    const double c1 = t0 + wave_incl_scan(p[1], lane);
+    const double total = __shfl(c1, 63, 64);
+    const double target = u * total;
+    const unsigned long long h0 = __ballot(p[0] > 0.0 && c0 > target), h1 = __ballot(p[1] > 0.0 && c1 > target);
+    int pick;
+    if (h0) pick = __ffsll((long long)h0) - 1;
+    else if (h1) pick = 64 + __ffsll((long long)h1) - 1;
+    else {   // rounding at the upper end: the last child with a positive probability
+        const unsigned long long q1 = __ballot(p[1] > 0.0), q0 = __ballot(p[0] > 0.0);
+        pick = q1 ? 127 - __clzll((long long)q1) : (q0 ? 63 - __clzll((long long)q0) : 0);
+    }
+    return pick;
 }
 
 // kernels' launch wrappers (cz_rules.hip / cz_search.hip)

@@ -1,0 +1,330 @@
+// cz_match.hip — the per-ply bookkeeping of an evaluation match between two players, device-resident.
+//
+// Restates, for G concurrent games at once (chengstone/cchess-zero main.py):
+//   cchess_main.policy_evaluate  :1207-1222   a match of the current net against an opponent (commented out there)
+//   cchess_main.get_action       :1332-1341   the move: the most visited root child (T -> 0), or softmax(log N) at T = 1
+//   cchess_main.human_move       :272-276     the opponent's tree follows the move played (update_tree)
+//   cchess_main.check_end        :1380-1392   a king is gone, or 60 plies without a capture
+// Each player has its own cz_ctx (its own trees, net and playout budget); slot g of both contexts belongs to the same game.
+// One wave64 workgroup per slot.  Games come from a queue: game i plays opening i / 2 with player A red when i is even,
+// so every opening is played once with each colour assignment.  A slot whose game ends takes the next game of the queue
+// at once, or parks when the queue is empty.  The host only reads the finished-games counter every few plies.
+#include "cz_internal.h"
+
+struct cz_match {
+    cz_ctx *a, *b;
+    int G, n_games, max_plies;
+    long long pair_base, pair_stride;   // global index of local opening p = pair_base + pair_stride * p (rank sharding)
+    void *block;
+};
+
+namespace {
+
+// The device view of a match: per slot the game it plays, per game the result.
+struct CzMatch {
+    int G, n_games, max_plies;
+    long long pair_base, pair_stride;
+    const uint8_t *open_board;    // [n_games / 2][90]
+    const uint8_t *open_side;     // [n_games / 2]
+    const int32_t *open_rr;       // [n_games / 2]
+    int32_t *queue;               // [2] next game to hand out, games finished
+    unsigned long long *sims;     // [1] simulations of the searches whose move was chosen
+    int32_t *game;                // [G] game of the slot, -1 = parked
+    int32_t *ply;                 // [G] plies played in the slot's game
+    uint8_t *mover_a;             // [G] player A is to move in the slot's game
+    uint8_t *act_a, *act_b;       // [G] mover masks: this player is to move and the game is live
+    uint8_t *stalled;             // [G] the last choose found no root child
+    int8_t *result;               // [n_games] +1 / 0 / -1 from A's point of view
+    uint8_t *a_red;               // [n_games] 1: A played red
+    int32_t *plies;               // [n_games]
+    uint8_t *reason;              // [n_games] CZ_MATCH_*
+    uint16_t *moves;              // [n_games][max_plies] labels played, 0xFFFF past the end
+};
+
+__device__ __forceinline__ unsigned long long splitmix64(unsigned long long x) {
+    x += 0x9E3779B97F4A7C15ull;
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+    return x ^ (x >> 31);
+}
+
+// the uniform of a sampled move (include/cchess_hip.h cz_match_choose): a pure function of (seed, global game, ply)
+__device__ __forceinline__ double match_uniform(unsigned long long seed, long long game, int ply) {
+    const unsigned long long h = splitmix64(seed ^ splitmix64(((unsigned long long)game << 16) | (unsigned long long)ply));
+    return (double)(h >> 11) * 0x1.0p-53;
+}
+
+__device__ __forceinline__ long long global_game(const CzMatch &m, int game) {
+    return 2 * (m.pair_base + m.pair_stride * (long long)(game >> 1)) + (game & 1);
+}
+
+// a fresh, unexpanded root on a position (MCTS_tree.reload, main.py:255-259), the tree's evaluation cache emptied
+__device__ __forceinline__ void fresh_tree(const CzTrees &t, int g, const uint8_t *board, int side, int rr, int lane) {
+    if (board)
+        for (int i = lane; i < CZD_BOARD_LDS; i += 64) t.root_board[(size_t)g * CZD_BOARD_LDS + i] = i < CZ_NSQ ? board[i] : (uint8_t)0;
+    if (lane == 0) {
+        if (board) { t.root_side[g] = (uint8_t)side; t.root_rr[g] = rr; }
+        t.root_node[g] = 0; t.n_nodes[g] = 1; t.status[g] = 0; t.sims[g] = 0; t.last_depth[g] = 0; t.root_ply[g] = 0;
+        t.pend_kind[g] = 0;
+        init_root(view_of(t, g), 0);
+    }
+    ec_clear_tree(t, g, lane, 64);
+}
+
+// slot g takes game `game` of the queue (both trees on its opening), or parks (game >= n_games): both trees keep a
+// fresh root with no simulation, and neither mover mask names the slot, so no search touches it again
+__device__ __forceinline__ void take_game(const CzTrees &ta, const CzTrees &tb, const CzMatch &m, int g, int game, int lane) {
+    if (game < m.n_games) {
+        const int p = game >> 1;
+        const uint8_t *ob = m.open_board + (size_t)p * CZ_NSQ;
+        const int side = m.open_side[p] ? 1 : 0, rr = m.open_rr[p];
+        fresh_tree(ta, g, ob, side, rr, lane);
+        fresh_tree(tb, g, ob, side, rr, lane);
+        if (lane == 0) {
+            const bool a_red = (game & 1) == 0;
+            const bool ma = (side == 0) == a_red;
+            m.game[g] = game; m.ply[g] = 0; m.stalled[g] = 0;
+            m.mover_a[g] = ma ? 1 : 0; m.act_a[g] = ma ? 1 : 0; m.act_b[g] = ma ? 0 : 1;
+        }
+    } else {
+        fresh_tree(ta, g, nullptr, 0, 0, lane);
+        fresh_tree(tb, g, nullptr, 0, 0, lane);
+        if (lane == 0) { m.game[g] = -1; m.act_a[g] = 0; m.act_b[g] = 0; m.stalled[g] = 0; }
+    }
+}
+
+__global__ __launch_bounds__(64) void k_match_start(CzTrees ta, CzTrees tb, CzMatch m) {
+    const int g = blockIdx.x, lane = threadIdx.x;
+    if (g >= m.G) return;
+    if (g == 0 && lane == 0) { m.queue[0] = min(m.G, m.n_games); m.queue[1] = 0; *m.sims = 0ull; }
+    take_game(ta, tb, m, g, g, lane);
+}
+
+// get_action of the mover (main.py:1332-1341) on its own tree: greedy, or sampled for the game's first sample_plies plies
+__device__ __forceinline__ void choose_on(const CzTrees &t, const CzMatch &m, int g, int game, int sample_plies,
+                                          unsigned long long seed, uint16_t *__restrict__ played, int lane) {
+    if (lane == 0) atomicAdd(m.sims, (unsigned long long)t.sims[g]);
+    const TreeView v = view_of(t, g);
+    const int root = t.root_node[g];
+    const int cb = v.child_begin[root];
+    const int n = cb < 0 ? 0 : (int)v.child_count[root];
+    if (n == 0 || (t.status[g] & (CZ_ST_NO_MOVES | CZ_ST_MOVE_OVERFLOW)) != 0) {
+        // no child to play (node pool exhausted at the root, or a rules overflow): the game is aborted by the adjudication
+        if (lane == 0) { played[g] = 0xFFFF; m.stalled[g] = 1; }
+        return;
+    }
+    const int ply = m.ply[g];
+    int pick;
+    if (ply < sample_plies) {
+        // select_move -> get_action(state, temperature = 1) (main.py:1123,1433-1435): no Dirichlet noise
+        int N[2] = {0, 0};
+        double pi[2];
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            const int i = lane + 64 * r;
+            if (i < n) N[r] = v.N[cb + i];
+        }
+        wave_visit_policy(N, n, 1.0, lane, pi);
+        pick = wave_pick_inverse_cdf(pi, match_uniform(seed, global_game(m, game), ply), lane);
+    } else {
+        pick = wave_most_visited(v, cb, n, lane);
+    }
+    if (lane == 0) {
+        const uint16_t mv = v.move[cb + pick];
+        if (ply < m.max_plies) m.moves[(size_t)game * m.max_plies + ply] = mv;
+        played[g] = mv;
+        m.ply[g] = ply + 1;
+    }
+}
+
+__global__ __launch_bounds__(64) void k_match_choose(CzTrees ta, CzTrees tb, CzMatch m, int sample_plies, unsigned long long seed,
+                                                     uint16_t *__restrict__ played) {
+    const int g = blockIdx.x, lane = threadIdx.x;
+    if (g >= m.G) return;
+    const int game = m.game[g];
+    if (game < 0) { if (lane == 0) played[g] = 0xFFFF; return; }
+    if (m.mover_a[g]) choose_on(ta, m, g, game, sample_plies, seed, played, lane);
+    else choose_on(tb, m, g, game, sample_plies, seed, played, lane);
+}
+
+// After cz_search_advance(played) on both contexts: the follower's failed advance (its root was never expanded, so it has no
+// child for the move) is its normal case — it starts a fresh root on the new position; then check_end (main.py:1380-1392)
+// plus the match's own endings (ply cap, aborted game), the result, and the slot's next game.
+__global__ __launch_bounds__(64) void k_match_adjudicate(CzTrees ta, CzTrees tb, CzMatch m, const uint16_t *__restrict__ played) {
+    const int g = blockIdx.x, lane = threadIdx.x;
+    if (g >= m.G) return;
+    const int game = m.game[g];
+    if (game < 0) return;
+    const bool ma = m.mover_a[g] != 0;
+    const CzRecField<int32_t, offsetof(CzTreeRec, status)> mst = ma ? ta.status : tb.status, fst = ma ? tb.status : ta.status;
+    const bool aborted = m.stalled[g] != 0 || played[g] >= CZ_NLABELS || (mst[g] & CZ_ST_BAD_ADVANCE) != 0;
+    const uint8_t *rb = (ma ? ta.root_board : tb.root_board) + (size_t)g * CZD_BOARD_LDS;
+    const int c0 = rb[lane], c1 = (lane + 64 < CZ_NSQ) ? rb[lane + 64] : 0;
+    const bool Kmiss = (__ballot(c0 == 1) | __ballot(c1 == 1)) == 0ull;
+    const bool kmiss = (__ballot(c0 == 8) | __ballot(c1 == 8)) == 0ull;
+    const int ply = m.ply[g];
+    const int rr = ma ? ta.root_rr[g] : tb.root_rr[g];
+    int reason = 0;
+    if (aborted) reason = CZ_MATCH_ABORTED;
+    else if (Kmiss || kmiss) reason = CZ_MATCH_KING;
+    else if (rr >= 60) reason = CZ_MATCH_RR60;
+    else if (ply >= m.max_plies) reason = CZ_MATCH_PLY_CAP;
+    if (lane == 0) fst[g] &= ~CZ_ST_BAD_ADVANCE;
+    if (!reason) {
+        if (lane == 0) { m.mover_a[g] = ma ? 0 : 1; m.act_a[g] = ma ? 0 : 1; m.act_b[g] = ma ? 1 : 0; }
+        return;
+    }
+    int next = 0;
+    if (lane == 0) {
+        const bool a_red = (game & 1) == 0;
+        // winner: 'K' missing -> black, 'k' missing -> red (main.py:1384-1389)
+        const bool a_wins = Kmiss ? !a_red : a_red;
+        m.result[game] = (int8_t)(reason == CZ_MATCH_KING ? (a_wins ? 1 : -1) : 0);
+        m.a_red[game] = a_red ? 1 : 0;
+        m.plies[game] = ply;
+        m.reason[game] = (uint8_t)reason;
+        atomicAdd(&m.queue[1], 1);
+        next = atomicAdd(&m.queue[0], 1);
+    }
+    next = __shfl(next, 0, 64);
+    take_game(ta, tb, m, g, next, lane);
+}
+
+}  // namespace
+
+// the match's arrays inside its one allocation (base NULL: only the size) -> bytes
+static size_t carve(const cz_match *mh, char *base, CzMatch &m) {
+    size_t off = 0;
+    auto take = [&](size_t bytes) { char *q = base ? base + off : nullptr; off += (bytes + 255) & ~(size_t)255; return q; };
+    const size_t G = (size_t)mh->G, n = (size_t)mh->n_games, np = n / 2;
+    m.G = mh->G; m.n_games = mh->n_games; m.max_plies = mh->max_plies;
+    m.pair_base = mh->pair_base; m.pair_stride = mh->pair_stride;
+    m.open_board = (const uint8_t *)take(np * CZ_NSQ);
+    m.open_side = (const uint8_t *)take(np);
+    m.open_rr = (const int32_t *)take(np * 4);
+    m.queue = (int32_t *)take(8);
+    m.sims = (unsigned long long *)take(8);
+    m.game = (int32_t *)take(G * 4);
+    m.ply = (int32_t *)take(G * 4);
+    m.mover_a = (uint8_t *)take(G);
+    m.act_a = (uint8_t *)take(G);
+    m.act_b = (uint8_t *)take(G);
+    m.stalled = (uint8_t *)take(G);
+    m.result = (int8_t *)take(n);
+    m.a_red = (uint8_t *)take(n);
+    m.plies = (int32_t *)take(n * 4);
+    m.reason = (uint8_t *)take(n);
+    m.moves = (uint16_t *)take(n * (size_t)mh->max_plies * 2);
+    return off;
+}
+
+static CzMatch device_view(const cz_match *mh) {
+    CzMatch m;
+    carve(mh, (char *)mh->block, m);
+    return m;
+}
+
+int cz_match_create(cz_ctx *a, cz_ctx *b, const uint8_t *boards, const uint8_t *side, const int32_t *rr, int n_openings,
+                    long long pair_base, long long pair_stride, int max_plies, cz_match **out) {
+    CZ_REQUIRE(out, "cz_match_create: null out");
+    *out = nullptr;
+    CZ_REQUIRE(a && b && a != b, "cz_match_create: two distinct contexts required");
+    CZ_REQUIRE(a->G > 0 && a->G == b->G, "cz_match_create: cz_search_reset both contexts to the same number of slots first");
+    CZ_REQUIRE(a->device == b->device && a->stream == b->stream, "cz_match_create: both contexts must be bound to the same device and stream");
+    CZ_REQUIRE(a->width == 1 && b->width == 1, "cz_match_create: players search with width 1");
+    CZ_REQUIRE(boards && side && n_openings >= 1 && n_openings <= (1 << 29), "cz_match_create: 1 <= n_openings and opening arrays required");
+    CZ_REQUIRE(pair_base >= 0 && pair_stride >= 1, "cz_match_create: pair_base >= 0, pair_stride >= 1");
+    CZ_REQUIRE(max_plies >= 1 && max_plies <= 65535, "cz_match_create: 1 <= max_plies <= 65535");
+    cz_match *mh = new cz_match();
+    mh->a = a; mh->b = b; mh->G = a->G; mh->n_games = 2 * n_openings; mh->max_plies = max_plies;
+    mh->pair_base = pair_base; mh->pair_stride = pair_stride;
+    CzMatch sizing;
+    const size_t bytes = carve(mh, nullptr, sizing);
+    if (hipMalloc(&mh->block, bytes) != hipSuccess) {
+        mh->block = nullptr;
+        delete mh;
+        cz_set_error("cz_match_create: hipMalloc(%zu B) failed", bytes);
+        return CZ_ENOMEM;
+    }
+    const CzMatch m = device_view(mh);
+    const size_t np = (size_t)n_openings;
+    int rc = CZ_OK;
+    auto fail = [&](hipError_t e, const char *what) {
+        cz_set_error("cz_match_create: %s failed: %s", what, hipGetErrorString(e));
+        rc = CZ_EHIP;
+    };
+    hipError_t e;
+    if ((e = hipMemsetAsync(mh->block, 0, bytes, a->stream)) != hipSuccess) fail(e, "hipMemsetAsync");
+    else if ((e = hipMemsetAsync(m.moves, 0xFF, (size_t)mh->n_games * max_plies * 2, a->stream)) != hipSuccess) fail(e, "hipMemsetAsync");
+    else if ((e = hipMemcpyAsync((void *)m.open_board, boards, np * CZ_NSQ, hipMemcpyDeviceToDevice, a->stream)) != hipSuccess) fail(e, "hipMemcpyAsync");
+    else if ((e = hipMemcpyAsync((void *)m.open_side, side, np, hipMemcpyDeviceToDevice, a->stream)) != hipSuccess) fail(e, "hipMemcpyAsync");
+    else if (rr && (e = hipMemcpyAsync((void *)m.open_rr, rr, np * 4, hipMemcpyDeviceToDevice, a->stream)) != hipSuccess) fail(e, "hipMemcpyAsync");
+    if (rc == CZ_OK) {
+        hipLaunchKernelGGL(k_match_start, dim3(mh->G), dim3(64), 0, a->stream, a->t, b->t, m);
+        if ((e = hipGetLastError()) != hipSuccess) fail(e, "k_match_start");
+    }
+    if (rc != CZ_OK) {
+        (void)hipStreamSynchronize(a->stream);
+        (void)hipFree(mh->block);
+        delete mh;
+        return rc;
+    }
+    *out = mh;
+    return CZ_OK;
+}
+
+void cz_match_destroy(cz_match *mh) {
+    if (!mh) return;
+    (void)hipStreamSynchronize(mh->a->stream);
+    (void)hipFree(mh->block);
+    delete mh;
+}
+
+int cz_match_active(cz_match *mh, int player, const uint8_t **mask) {
+    CZ_REQUIRE(mh && mask && (player == 0 || player == 1), "cz_match_active: player 0 (A) or 1 (B), non-null mask");
+    const CzMatch m = device_view(mh);
+    *mask = player == 0 ? m.act_a : m.act_b;
+    return CZ_OK;
+}
+
+int cz_match_choose(cz_match *mh, int sample_plies, unsigned long long seed, uint16_t *played) {
+    CZ_REQUIRE(mh && played && sample_plies >= 0, "cz_match_choose: null argument / sample_plies < 0");
+    CZ_REQUIRE(mh->a->G == mh->G && mh->b->G == mh->G, "cz_match_choose: a context was reset to another number of slots");
+    hipLaunchKernelGGL(k_match_choose, dim3(mh->G), dim3(64), 0, mh->a->stream, mh->a->t, mh->b->t, device_view(mh), sample_plies, seed, played);
+    CZ_HIP(hipGetLastError());
+    return CZ_OK;
+}
+
+int cz_match_adjudicate(cz_match *mh, const uint16_t *played) {
+    CZ_REQUIRE(mh && played, "cz_match_adjudicate: null argument");
+    CZ_REQUIRE(mh->a->G == mh->G && mh->b->G == mh->G, "cz_match_adjudicate: a context was reset to another number of slots");
+    hipLaunchKernelGGL(k_match_adjudicate, dim3(mh->G), dim3(64), 0, mh->a->stream, mh->a->t, mh->b->t, device_view(mh), played);
+    CZ_HIP(hipGetLastError());
+    return CZ_OK;
+}
+
+int cz_match_results(cz_match *mh, const int8_t **result, const uint8_t **a_red, const int32_t **plies, const uint8_t **reason,
+                     const uint16_t **moves, const int32_t **slot_game) {
+    CZ_REQUIRE(mh, "cz_match_results: null match");
+    const CzMatch m = device_view(mh);
+    if (result) *result = m.result;
+    if (a_red) *a_red = m.a_red;
+    if (plies) *plies = m.plies;
+    if (reason) *reason = m.reason;
+    if (moves) *moves = m.moves;
+    if (slot_game) *slot_game = m.game;
+    return CZ_OK;
+}
+
+int cz_match_finished(cz_match *mh, int32_t *finished, unsigned long long *sims) {
+    CZ_REQUIRE(mh, "cz_match_finished: null match");
+    const CzMatch m = device_view(mh);
+    int32_t q[2] = {0, 0};
+    unsigned long long s = 0ull;
+    CZ_HIP(hipMemcpyAsync(q, m.queue, sizeof(q), hipMemcpyDeviceToHost, mh->a->stream));
+    CZ_HIP(hipMemcpyAsync(&s, m.sims, sizeof(s), hipMemcpyDeviceToHost, mh->a->stream));
+    CZ_HIP(hipStreamSynchronize(mh->a->stream));
+    if (finished) *finished = q[1];
+    if (sims) *sims = s;
+    return CZ_OK;
+}

@@ -56,16 +56,7 @@ __global__ __launch_bounds__(64) void k_pick_ready(CzTrees t, int G, int32_t *__
         const int cb = v.child_begin[root];
         const int n = cb < 0 ? 0 : v.child_count[root];
         // first maximum of N in generation order (Python max() over root.child.items())
-        int bn = -1, bi = 0x7fffffff;
-        for (int i = lane; i < n; i += 64) {
-            const int x = v.N[cb + i];
-            if (x > bn) { bn = x; bi = i; }
-        }
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) {
-            const int on = __shfl_xor(bn, d, 64), oi = __shfl_xor(bi, d, 64);
-            if (on > bn || (on == bn && oi < bi)) { bn = on; bi = oi; }
-        }
+        const int bi = wave_most_visited(v, cb, n, lane);
         if (n > 0) label = v.move[cb + bi];
         if (lane == 0) {
             thr[g] = next_thr;

@@ -17,26 +17,6 @@
 
 namespace {
 
-__device__ __forceinline__ double wave_sum(double x) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) x += __shfl_xor(x, d, 64);
-    return x;
-}
-__device__ __forceinline__ double wave_max(double x) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) x = fmax(x, __shfl_xor(x, d, 64));
-    return x;
-}
-__device__ __forceinline__ double wave_incl_scan(double v, int lane) {
-    double x = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const double y = __shfl_up(x, d, 64);
-        if (lane >= d) x += y;
-    }
-    return x;
-}
-
 __device__ __forceinline__ void seed_slot(const CzTrees &t, const CzSelfplay &sp, int g, int lane) {
     // MCTS_tree.reload + GameBoard.reload (main.py:255-259, 582-588): a fresh, unexpanded root on the slot's start position
     for (int i = lane; i < CZD_BOARD_LDS; i += 64)
@@ -94,18 +74,13 @@ __global__ __launch_bounds__(64) void k_sp_choose(CzTrees t, CzSelfplay sp, int 
     }
     int N[2] = {0, 0};
     uint16_t lab[2] = {0xFFFF, 0xFFFF};
-    double x[2], e[2], p[2];
+    double pi[2], p[2];
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
         const int i = lane + 64 * r;
         if (i < n) { N[r] = v.N[cb + i]; lab[r] = v.move[cb + i]; }
-        // probs = softmax(1.0 / temperature * np.log(visits)), main.py:1341: log(0) = -inf -> probability 0
-        x[r] = (i < n && N[r] > 0) ? inv_temp * log((double)N[r]) : -INFINITY;
     }
-    const double m = wave_max(fmax(x[0], x[1]));
-#pragma unroll
-    for (int r = 0; r < 2; ++r) e[r] = (x[r] == -INFINITY || m == -INFINITY) ? 0.0 : exp(x[r] - m);
-    const double se = wave_sum(e[0] + e[1]);
+    wave_visit_policy(N, n, inv_temp, lane, pi);
     double gm[2] = {0.0, 0.0};
     if (gamma && eps > 0.f) {
 #pragma unroll
@@ -119,25 +94,10 @@ __global__ __launch_bounds__(64) void k_sp_choose(CzTrees t, CzSelfplay sp, int 
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
         const int i = lane + 64 * r;
-        // with no visit at all (zero playouts) the reference's softmax is NaN and np.random.choice raises; play uniformly
-        const double pi = se > 0.0 ? e[r] / se : (i < n ? 1.0 / (double)n : 0.0);
         // 0.75 * probs + 0.25 * np.random.dirichlet(0.3 * np.ones(len(probs))), main.py:1346
-        p[r] = i < n ? (noise ? (1.0 - (double)eps) * pi + (double)eps * (gm[r] / sg) : pi) : 0.0;
+        p[r] = i < n ? (noise ? (1.0 - (double)eps) * pi[r] + (double)eps * (gm[r] / sg) : pi[r]) : 0.0;
     }
-    // np.random.choice(actions, p = ...): inverse CDF over the children in generation order
-    const double c0 = wave_incl_scan(p[0], lane);
-    const double t0 = __shfl(c0, 63, 64);
-    const double c1 = t0 + wave_incl_scan(p[1], lane);
-    const double total = __shfl(c1, 63, 64);
-    const double target = (double)u[g] * total;
-    const unsigned long long h0 = __ballot(p[0] > 0.0 && c0 > target), h1 = __ballot(p[1] > 0.0 && c1 > target);
-    int pick;
-    if (h0) pick = __ffsll((long long)h0) - 1;
-    else if (h1) pick = 64 + __ffsll((long long)h1) - 1;
-    else {   // rounding at the upper end: the last child with a positive probability
-        const unsigned long long q1 = __ballot(p[1] > 0.0), q0 = __ballot(p[0] > 0.0);
-        pick = q1 ? 127 - __clzll((long long)q1) : (q0 ? 63 - __clzll((long long)q0) : 0);
-    }
+    const int pick = wave_pick_inverse_cdf(p, (double)u[g], lane);
     int mv = __shfl(pick < 64 ? (int)lab[0] : (int)lab[1], pick & 63, 64);
     if (forced && forced[g] < CZ_NLABELS) mv = forced[g];
     // the record of this ply: state before the move, mover, children and their visits

@@ -26,6 +26,23 @@ def _mask(active, dev):
     return torch.as_tensor(active).to(dev).to(torch.uint8).contiguous()
 
 
+def plane_format(forward):
+    """(plane dtype, channels) the select kernel writes a player's leaf planes in: a PolicyValueNet on the fused path (hip
+    backend, or the strict ladder) reads 16 channels of its 16-bit type straight from the select kernel; any other net or a
+    plain forward(planes) -> (logits, value) callable gets the reference's 14 float32 planes."""
+    net = getattr(forward, "__self__", forward)
+    dtype = getattr(net, "dtype", None)
+    fused = hasattr(net, "strict_auto") and (net.backend == "hip" or net.strict_auto) and dtype in (torch.float16, torch.bfloat16)
+    return (dtype, 16) if fused else (torch.float32, 14)
+
+
+def pool_nodes(playouts):
+    """Node pool per tree for a search of `playouts` simulations per move: a ply adds ~40 nodes per simulation on top of the
+    subtree kept from the previous ply; a tree that fills its pool stops expanding for the rest of that ply (the move is
+    chosen from the visits it has) and gets its room back when cz_search_advance compacts it."""
+    return max(4096, (int(playouts) + 2) * 128)
+
+
 class Context:
     """Owns a cz_ctx bound to one GPU and to torch's current stream on it."""
 

@@ -329,6 +329,51 @@ int cz_selfplay_flush(cz_ctx *, const int32_t *fin_n, const long long *offset, u
                       const long long *read_cursor);
 int cz_selfplay_stats(cz_ctx *, long long *stats_dev);
 
+/* ---- device-resident evaluation matches between two players (one wave per game slot; no host round trip per ply) -------
+ * replaces: cchess_main.policy_evaluate (main.py:1207-1222, commented out in the reference) — many games of player A
+ * against player B, both colours, for the G slots of two contexts at once.  Each player has its own cz_ctx (trees, net,
+ * playout budget); slot g of both contexts belongs to the same game.  One ply of every game =
+ *     cz_search_select/expand_backup... on A's context with mask cz_match_active(A), the same on B's with its mask
+ *     cz_match_choose        the mover's move on the mover's tree (get_action, main.py:1332-1341), logged per game
+ *     cz_search_advance      on BOTH contexts with the same `played`: the mover re-roots on its child; the other player's
+ *                            tree keeps its subtree for the move if it has one (update_tree after the opponent's move,
+ *                            main.py:272-276), else starts a fresh root on the new position
+ *     cz_match_adjudicate    check_end (main.py:1380-1392) and the match's own endings; the slot's next game
+ * cz_match_create (after cz_search_reset of both contexts to the same G, bound to the same stream): a queue of
+ *   n_games = 2 n_openings games; game i plays opening i / 2 (boards [n][90], side [n], rr [n] or NULL = 0, device arrays)
+ *   with player A red when i is even.  Slot g starts game g; a slot whose game ends takes the next game of the queue at
+ *   once, or parks (both trees keep a fresh root with no simulation; neither mask names it).  pair_base / pair_stride: the
+ *   GLOBAL index of local opening p is pair_base + pair_stride p (several ranks share one match; 0 / 1 otherwise).
+ *   A game ends when a king is missing, when restrict_round reaches 60, at max_plies plies (a draw), or when the mover has
+ *   no child to play (node pool exhausted at the root, or a rules overflow: CZ_MATCH_ABORTED, not scored).
+ * cz_match_active: player 0 = A, 1 = B -> device uint8 [G] mask "this player is to move in slot g and the game is live",
+ *   the `active` argument of that player's cz_search_select.
+ * cz_match_choose: greedy — the first maximum of N in generation order (get_action's T -> 0 limit, as
+ *   cz_search_pick_ready) — or, for the first sample_plies plies of a game, sampled from softmax(log N) (temperature 1,
+ *   no Dirichlet noise: select_move -> get_action(state, 1), main.py:1123,1433-1435) by inverse CDF with the uniform
+ *   u = (splitmix64(seed ^ splitmix64(game << 16 | ply)) >> 11) * 2^-53 of the GLOBAL game index: a game's moves do not
+ *   depend on the slot it ran in, on G or on the rank.  played [G] out (0xFFFF: parked, or no child to play).
+ * cz_match_adjudicate: after both advances; clears the follower's CZ_ST_BAD_ADVANCE (its fresh root is no error); the
+ *   mover's is an abort.
+ * cz_match_results: device arrays owned by the match — result int8 [n_games] (+1 / 0 / -1 from A's point of view),
+ *   a_red uint8 [n_games], plies int32 [n_games], reason uint8 [n_games] (CZ_MATCH_*, 0 = not finished), moves uint16
+ *   [n_games][max_plies] (0xFFFF past the game's end), slot_game int32 [G] (the game of each slot, -1 = parked); any may be NULL.
+ * cz_match_finished: synchronises the stream; host <- games finished, simulations of the searches whose move was chosen. */
+#define CZ_MATCH_KING 1      /* a king was captured */
+#define CZ_MATCH_RR60 2      /* 60 plies without a capture: a draw (main.py:1390) */
+#define CZ_MATCH_PLY_CAP 3   /* max_plies plies: a draw (the reference has no such limit) */
+#define CZ_MATCH_ABORTED 4   /* the mover had no child to play: not scored */
+typedef struct cz_match cz_match;
+int cz_match_create(cz_ctx *a, cz_ctx *b, const uint8_t *open_boards, const uint8_t *open_side, const int32_t *open_rr,
+                    int n_openings, long long pair_base, long long pair_stride, int max_plies, cz_match **out);
+void cz_match_destroy(cz_match *);
+int cz_match_active(cz_match *, int player, const uint8_t **mask_dev);
+int cz_match_choose(cz_match *, int sample_plies, unsigned long long seed, uint16_t *played);
+int cz_match_adjudicate(cz_match *, const uint16_t *played);
+int cz_match_results(cz_match *, const int8_t **result, const uint8_t **a_red, const int32_t **plies, const uint8_t **reason,
+                     const uint16_t **moves, const int32_t **slot_game);
+int cz_match_finished(cz_match *, int32_t *finished, unsigned long long *sims);
+
 /* ---- N1: policy/value network kernels ---------------------------------------------------------
  * One residual-tower layer: 3x3 SAME convolution 128->128 over [B][9][10] boards, NHWC bf16, with the
  * (BN-folded) bias, optional residual add and optional ReLU fused in.

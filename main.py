@@ -336,6 +336,9 @@ class cchess_main(object):
         self.games = games
         self.num_gpus = num_gpus
         self.update_seed = 20260925   # mini-batch / shuffle seed shared by all ranks (rank-consistent control flow)
+        self.eval_every = 0           # run(): policy_evaluate every this many batches (0 = off; --eval_every)
+        self.eval_games = 256
+        self.last_evaluation = None
 
     @staticmethod
     def flip_policy(prob):
@@ -494,21 +497,17 @@ class cchess_main(object):
         (main.py:1228-1240); stopping all slots at a batch boundary would keep only the games shorter than the batch."""
         import torch
         from cchess_zero_amd import parallel
-        from cchess_zero_amd.engine import SearchEngine
+        from cchess_zero_amd.engine import SearchEngine, plane_format, pool_nodes
         from cchess_zero_amd.selfplay import SelfPlay
         G = games or self.games
         target = target_games or G
-        # a ply adds ~40 nodes per simulation on top of the subtree kept from the previous ply; a tree that fills its pool
-        # stops expanding for the rest of that ply (the move is chosen from the visits it has) and gets its room back when
-        # cz_search_advance compacts it
-        cap = max(4096, (self.playout_counts + 2) * 128)
+        cap = pool_nodes(self.playout_counts)
         net = self.policy_value_netowrk.net
         sp = getattr(self, "_sp", None)
         if sp is None or sp.eng.G != G or sp.eng.ctx.cap < cap or sp.playouts != self.playout_counts or sp.net is not net:
             # planes are written by the select kernel straight in the fused net's input format (16 channels of its 16-bit type)
-            fused = (net.backend == "hip" or net.strict_auto) and net.dtype in (torch.float16, torch.bfloat16)
-            eng = SearchEngine(G, cap, torch.cuda.current_device(), plane_dtype=net.dtype if fused else torch.float32,
-                               channels=16 if fused else 14)
+            plane_dtype, channels = plane_format(net)
+            eng = SearchEngine(G, cap, torch.cuda.current_device(), plane_dtype=plane_dtype, channels=channels)
             # every rank seeds its games differently but reproducibly from the shared Python RNG state
             base_seed = random.randrange(1 << 30)
             rank = int(os.environ.get("RANK", "0"))
@@ -551,6 +550,42 @@ class cchess_main(object):
         self.last_selfplay_sims = self.last_selfplay_stats["sims"]
         rec = torch.cat(chunks, 0) if chunks else sp.ring[:0]
         return parallel.gather_records(rec)
+
+    def policy_evaluate(self, n_games=10, opponent=None):
+        """Reference: main.py:1207-1222 (commented out there) — a match of the live net against `opponent` on the GPU
+        (cchess_zero_amd/arena.py): a policy_value_network, a checkpoint path (own .pt, reference TF bundle, .npz), or None =
+        a frozen snapshot of the weights, taken at the first call and replaced when the live net scores >= 0.55 against it
+        (AlphaGo Zero's margin).  n_games is rounded up to an even number (each opening with both colours); both players
+        search playout_counts simulations per move, greedily.  Returns win_ratio = (W + 0.5 D) / scored games for the live
+        net, like the stub; the whole MatchResult is in self.last_evaluation.  The live net, global_step and the self-play
+        state are untouched."""
+        from cchess_zero_amd.arena import Match, load_player, random_openings
+        live = self.policy_value_netowrk.net
+        pairs = max(1, (int(n_games) + 1) // 2)
+        if opponent is None:
+            if getattr(self, "_eval_snapshot", None) is None:
+                self._eval_snapshot = self._snapshot_net()
+            opp = self._eval_snapshot
+        elif isinstance(opponent, (str, os.PathLike)):
+            opp = load_player(str(opponent), live.res_block_nums).net
+        else:
+            opp = getattr(opponent, "net", opponent)
+        self._eval_round = getattr(self, "_eval_round", 0) + 1
+        openings = random_openings(pairs, 4, seed=self.update_seed + self._eval_round)
+        res = Match((live, self.playout_counts), (opp, self.playout_counts), openings, slots=max(2, min(2 * pairs, self.games)),
+                    seed=self.update_seed + self._eval_round).play()
+        self.last_evaluation = res
+        if opponent is None and res.score is not None and res.score >= 0.55:
+            self._eval_snapshot = self._snapshot_net()
+        return 0.0 if res.score is None else float(res.score)
+
+    def _snapshot_net(self):
+        """A frozen copy of the live net's weights with the same engine settings (policy_evaluate's default opponent)."""
+        import copy
+        from cchess_zero_amd.net import PolicyValueNet
+        live = self.policy_value_netowrk.net
+        split = "strict" if live.strict_auto else ("mx" if live.mx else live.split)
+        return PolicyValueNet(live.res_block_nums, live.device, live.dtype, module=copy.deepcopy(live.module), split=split)
 
     def policy_update(self, save=True):
         from cchess_zero_amd.train import policy_update
@@ -607,6 +642,14 @@ class cchess_main(object):
                 print(msg, flush=True)
                 self.log_file.write(msg + '\n')
                 self.log_file.flush()
+                if self.eval_every and batch_iter % self.eval_every == 0:   # reports only: self-play keeps the live net
+                    self.policy_evaluate(self.eval_games)
+                    d = self.last_evaluation.to_dict()
+                    d["batch"] = batch_iter
+                    msg = "evaluation: " + json.dumps(d)
+                    print(msg, flush=True)
+                    self.log_file.write(msg + '\n')
+                    self.log_file.flush()
         except KeyboardInterrupt:
             self.log_file.close()
             self.policy_value_netowrk.save(self.global_step)
@@ -658,6 +701,9 @@ if __name__ == '__main__':
     # additions (not in the reference): size of the lock-step game pool per GPU, bounded runs for scripts
     parser.add_argument('--games', default=256, type=int, help='parallel self-play games per GPU')
     parser.add_argument('--max_batches', default=None, type=int, help='stop after this many self-play batches')
+    parser.add_argument('--eval_every', default=0, type=int,
+                        help='every this many batches, a match of the live net against a frozen snapshot (policy_evaluate); 0 = off')
+    parser.add_argument('--eval_games', default=256, type=int, help='games of each evaluation match')
     parser.add_argument('--net_precision', default=None, choices=['strict', 'mx6', 'fp16x2', 'fp16', 'bf16', 'bf16x2', 'fp32'], type=str,
                         help='net engine (policy_value_network.PRECISIONS): strict (default) = measured within 5e-4 absolute of the '
                              'fp32 graph on 64 positions with the LIVE weights after every weight change, falling over mx6 -> fp16x2 -> '
@@ -686,6 +732,7 @@ if __name__ == '__main__':
     if args.mode == 'train':
         train_main = cchess_main(args.train_playout, args.batch_size, True, args.search_threads, args.processor, args.num_gpus,
                                  args.res_block_nums, args.human_color, games=args.games)
+        train_main.eval_every, train_main.eval_games = args.eval_every, args.eval_games
         train_main.run(args.max_batches)
         if os.environ.get("CCHESS_WEIGHT_DIGEST_DIR"):   # tests: every rank leaves a digest of its replica (they must be equal)
             import hashlib
