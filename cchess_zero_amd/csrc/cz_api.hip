@@ -178,7 +178,9 @@ void cz_destroy(cz_ctx *c) {
     if (c->pool_block) (void)hipFree(c->pool_block);
     if (c->sp_block) (void)hipFree(c->sp_block);
     if (c->ec_block) (void)hipFree(c->ec_block);
+#if defined(CZ_EXPERIMENT_MX2) || defined(CZ_EXPERIMENT_MX12)
     if (c->mx_xbuf) (void)hipFree(c->mx_xbuf);
+#endif
     delete c;
 }
 

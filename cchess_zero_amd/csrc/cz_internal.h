@@ -168,10 +168,12 @@ struct cz_ctx {
     bool adv_attr_set;   // dynamic-LDS opt-in of k_advance_lds done
     bool adv_force_global;   // cz_search_debug_advance_in_global_memory (tests): take the path of pools whose bitmap exceeds LDS
     bool conv_attr_set, tower_attr_set, split_attr_set, mx_attr_set;  // dynamic-LDS opt-in of the MFMA kernels done for this device
+#if defined(CZ_EXPERIMENT_MX2) || defined(CZ_EXPERIMENT_MX12)   // experiment builds only (tools/experiments/mx_ablate.sh)
     bool mx2_attr_set;
-    int mx_kernel;       // cz_net_trunk_mx: 0 = not chosen yet, 1 = k_trunk_mx_c128, 2 = k_trunk_mx2_c128 (default; CCHESS_MX_KERNEL=1 selects the former)
+    int mx_kernel;       // cz_net_trunk_mx: 0 = not chosen yet, 1 = k_trunk_mx_c128, 2 = k_trunk_mx2_c128 (CCHESS_MX_KERNEL=2 selects the latter)
     void *mx_xbuf;       // k_trunk_mx2_c128's block-input scratch (98,304 B per workgroup), grown on demand
     size_t mx_xbuf_bytes;
+#endif
     int width;         // simulations in flight per tree the pending arrays are sized for (cz_search_set_width)
     void *pend_block;  // separate allocation of the pending arrays when width > 1
     int terminal_extra;   // cz_search_set_terminal_extra: terminal simulations a tree may complete inside one select launch
@@ -202,7 +204,7 @@ __host__ __device__ __forceinline__ uint16_t *czx_moves(const CzTrees &t) { retu
 __host__ __device__ __forceinline__ uint16_t *czx_sd(const CzTrees &t) { return reinterpret_cast<uint16_t *>(t.xc_base + czx_n(t) * 320 + 64); }
 __host__ __device__ __forceinline__ float *czx_P(const CzTrees &t) { return reinterpret_cast<float *>(t.xc_base + czx_n(t) * 576 + 64); }
 
-// ---- device helpers shared by cz_search.hip / cz_selfplay.hip -----------------------------------
+// ---- device helpers shared by cz_search.hip / cz_selfplay.hip / cz_match.hip ----------------------
 struct TreeView {
     float *P, *W, *Q;
     int32_t *N, *parent, *child_begin;
@@ -231,6 +233,53 @@ __device__ __forceinline__ void ec_clear_tree(const CzTrees &t, int g, int tid, 
     if (!t.ec_key) return;
     unsigned long long *k = t.ec_key + (size_t)g * CZ_EC_ENTRIES;
     for (int i = tid; i < CZ_EC_ENTRIES; i += nthreads) k[i] = 0ull;
+}
+
+// ---- a game at a root (the bench loop of cz_search.hip, cz_selfplay.hip, cz_match.hip) -----------
+// MCTS_tree.reload (main.py:255-259): a fresh, unexpanded root for tree g on the position the root has, by one wave64.
+// This is the whole list of what a fresh root owns besides its position: the counters, the pending leaf, node 0 and an
+// empty evaluation cache.  Of the pending leaf only pend_kind = 0 is ever observed (k_expand_backup returns on it before
+// it reads the other four, and select_body writes all five together); they are cleared with it so that the record of a
+// fresh root does not depend on the tree's past.
+__device__ __forceinline__ void fresh_root(const CzTrees &t, int g, int lane) {
+    if (lane == 0) {
+        t.root_node[g] = 0; t.n_nodes[g] = 1; t.status[g] = 0; t.sims[g] = 0; t.last_depth[g] = 0; t.root_ply[g] = 0;
+        t.pend_kind[g] = 0; t.pend_leaf[g] = 0; t.pend_value[g] = 0.f; t.pend_side[g] = 0; t.pend_nmoves[g] = 0;
+        init_root(view_of(t, g), 0);
+    }
+    ec_clear_tree(t, g, lane, 64);
+}
+// ... on position i of the caller's arrays: the squares boards[i * stride + 0 .. 89] (stored as the 96-byte root board, padding 0),
+// the mover side[i], the restrict round rr[i] (rr == nullptr: 0).  The arrays, not their values: only lane 0 reads side and rr.
+__device__ __forceinline__ void fresh_root(const CzTrees &t, int g, int lane, const uint8_t *__restrict__ boards, int stride,
+                                           const uint8_t *__restrict__ side, const int32_t *__restrict__ rr, int i) {
+    for (int j = lane; j < CZD_BOARD_LDS; j += 64)
+        t.root_board[(size_t)g * CZD_BOARD_LDS + j] = j < CZ_NSQ ? boards[(size_t)i * stride + j] : (uint8_t)0;
+    if (lane == 0) { t.root_side[g] = side[i] ? 1 : 0; t.root_rr[g] = rr ? rr[i] : 0; }
+    fresh_root(t, g, lane);
+}
+
+// check_end (main.py:1380-1392) on a 96-byte board, by one wave64: is the red king ('K' = 1) / the black king ('k' = 8) gone
+__device__ __forceinline__ void wave_kings_missing(const uint8_t *board, int lane, bool &Kmiss, bool &kmiss) {
+    const int c0 = board[lane], c1 = (lane + 64 < CZ_NSQ) ? board[lane + 64] : 0;
+    Kmiss = __ballot(c0 == 1 || c1 == 1) == 0ull;
+    kmiss = __ballot(c0 == 8 || c1 == 8) == 0ull;
+}
+// the side code of the winner when a king is gone: 'K' missing -> black = 1, 'k' missing -> red = 0 (main.py:1384-1389, 1534-1537)
+__device__ __forceinline__ int king_capture_winner(bool Kmiss) { return Kmiss ? 1 : 0; }
+// check_end's tie: 60 plies without a capture (main.py:1388-1390)
+__device__ __forceinline__ bool restrict_round_draw(int rr) { return rr >= 60; }
+
+// root.child.items() (main.py:1339): the root's n children start at node cb of the view; n = 0 for an unexpanded root
+__device__ __forceinline__ void root_children(const CzTrees &t, int g, const TreeView &v, int &cb, int &n) {
+    const int root = t.root_node[g];
+    cb = v.child_begin[root];
+    n = cb < 0 ? 0 : (int)v.child_count[root];
+}
+// the mover has no child to play: the node pool was exhausted at the root, or the rules kernels overflowed (the reference
+// has no node limit, so it has no such case); the driver's adjudication ends the game
+__device__ __forceinline__ bool root_cannot_move(int status, int n) {
+    return n == 0 || (status & (CZ_ST_NO_MOVES | CZ_ST_MOVE_OVERFLOW)) != 0;
 }
 
 // ---- move choice at a root (k_pick_ready, k_sp_choose, k_match_choose) ---------------------------

@@ -58,37 +58,22 @@ __device__ __forceinline__ long long global_game(const CzMatch &m, int game) {
     return 2 * (m.pair_base + m.pair_stride * (long long)(game >> 1)) + (game & 1);
 }
 
-// a fresh, unexpanded root on a position (MCTS_tree.reload, main.py:255-259), the tree's evaluation cache emptied
-__device__ __forceinline__ void fresh_tree(const CzTrees &t, int g, const uint8_t *board, int side, int rr, int lane) {
-    if (board)
-        for (int i = lane; i < CZD_BOARD_LDS; i += 64) t.root_board[(size_t)g * CZD_BOARD_LDS + i] = i < CZ_NSQ ? board[i] : (uint8_t)0;
-    if (lane == 0) {
-        if (board) { t.root_side[g] = (uint8_t)side; t.root_rr[g] = rr; }
-        t.root_node[g] = 0; t.n_nodes[g] = 1; t.status[g] = 0; t.sims[g] = 0; t.last_depth[g] = 0; t.root_ply[g] = 0;
-        t.pend_kind[g] = 0;
-        init_root(view_of(t, g), 0);
-    }
-    ec_clear_tree(t, g, lane, 64);
-}
-
 // slot g takes game `game` of the queue (both trees on its opening), or parks (game >= n_games): both trees keep a
 // fresh root with no simulation, and neither mover mask names the slot, so no search touches it again
 __device__ __forceinline__ void take_game(const CzTrees &ta, const CzTrees &tb, const CzMatch &m, int g, int game, int lane) {
     if (game < m.n_games) {
         const int p = game >> 1;
-        const uint8_t *ob = m.open_board + (size_t)p * CZ_NSQ;
-        const int side = m.open_side[p] ? 1 : 0, rr = m.open_rr[p];
-        fresh_tree(ta, g, ob, side, rr, lane);
-        fresh_tree(tb, g, ob, side, rr, lane);
+        fresh_root(ta, g, lane, m.open_board, CZ_NSQ, m.open_side, m.open_rr, p);
+        fresh_root(tb, g, lane, m.open_board, CZ_NSQ, m.open_side, m.open_rr, p);
         if (lane == 0) {
             const bool a_red = (game & 1) == 0;
-            const bool ma = (side == 0) == a_red;
+            const bool ma = (m.open_side[p] == 0) == a_red;
             m.game[g] = game; m.ply[g] = 0; m.stalled[g] = 0;
             m.mover_a[g] = ma ? 1 : 0; m.act_a[g] = ma ? 1 : 0; m.act_b[g] = ma ? 0 : 1;
         }
     } else {
-        fresh_tree(ta, g, nullptr, 0, 0, lane);
-        fresh_tree(tb, g, nullptr, 0, 0, lane);
+        fresh_root(ta, g, lane);
+        fresh_root(tb, g, lane);
         if (lane == 0) { m.game[g] = -1; m.act_a[g] = 0; m.act_b[g] = 0; m.stalled[g] = 0; }
     }
 }
@@ -105,11 +90,9 @@ __device__ __forceinline__ void choose_on(const CzTrees &t, const CzMatch &m, in
                                           unsigned long long seed, uint16_t *__restrict__ played, int lane) {
     if (lane == 0) atomicAdd(m.sims, (unsigned long long)t.sims[g]);
     const TreeView v = view_of(t, g);
-    const int root = t.root_node[g];
-    const int cb = v.child_begin[root];
-    const int n = cb < 0 ? 0 : (int)v.child_count[root];
-    if (n == 0 || (t.status[g] & (CZ_ST_NO_MOVES | CZ_ST_MOVE_OVERFLOW)) != 0) {
-        // no child to play (node pool exhausted at the root, or a rules overflow): the game is aborted by the adjudication
+    int cb, n;
+    root_children(t, g, v, cb, n);
+    if (root_cannot_move(t.status[g], n)) {   // the game is aborted by the adjudication
         if (lane == 0) { played[g] = 0xFFFF; m.stalled[g] = 1; }
         return;
     }
@@ -156,20 +139,17 @@ __global__ __launch_bounds__(64) void k_match_adjudicate(CzTrees ta, CzTrees tb,
     const int game = m.game[g];
     if (game < 0) return;
     const bool ma = m.mover_a[g] != 0;
-    const CzRecField<int32_t, offsetof(CzTreeRec, status)> mst = ma ? ta.status : tb.status, fst = ma ? tb.status : ta.status;
-    const bool aborted = m.stalled[g] != 0 || played[g] >= CZ_NLABELS || (mst[g] & CZ_ST_BAD_ADVANCE) != 0;
-    const uint8_t *rb = (ma ? ta.root_board : tb.root_board) + (size_t)g * CZD_BOARD_LDS;
-    const int c0 = rb[lane], c1 = (lane + 64 < CZ_NSQ) ? rb[lane + 64] : 0;
-    const bool Kmiss = (__ballot(c0 == 1) | __ballot(c1 == 1)) == 0ull;
-    const bool kmiss = (__ballot(c0 == 8) | __ballot(c1 == 8)) == 0ull;
+    const CzTrees &mv = ma ? ta : tb, &fo = ma ? tb : ta;   // the mover's tree, the follower's
+    const bool aborted = m.stalled[g] != 0 || played[g] >= CZ_NLABELS || (mv.status[g] & CZ_ST_BAD_ADVANCE) != 0;
+    bool Kmiss, kmiss;
+    wave_kings_missing(mv.root_board + (size_t)g * CZD_BOARD_LDS, lane, Kmiss, kmiss);
     const int ply = m.ply[g];
-    const int rr = ma ? ta.root_rr[g] : tb.root_rr[g];
     int reason = 0;
     if (aborted) reason = CZ_MATCH_ABORTED;
     else if (Kmiss || kmiss) reason = CZ_MATCH_KING;
-    else if (rr >= 60) reason = CZ_MATCH_RR60;
+    else if (restrict_round_draw(mv.root_rr[g])) reason = CZ_MATCH_RR60;
     else if (ply >= m.max_plies) reason = CZ_MATCH_PLY_CAP;
-    if (lane == 0) fst[g] &= ~CZ_ST_BAD_ADVANCE;
+    if (lane == 0) fo.status[g] &= ~CZ_ST_BAD_ADVANCE;
     if (!reason) {
         if (lane == 0) { m.mover_a[g] = ma ? 0 : 1; m.act_a[g] = ma ? 0 : 1; m.act_b[g] = ma ? 1 : 0; }
         return;
@@ -177,8 +157,7 @@ __global__ __launch_bounds__(64) void k_match_adjudicate(CzTrees ta, CzTrees tb,
     int next = 0;
     if (lane == 0) {
         const bool a_red = (game & 1) == 0;
-        // winner: 'K' missing -> black, 'k' missing -> red (main.py:1384-1389)
-        const bool a_wins = Kmiss ? !a_red : a_red;
+        const bool a_wins = (king_capture_winner(Kmiss) == 0) == a_red;
         m.result[game] = (int8_t)(reason == CZ_MATCH_KING ? (a_wins ? 1 : -1) : 0);
         m.a_red[game] = a_red ? 1 : 0;
         m.plies[game] = ply;

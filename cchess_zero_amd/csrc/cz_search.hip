@@ -17,26 +17,12 @@
 namespace {
 
 // ---- reset: MCTS_tree.__init__ / reload, main.py:235-259 ---------------------------------------
-__device__ __forceinline__ void reset_tree(const CzTrees &t, int g, int lane, const uint8_t *__restrict__ boards,
-                                           const uint8_t *__restrict__ side, const int32_t *__restrict__ rr) {
-    for (int i = lane; i < CZD_BOARD_LDS; i += 64)
-        t.root_board[(size_t)g * CZD_BOARD_LDS + i] = i < CZ_NSQ ? boards[(size_t)g * CZ_NSQ + i] : 0;
-    if (lane == 0) {
-        t.root_side[g] = side[g] ? 1 : 0;
-        t.root_rr[g] = rr ? rr[g] : 0;
-        t.root_node[g] = 0; t.n_nodes[g] = 1; t.status[g] = 0; t.sims[g] = 0; t.last_depth[g] = 0; t.root_ply[g] = 0;
-        t.pend_kind[g] = 0; t.pend_leaf[g] = 0; t.pend_value[g] = 0.f; t.pend_side[g] = 0; t.pend_nmoves[g] = 0;
-        init_root(view_of(t, g), 0);
-    }
-    ec_clear_tree(t, g, lane, 64);
-}
-
 __global__ __launch_bounds__(64) void k_reset(CzTrees t, const uint8_t *__restrict__ boards,
                                               const uint8_t *__restrict__ side, const int32_t *__restrict__ rr, int G,
                                               const uint8_t *__restrict__ which) {
     const int g = blockIdx.x, lane = threadIdx.x;
     if (g >= G || (which && !which[g])) return;   // cz_search_reload: only the trees whose game is over start afresh
-    reset_tree(t, g, lane, boards, side, rr);
+    fresh_root(t, g, lane, boards, CZ_NSQ, side, rr, g);
 }
 
 // ---- greedy re-rooting driver: the temperature -> 0 limit of get_action (main.py:1332-1341: softmax(log(visits) / 1e-3) is
@@ -52,9 +38,8 @@ __global__ __launch_bounds__(64) void k_pick_ready(CzTrees t, int G, int32_t *__
     uint16_t label = 0xFFFF;
     if (ready) {
         const TreeView v = view_of(t, g);
-        const int root = t.root_node[g];
-        const int cb = v.child_begin[root];
-        const int n = cb < 0 ? 0 : v.child_count[root];
+        int cb, n;
+        root_children(t, g, v, cb, n);
         // first maximum of N in generation order (Python max() over root.child.items())
         const int bi = wave_most_visited(v, cb, n, lane);
         if (n > 0) label = v.move[cb + bi];
@@ -72,13 +57,12 @@ __global__ __launch_bounds__(64) void k_reload_finished(CzTrees t, int G, const 
                                                         unsigned long long *__restrict__ reloaded) {
     const int g = blockIdx.x, lane = threadIdx.x;
     if (g >= G || !ready[g]) return;
-    const uint8_t *b = t.root_board + (size_t)g * CZD_BOARD_LDS;
-    const int c0 = b[lane], c1 = lane + 64 < CZ_NSQ ? b[lane + 64] : 0;
-    const bool hasK = __ballot(c0 == 1 || c1 == 1) != 0ull, hask = __ballot(c0 == 8 || c1 == 8) != 0ull;
+    bool Kmiss, kmiss;
+    wave_kings_missing(t.root_board + (size_t)g * CZD_BOARD_LDS, lane, Kmiss, kmiss);
     // check_end (main.py:1380-1392): a king is gone or 60 plies without a capture; a root without a move to play is over too
-    const bool over = !hasK || !hask || t.root_rr[g] >= 60 || played[g] == 0xFFFF;
+    const bool over = Kmiss || kmiss || restrict_round_draw(t.root_rr[g]) || played[g] == 0xFFFF;
     if (!over) return;
-    reset_tree(t, g, lane, boards, side, rr);
+    fresh_root(t, g, lane, boards, CZ_NSQ, side, rr, g);
     if (lane == 0 && reloaded) atomicAdd(reloaded, 1ull);
 }
 
@@ -221,7 +205,7 @@ __device__ __forceinline__ void select_body(const CzTrees &t, const CzTables &ta
         const TreeView v = view_of(t, g);
         const int root = t.root_node[g];
         const int root_rr = t.root_rr[g], root_side = side, s0 = t.sims[g];
-        // kings present on the root board ('K' = 1, 'k' = 8)
+        // kings present on the root board ('K' = 1, 'k' = 8); here and in k_select_k not wave_kings_missing, whose form compiles differently
         const int c0 = b[lane], c1 = (lane + 64 < CZ_NSQ) ? b[lane + 64] : 0;
         const bool Kmiss0 = (__ballot(c0 == 1) | __ballot(c1 == 1)) == 0ull;
         const bool kmiss0 = (__ballot(c0 == 8) | __ballot(c1 == 8)) == 0ull;
@@ -974,9 +958,8 @@ __global__ __launch_bounds__(64) void k_root_stats(CzTrees t, int G, uint16_t *_
     const int g = blockIdx.x, lane = threadIdx.x;
     if (g >= G) return;
     const TreeView v = view_of(t, g);
-    const int root = t.root_node[g];
-    const int cb = v.child_begin[root];
-    const int n = cb < 0 ? 0 : v.child_count[root];
+    int cb, n;
+    root_children(t, g, v, cb, n);
     if (lane == 0 && count) count[g] = (uint16_t)n;
     for (int i = lane; i < CZD_MAXMOVES; i += 64) {
         const size_t o = (size_t)g * CZD_MAXMOVES + i;
@@ -1034,10 +1017,9 @@ __device__ __forceinline__ void advance_tree(const CzTrees &t, const CzTables &t
     const TreeView v = view_of(t, g);
     unsigned long long *bits = LDS_BITS ? adv_lds : t.mark_bits + (size_t)g * t.words;                 // [t.words]
     uint32_t *rank = LDS_BITS ? (uint32_t *)(adv_lds + t.words) : t.mark_rank + (size_t)g * t.words;   // [t.words]
-    const int root = t.root_node[g];
     const int n = t.n_nodes[g];
-    const int cb = v.child_begin[root];
-    const int cc = cb < 0 ? 0 : v.child_count[root];
+    int cb, cc;
+    root_children(t, g, v, cb, cc);
     if (tid == 0) s_found = -1;
     __syncthreads();
     if (tid < cc && v.move[cb + tid] == l) s_found = cb + tid;
@@ -1054,6 +1036,7 @@ __device__ __forceinline__ void advance_tree(const CzTrees &t, const CzTables &t
     __syncthreads();
     const int found = s_found;
     if (found < 0) {
+        // not fresh_root: CZ_ADV_T threads, and the root keeps its ply and accumulated status
         if (tid == 0) {
             t.status[g] = (t.status[g] & ~CZ_ST_POOL_EXHAUSTED) | CZ_ST_BAD_ADVANCE;
             init_root(v, 0);

@@ -17,20 +17,6 @@
 
 namespace {
 
-__device__ __forceinline__ void seed_slot(const CzTrees &t, const CzSelfplay &sp, int g, int lane) {
-    // MCTS_tree.reload + GameBoard.reload (main.py:255-259, 582-588): a fresh, unexpanded root on the slot's start position
-    for (int i = lane; i < CZD_BOARD_LDS; i += 64)
-        t.root_board[(size_t)g * CZD_BOARD_LDS + i] = sp.start_board[(size_t)g * CZD_BOARD_LDS + i];
-    if (lane == 0) {
-        t.root_side[g] = sp.start_side[g];
-        t.root_rr[g] = sp.start_rr[g];
-        t.root_node[g] = 0; t.n_nodes[g] = 1; t.status[g] = 0; t.sims[g] = 0; t.last_depth[g] = 0; t.root_ply[g] = 0;
-        init_root(view_of(t, g), 0);
-        sp.ply[g] = 0; sp.stalled[g] = 0;
-    }
-    ec_clear_tree(t, g, lane, 64);
-}
-
 __global__ __launch_bounds__(64) void k_sp_seed(CzTrees t, CzSelfplay sp, int G, const uint8_t *__restrict__ boards,
                                                 const uint8_t *__restrict__ side, const int32_t *__restrict__ rr) {
     const int g = blockIdx.x, lane = threadIdx.x;
@@ -63,12 +49,9 @@ __global__ __launch_bounds__(64) void k_sp_choose(CzTrees t, CzSelfplay sp, int 
     }
     if (lane == 0) atomicAdd((unsigned long long *)&sp.stats[CZ_SP_SIMS], (unsigned long long)t.sims[g]);
     const TreeView v = view_of(t, g);
-    const int root = t.root_node[g];
-    const int cb = v.child_begin[root];
-    const int n = cb < 0 ? 0 : (int)v.child_count[root];
-    if (n == 0 || (t.status[g] & (CZ_ST_NO_MOVES | CZ_ST_MOVE_OVERFLOW)) != 0) {
-        // no child to play (node pool exhausted at the root, or a rules overflow): the game cannot continue; the
-        // adjudication drops it and re-seeds the slot (the reference has no node limit, so it has no such case)
+    int cb, n;
+    root_children(t, g, v, cb, n);
+    if (root_cannot_move(t.status[g], n)) {   // the adjudication drops the game and re-seeds the slot
         if (lane == 0) { played[g] = 0xFFFF; sp.stalled[g] = 1; }
         return;
     }
@@ -135,17 +118,14 @@ __global__ __launch_bounds__(64) void k_sp_adjudicate(CzTrees t, CzSelfplay sp, 
     if (!sp.active[g]) { if (lane == 0) fin_n[g] = 0; return; }
     // asynchronous plies: only the slots that just moved (or stalled) can have ended their game
     if (played && played[g] == 0xFFFF && !sp.stalled[g]) { if (lane == 0) fin_n[g] = 0; return; }
-    const uint8_t *rb = t.root_board + (size_t)g * CZD_BOARD_LDS;
-    const int c0 = rb[lane], c1 = (lane + 64 < CZ_NSQ) ? rb[lane + 64] : 0;
-    const bool Kmiss = (__ballot(c0 == 1) | __ballot(c1 == 1)) == 0ull;
-    const bool kmiss = (__ballot(c0 == 8) | __ballot(c1 == 8)) == 0ull;
+    bool Kmiss, kmiss;
+    wave_kings_missing(t.root_board + (size_t)g * CZD_BOARD_LDS, lane, Kmiss, kmiss);
     const int ply = sp.ply[g];
     const bool stalled = sp.stalled[g] != 0 || (t.status[g] & CZ_ST_BAD_ADVANCE) != 0;
     const bool decided = Kmiss || kmiss;
-    const bool draw = !decided && (t.root_rr[g] >= 60 || ply >= sp.max_plies);
+    const bool draw = !decided && (restrict_round_draw(t.root_rr[g]) || ply >= sp.max_plies);
     if (!(decided || draw || stalled)) { if (lane == 0) fin_n[g] = 0; return; }
-    // winner: 'K' missing -> "b", 'k' missing -> "w" (main.py:1534-1537); side codes 1 / 0
-    const int winner = Kmiss ? 1 : 0;
+    const int winner = king_capture_winner(Kmiss);
     const int n = stalled ? 0 : min(ply, sp.max_plies);
     for (int j = lane; j < n; j += 64) {
         uint8_t *rec = sp.hist + ((size_t)g * sp.max_plies + j) * CZ_REC_BYTES;
@@ -161,8 +141,10 @@ __global__ __launch_bounds__(64) void k_sp_adjudicate(CzTrees t, CzSelfplay sp, 
         else atomicAdd((unsigned long long *)&sp.stats[CZ_SP_DRAWS], 1ull);
         atomicAdd((unsigned long long *)&sp.stats[CZ_SP_PLIES], (unsigned long long)n);
     }
-    if (reseed) seed_slot(t, sp, g, lane);
-    else if (lane == 0) sp.active[g] = 0;
+    if (reseed) {   // the slot's next game: a fresh root on its start position
+        fresh_root(t, g, lane, sp.start_board, CZD_BOARD_LDS, sp.start_side, sp.start_rr, g);
+        if (lane == 0) { sp.ply[g] = 0; sp.stalled[g] = 0; }
+    } else if (lane == 0) sp.active[g] = 0;
 }
 
 // Copies the records of the games k_sp_adjudicate finished to ring[(offset[g] + j) % ring_records].  The offsets are an
