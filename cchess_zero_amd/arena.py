@@ -27,11 +27,18 @@ import time
 import numpy as np
 import torch
 
-from ._lib import MATCH_ABORTED, MATCH_KING, MATCH_PLY_CAP, MATCH_RR60, NSQ, check, lib, tables
+from ._lib import MATCH_ABORTED, MATCH_KING, MATCH_MATE, MATCH_PLY_CAP, MATCH_RR60, NSQ, check, lib, tables
 from .engine import SearchEngine, _ptr, plane_format, pool_nodes
 from .notation import player_to_side, state_to_board
 
-REASONS = {0: "unfinished", MATCH_KING: "king", MATCH_RR60: "rr60", MATCH_PLY_CAP: "ply_cap", MATCH_ABORTED: "aborted"}
+REASONS = {0: "unfinished", MATCH_KING: "king", MATCH_RR60: "rr60", MATCH_PLY_CAP: "ply_cap", MATCH_ABORTED: "aborted", MATCH_MATE: "mate"}
+RULES = {"capture": 0, "xiangqi": 1}   # cz_match_set_rules
+
+
+def is_scored(reason):
+    """A finished game that counts: every ending but "aborted" (a mate, rules="xiangqi", is a loss for the mated side)."""
+    reason = np.asarray(reason, np.int64)
+    return ((reason >= MATCH_KING) & (reason <= MATCH_PLY_CAP)) | (reason == MATCH_MATE)
 
 
 # ---- openings ------------------------------------------------------------------------------------------------------------
@@ -136,7 +143,7 @@ def pentanomial(result, reason):
     pairs (games 2p, 2p + 1) whose two games were both scored (an aborted game drops its pair)."""
     result = np.asarray(result, np.int64)
     reason = np.asarray(reason, np.int64)
-    scored = (reason >= MATCH_KING) & (reason <= MATCH_PLY_CAP)
+    scored = is_scored(reason)
     pair_ok = scored[0::2] & scored[1::2]
     x = (result[0::2] + 1) + (result[1::2] + 1)          # twice A's points of the pair: 0..4
     return np.bincount(x[pair_ok], minlength=5)[:5].astype(np.int64)
@@ -159,9 +166,10 @@ def pentanomial_interval(counts, z=1.959963984540054):
 class MatchResult:
     """Per game (global game index): result (+1 / 0 / -1 for A), a_red, plies, reason (REASONS), moves (ICCS labels).
     W / D / L for A overall and by colour over the scored games (aborted games excluded), score = (W + D / 2) / scored,
-    elo and its 95 % interval from the pentanomial distribution of the opening pairs, simulations, seconds, sims_per_s."""
+    elo and its 95 % interval from the pentanomial distribution of the opening pairs, simulations, seconds, sims_per_s;
+    rules ("capture" / "xiangqi") and mates: the games that ended because the mover had no king-safe move."""
 
-    def __init__(self, result, a_red, plies, reason, moves, simulations, seconds, players):
+    def __init__(self, result, a_red, plies, reason, moves, simulations, seconds, players, rules="capture"):
         self.result = np.asarray(result, np.int8)
         self.a_red = np.asarray(a_red, np.uint8)
         self.plies = np.asarray(plies, np.int32)
@@ -169,7 +177,9 @@ class MatchResult:
         lab = tables()["labels"] if moves is not None else None
         self.moves = [[lab[int(x)] for x in row if x != 0xFFFF] for row in moves] if moves is not None else None
         self.games = len(self.result)
-        scored = (self.reason >= MATCH_KING) & (self.reason <= MATCH_PLY_CAP)
+        scored = is_scored(self.reason)
+        self.rules = rules
+        self.mates = int((self.reason == MATCH_MATE).sum())
         self.aborted = int((self.reason == MATCH_ABORTED).sum())
         self.unfinished = int((self.reason == 0).sum())
         self.scored = int(scored.sum())
@@ -194,7 +204,7 @@ class MatchResult:
     def to_dict(self):
         """The summary (no per-game arrays): what `python -m cchess_zero_amd.arena` prints.  elo None = infinite (every
         scored game won or lost) or no scored game; an interval end None = unbounded on that side."""
-        return dict(games=self.games, scored=self.scored, aborted=self.aborted, unfinished=self.unfinished, W=self.wins,
+        return dict(rules=self.rules, mates=self.mates, games=self.games, scored=self.scored, aborted=self.aborted, unfinished=self.unfinished, W=self.wins,
                     D=self.draws, L=self.losses, by_colour=self.by_colour, score=self.score, elo=self.elo,
                     elo_95=None if self.elo_95 is None else list(self.elo_95), pentanomial=self.pentanomial.tolist(),
                     mean_plies=float(self.plies.mean()) if self.games else 0.0,
@@ -262,10 +272,15 @@ def _describe(p):
 class Match:
     """G = slots concurrent games of player A against player B over every opening with both colour assignments.
     max_plies: a game that reaches it is a draw; sample_plies: the first plies of a game are sampled from softmax(log N)
-    (temperature 1) with uniforms that are a pure function of (seed, game, ply), the rest are greedy (most visits)."""
+    (temperature 1) with uniforms that are a pure function of (seed, game, ply), the rest are greedy (most visits).
+    rules: "capture" — the reference's games: pseudo-legal moves, a game ends when a king is taken; "xiangqi" — the move is
+    chosen among the king-safe root children only (cz_movegen_kingsafe), and a mover without one has lost ("mate")."""
 
     def __init__(self, player_a, player_b, openings, slots, max_plies=512, sample_plies=0, seed=0, check_every=8,
-                 nodes_per_tree=None):
+                 nodes_per_tree=None, rules="capture"):
+        if rules not in RULES:
+            raise ValueError("Match: rules is 'capture' or 'xiangqi', not %r" % (rules,))
+        self.rules = rules
         self.players = [_player(player_a), _player(player_b)]
         self.openings = as_openings(openings)
         self.slots = int(slots)
@@ -292,7 +307,7 @@ class Match:
         if multi:
             local = merge_ranks(local, n_pairs, rank, world)
         return MatchResult(local["result"], local["a_red"], local["plies"], local["reason"], local["moves"], local["simulations"],
-                           local["seconds"], [_describe(p) for p in self.players])
+                           local["seconds"], [_describe(p) for p in self.players], rules=self.rules)
 
     def _play_local(self, op, pair_base, pair_stride):
         self.start(op, pair_base, pair_stride)
@@ -341,6 +356,8 @@ class Match:
         self._h = C.c_void_p()
         check(L.cz_match_create(ea.ctx.h, eb.ctx.h, *[_ptr(x) for x in self._op_dev], len(op), int(pair_base), int(pair_stride),
                                 self.max_plies, C.byref(self._h)), "cz_match_create")
+        if RULES[self.rules]:
+            check(L.cz_match_set_rules(self._h, RULES[self.rules]), "cz_match_set_rules")
         self.masks = []
         for player in (0, 1):
             p = C.c_void_p()
@@ -437,13 +454,15 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=0, help="openings and sampled plies")
     ap.add_argument("--max_plies", type=int, default=512, help="a game reaching it is a draw")
     ap.add_argument("--sample_plies", type=int, default=0, help="plies sampled from softmax(log N) at the start of a game")
+    ap.add_argument("--rules", choices=sorted(RULES), default="capture",
+                    help="capture: the reference's king-capture games; xiangqi: king-safe moves only, no safe move loses")
     args = ap.parse_args(argv)
     a = load_player(args.a, args.blocks)
     b = a if args.b == args.a else load_player(args.b, args.blocks)
     pairs = (args.games + 1) // 2
     op = random_openings(pairs, args.opening_plies, args.seed)
     res = Match((a, args.playout), (b, args.playout_b or args.playout), op, slots=args.slots or 2 * pairs, max_plies=args.max_plies,
-                sample_plies=args.sample_plies, seed=args.seed).play()
+                sample_plies=args.sample_plies, seed=args.seed, rules=args.rules).play()
     d = res.to_dict()
     d.update(a=args.a, b=args.b, blocks=args.blocks, opening_plies=args.opening_plies, slots=min(args.slots or 2 * pairs, 2 * pairs),
              seed=args.seed)

@@ -234,6 +234,15 @@ int cz_movegen_ex(cz_ctx *c, const uint8_t *boards, const uint8_t *side, int G, 
     CZ_REQUIRE(boards && side && count, "cz_movegen_ex: boards, side, count required");
     return czk_movegen(c, boards, side, G, moves, count, mask, flags);
 }
+int cz_movegen_kingsafe(cz_ctx *c, const uint8_t *boards, const uint8_t *side, int G, uint16_t *moves, uint16_t *count, uint32_t *mask,
+                        uint8_t *pos_flags, int flags) {
+    CZ_REQUIRE(c && G >= 0, "cz_movegen_kingsafe: null ctx / negative G");
+    CZ_REQUIRE((flags & ~CZ_MOVES_NO_PAD) == 0, "cz_movegen_kingsafe: unknown flag");
+    if (G == 0) return CZ_OK;
+    CZ_REQUIRE(boards && side, "cz_movegen_kingsafe: boards, side required");
+    CZ_REQUIRE(moves || count || mask || pos_flags, "cz_movegen_kingsafe: no output requested");
+    return czk_movegen_kingsafe(c, boards, side, G, moves, count, mask, pos_flags, flags);
+}
 int cz_apply_move(cz_ctx *c, uint8_t *boards, uint8_t *side, const uint16_t *label, int G, uint64_t *hash, uint8_t *captured, int8_t *terminal) {
     CZ_REQUIRE(c && G >= 0, "cz_apply_move: null ctx / negative G");
     if (G == 0) return CZ_OK;

@@ -16,6 +16,8 @@ struct cz_match {
     int G, n_games, max_plies;
     long long pair_base, pair_stride;   // global index of local opening p = pair_base + pair_stride * p (rank sharding)
     void *block;
+    int rules;                          // 0: king capture (the reference's games), 1: xiangqi (cz_match_set_rules)
+    void *xq_block;                     // rules = 1: the mover's root positions, their king-safe sets and the mated flags
 };
 
 namespace {
@@ -85,20 +87,77 @@ __global__ __launch_bounds__(64) void k_match_start(CzTrees ta, CzTrees tb, CzMa
     take_game(ta, tb, m, g, g, lane);
 }
 
-// get_action of the mover (main.py:1332-1341) on its own tree: greedy, or sampled for the game's first sample_plies plies
+// rules = 1 (cz_match_set_rules): what the xiangqi kernels have beside the match
+struct CzMatchXq {
+    uint8_t *board;     // [G][90] the mover's root position of every slot (an empty board for a parked slot)
+    uint8_t *side;      // [G]
+    uint32_t *safe;     // [G][66] its king-safe set (cz_movegen_kingsafe)
+    uint8_t *mated;     // [G] the last choose found children, none of them king-safe
+};
+
+// the first maximum of N over children 0 .. n - 1 (N[r] of child lane + 64 r), wave-uniform: wave_most_visited on registers
+__device__ __forceinline__ int wave_first_max(const int N[2], int n, int lane) {
+    int bn = -1, bi = 0x7fffffff;
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+        if (lane + 64 * r < n && N[r] > bn) { bn = N[r]; bi = lane + 64 * r; }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const int on = __shfl_xor(bn, d, 64), oi = __shfl_xor(bi, d, 64);
+        if (on > bn || (on == bn && oi < bi)) { bn = on; bi = oi; }
+    }
+    return bi;
+}
+
+// get_action of the mover (main.py:1332-1341) on its own tree: greedy, or sampled for the game's first sample_plies plies.
+// XQ: among the root children whose move is in the slot's king-safe set — they are compacted, in generation order, and the
+// choice runs on the compacted visit counts exactly as it runs on all children under king-capture rules
+template <bool XQ>
 __device__ __forceinline__ void choose_on(const CzTrees &t, const CzMatch &m, int g, int game, int sample_plies,
-                                          unsigned long long seed, uint16_t *__restrict__ played, int lane) {
+                                          unsigned long long seed, uint16_t *__restrict__ played, int lane, const CzMatchXq &x) {
     if (lane == 0) atomicAdd(m.sims, (unsigned long long)t.sims[g]);
     const TreeView v = view_of(t, g);
     int cb, n;
     root_children(t, g, v, cb, n);
+    if (XQ && lane == 0) x.mated[g] = 0;
     if (root_cannot_move(t.status[g], n)) {   // the game is aborted by the adjudication
         if (lane == 0) { played[g] = 0xFFFF; m.stalled[g] = 1; }
         return;
     }
     const int ply = m.ply[g];
     int pick;
-    if (ply < sample_plies) {
+    if constexpr (XQ) {
+        __shared__ int sN[128], sI[128];
+        const uint32_t *safe = x.safe + (size_t)g * CZ_MASK_WORDS;
+        bool ok[2];
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            const int i = lane + 64 * r;
+            const uint32_t mv = i < n ? v.move[cb + i] : 0xFFFFu;
+            ok[r] = mv < CZ_NLABELS && ((safe[mv >> 5] >> (mv & 31)) & 1u) != 0u;
+        }
+        const unsigned long long b0 = __ballot(ok[0]), b1 = __ballot(ok[1]), below = (1ull << lane) - 1ull;
+        const int n0 = __popcll(b0), ns = n0 + __popcll(b1);
+        if (ok[0]) { const int at = __popcll(b0 & below); sN[at] = v.N[cb + lane]; sI[at] = lane; }
+        if (ok[1]) { const int at = n0 + __popcll(b1 & below); sN[at] = v.N[cb + lane + 64]; sI[at] = lane + 64; }
+        __syncthreads();
+        if (ns == 0) {   // children, none of them king-safe: checkmate or stalemate, the mover loses (k_match_adjudicate_xq)
+            if (lane == 0) { played[g] = 0xFFFF; x.mated[g] = 1; }
+            return;
+        }
+        int N[2];
+#pragma unroll
+        for (int r = 0; r < 2; ++r) N[r] = lane + 64 * r < ns ? sN[lane + 64 * r] : 0;
+        int at;
+        if (ply < sample_plies) {
+            double pi[2];
+            wave_visit_policy(N, ns, 1.0, lane, pi);
+            at = wave_pick_inverse_cdf(pi, match_uniform(seed, global_game(m, game), ply), lane);
+        } else {
+            at = wave_first_max(N, ns, lane);
+        }
+        pick = sI[at];
+    } else if (ply < sample_plies) {
         // select_move -> get_action(state, temperature = 1) (main.py:1123,1433-1435): no Dirichlet noise
         int N[2] = {0, 0};
         double pi[2];
@@ -126,14 +185,35 @@ __global__ __launch_bounds__(64) void k_match_choose(CzTrees ta, CzTrees tb, CzM
     if (g >= m.G) return;
     const int game = m.game[g];
     if (game < 0) { if (lane == 0) played[g] = 0xFFFF; return; }
-    if (m.mover_a[g]) choose_on(ta, m, g, game, sample_plies, seed, played, lane);
-    else choose_on(tb, m, g, game, sample_plies, seed, played, lane);
+    if (m.mover_a[g]) choose_on<false>(ta, m, g, game, sample_plies, seed, played, lane, CzMatchXq{});
+    else choose_on<false>(tb, m, g, game, sample_plies, seed, played, lane, CzMatchXq{});
+}
+
+// rules = 1, before the choice: the mover's root position of every slot, for cz_movegen_kingsafe
+__global__ __launch_bounds__(64) void k_match_roots_xq(CzTrees ta, CzTrees tb, CzMatch m, CzMatchXq x) {
+    const int g = blockIdx.x, lane = threadIdx.x;
+    if (g >= m.G) return;
+    const bool live = m.game[g] >= 0;
+    const CzTrees &t = m.mover_a[g] ? ta : tb;
+    for (int j = lane; j < CZ_NSQ; j += 64) x.board[(size_t)g * CZ_NSQ + j] = live ? t.root_board[(size_t)g * CZD_BOARD_LDS + j] : (uint8_t)0;
+    if (lane == 0) x.side[g] = live ? t.root_side[g] : (uint8_t)0;
+}
+__global__ __launch_bounds__(64) void k_match_choose_xq(CzTrees ta, CzTrees tb, CzMatch m, int sample_plies, unsigned long long seed,
+                                                        uint16_t *__restrict__ played, CzMatchXq x) {
+    const int g = blockIdx.x, lane = threadIdx.x;
+    if (g >= m.G) return;
+    const int game = m.game[g];
+    if (game < 0) { if (lane == 0) played[g] = 0xFFFF; return; }
+    if (m.mover_a[g]) choose_on<true>(ta, m, g, game, sample_plies, seed, played, lane, x);
+    else choose_on<true>(tb, m, g, game, sample_plies, seed, played, lane, x);
 }
 
 // After cz_search_advance(played) on both contexts: the follower's failed advance (its root was never expanded, so it has no
 // child for the move) is its normal case — it starts a fresh root on the new position; then check_end (main.py:1380-1392)
 // plus the match's own endings (ply cap, aborted game), the result, and the slot's next game.
-__global__ __launch_bounds__(64) void k_match_adjudicate(CzTrees ta, CzTrees tb, CzMatch m, const uint16_t *__restrict__ played) {
+// mated (rules = 1 only, else nullptr): the slot's mover had no king-safe move — CZ_MATCH_MATE, before every other ending
+template <bool XQ>
+__device__ __forceinline__ void adjudicate_body(const CzTrees &ta, const CzTrees &tb, const CzMatch &m, const uint16_t *__restrict__ played, uint8_t *mated) {
     const int g = blockIdx.x, lane = threadIdx.x;
     if (g >= m.G) return;
     const int game = m.game[g];
@@ -145,7 +225,8 @@ __global__ __launch_bounds__(64) void k_match_adjudicate(CzTrees ta, CzTrees tb,
     wave_kings_missing(mv.root_board + (size_t)g * CZD_BOARD_LDS, lane, Kmiss, kmiss);
     const int ply = m.ply[g];
     int reason = 0;
-    if (aborted) reason = CZ_MATCH_ABORTED;
+    if (XQ && mated[g]) reason = CZ_MATCH_MATE;
+    else if (aborted) reason = CZ_MATCH_ABORTED;
     else if (Kmiss || kmiss) reason = CZ_MATCH_KING;
     else if (restrict_round_draw(mv.root_rr[g])) reason = CZ_MATCH_RR60;
     else if (ply >= m.max_plies) reason = CZ_MATCH_PLY_CAP;
@@ -158,7 +239,8 @@ __global__ __launch_bounds__(64) void k_match_adjudicate(CzTrees ta, CzTrees tb,
     if (lane == 0) {
         const bool a_red = (game & 1) == 0;
         const bool a_wins = (king_capture_winner(Kmiss) == 0) == a_red;
-        m.result[game] = (int8_t)(reason == CZ_MATCH_KING ? (a_wins ? 1 : -1) : 0);
+        m.result[game] = (int8_t)(reason == CZ_MATCH_KING ? (a_wins ? 1 : -1) : (reason == CZ_MATCH_MATE ? (ma ? -1 : 1) : 0));
+        if (XQ) mated[g] = 0;
         m.a_red[game] = a_red ? 1 : 0;
         m.plies[game] = ply;
         m.reason[game] = (uint8_t)reason;
@@ -167,6 +249,12 @@ __global__ __launch_bounds__(64) void k_match_adjudicate(CzTrees ta, CzTrees tb,
     }
     next = __shfl(next, 0, 64);
     take_game(ta, tb, m, g, next, lane);
+}
+__global__ __launch_bounds__(64) void k_match_adjudicate(CzTrees ta, CzTrees tb, CzMatch m, const uint16_t *__restrict__ played) {
+    adjudicate_body<false>(ta, tb, m, played, nullptr);
+}
+__global__ __launch_bounds__(64) void k_match_adjudicate_xq(CzTrees ta, CzTrees tb, CzMatch m, const uint16_t *__restrict__ played, uint8_t *mated) {
+    adjudicate_body<true>(ta, tb, m, played, mated);
 }
 
 }  // namespace
@@ -194,6 +282,18 @@ static size_t carve(const cz_match *mh, char *base, CzMatch &m) {
     m.plies = (int32_t *)take(n * 4);
     m.reason = (uint8_t *)take(n);
     m.moves = (uint16_t *)take(n * (size_t)mh->max_plies * 2);
+    return off;
+}
+
+// rules = 1: the arrays of the xiangqi kernels inside their own allocation
+static size_t carve_xq(const cz_match *mh, char *base, CzMatchXq &x) {
+    size_t off = 0;
+    auto take = [&](size_t bytes) { char *q = base ? base + off : nullptr; off += (bytes + 255) & ~(size_t)255; return q; };
+    const size_t G = (size_t)mh->G;
+    x.board = (uint8_t *)take(G * CZ_NSQ);
+    x.side = (uint8_t *)take(G);
+    x.safe = (uint32_t *)take(G * CZ_MASK_WORDS * 4);
+    x.mated = (uint8_t *)take(G);
     return off;
 }
 
@@ -252,10 +352,27 @@ int cz_match_create(cz_ctx *a, cz_ctx *b, const uint8_t *boards, const uint8_t *
     return CZ_OK;
 }
 
+int cz_match_set_rules(cz_match *mh, int rules) {
+    CZ_REQUIRE(mh && (rules == 0 || rules == 1), "cz_match_set_rules: rules 0 (king capture) or 1 (xiangqi)");
+    if (rules == 1 && !mh->xq_block) {
+        CzMatchXq sizing;
+        const size_t bytes = carve_xq(mh, nullptr, sizing);
+        if (hipMalloc(&mh->xq_block, bytes) != hipSuccess) {
+            mh->xq_block = nullptr;
+            cz_set_error("cz_match_set_rules: hipMalloc(%zu B) failed", bytes);
+            return CZ_ENOMEM;
+        }
+        CZ_HIP(hipMemsetAsync(mh->xq_block, 0, bytes, mh->a->stream));
+    }
+    mh->rules = rules;
+    return CZ_OK;
+}
+
 void cz_match_destroy(cz_match *mh) {
     if (!mh) return;
     (void)hipStreamSynchronize(mh->a->stream);
     (void)hipFree(mh->block);
+    if (mh->xq_block) (void)hipFree(mh->xq_block);
     delete mh;
 }
 
@@ -269,6 +386,17 @@ int cz_match_active(cz_match *mh, int player, const uint8_t **mask) {
 int cz_match_choose(cz_match *mh, int sample_plies, unsigned long long seed, uint16_t *played) {
     CZ_REQUIRE(mh && played && sample_plies >= 0, "cz_match_choose: null argument / sample_plies < 0");
     CZ_REQUIRE(mh->a->G == mh->G && mh->b->G == mh->G, "cz_match_choose: a context was reset to another number of slots");
+    if (mh->rules == 1) {   // the king-safe set of every slot's root position, then the choice among the children in it
+        CzMatchXq x;
+        carve_xq(mh, (char *)mh->xq_block, x);
+        hipLaunchKernelGGL(k_match_roots_xq, dim3(mh->G), dim3(64), 0, mh->a->stream, mh->a->t, mh->b->t, device_view(mh), x);
+        CZ_HIP(hipGetLastError());
+        const int rc = czk_movegen_kingsafe(mh->a, x.board, x.side, mh->G, nullptr, nullptr, x.safe, nullptr, 0);
+        if (rc != CZ_OK) return rc;
+        hipLaunchKernelGGL(k_match_choose_xq, dim3(mh->G), dim3(64), 0, mh->a->stream, mh->a->t, mh->b->t, device_view(mh), sample_plies, seed, played, x);
+        CZ_HIP(hipGetLastError());
+        return CZ_OK;
+    }
     hipLaunchKernelGGL(k_match_choose, dim3(mh->G), dim3(64), 0, mh->a->stream, mh->a->t, mh->b->t, device_view(mh), sample_plies, seed, played);
     CZ_HIP(hipGetLastError());
     return CZ_OK;
@@ -277,7 +405,13 @@ int cz_match_choose(cz_match *mh, int sample_plies, unsigned long long seed, uin
 int cz_match_adjudicate(cz_match *mh, const uint16_t *played) {
     CZ_REQUIRE(mh && played, "cz_match_adjudicate: null argument");
     CZ_REQUIRE(mh->a->G == mh->G && mh->b->G == mh->G, "cz_match_adjudicate: a context was reset to another number of slots");
-    hipLaunchKernelGGL(k_match_adjudicate, dim3(mh->G), dim3(64), 0, mh->a->stream, mh->a->t, mh->b->t, device_view(mh), played);
+    if (mh->rules == 1) {
+        CzMatchXq x;
+        carve_xq(mh, (char *)mh->xq_block, x);
+        hipLaunchKernelGGL(k_match_adjudicate_xq, dim3(mh->G), dim3(64), 0, mh->a->stream, mh->a->t, mh->b->t, device_view(mh), played, x.mated);
+    } else {
+        hipLaunchKernelGGL(k_match_adjudicate, dim3(mh->G), dim3(64), 0, mh->a->stream, mh->a->t, mh->b->t, device_view(mh), played);
+    }
     CZ_HIP(hipGetLastError());
     return CZ_OK;
 }

@@ -72,6 +72,33 @@ class Rules:
             self.check_counts(count)
         return moves, count, mask
 
+    def movegen_kingsafe(self, boards, side, want_mask=True, want_moves=True, pad=True):
+        """The king-safe moves of G positions (cz_movegen_kingsafe: get_legal_moves' list without the moves that leave the
+        mover's king attacked) -> (moves [G,128] i16(u16 bits) or None, count [G], mask [G,66] i32 or None, pos_flags [G] u8:
+        POS_IN_CHECK | POS_CAN_TAKE_KING | POS_NO_SAFE_MOVE).  pad=False: CZ_MOVES_NO_PAD, as in movegen.  A board movegen
+        refuses answers count -1 (0xFFFF) here too."""
+        self.ctx.bind_stream()   # torch's current stream
+        boards = self._dev(boards, torch.uint8).reshape(-1, NSQ)
+        side = self._dev(side, torch.uint8)
+        G = boards.shape[0]
+        moves = torch.empty((G, MAXMOVES), dtype=torch.int16, device=self.dev) if want_moves else None
+        count = torch.empty(G, dtype=torch.int16, device=self.dev)
+        mask = torch.empty((G, MASK_WORDS), dtype=torch.int32, device=self.dev) if want_mask else None
+        pos_flags = torch.empty(G, dtype=torch.uint8, device=self.dev)
+        check(lib().cz_movegen_kingsafe(self.ctx.h, _ptr(boards), _ptr(side), G, _ptr(moves), _ptr(count), _ptr(mask), _ptr(pos_flags), 0 if pad else 1),
+              "cz_movegen_kingsafe")
+        return moves, count, mask, pos_flags
+
+    def in_check(self, boards, side):
+        """-> pos_flags [G] u8 alone (bit 0: the side to move is in check, bit 1: it can take the king, bit 2: it has no
+        king-safe move): the launch that builds neither list nor set."""
+        self.ctx.bind_stream()   # torch's current stream
+        boards = self._dev(boards, torch.uint8).reshape(-1, NSQ)
+        side = self._dev(side, torch.uint8)
+        pos_flags = torch.empty(boards.shape[0], dtype=torch.uint8, device=self.dev)
+        check(lib().cz_movegen_kingsafe(self.ctx.h, _ptr(boards), _ptr(side), boards.shape[0], None, None, None, _ptr(pos_flags), 0), "cz_movegen_kingsafe")
+        return pos_flags
+
     @staticmethod
     def check_counts(count):
         """Raises if any position answered count 0xFFFF (k_movegen_list / k_movegen_mask refuse boards that are not a Xiangqi

@@ -132,6 +132,22 @@ int cz_movegen(cz_ctx *, const uint8_t *boards, const uint8_t *side, int G, uint
 #define CZ_MOVES_NO_PAD 1
 int cz_movegen_ex(cz_ctx *, const uint8_t *boards, const uint8_t *side, int G, uint16_t *moves,
                   uint16_t *count, uint32_t *mask, int flags);
+/* K1s KING-SAFE move generation.  No reference function: the reference plays king-capture games and its get_legal_moves
+ *     (main.py:743-1109, the generator this entry point filters) lets a side leave its king attacked.  Here a side is
+ *     ATTACKED when it has a king and the other side has a pseudo-legal move onto the king's square — the flying general
+ *     (main.py:1097-1107) is such a move — and a pseudo-legal move is KING-SAFE when the mover is not attacked after it (one
+ *     rule, also for a move that takes the king and for a board without the mover's king: every move is safe there).
+ *     moves [G][128]: the king-safe moves in get_legal_moves' order (0xFFFF padding; CZ_MOVES_NO_PAD as in cz_movegen_ex);
+ *     count [G]: their number; mask [G][66]: their set; pos_flags [G]: CZ_POS_*.  Any of the four may be NULL; with only
+ *     pos_flags (and / or count) this is the "in check?" query and neither list nor set rows are built.
+ *     Alignment as for cz_movegen: `moves` 16-byte aligned, everything else at any address.  A board cz_movegen answers with
+ *     count 0xFFFF answers count 0xFFFF here too (its rows are undefined, its flags 0).  Repetition and perpetual check /
+ *     chase are not rules of this library. */
+#define CZ_POS_IN_CHECK 1        /* the side to move is attacked */
+#define CZ_POS_CAN_TAKE_KING 2   /* the other side is attacked: the side to move can take its king */
+#define CZ_POS_NO_SAFE_MOVE 4    /* no king-safe move: checkmate or stalemate, both lost in Xiangqi */
+int cz_movegen_kingsafe(cz_ctx *, const uint8_t *boards, const uint8_t *side, int G, uint16_t *moves, uint16_t *count,
+                        uint32_t *mask, uint8_t *pos_flags, int flags);
 /* K2  replaces GameBoard.sim_do_action (main.py:647-702), is_kill_move (:226) and the king test
  *     (:409-413).  Updates boards/side in place.  hash: in/out incremental Zobrist (may be NULL);
  *     captured [G] = captured piece code or 0; terminal [G]: bit0 'K' missing, bit1 'k' missing.
@@ -363,10 +379,18 @@ int cz_selfplay_stats(cz_ctx *, long long *stats_dev);
 #define CZ_MATCH_RR60 2      /* 60 plies without a capture: a draw (main.py:1390) */
 #define CZ_MATCH_PLY_CAP 3   /* max_plies plies: a draw (the reference has no such limit) */
 #define CZ_MATCH_ABORTED 4   /* the mover had no child to play: not scored */
+#define CZ_MATCH_MATE 5      /* rules = 1: the mover had no king-safe move (checkmate or stalemate): it loses */
 typedef struct cz_match cz_match;
 int cz_match_create(cz_ctx *a, cz_ctx *b, const uint8_t *open_boards, const uint8_t *open_side, const int32_t *open_rr,
                     int n_openings, long long pair_base, long long pair_stride, int max_plies, cz_match **out);
 void cz_match_destroy(cz_match *);
+/* cz_match_set_rules: 0 = king capture (the default: the reference's games, everything above), 1 = xiangqi.  With 1,
+ *   cz_match_choose first computes the king-safe set (cz_movegen_kingsafe) of every live slot's root position and then chooses
+ *   as above AMONG THE ROOT CHILDREN WHOSE MOVE IS IN THAT SET, in generation order: greedy = the first maximum of N over them
+ *   (a king-safe child with N = 0 is eligible), sampled = softmax(log N) over them alone with the same uniform.  A root with
+ *   children, none of them king-safe: played = 0xFFFF, and cz_match_adjudicate ends the game with CZ_MATCH_MATE — a loss for
+ *   the mover, plies = the plies actually played — before it looks at anything else.  A root without children aborts as above. */
+int cz_match_set_rules(cz_match *, int rules);
 int cz_match_active(cz_match *, int player, const uint8_t **mask_dev);
 int cz_match_choose(cz_match *, int sample_plies, unsigned long long seed, uint16_t *played);
 int cz_match_adjudicate(cz_match *, const uint16_t *played);

@@ -2,7 +2,10 @@
 """Throughput of the stand-alone rules kernels (K1 move generation, K2 make-move, K3 planes) on a batch large
 enough to fill the chip: positions/s and the HBM traffic that implies (SURVEY §8d quotes K1 at 312 B/position for
 a nibble board + mask; this ABI moves 90 B board + 1 B side in, 256 B ordered list + 264 B mask + 2 B count out).
-usage: python tools/rules_bench.py [N positions, default 1048576]"""
+usage: python tools/rules_bench.py [N positions, default 1048576]
+       python tools/rules_bench.py --kingsafe [N]     the king-safe generator (cz_movegen_kingsafe) on N positions of
+           rules.random_positions against (a) the pseudo-legal kernels on the same positions and (b) the same answer composed from
+           cz_movegen + cz_apply_move + cz_movegen + torch; one JSON line at the end"""
 import os
 import sys
 import time
@@ -15,9 +18,97 @@ import bench  # noqa: E402  (synthetic position generator)
 from cchess_zero_amd.engine import Context  # noqa: E402
 from cchess_zero_amd.rules import Rules  # noqa: E402
 
-N = int(sys.argv[1]) if len(sys.argv) > 1 else 1 << 20
+KINGSAFE = "--kingsafe" in sys.argv
+_args = [a for a in sys.argv[1:] if a != "--kingsafe"]
+N = int(_args[0]) if _args else 1 << 20
 ctx = Context(1, 2, 0)
 rules = Rules(ctx)
+
+
+def kingsafe_leg():
+    """Median of 25 launches (device events, 3 warm-up launches) per form; (b) is a chain of launches: host clock around a
+    synchronise, median of 5, on the first 131 072 positions (it holds ~35 child boards and masks per position)."""
+    import json
+    from cchess_zero_amd._lib import tables
+    from cchess_zero_amd.rules import random_positions
+    boards, side, _ = random_positions(rules, N, seed=17)
+
+    def median_ms(fn, launches=25, warm=3):
+        for _ in range(warm):
+            fn()
+        torch.cuda.synchronize()
+        ts = []
+        for _ in range(launches):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            ts.append(e0.elapsed_time(e1))
+        ts.sort()
+        return ts[len(ts) // 2], ts[0], ts[-1]
+
+    forms = {
+        "kingsafe_flags_only": lambda: rules.in_check(boards, side),
+        "kingsafe_set_only": lambda: rules.movegen_kingsafe(boards, side, want_moves=False),
+        "kingsafe_list_and_set": lambda: rules.movegen_kingsafe(boards, side, pad=False),
+        "pseudo_mask_kernel": lambda: rules.movegen(boards, side, want_moves=False),
+        "pseudo_list_and_mask_kernel": lambda: rules.movegen(boards, side, pad=False),
+    }
+    out = {"positions": N}
+    for name, fn in forms.items():
+        med, lo, hi = median_ms(fn)
+        out[name] = dict(ms=round(med, 4), min_ms=round(lo, 4), max_ms=round(hi, 4), positions_per_s=round(N / med * 1e3))
+        print("%-28s: median %.3f ms (min %.3f, max %.3f) = %.3f G positions/s" % (name, med, lo, hi, N / med / 1e6))
+    # (b) today's kernels composed: every pseudo-legal move applied to a copy of its position, the replies' set, and the bit
+    # test "does a reply land on the mover's king" in torch
+    M = min(N, 131072)
+    sd = tables()["srcdst"].astype(np.int64)
+    onto = np.zeros((90, 66), np.int64)
+    for l in range(len(sd)):
+        onto[sd[l] >> 8, l >> 5] |= 1 << (l & 31)
+    onto = torch.from_numpy(onto.astype(np.uint32).view(np.int32)).cuda()
+
+    def composed():
+        b, s = boards[:M], side[:M]
+        mv, cnt, _ = rules.movegen(b, s, want_mask=False)
+        c = cnt.to(torch.int64) & 0xFFFF
+        parent = torch.repeat_interleave(torch.arange(M, device=b.device), c)
+        first = torch.cumsum(c, 0) - c
+        k = torch.arange(parent.numel(), device=b.device) - first[parent]
+        lab = mv[parent, k].contiguous()
+        cb, cs = b[parent].contiguous(), s[parent].contiguous()
+        rules.apply_move(cb, cs, lab)
+        _, _, reply = rules.movegen(cb, cs, want_moves=False)
+        king = (cb == torch.where(s[parent] == 0, 1, 8).to(torch.uint8).unsqueeze(1))
+        has_king, ksq = king.any(1), king.to(torch.uint8).argmax(1)
+        unsafe = has_king & ((reply & onto[ksq]) != 0).any(1)
+        safe_count = torch.zeros(M, dtype=torch.int64, device=b.device).index_add_(0, parent, (~unsafe).to(torch.int64))
+        return safe_count, parent.numel()
+
+    sc, children = composed()
+    _, kc, _, _ = rules.movegen_kingsafe(boards[:M], side[:M], want_moves=False)
+    assert torch.equal(sc, kc.to(torch.int64) & 0xFFFF), "the composed answer and cz_movegen_kingsafe disagree"
+    ts = []
+    for _ in range(5):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        composed()
+        torch.cuda.synchronize()
+        ts.append((time.perf_counter() - t0) * 1e3)
+    ts.sort()
+    out["composed"] = dict(positions=M, child_positions=children, ms=round(ts[2], 3), positions_per_s=round(M / ts[2] * 1e3))
+    print("%-28s: median %.3f ms for %d positions (%d child positions) = %.4f G positions/s" % ("composed (b)", ts[2], M, children, M / ts[2] / 1e6))
+    ks = out["kingsafe_set_only"]["positions_per_s"]
+    out["set_vs_pseudo_mask_kernel"] = round(ks / out["pseudo_mask_kernel"]["positions_per_s"], 4)
+    out["list_and_set_vs_pseudo_list_kernel"] = round(out["kingsafe_list_and_set"]["positions_per_s"] / out["pseudo_list_and_mask_kernel"]["positions_per_s"], 4)
+    out["set_vs_composed"] = round(ks / out["composed"]["positions_per_s"], 2)
+    print(json.dumps(out), flush=True)
+
+
+if KINGSAFE:
+    kingsafe_leg()
+    sys.exit(0)
 b0, s0, _ = bench.synth_positions(rules, 8192, seed=5)
 rep = (N + 8191) // 8192
 boards = b0.repeat(rep, 1)[:N].contiguous()
