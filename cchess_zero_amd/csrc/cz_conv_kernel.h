@@ -10,8 +10,10 @@
 //   k_tower8_c128    first conv + ALL residual blocks + head 1x1 convs in ONE launch, activations resident in
 //                    LDS across layers, weights streamed L2 -> LDS by LDS-DMA, hand-scheduled slab loop
 //                    (see the block comment in front of it); bf16 or fp16 operands;
-//   k_trunk_x3       (cz_trunk_split.h) the same launch with every operand split into two 16-bit halves
-//                    (three MFMAs per product): the strict-precision engine.
+//   k_trunk_split_c128  (cz_trunk_split.h) the same launch with every operand split into two 16-bit halves
+//                    (three MFMAs per product), and k_trunk_mx_c128 (cz_trunk_mx.h), which folds the two cross terms
+//                    into one fp6 MFMA: the strict-precision engines.  cz_trunk_common.h holds what the three
+//                    launches share outside their layer loops.
 // The measured alternatives of rounds 1-3 (2 positions / 4 waves, one position per wave, two workgroups per CU,
 // skewed half-workgroups, ring-free) live in tools/experiments/ — they are not part of the library.
 // Common: GEMM view per layer M = B*90 board cells, N = 128, K = 9 taps * 128; v_mfma_f32_32x32x16_bf16 with
@@ -20,6 +22,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "cz_trunk_common.h"
 
 namespace czconv {
 
@@ -393,15 +396,7 @@ __global__ __launch_bounds__(P * 128, 2) void k_tower8_c128(const uint16_t *__re
         return row_of(p, y, x) * CV_ROWB + ((c ^ key_of(p, y, x)) << 4);
     };
 
-    auto dma_slab = [&](int slab) {   // prologue only; the loop issues its DMAs from the slab asm
-        const unsigned char *src = reinterpret_cast<const unsigned char *>(wpk) + (size_t)slab * Geo::SLAB_BYTES;
-        unsigned char *dst = smem + Geo::W_OFF + ((unsigned)slab & 3u) * Geo::SLAB_BYTES + (wave_u << 10);
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(src + voff0),
-                                         (__attribute__((address_space(3))) void *)dst, 16, 0, 0);
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(src + voff1),
-                                         (__attribute__((address_space(3))) void *)(dst + Geo::THREADS * 16), 16, 0, 0);
-    };
-    for (int q = 0; q < 3; ++q) dma_slab(q < nslabs ? q : nslabs - 1);
+    trunk_ring_prologue<Geo>(smem, reinterpret_cast<const unsigned char *>(wpk), nslabs, wave_u, voff0, voff1);
     if (planes == nullptr) {
         const uint4 *g = reinterpret_cast<const uint4 *>(in + (size_t)pos0 * 90 * 128);
         for (int idx = tid; idx < Geo::ROWS * 16; idx += Geo::THREADS) {
@@ -411,12 +406,7 @@ __global__ __launch_bounds__(P * 128, 2) void k_tower8_c128(const uint16_t *__re
             *reinterpret_cast<uint4 *>(smem + lds_of_natural(r, c)) = v;
         }
     } else {
-        const uint4 *g = reinterpret_cast<const uint4 *>(planes + (size_t)pos0 * 90 * 16);
-        for (int idx = tid; idx < Geo::ROWS * 2; idx += Geo::THREADS) {
-            uint4 v = make_uint4(0, 0, 0, 0);
-            if (idx < nrows * 2) v = g[idx];
-            *reinterpret_cast<uint4 *>(smem + Geo::PLANES_OFF + (idx << 4)) = v;
-        }
+        trunk_stage_planes<Geo>(smem, planes, pos0, nrows, tid);
     }
     if (tid < 16) *reinterpret_cast<uint4 *>(smem + Geo::ZERO_OFF + (tid << 4)) = make_uint4(0, 0, 0, 0);
     // the head conv weights are fetched here, behind the loads the prologue waits for anyway (the first version fetched
@@ -585,8 +575,7 @@ __global__ __launch_bounds__(P * 128, 2) void k_tower8_c128(const uint16_t *__re
         __syncthreads();
     }
 
-#define T8_SLAB(ASMSTR, NAB, NKEY)                                                                               \
-        asm volatile(ASMSTR                                                                                      \
+#define T8_OPERANDS(NAB, NKEY)                                                                                   \
             : [c00] "+v"(acc[0][0]), [c01] "+v"(acc[0][1]), [c10] "+v"(acc[1][0]), [c11] "+v"(acc[1][1]),          \
               [c20] "+v"(acc[2][0]), [c21] "+v"(acc[2][1]),                                                        \
               [f0a0] "+v"(f0.a[0]), [f0a1] "+v"(f0.a[1]), [f0a2] "+v"(f0.a[2]), [f0b0] "+v"(f0.b[0]), [f0b1] "+v"(f0.b[1]), \
@@ -595,25 +584,12 @@ __global__ __launch_bounds__(P * 128, 2) void k_tower8_c128(const uint16_t *__re
             : [ab0] "v"(ab[0]), [ab1] "v"(ab[1]), [ab2] "v"(ab[2]), [key0] "v"(key[0]), [key1] "v"(key[1]),          \
               [key2] "v"(key[2]), [nab0] "v"(NAB[0]), [nab1] "v"(NAB[1]), [nab2] "v"(NAB[2]), [nkey0] "v"(NKEY[0]),   \
               [nkey1] "v"(NKEY[1]), [nkey2] "v"(NKEY[2]), [vb] "v"(vb), [vbn] "v"(vbn), [voff0] "v"(voff0),          \
-              [voff1] "v"(voff1), [sbase] "s"(sbase), [ldst] "s"(ldst)                                                \
-            : "memory", "scc")   /* the bodies' s_add_u32 (M0 stepping) writes SCC */
-#define T8_SLAB_ARGS()                                                                                          \
-        const int vb = vb0 + (((unsigned)g & 3u) << Geo::SLAB_SHIFT), vbn = vb0 + ((((unsigned)g + 1u) & 3u) << Geo::SLAB_SHIFT); \
-        const int gn = g + 3 < nslabs ? g + 3 : nslabs - 1;                                                     \
-        const unsigned char *sbase = reinterpret_cast<const unsigned char *>(wpk) + (size_t)gn * Geo::SLAB_BYTES; \
-        const int ldst = Geo::W_OFF + ((((unsigned)g + 3u) & 3u) << Geo::SLAB_SHIFT) + (wave_u << 10);
-#define T8_SLABV(ASMSTR, NAB, NKEY)   /* the same operands + the wave-uniform skip mask; clobbers VCC */                 \
-        asm volatile(ASMSTR                                                                                      \
-            : [c00] "+v"(acc[0][0]), [c01] "+v"(acc[0][1]), [c10] "+v"(acc[1][0]), [c11] "+v"(acc[1][1]),          \
-              [c20] "+v"(acc[2][0]), [c21] "+v"(acc[2][1]),                                                        \
-              [f0a0] "+v"(f0.a[0]), [f0a1] "+v"(f0.a[1]), [f0a2] "+v"(f0.a[2]), [f0b0] "+v"(f0.b[0]), [f0b1] "+v"(f0.b[1]), \
-              [f1a0] "=&v"(f1.a[0]), [f1a1] "=&v"(f1.a[1]), [f1a2] "=&v"(f1.a[2]), [f1b0] "=&v"(f1.b[0]), [f1b1] "=&v"(f1.b[1]), \
-              [t0] "=&v"(t0), [t1] "=&v"(t1), [t2] "=&v"(t2), [keep] "=&s"(keep)                                     \
-            : [ab0] "v"(ab[0]), [ab1] "v"(ab[1]), [ab2] "v"(ab[2]), [key0] "v"(key[0]), [key1] "v"(key[1]),          \
-              [key2] "v"(key[2]), [nab0] "v"(NAB[0]), [nab1] "v"(NAB[1]), [nab2] "v"(NAB[2]), [nkey0] "v"(NKEY[0]),   \
-              [nkey1] "v"(NKEY[1]), [nkey2] "v"(NKEY[2]), [vb] "v"(vb), [vbn] "v"(vbn), [voff0] "v"(voff0),          \
-              [voff1] "v"(voff1), [sbase] "s"(sbase), [ldst] "s"(ldst), [skipm] "s"(skipm)                            \
-            : "memory", "vcc", "scc")
+              [voff1] "v"(voff1), [sbase] "s"(sbase), [ldst] "s"(ldst)
+#define T8_SLAB(ASMSTR, NAB, NKEY)    /* the bodies' s_add_u32 (M0 stepping) writes SCC */                        \
+        asm volatile(ASMSTR T8_OPERANDS(NAB, NKEY) : "memory", "scc")
+#define T8_SLABV(ASMSTR, NAB, NKEY)   /* the same operands + the wave-uniform skip mask; clobbers VCC */          \
+        asm volatile(ASMSTR T8_OPERANDS(NAB, NKEY), [skipm] "s"(skipm) : "memory", "vcc", "scc")
+#define T8_SLAB_ARGS() TRUNK_SLAB_ARGS(reinterpret_cast<const unsigned char *>(wpk), )
 #define T8_RUNV(BF, HF, NAB, NKEY)                                                                              \
         {                                                                                                       \
             T8_SLAB_ARGS()                                                                                      \
@@ -755,6 +731,7 @@ __global__ __launch_bounds__(P * 128, 2) void k_tower8_c128(const uint16_t *__re
         }
     }
 }
+#undef T8_OPERANDS
 #undef T8_SLAB
 #undef T8_SLABV
 #undef T8_SLAB_ARGS

@@ -12,8 +12,7 @@
 // (a_hi*w_hi) go to: 9 MFMAs per slab and wave instead of 18, 1.5 instead of 3 fp16-MFMA-equivalents per product.
 // Precision (tools/precision_mx_schemes.py, tests/mxemu.py): the cross terms keep 4 significant bits of each operand, i.e.
 // ~2^-16 of a product — 30-40x closer to fp32 than the one-value-per-operand fp16 engine, 15x further than three fp16 MFMAs:
-// |dlogit| 4.9e-4 / |dvalue| 2.2e-4 on trained-like weights at 7 blocks, 1.0e-3 / 1.1e-3 at 19 (so precision "strict" uses
-// this kernel up to 8 blocks and k_trunk_split_c128 beyond).
+// |dlogit| 4.9e-4 / |dvalue| 2.2e-4 on trained-like weights at 7 blocks, 1.0e-3 / 1.1e-3 at 19.
 // What was measured before this was built (tools/experiments/mx_probe.hip, profiles/r05a_mx_probe.txt): the fp6 conversion
 // v_cvt_scalef32_2xpk16_fp6_f32 d, s0, s1, scale puts q(s0[i] / 2^floor(log2 scale)) in slot 2i and q(s1[i] / ...) in slot
 // 2i+1 (RNE, saturating at 7.5) — and hipcc lets its builtin's destination overlap the sources (garbage from slot 12 on): it is
@@ -113,23 +112,8 @@ __global__ __launch_bounds__(512, 2) void k_trunk_mx_c128(const unsigned char *_
         return 20 * y + 10 * p + x;
     };
 
-    auto dma_slab = [&](int slab) {   // prologue only; the loop issues its DMAs from the slab asm
-        const unsigned char *src = wpk + (size_t)slab * Geo::SLAB_BYTES;
-        unsigned char *dst = smem + Geo::W_OFF + ((unsigned)slab & 3u) * Geo::SLAB_BYTES + (wave_u << 10);
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(src + voff0),
-                                         (__attribute__((address_space(3))) void *)dst, 16, 0, 0);
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(src + voff1),
-                                         (__attribute__((address_space(3))) void *)(dst + Geo::THREADS * 16), 16, 0, 0);
-    };
-    for (int q = 0; q < 3; ++q) dma_slab(q < nslabs ? q : nslabs - 1);
-    {
-        const uint4 *g = reinterpret_cast<const uint4 *>(planes + (size_t)pos0 * 90 * 16);
-        for (int idx = tid; idx < Geo::ROWS * 2; idx += Geo::THREADS) {
-            uint4 v = make_uint4(0, 0, 0, 0);
-            if (idx < nrows * 2) v = g[idx];
-            *reinterpret_cast<uint4 *>(smem + Geo::PLANES_OFF + (idx << 4)) = v;
-        }
-    }
+    trunk_ring_prologue<Geo>(smem, wpk, nslabs, wave_u, voff0, voff1);
+    trunk_stage_planes<Geo>(smem, planes, pos0, nrows, tid);
     // zero row of the hi halves; zero aliases 192 .. 223 of the X / Y planes; scale 127 (= 2^0) in the aliases of SC
     if (tid < 16) *reinterpret_cast<uint4 *>(smem + Geo::ZERO_OFF + (tid << 4)) = make_uint4(0, 0, 0, 0);
     if (tid < 256) *reinterpret_cast<uint4 *>(smem + Geo::X_OFF + (tid >> 5) * Geo::XPLANE + (192 + (tid & 31)) * 16) = make_uint4(0, 0, 0, 0);
@@ -302,12 +286,7 @@ __global__ __launch_bounds__(512, 2) void k_trunk_mx_c128(const unsigned char *_
 #define MX_CLOBBERS "memory", "scc", "v232", "v233", "v234", "v235", "v236", "v237", "v238", "v239", "v240", "v241", "v242", "v243", \
                     "v244", "v245", "v246", "v247", "v248", "v249", "v250", "v251", "v252", "v253", "v254", "v255"
 #define MX_ARGS()                                                                                                    \
-            const int slot = ((unsigned)g & 3u) << Geo::SLAB_SHIFT;                                                  \
-            const int vb = vb0 + slot, vy = vy0 + slot, vs = vs0 + slot;                                             \
-            const int vbn = vb0 + ((((unsigned)g + 1u) & 3u) << Geo::SLAB_SHIFT);                                    \
-            const int gn = g + 3 < nslabs ? g + 3 : nslabs - 1;                                                      \
-            const unsigned char *sbase = wpk + (size_t)gn * Geo::SLAB_BYTES;                                         \
-            const int ldst = Geo::W_OFF + ((((unsigned)g + 3u) & 3u) << Geo::SLAB_SHIFT) + (wave_u << 10);
+            TRUNK_SLAB_ARGS(wpk, const int vy = vy0 + slot; const int vs = vs0 + slot;)   /* + the fp6 blocks' last 8 bytes and their scale dwords */
 #define MX_RUN(ASMSTR, NAB, NKEY)                                                                                    \
         {                                                                                                            \
             MX_ARGS()                                                                                                \

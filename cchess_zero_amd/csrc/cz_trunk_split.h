@@ -139,23 +139,8 @@ __global__ __launch_bounds__(512, 2) void k_trunk_split_c128(const uint16_t *__r
         return 20 * y + 10 * p + x;
     };
 
-    auto dma_slab = [&](int slab) {   // prologue only; the loop issues its DMAs from the slab asm
-        const unsigned char *src = reinterpret_cast<const unsigned char *>(wpk) + (size_t)slab * Geo::SLAB_BYTES;
-        unsigned char *dst = smem + Geo::W_OFF + ((unsigned)slab & 3u) * Geo::SLAB_BYTES + (wave_u << 10);
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(src + voff0),
-                                         (__attribute__((address_space(3))) void *)dst, 16, 0, 0);
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(src + voff1),
-                                         (__attribute__((address_space(3))) void *)(dst + Geo::THREADS * 16), 16, 0, 0);
-    };
-    for (int q = 0; q < 3; ++q) dma_slab(q < nslabs ? q : nslabs - 1);
-    {
-        const uint4 *g = reinterpret_cast<const uint4 *>(planes + (size_t)pos0 * 90 * 16);
-        for (int idx = tid; idx < Geo::ROWS * 2; idx += Geo::THREADS) {
-            uint4 v = make_uint4(0, 0, 0, 0);
-            if (idx < nrows * 2) v = g[idx];
-            *reinterpret_cast<uint4 *>(smem + Geo::PLANES_OFF + (idx << 4)) = v;
-        }
-    }
+    trunk_ring_prologue<Geo>(smem, reinterpret_cast<const unsigned char *>(wpk), nslabs, wave_u, voff0, voff1);
+    trunk_stage_planes<Geo>(smem, planes, pos0, nrows, tid);
     if (tid < 16) {
         *reinterpret_cast<uint4 *>(smem + Geo::ZERO_OFF + (tid << 4)) = make_uint4(0, 0, 0, 0);
         *reinterpret_cast<uint4 *>(smem + Geo::ZERO_OFF + Geo::LO_OFF + (tid << 4)) = make_uint4(0, 0, 0, 0);
@@ -270,8 +255,7 @@ __global__ __launch_bounds__(512, 2) void k_trunk_split_c128(const uint16_t *__r
         __syncthreads();
     }
 
-#define XS_SLAB(ASMSTR, NAB, NKEY)                                                                               \
-        asm volatile(ASMSTR                                                                                      \
+#define XS_OPERANDS(NAB, NKEY)                                                                                  \
             : [c0] "+v"(acc[0]), [c1] "+v"(acc[1]), [c2] "+v"(acc[2]),                                             \
               [f0ah0] "+v"(f0.ah[0]), [f0ah1] "+v"(f0.ah[1]), [f0ah2] "+v"(f0.ah[2]),                             \
               [f0al0] "+v"(f0.al[0]), [f0al1] "+v"(f0.al[1]), [f0al2] "+v"(f0.al[2]),                             \
@@ -283,28 +267,12 @@ __global__ __launch_bounds__(512, 2) void k_trunk_split_c128(const uint16_t *__r
             : [ab0] "v"(ab[0]), [ab1] "v"(ab[1]), [ab2] "v"(ab[2]), [key0] "v"(key[0]), [key1] "v"(key[1]),          \
               [key2] "v"(key[2]), [nab0] "v"(NAB[0]), [nab1] "v"(NAB[1]), [nab2] "v"(NAB[2]), [nkey0] "v"(NKEY[0]),   \
               [nkey1] "v"(NKEY[1]), [nkey2] "v"(NKEY[2]), [vb] "v"(vb), [vbn] "v"(vbn), [voff0] "v"(voff0),          \
-              [voff1] "v"(voff1), [sbase] "s"(sbase), [ldst] "s"(ldst)                                                \
-            : "memory", "scc")
-#define XS_SLABV(ASMSTR, NAB, NKEY)   /* the same operands + the wave-uniform skip mask; clobbers VCC */                 \
-        asm volatile(ASMSTR                                                                                      \
-            : [c0] "+v"(acc[0]), [c1] "+v"(acc[1]), [c2] "+v"(acc[2]),                                             \
-              [f0ah0] "+v"(f0.ah[0]), [f0ah1] "+v"(f0.ah[1]), [f0ah2] "+v"(f0.ah[2]),                             \
-              [f0al0] "+v"(f0.al[0]), [f0al1] "+v"(f0.al[1]), [f0al2] "+v"(f0.al[2]),                             \
-              [f0wh] "+v"(f0.wh), [f0wl] "+v"(f0.wl),                                                            \
-              [f1ah0] "=&v"(f1.ah[0]), [f1ah1] "=&v"(f1.ah[1]), [f1ah2] "=&v"(f1.ah[2]),                          \
-              [f1al0] "=&v"(f1.al[0]), [f1al1] "=&v"(f1.al[1]), [f1al2] "=&v"(f1.al[2]),                          \
-              [f1wh] "=&v"(f1.wh), [f1wl] "=&v"(f1.wl),                                                          \
-              [t0] "=&v"(t0), [t1] "=&v"(t1), [t2] "=&v"(t2), [keep] "=&s"(keep)                                     \
-            : [ab0] "v"(ab[0]), [ab1] "v"(ab[1]), [ab2] "v"(ab[2]), [key0] "v"(key[0]), [key1] "v"(key[1]),          \
-              [key2] "v"(key[2]), [nab0] "v"(NAB[0]), [nab1] "v"(NAB[1]), [nab2] "v"(NAB[2]), [nkey0] "v"(NKEY[0]),   \
-              [nkey1] "v"(NKEY[1]), [nkey2] "v"(NKEY[2]), [vb] "v"(vb), [vbn] "v"(vbn), [voff0] "v"(voff0),          \
-              [voff1] "v"(voff1), [sbase] "s"(sbase), [ldst] "s"(ldst), [skipm] "s"(skipm)                            \
-            : "memory", "vcc", "scc")
-#define XS_ARGS()                                                                                               \
-            const int vb = vb0 + (((unsigned)g & 3u) << Geo::SLAB_SHIFT), vbn = vb0 + ((((unsigned)g + 1u) & 3u) << Geo::SLAB_SHIFT); \
-            const int gn = g + 3 < nslabs ? g + 3 : nslabs - 1;                                                 \
-            const unsigned char *sbase = reinterpret_cast<const unsigned char *>(wpk) + (size_t)gn * Geo::SLAB_BYTES; \
-            const int ldst = Geo::W_OFF + ((((unsigned)g + 3u) & 3u) << Geo::SLAB_SHIFT) + (wave_u << 10);
+              [voff1] "v"(voff1), [sbase] "s"(sbase), [ldst] "s"(ldst)
+#define XS_SLAB(ASMSTR, NAB, NKEY)    /* the bodies' s_add_u32 (M0 stepping) writes SCC */                        \
+        asm volatile(ASMSTR XS_OPERANDS(NAB, NKEY) : "memory", "scc")
+#define XS_SLABV(ASMSTR, NAB, NKEY)   /* the same operands + the wave-uniform skip mask; clobbers VCC */          \
+        asm volatile(ASMSTR XS_OPERANDS(NAB, NKEY), [skipm] "s"(skipm) : "memory", "vcc", "scc")
+#define XS_ARGS() TRUNK_SLAB_ARGS(reinterpret_cast<const unsigned char *>(wpk), )
 #define XS_RUNV(BF, HF, NAB, NKEY)                                                                              \
         {                                                                                                       \
             XS_ARGS()                                                                                           \
@@ -313,10 +281,7 @@ __global__ __launch_bounds__(512, 2) void k_trunk_split_c128(const uint16_t *__r
         }
 #define XS_RUN(BF, HF, NAB, NKEY)                                                                               \
         {                                                                                                       \
-            const int vb = vb0 + (((unsigned)g & 3u) << Geo::SLAB_SHIFT), vbn = vb0 + ((((unsigned)g + 1u) & 3u) << Geo::SLAB_SHIFT); \
-            const int gn = g + 3 < nslabs ? g + 3 : nslabs - 1;                                                 \
-            const unsigned char *sbase = reinterpret_cast<const unsigned char *>(wpk) + (size_t)gn * Geo::SLAB_BYTES; \
-            const int ldst = Geo::W_OFF + ((((unsigned)g + 3u) & 3u) << Geo::SLAB_SHIFT) + (wave_u << 10);      \
+            XS_ARGS()                                                                                           \
             if constexpr (F16) { XS_SLAB(HF, NAB, NKEY); } else { XS_SLAB(BF, NAB, NKEY); }                     \
             ++g;                                                                                                \
         }
@@ -425,6 +390,7 @@ __global__ __launch_bounds__(512, 2) void k_trunk_split_c128(const uint16_t *__r
         }
     }
 }
+#undef XS_OPERANDS
 #undef XS_SLAB
 #undef XS_SLABV
 #undef XS_ARGS

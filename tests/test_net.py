@@ -431,12 +431,15 @@ def test_mx_engine_matches_its_cpu_emulation(blocks, wset, tol):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("dt,split", [(torch.float16, True), (torch.bfloat16, True), (torch.float16, "mx")])
-def test_strict_engine_rows_are_independent_and_routes_agree(dt, split):
-    """k_trunk_split_c128 / k_trunk_mx_c128: (i) a position's outputs do not depend on its row in the batch, on the batch size (ragged last
-    workgroup: 2 positions per workgroup) or on the device-side row count of the compact path; (ii) zero-copy 16-channel planes
-    in the operand type == repacked f32 planes; (iii) the fp32 trunk output (hi + lo) through torch's fp32 head convs and FCs
-    agrees with the fused heads to fp32 summation-order noise."""
+@pytest.mark.parametrize("dt,split", [(torch.float16, True), (torch.bfloat16, True), (torch.float16, "mx"),
+                                      (torch.float16, False), (torch.bfloat16, False)])
+def test_trunk_engine_rows_are_independent_and_routes_agree(dt, split):
+    """k_trunk_split_c128 / k_trunk_mx_c128 / k_tower8_c128 (split False): (i) a position's outputs do not depend on its row in the
+    batch, on the batch size (ragged last workgroup: 2 positions per workgroup for the strict kernels, 4 for k_tower8_c128 — 37
+    rows leave a workgroup with one live position, the row count 11 one with three) or on the device-side row count of the
+    compact path; (ii) zero-copy 16-channel planes in the operand type == repacked f32 planes; (iii) strict engines: the fp32
+    trunk output (hi + lo) through torch's fp32 head convs and FCs agrees with the fused heads to fp32 summation-order noise
+    (the fast engines' trunk route: test_fp16_trunk_route_consistent, test_fused_net_kernel_paths_agree)."""
     import ctypes as C
     from cchess_zero_amd._lib import check, lib
     from cchess_zero_amd.net import PolicyValueNet
@@ -462,6 +465,8 @@ def test_strict_engine_rows_are_independent_and_routes_agree(dt, split):
     finally:
         check(lib().cz_set_batch_count(net._hip_ctx().h, None), "cz_set_batch_count")
     assert torch.equal(z_part[:11], z_full[:11])
+    if not split:
+        return
     # trunk route
     l3, v3 = net.heads(net.tower(x))
     dl, dv = float((l_all - l3).abs().max()), float((v_all - v3).abs().max())

@@ -10,6 +10,7 @@
 set -e
 cd "$(dirname "$0")/../.."
 mkdir -p tools/ab
+SOURCES=$(python3 -c "import sys; sys.path.insert(0, 'cchess_zero_amd'); import build; print(' '.join(build.SOURCES))")   # the library's own list
 for spec in "$@"; do
   name=${spec%%=*}; flags=${spec#*=}
   top=$(mktemp -d /tmp/mxab.XXXX); d=$top/pkg/csrc; mkdir -p $d $top/include
@@ -24,7 +25,7 @@ for spec in "$@"; do
                  define:*) DEF="-D${flags#define:}"; python3 tools/gen_tower_asm.py $d > /dev/null;;
                  *) MX_ABLATE=$flags python3 tools/gen_tower_asm.py $d > /dev/null;; esac
   ( cd $d && /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt $DEF \
-      -Wno-unused-function -o $OLDPWD/tools/ab/lib_mx_$name.so cz_api.hip cz_tables.hip cz_rules.hip cz_search.hip cz_selfplay.hip cz_conv.hip cz_heads.hip cz_probe.hip ) &
+      -Wno-unused-function -o $OLDPWD/tools/ab/lib_mx_$name.so $SOURCES ) &
 done
 wait
 ls -la tools/ab/
