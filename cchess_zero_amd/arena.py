@@ -27,18 +27,21 @@ import time
 import numpy as np
 import torch
 
-from ._lib import MATCH_ABORTED, MATCH_KING, MATCH_MATE, MATCH_PLY_CAP, MATCH_RR60, NSQ, check, lib, tables
+from ._lib import (MATCH_ABORTED, MATCH_KING, MATCH_MATE, MATCH_PERPETUAL, MATCH_PLY_CAP, MATCH_REPETITION, MATCH_RR60, NSQ, check, lib,
+                   tables)
 from .engine import SearchEngine, _ptr, plane_format, pool_nodes
 from .notation import player_to_side, state_to_board
 
-REASONS = {0: "unfinished", MATCH_KING: "king", MATCH_RR60: "rr60", MATCH_PLY_CAP: "ply_cap", MATCH_ABORTED: "aborted", MATCH_MATE: "mate"}
+REASONS = {0: "unfinished", MATCH_KING: "king", MATCH_RR60: "rr60", MATCH_PLY_CAP: "ply_cap", MATCH_ABORTED: "aborted", MATCH_MATE: "mate",
+           MATCH_REPETITION: "repetition", MATCH_PERPETUAL: "perpetual"}
 RULES = {"capture": 0, "xiangqi": 1}   # cz_match_set_rules
 
 
 def is_scored(reason):
-    """A finished game that counts: every ending but "aborted" (a mate, rules="xiangqi", is a loss for the mated side)."""
+    """A finished game that counts: every ending but "aborted" (a mate, rules="xiangqi", is a loss for the mated side; with
+    repetition != 0 a repetition is a draw and a perpetual check a loss for the checking side)."""
     reason = np.asarray(reason, np.int64)
-    return ((reason >= MATCH_KING) & (reason <= MATCH_PLY_CAP)) | (reason == MATCH_MATE)
+    return ((reason >= MATCH_KING) & (reason <= MATCH_PLY_CAP)) | ((reason >= MATCH_MATE) & (reason <= MATCH_PERPETUAL))
 
 
 # ---- openings ------------------------------------------------------------------------------------------------------------
@@ -167,9 +170,10 @@ class MatchResult:
     """Per game (global game index): result (+1 / 0 / -1 for A), a_red, plies, reason (REASONS), moves (ICCS labels).
     W / D / L for A overall and by colour over the scored games (aborted games excluded), score = (W + D / 2) / scored,
     elo and its 95 % interval from the pentanomial distribution of the opening pairs, simulations, seconds, sims_per_s;
-    rules ("capture" / "xiangqi") and mates: the games that ended because the mover had no king-safe move."""
+    rules ("capture" / "xiangqi") and mates: the games that ended because the mover had no king-safe move; repetition (the
+    fold, 0 = no such rule), repetitions: the games drawn by it, perpetuals: the games lost by perpetual check."""
 
-    def __init__(self, result, a_red, plies, reason, moves, simulations, seconds, players, rules="capture"):
+    def __init__(self, result, a_red, plies, reason, moves, simulations, seconds, players, rules="capture", repetition=0):
         self.result = np.asarray(result, np.int8)
         self.a_red = np.asarray(a_red, np.uint8)
         self.plies = np.asarray(plies, np.int32)
@@ -180,6 +184,9 @@ class MatchResult:
         scored = is_scored(self.reason)
         self.rules = rules
         self.mates = int((self.reason == MATCH_MATE).sum())
+        self.repetition = int(repetition)
+        self.repetitions = int((self.reason == MATCH_REPETITION).sum())
+        self.perpetuals = int((self.reason == MATCH_PERPETUAL).sum())
         self.aborted = int((self.reason == MATCH_ABORTED).sum())
         self.unfinished = int((self.reason == 0).sum())
         self.scored = int(scored.sum())
@@ -204,7 +211,8 @@ class MatchResult:
     def to_dict(self):
         """The summary (no per-game arrays): what `python -m cchess_zero_amd.arena` prints.  elo None = infinite (every
         scored game won or lost) or no scored game; an interval end None = unbounded on that side."""
-        return dict(rules=self.rules, mates=self.mates, games=self.games, scored=self.scored, aborted=self.aborted, unfinished=self.unfinished, W=self.wins,
+        return dict(rules=self.rules, mates=self.mates, repetition=self.repetition, repetitions=self.repetitions, perpetuals=self.perpetuals,
+                    games=self.games, scored=self.scored, aborted=self.aborted, unfinished=self.unfinished, W=self.wins,
                     D=self.draws, L=self.losses, by_colour=self.by_colour, score=self.score, elo=self.elo,
                     elo_95=None if self.elo_95 is None else list(self.elo_95), pentanomial=self.pentanomial.tolist(),
                     mean_plies=float(self.plies.mean()) if self.games else 0.0,
@@ -274,13 +282,21 @@ class Match:
     max_plies: a game that reaches it is a draw; sample_plies: the first plies of a game are sampled from softmax(log N)
     (temperature 1) with uniforms that are a pure function of (seed, game, ply), the rest are greedy (most visits).
     rules: "capture" — the reference's games: pseudo-legal moves, a game ends when a king is taken; "xiangqi" — the move is
-    chosen among the king-safe root children only (cz_movegen_kingsafe), and a mover without one has lost ("mate")."""
+    chosen among the king-safe root children only (cz_movegen_kingsafe), and a mover without one has lost ("mate").
+    repetition (rules="xiangqi" only): 0 — no repetition rule; 2..8 — a game ends when its position occurs for that many
+    times since the last capture (3 is the usual value): a draw ("repetition"), or a loss for the side that alone checked with
+    every move of the cycle ("perpetual"); perpetual chase is not judged (cz_match_set_repetition)."""
 
     def __init__(self, player_a, player_b, openings, slots, max_plies=512, sample_plies=0, seed=0, check_every=8,
-                 nodes_per_tree=None, rules="capture"):
+                 nodes_per_tree=None, rules="capture", repetition=0):
         if rules not in RULES:
             raise ValueError("Match: rules is 'capture' or 'xiangqi', not %r" % (rules,))
+        if isinstance(repetition, bool) or not isinstance(repetition, (int, np.integer)) or not (repetition == 0 or 2 <= repetition <= 8):
+            raise ValueError("Match: repetition is 0 (off) or 2..8, not %r" % (repetition,))
+        if repetition and rules != "xiangqi":
+            raise ValueError("Match: repetition needs rules='xiangqi' (the check flags come from the king-safe moves)")
         self.rules = rules
+        self.repetition = int(repetition)
         self.players = [_player(player_a), _player(player_b)]
         self.openings = as_openings(openings)
         self.slots = int(slots)
@@ -307,7 +323,7 @@ class Match:
         if multi:
             local = merge_ranks(local, n_pairs, rank, world)
         return MatchResult(local["result"], local["a_red"], local["plies"], local["reason"], local["moves"], local["simulations"],
-                           local["seconds"], [_describe(p) for p in self.players], rules=self.rules)
+                           local["seconds"], [_describe(p) for p in self.players], rules=self.rules, repetition=self.repetition)
 
     def _play_local(self, op, pair_base, pair_stride):
         self.start(op, pair_base, pair_stride)
@@ -358,6 +374,8 @@ class Match:
                                 self.max_plies, C.byref(self._h)), "cz_match_create")
         if RULES[self.rules]:
             check(L.cz_match_set_rules(self._h, RULES[self.rules]), "cz_match_set_rules")
+        if self.repetition:
+            check(L.cz_match_set_repetition(self._h, self.repetition), "cz_match_set_repetition")
         self.masks = []
         for player in (0, 1):
             p = C.c_void_p()
@@ -405,6 +423,17 @@ class Match:
         for o, p in zip(out, self.masks + [ptrs[5]]):
             check(L.cz_download(h, o.ctypes.data_as(C.c_void_p), p, o.nbytes), "cz_download")
         return tuple(out)
+
+    def history(self):
+        """(keys u64 [G, 64], checks u8 [G, 64]) on the host: the slots' position rings (cz_match_history; repetition != 0),
+        position i of a slot's game at [i & 63]."""
+        G, L, h = self.G, lib(), self.engines[0].ctx.h
+        pk, pc = C.c_void_p(), C.c_void_p()
+        check(L.cz_match_history(self._h, C.byref(pk), C.byref(pc)), "cz_match_history")
+        keys, checks = np.zeros((G, 64), np.uint64), np.zeros((G, 64), np.uint8)
+        for o, p in ((keys, pk), (checks, pc)):
+            check(L.cz_download(h, o.ctypes.data_as(C.c_void_p), p, o.nbytes), "cz_download")
+        return keys, checks
 
     def results(self):
         """The per-game arrays on the host: result, a_red, plies, reason, moves [games, max_plies] (0xFFFF past the end)."""
@@ -456,13 +485,18 @@ def main(argv=None):
     ap.add_argument("--sample_plies", type=int, default=0, help="plies sampled from softmax(log N) at the start of a game")
     ap.add_argument("--rules", choices=sorted(RULES), default="capture",
                     help="capture: the reference's king-capture games; xiangqi: king-safe moves only, no safe move loses")
+    ap.add_argument("--repetition", type=int, default=0,
+                    help="with --rules xiangqi: a game ends when its position occurs for the N-th time (3 is the usual value): a draw, "
+                         "or a loss for the side that checked perpetually; 0 = no repetition rule")
     args = ap.parse_args(argv)
+    if not (args.repetition == 0 or 2 <= args.repetition <= 8) or (args.repetition and args.rules != "xiangqi"):
+        ap.error("--repetition is 0 or 2..8 and needs --rules xiangqi")
     a = load_player(args.a, args.blocks)
     b = a if args.b == args.a else load_player(args.b, args.blocks)
     pairs = (args.games + 1) // 2
     op = random_openings(pairs, args.opening_plies, args.seed)
     res = Match((a, args.playout), (b, args.playout_b or args.playout), op, slots=args.slots or 2 * pairs, max_plies=args.max_plies,
-                sample_plies=args.sample_plies, seed=args.seed, rules=args.rules).play()
+                sample_plies=args.sample_plies, seed=args.seed, rules=args.rules, repetition=args.repetition).play()
     d = res.to_dict()
     d.update(a=args.a, b=args.b, blocks=args.blocks, opening_plies=args.opening_plies, slots=min(args.slots or 2 * pairs, 2 * pairs),
              seed=args.seed)

@@ -243,6 +243,15 @@ int cz_movegen_kingsafe(cz_ctx *c, const uint8_t *boards, const uint8_t *side, i
     CZ_REQUIRE(moves || count || mask || pos_flags, "cz_movegen_kingsafe: no output requested");
     return czk_movegen_kingsafe(c, boards, side, G, moves, count, mask, pos_flags, flags);
 }
+int cz_repetition(cz_ctx *c, const uint64_t *keys, const uint8_t *in_check, int stride, const int32_t *len, const int32_t *window,
+                  const uint8_t *side, int G, int fold, uint8_t *verdict, int32_t *first) {
+    CZ_REQUIRE(c && G >= 0, "cz_repetition: null ctx / negative G");
+    CZ_REQUIRE(fold >= 2 && fold <= 8, "cz_repetition: 2 <= fold <= 8");
+    CZ_REQUIRE(stride >= 1, "cz_repetition: stride >= 1");
+    if (G == 0) return CZ_OK;
+    CZ_REQUIRE(keys && in_check && len && side && verdict, "cz_repetition: keys, in_check, len, side, verdict required");
+    return czk_repetition(c, keys, in_check, stride, len, window, side, G, fold, verdict, first);
+}
 int cz_apply_move(cz_ctx *c, uint8_t *boards, uint8_t *side, const uint16_t *label, int G, uint64_t *hash, uint8_t *captured, int8_t *terminal) {
     CZ_REQUIRE(c && G >= 0, "cz_apply_move: null ctx / negative G");
     if (G == 0) return CZ_OK;

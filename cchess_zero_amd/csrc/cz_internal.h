@@ -362,6 +362,7 @@ __device__ __forceinline__ int wave_pick_inverse_cdf(const double p[2], double u
 // kernels' launch wrappers (cz_rules.hip / cz_search.hip)
 int czk_movegen(cz_ctx *, const uint8_t *, const uint8_t *, int, uint16_t *, uint16_t *, uint32_t *, int flags);
 int czk_movegen_kingsafe(cz_ctx *, const uint8_t *, const uint8_t *, int, uint16_t *, uint16_t *, uint32_t *, uint8_t *, int flags);   // cz_kingsafe.hip
+int czk_repetition(cz_ctx *, const uint64_t *, const uint8_t *, int, const int32_t *, const int32_t *, const uint8_t *, int, int, uint8_t *, int32_t *);   // cz_repetition.hip
 int czk_apply_move(cz_ctx *, uint8_t *, uint8_t *, const uint16_t *, int, uint64_t *, uint8_t *, int8_t *);
 int czk_hash(cz_ctx *, const uint8_t *, const uint8_t *, int, uint64_t *);
 int czk_encode_planes(cz_ctx *, const uint8_t *, const uint8_t *, int, void *, int, int, int);

@@ -10,6 +10,7 @@
 // so every opening is played once with each colour assignment.  A slot whose game ends takes the next game of the queue
 // at once, or parks when the queue is empty.  The host only reads the finished-games counter every few plies.
 #include "cz_internal.h"
+#include "cz_repetition.h"
 
 struct cz_match {
     cz_ctx *a, *b;
@@ -18,6 +19,9 @@ struct cz_match {
     void *block;
     int rules;                          // 0: king capture (the reference's games), 1: xiangqi (cz_match_set_rules)
     void *xq_block;                     // rules = 1: the mover's root positions, their king-safe sets and the mated flags
+    int fold;                           // 0: no repetition rule, 2..8: a fold-th occurrence ends the game (cz_match_set_repetition)
+    void *rep_block;                    // fold != 0: the slots' position rings and verdicts
+    bool chosen;                        // a cz_match_choose has run: the repetition rule can no longer be switched on
 };
 
 namespace {
@@ -95,6 +99,16 @@ struct CzMatchXq {
     uint8_t *mated;     // [G] the last choose found children, none of them king-safe
 };
 
+// fold != 0 (cz_match_set_repetition): the history of every slot's game, a ring over the position index
+struct CzMatchRep {
+    uint64_t *key;        // [G][64] cz_hash of position i of the slot's game at [i & 63]
+    uint8_t *check;       // [G][64] its side to move is in check
+    uint8_t *rep;         // [G] CZ_REP_* of the last choose: the game ends by repetition
+    uint8_t *flags;       // [G] CZ_POS_* of the mover's root position (cz_movegen_kingsafe)
+    uint64_t *root_key;   // [G] its cz_hash
+    int fold;
+};
+
 // the first maximum of N over children 0 .. n - 1 (N[r] of child lane + 64 r), wave-uniform: wave_most_visited on registers
 __device__ __forceinline__ int wave_first_max(const int N[2], int n, int lane) {
     int bn = -1, bi = 0x7fffffff;
@@ -111,10 +125,14 @@ __device__ __forceinline__ int wave_first_max(const int N[2], int n, int lane) {
 
 // get_action of the mover (main.py:1332-1341) on its own tree: greedy, or sampled for the game's first sample_plies plies.
 // XQ: among the root children whose move is in the slot's king-safe set — they are compacted, in generation order, and the
-// choice runs on the compacted visit counts exactly as it runs on all children under king-capture rules
-template <bool XQ>
+// choice runs on the compacted visit counts exactly as it runs on all children under king-capture rules.
+// REP (with XQ only): the root position goes into the slot's ring at the game's ply, and a fold-th occurrence inside the last
+// min(restrict_round, ply, 63) positions — a capture makes the earlier ones unreachable, and no read leaves the slot's current
+// game — ends the game before a move is chosen: no move is logged, the ply stays (k_match_adjudicate_rep)
+template <bool XQ, bool REP>
 __device__ __forceinline__ void choose_on(const CzTrees &t, const CzMatch &m, int g, int game, int sample_plies,
-                                          unsigned long long seed, uint16_t *__restrict__ played, int lane, const CzMatchXq &x) {
+                                          unsigned long long seed, uint16_t *__restrict__ played, int lane, const CzMatchXq &x,
+                                          const CzMatchRep &r) {
     if (lane == 0) atomicAdd(m.sims, (unsigned long long)t.sims[g]);
     const TreeView v = view_of(t, g);
     int cb, n;
@@ -125,6 +143,20 @@ __device__ __forceinline__ void choose_on(const CzTrees &t, const CzMatch &m, in
         return;
     }
     const int ply = m.ply[g];
+    if constexpr (REP) {
+        const uint64_t key = r.root_key[g];
+        const bool chk = (r.flags[g] & CZ_POS_IN_CHECK) != 0;
+        const uint64_t *ring_key = r.key + (size_t)g * 64;
+        const uint8_t *ring_check = r.check + (size_t)g * 64;
+        if (lane == 0) { r.key[(size_t)g * 64 + (ply & 63)] = key; r.check[(size_t)g * 64 + (ply & 63)] = chk ? 1 : 0; }
+        const int w = max(0, min(min(t.root_rr[g], ply), 63));   // entry ply & 63, just written, is never among the w read
+        int first;
+        const int verdict = wave_repetition(ring_key, ring_check, 63, ply, w, key, chk, x.side[g] ? 1 : 0, r.fold, lane, first);
+        if (verdict != CZ_REP_NONE) {
+            if (lane == 0) { played[g] = 0xFFFF; r.rep[g] = (uint8_t)verdict; }
+            return;
+        }
+    }
     int pick;
     if constexpr (XQ) {
         __shared__ int sN[128], sI[128];
@@ -185,8 +217,8 @@ __global__ __launch_bounds__(64) void k_match_choose(CzTrees ta, CzTrees tb, CzM
     if (g >= m.G) return;
     const int game = m.game[g];
     if (game < 0) { if (lane == 0) played[g] = 0xFFFF; return; }
-    if (m.mover_a[g]) choose_on<false>(ta, m, g, game, sample_plies, seed, played, lane, CzMatchXq{});
-    else choose_on<false>(tb, m, g, game, sample_plies, seed, played, lane, CzMatchXq{});
+    if (m.mover_a[g]) choose_on<false, false>(ta, m, g, game, sample_plies, seed, played, lane, CzMatchXq{}, CzMatchRep{});
+    else choose_on<false, false>(tb, m, g, game, sample_plies, seed, played, lane, CzMatchXq{}, CzMatchRep{});
 }
 
 // rules = 1, before the choice: the mover's root position of every slot, for cz_movegen_kingsafe
@@ -204,16 +236,28 @@ __global__ __launch_bounds__(64) void k_match_choose_xq(CzTrees ta, CzTrees tb, 
     if (g >= m.G) return;
     const int game = m.game[g];
     if (game < 0) { if (lane == 0) played[g] = 0xFFFF; return; }
-    if (m.mover_a[g]) choose_on<true>(ta, m, g, game, sample_plies, seed, played, lane, x);
-    else choose_on<true>(tb, m, g, game, sample_plies, seed, played, lane, x);
+    if (m.mover_a[g]) choose_on<true, false>(ta, m, g, game, sample_plies, seed, played, lane, x, CzMatchRep{});
+    else choose_on<true, false>(tb, m, g, game, sample_plies, seed, played, lane, x, CzMatchRep{});
+}
+__global__ __launch_bounds__(64) void k_match_choose_rep(CzTrees ta, CzTrees tb, CzMatch m, int sample_plies, unsigned long long seed,
+                                                         uint16_t *__restrict__ played, CzMatchXq x, CzMatchRep r) {
+    const int g = blockIdx.x, lane = threadIdx.x;
+    if (g >= m.G) return;
+    const int game = m.game[g];
+    if (game < 0) { if (lane == 0) played[g] = 0xFFFF; return; }   // a parked slot: before the ring is touched
+    if (m.mover_a[g]) choose_on<true, true>(ta, m, g, game, sample_plies, seed, played, lane, x, r);
+    else choose_on<true, true>(tb, m, g, game, sample_plies, seed, played, lane, x, r);
 }
 
 // After cz_search_advance(played) on both contexts: the follower's failed advance (its root was never expanded, so it has no
 // child for the move) is its normal case — it starts a fresh root on the new position; then check_end (main.py:1380-1392)
 // plus the match's own endings (ply cap, aborted game), the result, and the slot's next game.
 // mated (rules = 1 only, else nullptr): the slot's mover had no king-safe move — CZ_MATCH_MATE, before every other ending
-template <bool XQ>
-__device__ __forceinline__ void adjudicate_body(const CzTrees &ta, const CzTrees &tb, const CzMatch &m, const uint16_t *__restrict__ played, uint8_t *mated) {
+// rep (fold != 0 only, else nullptr): the slot's choose found a fold-th occurrence — CZ_MATCH_REPETITION (a draw) or
+// CZ_MATCH_PERPETUAL (the side that checked with every move of the cycle loses), before mate and everything else
+template <bool XQ, bool REP>
+__device__ __forceinline__ void adjudicate_body(const CzTrees &ta, const CzTrees &tb, const CzMatch &m, const uint16_t *__restrict__ played, uint8_t *mated,
+                                                uint8_t *rep) {
     const int g = blockIdx.x, lane = threadIdx.x;
     if (g >= m.G) return;
     const int game = m.game[g];
@@ -224,8 +268,10 @@ __device__ __forceinline__ void adjudicate_body(const CzTrees &ta, const CzTrees
     bool Kmiss, kmiss;
     wave_kings_missing(mv.root_board + (size_t)g * CZD_BOARD_LDS, lane, Kmiss, kmiss);
     const int ply = m.ply[g];
-    int reason = 0;
-    if (XQ && mated[g]) reason = CZ_MATCH_MATE;
+    int reason = 0, verdict = CZ_REP_NONE;
+    if constexpr (REP) verdict = rep[g];
+    if (verdict != CZ_REP_NONE) reason = verdict == CZ_REP_DRAW ? CZ_MATCH_REPETITION : CZ_MATCH_PERPETUAL;
+    else if (XQ && mated[g]) reason = CZ_MATCH_MATE;
     else if (aborted) reason = CZ_MATCH_ABORTED;
     else if (Kmiss || kmiss) reason = CZ_MATCH_KING;
     else if (restrict_round_draw(mv.root_rr[g])) reason = CZ_MATCH_RR60;
@@ -239,8 +285,13 @@ __device__ __forceinline__ void adjudicate_body(const CzTrees &ta, const CzTrees
     if (lane == 0) {
         const bool a_red = (game & 1) == 0;
         const bool a_wins = (king_capture_winner(Kmiss) == 0) == a_red;
-        m.result[game] = (int8_t)(reason == CZ_MATCH_KING ? (a_wins ? 1 : -1) : (reason == CZ_MATCH_MATE ? (ma ? -1 : 1) : 0));
+        int8_t result = (int8_t)(reason == CZ_MATCH_KING ? (a_wins ? 1 : -1) : (reason == CZ_MATCH_MATE ? (ma ? -1 : 1) : 0));
+        if constexpr (REP) {
+            if (reason == CZ_MATCH_PERPETUAL) result = (int8_t)(((verdict == CZ_REP_RED_LOSES) == a_red) ? -1 : 1);   // A has the losing colour
+        }
+        m.result[game] = result;
         if (XQ) mated[g] = 0;
+        if constexpr (REP) rep[g] = CZ_REP_NONE;
         m.a_red[game] = a_red ? 1 : 0;
         m.plies[game] = ply;
         m.reason[game] = (uint8_t)reason;
@@ -251,10 +302,14 @@ __device__ __forceinline__ void adjudicate_body(const CzTrees &ta, const CzTrees
     take_game(ta, tb, m, g, next, lane);
 }
 __global__ __launch_bounds__(64) void k_match_adjudicate(CzTrees ta, CzTrees tb, CzMatch m, const uint16_t *__restrict__ played) {
-    adjudicate_body<false>(ta, tb, m, played, nullptr);
+    adjudicate_body<false, false>(ta, tb, m, played, nullptr, nullptr);
 }
 __global__ __launch_bounds__(64) void k_match_adjudicate_xq(CzTrees ta, CzTrees tb, CzMatch m, const uint16_t *__restrict__ played, uint8_t *mated) {
-    adjudicate_body<true>(ta, tb, m, played, mated);
+    adjudicate_body<true, false>(ta, tb, m, played, mated, nullptr);
+}
+__global__ __launch_bounds__(64) void k_match_adjudicate_rep(CzTrees ta, CzTrees tb, CzMatch m, const uint16_t *__restrict__ played, uint8_t *mated,
+                                                             uint8_t *rep) {
+    adjudicate_body<true, true>(ta, tb, m, played, mated, rep);
 }
 
 }  // namespace
@@ -294,6 +349,20 @@ static size_t carve_xq(const cz_match *mh, char *base, CzMatchXq &x) {
     x.side = (uint8_t *)take(G);
     x.safe = (uint32_t *)take(G * CZ_MASK_WORDS * 4);
     x.mated = (uint8_t *)take(G);
+    return off;
+}
+
+// fold != 0: the repetition arrays inside their own allocation
+static size_t carve_rep(const cz_match *mh, char *base, CzMatchRep &r) {
+    size_t off = 0;
+    auto take = [&](size_t bytes) { char *q = base ? base + off : nullptr; off += (bytes + 255) & ~(size_t)255; return q; };
+    const size_t G = (size_t)mh->G;
+    r.key = (uint64_t *)take(G * 64 * 8);
+    r.check = (uint8_t *)take(G * 64);
+    r.rep = (uint8_t *)take(G);
+    r.flags = (uint8_t *)take(G);
+    r.root_key = (uint64_t *)take(G * 8);
+    r.fold = mh->fold;
     return off;
 }
 
@@ -354,6 +423,7 @@ int cz_match_create(cz_ctx *a, cz_ctx *b, const uint8_t *boards, const uint8_t *
 
 int cz_match_set_rules(cz_match *mh, int rules) {
     CZ_REQUIRE(mh && (rules == 0 || rules == 1), "cz_match_set_rules: rules 0 (king capture) or 1 (xiangqi)");
+    CZ_REQUIRE(rules == 1 || mh->fold == 0, "cz_match_set_rules: the repetition rule needs rules 1: cz_match_set_repetition(match, 0) first");
     if (rules == 1 && !mh->xq_block) {
         CzMatchXq sizing;
         const size_t bytes = carve_xq(mh, nullptr, sizing);
@@ -368,11 +438,39 @@ int cz_match_set_rules(cz_match *mh, int rules) {
     return CZ_OK;
 }
 
+int cz_match_set_repetition(cz_match *mh, int fold) {
+    CZ_REQUIRE(mh && (fold == 0 || (fold >= 2 && fold <= 8)), "cz_match_set_repetition: fold 0 (off) or 2..8");
+    CZ_REQUIRE(fold == 0 || mh->rules == 1, "cz_match_set_repetition: cz_match_set_rules(match, 1) first (the check flags are the king-safe pass's)");
+    CZ_REQUIRE(!mh->chosen,"cz_match_set_repetition: before the first cz_match_choose only (the history starts at the openings)");
+    if (fold != 0 && !mh->rep_block) {
+        CzMatchRep sizing;
+        const size_t bytes = carve_rep(mh, nullptr, sizing);
+        if (hipMalloc(&mh->rep_block, bytes) != hipSuccess) {
+            mh->rep_block = nullptr;
+            cz_set_error("cz_match_set_repetition: hipMalloc(%zu B) failed", bytes);
+            return CZ_ENOMEM;
+        }
+        CZ_HIP(hipMemsetAsync(mh->rep_block, 0, bytes, mh->a->stream));
+    }
+    mh->fold = fold;
+    return CZ_OK;
+}
+
+int cz_match_history(cz_match *mh, const uint64_t **keys, const uint8_t **checks) {
+    CZ_REQUIRE(mh && mh->fold != 0 && mh->rep_block, "cz_match_history: cz_match_set_repetition first");
+    CzMatchRep r;
+    carve_rep(mh, (char *)mh->rep_block, r);
+    if (keys) *keys = r.key;
+    if (checks) *checks = r.check;
+    return CZ_OK;
+}
+
 void cz_match_destroy(cz_match *mh) {
     if (!mh) return;
     (void)hipStreamSynchronize(mh->a->stream);
     (void)hipFree(mh->block);
     if (mh->xq_block) (void)hipFree(mh->xq_block);
+    if (mh->rep_block) (void)hipFree(mh->rep_block);
     delete mh;
 }
 
@@ -386,6 +484,21 @@ int cz_match_active(cz_match *mh, int player, const uint8_t **mask) {
 int cz_match_choose(cz_match *mh, int sample_plies, unsigned long long seed, uint16_t *played) {
     CZ_REQUIRE(mh && played && sample_plies >= 0, "cz_match_choose: null argument / sample_plies < 0");
     CZ_REQUIRE(mh->a->G == mh->G && mh->b->G == mh->G, "cz_match_choose: a context was reset to another number of slots");
+    mh->chosen = true;
+    if (mh->rules == 1 && mh->fold != 0) {   // as below, with the root positions' check flags and keys for the repetition rule
+        CzMatchXq x;
+        CzMatchRep r;
+        carve_xq(mh, (char *)mh->xq_block, x);
+        carve_rep(mh, (char *)mh->rep_block, r);
+        hipLaunchKernelGGL(k_match_roots_xq, dim3(mh->G), dim3(64), 0, mh->a->stream, mh->a->t, mh->b->t, device_view(mh), x);
+        CZ_HIP(hipGetLastError());
+        int rc = czk_movegen_kingsafe(mh->a, x.board, x.side, mh->G, nullptr, nullptr, x.safe, r.flags, 0);
+        if (rc != CZ_OK) return rc;
+        if ((rc = czk_hash(mh->a, x.board, x.side, mh->G, r.root_key)) != CZ_OK) return rc;
+        hipLaunchKernelGGL(k_match_choose_rep, dim3(mh->G), dim3(64), 0, mh->a->stream, mh->a->t, mh->b->t, device_view(mh), sample_plies, seed, played, x, r);
+        CZ_HIP(hipGetLastError());
+        return CZ_OK;
+    }
     if (mh->rules == 1) {   // the king-safe set of every slot's root position, then the choice among the children in it
         CzMatchXq x;
         carve_xq(mh, (char *)mh->xq_block, x);
@@ -405,7 +518,13 @@ int cz_match_choose(cz_match *mh, int sample_plies, unsigned long long seed, uin
 int cz_match_adjudicate(cz_match *mh, const uint16_t *played) {
     CZ_REQUIRE(mh && played, "cz_match_adjudicate: null argument");
     CZ_REQUIRE(mh->a->G == mh->G && mh->b->G == mh->G, "cz_match_adjudicate: a context was reset to another number of slots");
-    if (mh->rules == 1) {
+    if (mh->rules == 1 && mh->fold != 0) {
+        CzMatchXq x;
+        CzMatchRep r;
+        carve_xq(mh, (char *)mh->xq_block, x);
+        carve_rep(mh, (char *)mh->rep_block, r);
+        hipLaunchKernelGGL(k_match_adjudicate_rep, dim3(mh->G), dim3(64), 0, mh->a->stream, mh->a->t, mh->b->t, device_view(mh), played, x.mated, r.rep);
+    } else if (mh->rules == 1) {
         CzMatchXq x;
         carve_xq(mh, (char *)mh->xq_block, x);
         hipLaunchKernelGGL(k_match_adjudicate_xq, dim3(mh->G), dim3(64), 0, mh->a->stream, mh->a->t, mh->b->t, device_view(mh), played, x.mated);

@@ -99,6 +99,26 @@ class Rules:
         check(lib().cz_movegen_kingsafe(self.ctx.h, _ptr(boards), _ptr(side), boards.shape[0], None, None, None, _ptr(pos_flags), 0), "cz_movegen_kingsafe")
         return pos_flags
 
+    def repetition(self, keys, in_check, side, length=None, window=None, fold=3):
+        """Repetition and perpetual check on G game records (cz_repetition): keys [G, stride] i64 (cz_hash of every position,
+        position 0 the opening), in_check [G, stride] u8 (the side to move is attacked: bit 0 of in_check()'s flags), side [G] u8
+        (the side to move in the current position), length [G] i32 (positions recorded; None: stride), window [G] i32 (how
+        many earlier positions count; None: all) -> (verdict [G] u8: REP_NONE / REP_DRAW / REP_RED_LOSES / REP_BLACK_LOSES,
+        first [G] i32: the earlier occurrence the cycle starts from, -1 without a verdict)."""
+        self.ctx.bind_stream()   # torch's current stream
+        keys = self._dev(keys, torch.int64)
+        keys = keys.reshape(-1, keys.shape[-1])
+        G, stride = keys.shape
+        in_check = self._dev(in_check, torch.uint8).reshape(G, stride)
+        side = self._dev(side, torch.uint8).reshape(G)
+        length = torch.full((G,), stride, dtype=torch.int32, device=self.dev) if length is None else self._dev(length, torch.int32).reshape(G)
+        window = None if window is None else self._dev(window, torch.int32).reshape(G)
+        verdict = torch.empty(G, dtype=torch.uint8, device=self.dev)
+        first = torch.empty(G, dtype=torch.int32, device=self.dev)
+        check(lib().cz_repetition(self.ctx.h, _ptr(keys), _ptr(in_check), stride, _ptr(length), _ptr(window), _ptr(side), G, int(fold),
+                                  _ptr(verdict), _ptr(first)), "cz_repetition")
+        return verdict, first
+
     @staticmethod
     def check_counts(count):
         """Raises if any position answered count 0xFFFF (k_movegen_list / k_movegen_mask refuse boards that are not a Xiangqi

@@ -141,13 +141,37 @@ int cz_movegen_ex(cz_ctx *, const uint8_t *boards, const uint8_t *side, int G, u
  *     count [G]: their number; mask [G][66]: their set; pos_flags [G]: CZ_POS_*.  Any of the four may be NULL; with only
  *     pos_flags (and / or count) this is the "in check?" query and neither list nor set rows are built.
  *     Alignment as for cz_movegen: `moves` 16-byte aligned, everything else at any address.  A board cz_movegen answers with
- *     count 0xFFFF answers count 0xFFFF here too (its rows are undefined, its flags 0).  Repetition and perpetual check /
- *     chase are not rules of this library. */
+ *     count 0xFFFF answers count 0xFFFF here too (its rows are undefined, its flags 0).  Repetition and perpetual check
+ *     are judged by cz_repetition below, on a game's history; perpetual chase is not a rule of this library. */
 #define CZ_POS_IN_CHECK 1        /* the side to move is attacked */
 #define CZ_POS_CAN_TAKE_KING 2   /* the other side is attacked: the side to move can take its king */
 #define CZ_POS_NO_SAFE_MOVE 4    /* no king-safe move: checkmate or stalemate, both lost in Xiangqi */
 int cz_movegen_kingsafe(cz_ctx *, const uint8_t *boards, const uint8_t *side, int G, uint16_t *moves, uint16_t *count,
                         uint32_t *mask, uint8_t *pos_flags, int flags);
+/* K1r REPETITION AND PERPETUAL CHECK on G game records that the caller keeps.  No reference function: the reference's games
+ *     have no repetition rule.  A game's history is the sequence of its positions: position i is the position after i plies
+ *     (position 0 is the opening), with key[i] = its cz_hash (board and side to move; equal keys are taken as equal positions)
+ *     and in_check[i] != 0 when the side to move at i is attacked (CZ_POS_IN_CHECK).  Let n be the current position and w how
+ *     far back to look:
+ *       1. the earlier occurrences are the i with n - w <= i < n and key[i] == key[n];
+ *       2. with fewer than fold - 1 of them there is no verdict;
+ *       3. otherwise j is the (fold - 1)-th most recent of them, and the cycle is the positions j + 1 .. n;
+ *       4. side X checked perpetually when every position of the cycle with side 1 - X to move — the positions X's moves
+ *          led to — has in_check set, and there is at least one such position;
+ *       5. exactly one side checked perpetually: that side loses; neither or both: a draw.
+ *     Perpetual CHASE is not judged (it needs an attack-and-protection analysis of its own): a chase that repeats is a draw here.
+ *     keys uint64 [G][stride], in_check uint8 [G][stride]: position i of game g at g * stride + i; len int32 [G]: 1 <= len[g] <=
+ *     stride, the current position is len[g] - 1 (a length outside that range answers CZ_REP_NONE / -1: nothing is read);
+ *     window int32 [G]: w, clamped to 0 .. len[g] - 1, or NULL = every earlier position; side uint8 [G]: the side to move in the
+ *     current position (the earlier sides follow by parity); 2 <= fold <= 8 (3: the usual threefold rule).
+ *     verdict uint8 [G] out: CZ_REP_*; first int32 [G] out (may be NULL): j, or -1 without a verdict.  One wave per game, the
+ *     history in chunks of 64 positions, most recent first.  All device arrays, at any address their element type allows. */
+#define CZ_REP_NONE 0          /* fewer than fold occurrences inside the window */
+#define CZ_REP_DRAW 1          /* repeated; neither side, or both, checked with every move of the cycle */
+#define CZ_REP_RED_LOSES 2     /* red checked with every move of the cycle, black did not */
+#define CZ_REP_BLACK_LOSES 3   /* black checked with every move of the cycle, red did not */
+int cz_repetition(cz_ctx *, const uint64_t *keys, const uint8_t *in_check, int stride, const int32_t *len, const int32_t *window,
+                  const uint8_t *side, int G, int fold, uint8_t *verdict, int32_t *first);
 /* K2  replaces GameBoard.sim_do_action (main.py:647-702), is_kill_move (:226) and the king test
  *     (:409-413).  Updates boards/side in place.  hash: in/out incremental Zobrist (may be NULL);
  *     captured [G] = captured piece code or 0; terminal [G]: bit0 'K' missing, bit1 'k' missing.
@@ -380,6 +404,8 @@ int cz_selfplay_stats(cz_ctx *, long long *stats_dev);
 #define CZ_MATCH_PLY_CAP 3   /* max_plies plies: a draw (the reference has no such limit) */
 #define CZ_MATCH_ABORTED 4   /* the mover had no child to play: not scored */
 #define CZ_MATCH_MATE 5      /* rules = 1: the mover had no king-safe move (checkmate or stalemate): it loses */
+#define CZ_MATCH_REPETITION 6   /* cz_match_set_repetition: the position occurred for the fold-th time: a draw */
+#define CZ_MATCH_PERPETUAL 7    /* ... and one side alone checked with every move of the cycle: that side loses */
 typedef struct cz_match cz_match;
 int cz_match_create(cz_ctx *a, cz_ctx *b, const uint8_t *open_boards, const uint8_t *open_side, const int32_t *open_rr,
                     int n_openings, long long pair_base, long long pair_stride, int max_plies, cz_match **out);
@@ -391,6 +417,23 @@ void cz_match_destroy(cz_match *);
  *   children, none of them king-safe: played = 0xFFFF, and cz_match_adjudicate ends the game with CZ_MATCH_MATE — a loss for
  *   the mover, plies = the plies actually played — before it looks at anything else.  A root without children aborts as above. */
 int cz_match_set_rules(cz_match *, int rules);
+/* cz_match_set_repetition: fold 0 = no repetition rule (the default: everything above, launch for launch), 2 <= fold <= 8 =
+ *   a game ends when its position occurs for the fold-th time (cz_repetition's rule; 3 is the usual value).  Needs
+ *   cz_match_set_rules(match, 1) first — the check flags are the king-safe pass's — and is refused (CZ_EINVAL) under rules 0
+ *   and once a cz_match_choose has run on the match (a history recorded from mid-game would be wrong); cz_match_set_rules(match,
+ *   0) is refused while the fold is not 0.  With it, cz_match_choose also takes every root position's CZ_POS_* flags and cz_hash,
+ *   writes them into the slot's ring of 64 positions at entry ply & 63 (every ring index is masked; a parked slot returns
+ *   before it touches the ring) and evaluates the rule with w = min(restrict_round of the root, ply, 63): a capture makes the
+ *   earlier positions unreachable, w <= ply keeps every read inside the slot's current game (no reset when a slot takes its
+ *   next game), and restrict_round is below 60 in every live game.  Order: a root without children aborts as above, then
+ *   repetition, then mate (a repeated position was moved from before: the two cannot both hold).  On a verdict played =
+ *   0xFFFF, no move is logged, the ply is not advanced, and cz_match_adjudicate ends the game before it looks at anything else:
+ *   CZ_MATCH_REPETITION (result 0) or CZ_MATCH_PERPETUAL (result -1 when the losing side is A's colour in that game, else +1),
+ *   plies = the plies actually played.
+ * cz_match_history: the device pointers of the two rings, owned by the match — keys uint64 [G][64], checks uint8 [G][64]:
+ *   position i of the game in slot g at [g][i & 63]; either may be NULL.  CZ_EINVAL while the repetition rule is off. */
+int cz_match_set_repetition(cz_match *, int fold);
+int cz_match_history(cz_match *, const uint64_t **keys, const uint8_t **checks);
 int cz_match_active(cz_match *, int player, const uint8_t **mask_dev);
 int cz_match_choose(cz_match *, int sample_plies, unsigned long long seed, uint16_t *played);
 int cz_match_adjudicate(cz_match *, const uint16_t *played);
