@@ -19,6 +19,7 @@ F32, BF16, F16 = 0, 1, 2
 # one packed self-play record (include/cchess_hip.h: CZ_REC_*)
 REC_BYTES, REC_SIDE, REC_COUNT, REC_Z, REC_FLAGS, REC_PLY, REC_LABELS, REC_VISITS = 608, 90, 91, 92, 93, 94, 96, 352
 SP_STATS = ("games", "red_wins", "black_wins", "draws", "plies", "stalled", "dropped", "sims")
+SP_RULES_STATS = ("mates", "repetitions", "perpetuals")   # cz_selfplay_rules_stats
 # why a match game ended (include/cchess_hip.h: CZ_MATCH_*); 0 = not finished
 MATCH_KING, MATCH_RR60, MATCH_PLY_CAP, MATCH_ABORTED, MATCH_MATE, MATCH_REPETITION, MATCH_PERPETUAL = 1, 2, 3, 4, 5, 6, 7
 # verdicts of cz_repetition (include/cchess_hip.h: CZ_REP_*)
@@ -88,6 +89,10 @@ _SIGS = {
     "cz_selfplay_adjudicate": (C.c_int, [C.c_void_p, C.c_int, _u16p, _i32p]),
     "cz_selfplay_flush": (C.c_int, [C.c_void_p, _i32p, _vp, _u8p, C.c_longlong, _vp]),
     "cz_selfplay_stats": (C.c_int, [C.c_void_p, _vp]),
+    "cz_selfplay_set_rules": (C.c_int, [C.c_void_p, C.c_int]),
+    "cz_selfplay_set_repetition": (C.c_int, [C.c_void_p, C.c_int]),
+    "cz_selfplay_history": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "cz_selfplay_rules_stats": (C.c_int, [C.c_void_p, _vp]),
     "cz_match_create": (C.c_int, [C.c_void_p, C.c_void_p, _u8p, _u8p, _i32p, C.c_int, C.c_longlong, C.c_longlong, C.c_int,
                                   C.POINTER(C.c_void_p)]),
     "cz_match_destroy": (None, [C.c_void_p]),

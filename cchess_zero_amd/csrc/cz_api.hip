@@ -563,6 +563,16 @@ int cz_selfplay_begin(cz_ctx *c, int max_plies, const uint8_t *boards, const uin
             sp.start_side = k.take<uint8_t>(G);
             sp.start_rr = k.take<int32_t>(G);
             sp.stats = k.take<long long>(CZ_SP_NSTATS);
+            sp.xq_board = k.take<uint8_t>(G * CZ_NSQ);
+            sp.xq_side = k.take<uint8_t>(G);
+            sp.safe = k.take<uint32_t>(G * CZ_MASK_WORDS);
+            sp.mated = k.take<uint8_t>(G);
+            sp.xq_stats = k.take<long long>(3);
+            sp.ring_key = k.take<uint64_t>(G * 64);
+            sp.ring_check = k.take<uint8_t>(G * 64);
+            sp.rep = k.take<uint8_t>(G);
+            sp.flags = k.take<uint8_t>(G);
+            sp.root_key = k.take<uint64_t>(G);
         };
         Carver m{nullptr};
         CzSelfplay dummy;
@@ -572,7 +582,35 @@ int cz_selfplay_begin(cz_ctx *c, int max_plies, const uint8_t *boards, const uin
         carve(k, c->sp);
         c->sp.max_plies = max_plies;
     }
+    c->sp_rules = 0; c->sp_fold = 0; c->sp_state = 1;
     return czk_selfplay_seed(c, boards, side, rr);
+}
+int cz_selfplay_set_rules(cz_ctx *c, int rules) {
+    CZ_REQUIRE(c && c->sp_block && c->sp_state != 0, "cz_selfplay_set_rules: call cz_selfplay_begin first");
+    CZ_REQUIRE(rules == 0 || rules == 1, "cz_selfplay_set_rules: rules 0 (king capture) or 1 (xiangqi)");
+    CZ_REQUIRE(c->sp_state == 1, "cz_selfplay_set_rules: before the first cz_selfplay_choose only (a game is played under one set of rules)");
+    CZ_REQUIRE(rules == 1 || c->sp_fold == 0, "cz_selfplay_set_rules: the repetition rule needs rules 1: cz_selfplay_set_repetition(ctx, 0) first");
+    c->sp_rules = rules;
+    return CZ_OK;
+}
+int cz_selfplay_set_repetition(cz_ctx *c, int fold) {
+    CZ_REQUIRE(c && c->sp_block && c->sp_state != 0, "cz_selfplay_set_repetition: call cz_selfplay_begin first");
+    CZ_REQUIRE(fold == 0 || (fold >= 2 && fold <= 8), "cz_selfplay_set_repetition: fold 0 (off) or 2..8");
+    CZ_REQUIRE(c->sp_state == 1, "cz_selfplay_set_repetition: before the first cz_selfplay_choose only (the history starts at the games' first positions)");
+    CZ_REQUIRE(fold == 0 || c->sp_rules == 1, "cz_selfplay_set_repetition: cz_selfplay_set_rules(ctx, 1) first (the check flags are the king-safe pass's)");
+    c->sp_fold = fold;
+    return CZ_OK;
+}
+int cz_selfplay_history(cz_ctx *c, const uint64_t **keys, const uint8_t **checks) {
+    CZ_REQUIRE(c && c->sp_block && c->sp_fold != 0, "cz_selfplay_history: cz_selfplay_set_repetition first");
+    if (keys) *keys = c->sp.ring_key;
+    if (checks) *checks = c->sp.ring_check;
+    return CZ_OK;
+}
+int cz_selfplay_rules_stats(cz_ctx *c, long long *stats_dev) {
+    CZ_REQUIRE(c && c->sp_block && stats_dev, "cz_selfplay_rules_stats: call cz_selfplay_begin first / null argument");
+    CZ_HIP(hipMemcpyAsync(stats_dev, c->sp.xq_stats, sizeof(long long) * 3, hipMemcpyDeviceToDevice, c->stream));
+    return CZ_OK;
 }
 int cz_selfplay_active(cz_ctx *c, const uint8_t **active) {
     CZ_REQUIRE(c && c->sp_block && active, "cz_selfplay_active: call cz_selfplay_begin first");
@@ -584,6 +622,7 @@ int cz_selfplay_choose(cz_ctx *c, const float *gamma, const float *u, const uint
     CZ_REQUIRE(u && played, "cz_selfplay_choose: u and played required");
     CZ_REQUIRE(temperature > 0.0 && eps >= 0.f && eps <= 1.f, "cz_selfplay_choose: temperature > 0 and 0 <= noise_eps <= 1 required");
     CZ_REQUIRE(min_sims >= 0, "cz_selfplay_choose: min_sims >= 0 required");
+    c->sp_state = 2;
     return czk_selfplay_choose(c, gamma, u, forced, temperature, eps, min_sims, played);
 }
 int cz_selfplay_adjudicate(cz_ctx *c, int reseed, const uint16_t *played, int32_t *fin_n) {

@@ -62,6 +62,18 @@ struct CzSelfplay {
     uint8_t *start_side;         // [max_games]
     int32_t *start_rr;           // [max_games]
     long long *stats;            // [CZ_SP_NSTATS]
+    // cz_selfplay_set_rules(1): what the xiangqi kernels keep beside the games (the arrays of cz_match.hip's CzMatchXq / CzMatchRep)
+    uint8_t *xq_board;           // [max_games][90] the root position of every slot at the last choose (an empty board for a parked slot)
+    uint8_t *xq_side;            // [max_games]
+    uint32_t *safe;              // [max_games][66] its king-safe set (cz_movegen_kingsafe)
+    uint8_t *mated;              // [max_games] the last choose found children, none of them king-safe
+    long long *xq_stats;         // [3] games ended by mate, by a repetition draw, by perpetual check (cz_selfplay_rules_stats)
+    // cz_selfplay_set_repetition(fold != 0): the history of every slot's game, a ring over the position index
+    uint64_t *ring_key;          // [max_games][64] cz_hash of position i of the slot's game at [i & 63]
+    uint8_t *ring_check;         // [max_games][64] its side to move is in check
+    uint8_t *rep;                // [max_games] CZ_REP_* of the last choose: the game ends by repetition
+    uint8_t *flags;              // [max_games] CZ_POS_* of the root position (cz_movegen_kingsafe)
+    uint64_t *root_key;          // [max_games] its cz_hash
 };
 
 #define CZ_EC_BUCKETS 128
@@ -187,6 +199,9 @@ struct cz_ctx {
     int clock_probe_wgs, clock_probe_last_grid;
     CzSelfplay sp;     // cz_selfplay_begin
     void *sp_block;
+    int sp_rules;      // cz_selfplay_set_rules: 0 king capture, 1 xiangqi
+    int sp_fold;       // cz_selfplay_set_repetition: 0 off, 2..8
+    int sp_state;      // 0: no cz_selfplay_begin yet, 1: begun (the setters may be called), 2: a cz_selfplay_choose has run since
     void *ec_block;    // cz_search_set_eval_cache
 };
 
@@ -280,6 +295,26 @@ __device__ __forceinline__ void root_children(const CzTrees &t, int g, const Tre
 // has no node limit, so it has no such case); the driver's adjudication ends the game
 __device__ __forceinline__ bool root_cannot_move(int status, int n) {
     return n == 0 || (status & (CZ_ST_NO_MOVES | CZ_ST_MOVE_OVERFLOW)) != 0;
+}
+
+// rules = 1 (cz_match_set_rules, cz_selfplay_set_rules): the root children whose move is in the king-safe set `safe`
+// ([CZ_MASK_WORDS], cz_movegen_kingsafe of the root position), compacted in generation order by one wave64 — sN[j] / sI[j]
+// (LDS, 128 ints each) = the visit count / the child index of the j-th of them, visible to every lane on return -> their number
+__device__ __forceinline__ int wave_kingsafe_children(const TreeView &v, int cb, int n, const uint32_t *__restrict__ safe, int lane,
+                                                      int *sN, int *sI) {
+    bool ok[2];
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        const int i = lane + 64 * r;
+        const uint32_t mv = i < n ? v.move[cb + i] : 0xFFFFu;
+        ok[r] = mv < CZ_NLABELS && ((safe[mv >> 5] >> (mv & 31)) & 1u) != 0u;
+    }
+    const unsigned long long b0 = __ballot(ok[0]), b1 = __ballot(ok[1]), below = (1ull << lane) - 1ull;
+    const int n0 = __popcll(b0), ns = n0 + __popcll(b1);
+    if (ok[0]) { const int at = __popcll(b0 & below); sN[at] = v.N[cb + lane]; sI[at] = lane; }
+    if (ok[1]) { const int at = n0 + __popcll(b1 & below); sN[at] = v.N[cb + lane + 64]; sI[at] = lane + 64; }
+    __syncthreads();
+    return ns;
 }
 
 // ---- move choice at a root (k_pick_ready, k_sp_choose, k_match_choose) ---------------------------
@@ -379,6 +414,6 @@ int czk_search_reload_finished(cz_ctx *, const uint8_t *, const uint16_t *, cons
 int czk_search_select_k(cz_ctx *, int, int, const uint8_t *, void *, int, int, uint8_t *);
 int czk_search_expand_backup_k(cz_ctx *, int, const void *, const void *, int);
 int czk_selfplay_seed(cz_ctx *, const uint8_t *, const uint8_t *, const int32_t *);
-int czk_selfplay_choose(cz_ctx *, const float *, const float *, const uint16_t *, double, float, int, uint16_t *);
+int czk_selfplay_choose(cz_ctx *, const float *, const float *, const uint16_t *, double, float, int, uint16_t *);   // by c->sp_rules / c->sp_fold
 int czk_selfplay_adjudicate(cz_ctx *, int, const uint16_t *, int32_t *);
 int czk_selfplay_flush(cz_ctx *, const int32_t *, const long long *, uint8_t *, long long, const long long *);

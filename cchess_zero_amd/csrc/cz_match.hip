@@ -160,19 +160,7 @@ __device__ __forceinline__ void choose_on(const CzTrees &t, const CzMatch &m, in
     int pick;
     if constexpr (XQ) {
         __shared__ int sN[128], sI[128];
-        const uint32_t *safe = x.safe + (size_t)g * CZ_MASK_WORDS;
-        bool ok[2];
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-            const int i = lane + 64 * r;
-            const uint32_t mv = i < n ? v.move[cb + i] : 0xFFFFu;
-            ok[r] = mv < CZ_NLABELS && ((safe[mv >> 5] >> (mv & 31)) & 1u) != 0u;
-        }
-        const unsigned long long b0 = __ballot(ok[0]), b1 = __ballot(ok[1]), below = (1ull << lane) - 1ull;
-        const int n0 = __popcll(b0), ns = n0 + __popcll(b1);
-        if (ok[0]) { const int at = __popcll(b0 & below); sN[at] = v.N[cb + lane]; sI[at] = lane; }
-        if (ok[1]) { const int at = n0 + __popcll(b1 & below); sN[at] = v.N[cb + lane + 64]; sI[at] = lane + 64; }
-        __syncthreads();
+        const int ns = wave_kingsafe_children(v, cb, n, x.safe + (size_t)g * CZ_MASK_WORDS, lane, sN, sI);
         if (ns == 0) {   // children, none of them king-safe: checkmate or stalemate, the mover loses (k_match_adjudicate_xq)
             if (lane == 0) { played[g] = 0xFFFF; x.mated[g] = 1; }
             return;

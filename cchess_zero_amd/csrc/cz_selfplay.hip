@@ -11,7 +11,13 @@
 // children in generation order with their visit counts, the game result from the mover's point of view.  pi is not
 // stored: the reference's pi = softmax(1/T * log(visits)) (main.py:1341) is a pure function of the visit counts, so
 // the host recomputes it in float64 with the reference's own expression and gets it bit for bit.
+//
+// cz_selfplay_set_rules(1) — the games are Xiangqi, as the arena's (cz_match.hip with cz_match_set_rules / _set_repetition): the
+// rules act AT THE ROOT ONLY.  The move is chosen, and the record written, over the root children whose move is king-safe; a mover
+// without one is mated; with a fold, a fold-th occurrence of the root position ends the game.  The search below the root is
+// untouched: in the tree a mate is a king capture two plies down, which it already sees.
 #include "cz_internal.h"
+#include "cz_repetition.h"
 
 #include <math.h>
 
@@ -29,15 +35,36 @@ __global__ __launch_bounds__(64) void k_sp_seed(CzTrees t, CzSelfplay sp, int G,
         sp.start_side[g] = boards ? (side[g] ? 1 : 0) : t.root_side[g];
         sp.start_rr[g] = boards ? (rr ? rr[g] : 0) : t.root_rr[g];
         sp.ply[g] = 0; sp.stalled[g] = 0; sp.active[g] = 1;
-        if (g == 0)
+        sp.mated[g] = 0; sp.rep[g] = CZ_REP_NONE;
+        if (g == 0) {
             for (int k = 0; k < CZ_SP_NSTATS; ++k) sp.stats[k] = 0;
+            for (int k = 0; k < 3; ++k) sp.xq_stats[k] = 0;
+        }
     }
+    sp.ring_key[(size_t)g * 64 + lane] = 0ull;
+    sp.ring_check[(size_t)g * 64 + lane] = 0;
+}
+
+// rules = 1, before the choice: the root position of every slot, for cz_movegen_kingsafe (k_match_roots_xq)
+__global__ __launch_bounds__(64) void k_sp_roots_xq(CzTrees t, CzSelfplay sp, int G) {
+    const int g = blockIdx.x, lane = threadIdx.x;
+    if (g >= G) return;
+    const bool live = sp.active[g] != 0;
+    for (int j = lane; j < CZ_NSQ; j += 64) sp.xq_board[(size_t)g * CZ_NSQ + j] = live ? t.root_board[(size_t)g * CZD_BOARD_LDS + j] : (uint8_t)0;
+    if (lane == 0) sp.xq_side[g] = live ? t.root_side[g] : (uint8_t)0;
 }
 
 // get_action (main.py:1337-1351) + the record append of selfplay (:1504-1518) for every active game.
-__global__ __launch_bounds__(64) void k_sp_choose(CzTrees t, CzSelfplay sp, int G, const float *__restrict__ gamma,
-                                                  const float *__restrict__ u, const uint16_t *__restrict__ forced,
-                                                  double inv_temp, float eps, int min_sims, uint16_t *__restrict__ played) {
+// XQ (cz_selfplay_set_rules(1)): over the root children whose move is in the slot's king-safe set — they are compacted, in
+// generation order, and pi, the noise (gamma[g][j] of compacted child j: a Dirichlet over len(probs) entries), the pick and the
+// record run on the ns compacted children exactly as they run on all n under king-capture rules.  ns = 0: the mover is mated.
+// fold != 0 (XQ only): the root position goes into the slot's ring at the game's ply first, and a fold-th occurrence inside the
+// last min(restrict_round, ply, 63) positions ends the game (choose_on<XQ, REP> of cz_match.hip).  On either ending played =
+// 0xFFFF, no record is written and the ply stays; k_sp_adjudicate_xq ends the game.  A forced label is played as given.
+template <bool XQ>
+__device__ __forceinline__ void sp_choose(const CzTrees &t, const CzSelfplay &sp, int G, const float *__restrict__ gamma,
+                                          const float *__restrict__ u, const uint16_t *__restrict__ forced, double inv_temp,
+                                          float eps, int min_sims, uint16_t *__restrict__ played, int fold) {
     const int g = blockIdx.x, lane = threadIdx.x;
     if (g >= G) return;
     if (!sp.active[g]) { if (lane == 0) played[g] = 0xFFFF; return; }
@@ -51,17 +78,47 @@ __global__ __launch_bounds__(64) void k_sp_choose(CzTrees t, CzSelfplay sp, int 
     const TreeView v = view_of(t, g);
     int cb, n;
     root_children(t, g, v, cb, n);
+    if (XQ && lane == 0) { sp.mated[g] = 0; sp.rep[g] = CZ_REP_NONE; }
     if (root_cannot_move(t.status[g], n)) {   // the adjudication drops the game and re-seeds the slot
         if (lane == 0) { played[g] = 0xFFFF; sp.stalled[g] = 1; }
         return;
     }
+    const int ply = sp.ply[g];
     int N[2] = {0, 0};
     uint16_t lab[2] = {0xFFFF, 0xFFFF};
     double pi[2], p[2];
+    if constexpr (XQ) {
+        if (fold != 0) {
+            const uint64_t key = sp.root_key[g];
+            const bool chk = (sp.flags[g] & CZ_POS_IN_CHECK) != 0;
+            uint64_t *ring_key = sp.ring_key + (size_t)g * 64;
+            uint8_t *ring_check = sp.ring_check + (size_t)g * 64;
+            if (lane == 0) { ring_key[ply & 63] = key; ring_check[ply & 63] = chk ? 1 : 0; }
+            const int w = max(0, min(min(t.root_rr[g], ply), 63));   // entry ply & 63, just written, is never among the w read
+            int first;
+            const int verdict = wave_repetition(ring_key, ring_check, 63, ply, w, key, chk, sp.xq_side[g] ? 1 : 0, fold, lane, first);
+            if (verdict != CZ_REP_NONE) {
+                if (lane == 0) { played[g] = 0xFFFF; sp.rep[g] = (uint8_t)verdict; }
+                return;
+            }
+        }
+        __shared__ int sN[128], sI[128];
+        n = wave_kingsafe_children(v, cb, n, sp.safe + (size_t)g * CZ_MASK_WORDS, lane, sN, sI);
+        if (n == 0) {   // children, none of them king-safe: checkmate or stalemate, the mover loses
+            if (lane == 0) { played[g] = 0xFFFF; sp.mated[g] = 1; }
+            return;
+        }
 #pragma unroll
-    for (int r = 0; r < 2; ++r) {
-        const int i = lane + 64 * r;
-        if (i < n) { N[r] = v.N[cb + i]; lab[r] = v.move[cb + i]; }
+        for (int r = 0; r < 2; ++r) {
+            const int i = lane + 64 * r;
+            if (i < n) { N[r] = sN[i]; lab[r] = v.move[cb + sI[i]]; }
+        }
+    } else {
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            const int i = lane + 64 * r;
+            if (i < n) { N[r] = v.N[cb + i]; lab[r] = v.move[cb + i]; }
+        }
     }
     wave_visit_policy(N, n, inv_temp, lane, pi);
     double gm[2] = {0.0, 0.0};
@@ -84,7 +141,6 @@ __global__ __launch_bounds__(64) void k_sp_choose(CzTrees t, CzSelfplay sp, int 
     int mv = __shfl(pick < 64 ? (int)lab[0] : (int)lab[1], pick & 63, 64);
     if (forced && forced[g] < CZ_NLABELS) mv = forced[g];
     // the record of this ply: state before the move, mover, children and their visits
-    const int ply = sp.ply[g];
     if (ply < sp.max_plies) {
         uint8_t *rec = sp.hist + ((size_t)g * sp.max_plies + ply) * CZ_REC_BYTES;
         const uint8_t *rb = t.root_board + (size_t)g * CZD_BOARD_LDS;
@@ -107,25 +163,41 @@ __global__ __launch_bounds__(64) void k_sp_choose(CzTrees t, CzSelfplay sp, int 
     }
     if (lane == 0) { played[g] = (uint16_t)mv; sp.ply[g] = ply + 1; }
 }
+__global__ __launch_bounds__(64) void k_sp_choose(CzTrees t, CzSelfplay sp, int G, const float *__restrict__ gamma,
+                                                  const float *__restrict__ u, const uint16_t *__restrict__ forced,
+                                                  double inv_temp, float eps, int min_sims, uint16_t *__restrict__ played) {
+    sp_choose<false>(t, sp, G, gamma, u, forced, inv_temp, eps, min_sims, played, 0);
+}
+__global__ __launch_bounds__(64) void k_sp_choose_xq(CzTrees t, CzSelfplay sp, int G, const float *__restrict__ gamma,
+                                                     const float *__restrict__ u, const uint16_t *__restrict__ forced,
+                                                     double inv_temp, float eps, int min_sims, uint16_t *__restrict__ played, int fold) {
+    sp_choose<true>(t, sp, G, gamma, u, forced, inv_temp, eps, min_sims, played, fold);
+}
 
 // The game-end tests of selfplay (main.py:1532-1545) on the position after the move, z for every recorded ply, and —
 // reseed != 0 — MCTS_tree.reload / GameBoard.reload for the next game of the slot (:1549-1551, :1494).
 // fin_n[g] = number of records the finished game hands to the ring (0: not finished, or dropped).
-__global__ __launch_bounds__(64) void k_sp_adjudicate(CzTrees t, CzSelfplay sp, int G, int reseed, const uint16_t *__restrict__ played,
-                                                      int32_t *__restrict__ fin_n) {
+// XQ: before those tests, the endings the last choose found on the root it left untouched — a repetition verdict (a draw, or a
+// loss for the side that checked perpetually), then a mated mover (the side to move loses); z as for a king capture.
+template <bool XQ>
+__device__ __forceinline__ void sp_adjudicate(const CzTrees &t, const CzSelfplay &sp, int G, int reseed, const uint16_t *__restrict__ played,
+                                              int32_t *__restrict__ fin_n) {
     const int g = blockIdx.x, lane = threadIdx.x;
     if (g >= G) return;
     if (!sp.active[g]) { if (lane == 0) fin_n[g] = 0; return; }
-    // asynchronous plies: only the slots that just moved (or stalled) can have ended their game
-    if (played && played[g] == 0xFFFF && !sp.stalled[g]) { if (lane == 0) fin_n[g] = 0; return; }
+    const int verdict = XQ ? (int)sp.rep[g] : CZ_REP_NONE;
+    const bool mated = XQ && verdict == CZ_REP_NONE && sp.mated[g] != 0;
+    const bool by_rules = verdict != CZ_REP_NONE || mated;
+    // asynchronous plies: only the slots that just moved (or stalled, or ended by the rules) can have ended their game
+    if (played && played[g] == 0xFFFF && !sp.stalled[g] && !by_rules) { if (lane == 0) fin_n[g] = 0; return; }
     bool Kmiss, kmiss;
     wave_kings_missing(t.root_board + (size_t)g * CZD_BOARD_LDS, lane, Kmiss, kmiss);
     const int ply = sp.ply[g];
-    const bool stalled = sp.stalled[g] != 0 || (t.status[g] & CZ_ST_BAD_ADVANCE) != 0;
-    const bool decided = Kmiss || kmiss;
-    const bool draw = !decided && (restrict_round_draw(t.root_rr[g]) || ply >= sp.max_plies);
+    const bool stalled = !by_rules && (sp.stalled[g] != 0 || (t.status[g] & CZ_ST_BAD_ADVANCE) != 0);
+    const bool decided = by_rules ? verdict != CZ_REP_DRAW : (Kmiss || kmiss);
+    const bool draw = !decided && (by_rules || restrict_round_draw(t.root_rr[g]) || ply >= sp.max_plies);
     if (!(decided || draw || stalled)) { if (lane == 0) fin_n[g] = 0; return; }
-    const int winner = king_capture_winner(Kmiss);
+    const int winner = mated ? 1 - (int)t.root_side[g] : (verdict == CZ_REP_RED_LOSES ? 1 : (verdict == CZ_REP_BLACK_LOSES ? 0 : king_capture_winner(Kmiss)));
     const int n = stalled ? 0 : min(ply, sp.max_plies);
     for (int j = lane; j < n; j += 64) {
         uint8_t *rec = sp.hist + ((size_t)g * sp.max_plies + j) * CZ_REC_BYTES;
@@ -140,11 +212,23 @@ __global__ __launch_bounds__(64) void k_sp_adjudicate(CzTrees t, CzSelfplay sp, 
         else if (decided) atomicAdd((unsigned long long *)&sp.stats[winner ? CZ_SP_BLACK_WINS : CZ_SP_RED_WINS], 1ull);
         else atomicAdd((unsigned long long *)&sp.stats[CZ_SP_DRAWS], 1ull);
         atomicAdd((unsigned long long *)&sp.stats[CZ_SP_PLIES], (unsigned long long)n);
+        if constexpr (XQ) {
+            if (by_rules) atomicAdd((unsigned long long *)&sp.xq_stats[mated ? 0 : (verdict == CZ_REP_DRAW ? 1 : 2)], 1ull);
+            sp.mated[g] = 0; sp.rep[g] = CZ_REP_NONE;
+        }
     }
     if (reseed) {   // the slot's next game: a fresh root on its start position
         fresh_root(t, g, lane, sp.start_board, CZD_BOARD_LDS, sp.start_side, sp.start_rr, g);
         if (lane == 0) { sp.ply[g] = 0; sp.stalled[g] = 0; }
     } else if (lane == 0) sp.active[g] = 0;
+}
+__global__ __launch_bounds__(64) void k_sp_adjudicate(CzTrees t, CzSelfplay sp, int G, int reseed, const uint16_t *__restrict__ played,
+                                                      int32_t *__restrict__ fin_n) {
+    sp_adjudicate<false>(t, sp, G, reseed, played, fin_n);
+}
+__global__ __launch_bounds__(64) void k_sp_adjudicate_xq(CzTrees t, CzSelfplay sp, int G, int reseed, const uint16_t *__restrict__ played,
+                                                         int32_t *__restrict__ fin_n) {
+    sp_adjudicate<true>(t, sp, G, reseed, played, fin_n);
 }
 
 // Copies the records of the games k_sp_adjudicate finished to ring[(offset[g] + j) % ring_records].  The offsets are an
@@ -178,13 +262,26 @@ int czk_selfplay_seed(cz_ctx *c, const uint8_t *boards, const uint8_t *side, con
 
 int czk_selfplay_choose(cz_ctx *c, const float *gamma, const float *u, const uint16_t *forced, double temperature, float eps,
                         int min_sims, uint16_t *played) {
+    if (c->sp_rules == 1) {   // the king-safe set of every slot's root position (with a fold: its check flag and key), then the choice
+        const CzSelfplay &sp = c->sp;
+        hipLaunchKernelGGL(k_sp_roots_xq, dim3(c->G), dim3(64), 0, c->stream, c->t, sp, c->G);
+        CZ_HIP(hipGetLastError());
+        int rc = czk_movegen_kingsafe(c, sp.xq_board, sp.xq_side, c->G, nullptr, nullptr, sp.safe, c->sp_fold ? sp.flags : nullptr, 0);
+        if (rc != CZ_OK) return rc;
+        if (c->sp_fold && (rc = czk_hash(c, sp.xq_board, sp.xq_side, c->G, sp.root_key)) != CZ_OK) return rc;
+        hipLaunchKernelGGL(k_sp_choose_xq, dim3(c->G), dim3(64), 0, c->stream, c->t, sp, c->G, gamma, u, forced, 1.0 / temperature, eps, min_sims, played,
+                           c->sp_fold);
+        CZ_HIP(hipGetLastError());
+        return CZ_OK;
+    }
     hipLaunchKernelGGL(k_sp_choose, dim3(c->G), dim3(64), 0, c->stream, c->t, c->sp, c->G, gamma, u, forced, 1.0 / temperature, eps, min_sims, played);
     CZ_HIP(hipGetLastError());
     return CZ_OK;
 }
 
 int czk_selfplay_adjudicate(cz_ctx *c, int reseed, const uint16_t *played, int32_t *fin_n) {
-    hipLaunchKernelGGL(k_sp_adjudicate, dim3(c->G), dim3(64), 0, c->stream, c->t, c->sp, c->G, reseed, played, fin_n);
+    if (c->sp_rules == 1) hipLaunchKernelGGL(k_sp_adjudicate_xq, dim3(c->G), dim3(64), 0, c->stream, c->t, c->sp, c->G, reseed, played, fin_n);
+    else hipLaunchKernelGGL(k_sp_adjudicate, dim3(c->G), dim3(64), 0, c->stream, c->t, c->sp, c->G, reseed, played, fin_n);
     CZ_HIP(hipGetLastError());
     return CZ_OK;
 }

@@ -8,6 +8,9 @@ Mirrors, for G games at once, cchess_main.get_action (main.py:1332-1358) and cch
     rank-flipped for black, main.py:1507-1512 — and the mover),
   * a game ends when a king is captured (z = +1 for the winner's plies, -1 for the loser's) or after
     60 plies without capture (z = 0), main.py:1532-1545.
+With rules="xiangqi" (cz_selfplay_set_rules / cz_selfplay_set_repetition, as arena.Match) the games are Xiangqi: pi and the
+played move are over the king-safe root children only, a mover without one is mated, and with repetition=N the N-th occurrence
+of a position ends the game — the rules act at the root, the search below it stays the reference's.
 All of it runs on the device (cz_selfplay_choose / cz_search_advance / cz_selfplay_adjudicate / cz_selfplay_flush,
 csrc/cz_selfplay.hip): there is no per-ply host synchronisation and no per-game Python loop; finished games hand their
 records to a device ring and — in continuous mode — their slot starts the next game at once, so the device stays full
@@ -24,9 +27,10 @@ import numpy as np
 import torch
 
 from ._lib import (MAXMOVES, NLABELS, NSQ, REC_BYTES, REC_COUNT, REC_FLAGS, REC_LABELS, REC_PLY, REC_SIDE, REC_VISITS, REC_Z,
-                   SP_STATS, check, lib, tables)
+                   SP_RULES_STATS, SP_STATS, check, lib, tables)
 
 REC_MAXMOVES = MAXMOVES
+RULES = {"capture": 0, "xiangqi": 1}   # cz_selfplay_set_rules (arena.RULES)
 
 
 def pack_records(boards, side, labels, visits, counts, z, ply=None):
@@ -81,9 +85,14 @@ def canonical_planes(boards, side):
 
 def visit_policy(visits, temperature=1.0):
     """get_action's probs (main.py:1341, softmax :1111-1116) with the reference's own float64 expression:
-    softmax(1.0 / temperature * np.log(visits)); zero visits -> log 0 = -inf -> probability 0."""
+    softmax(1.0 / temperature * np.log(visits)); zero visits -> log 0 = -inf -> probability 0.  No visit at all — under
+    rules="xiangqi" every simulation of a search can go to children that are not king-safe and so are not in the record — is
+    1 / k for each, what the choose kernel played from (wave_visit_policy; the reference's expression is NaN there)."""
+    visits = np.asarray(visits, dtype=np.int64)
+    if not visits.any():
+        return np.full(len(visits), 1.0 / len(visits))
     with np.errstate(divide="ignore"):
-        x = 1.0 / temperature * np.log(np.asarray(visits, dtype=np.int64))
+        x = 1.0 / temperature * np.log(visits)
     probs = np.exp(x - np.max(x))
     probs /= np.sum(probs)
     return probs
@@ -111,6 +120,7 @@ def to_dense(rec, temperature=1.0, exact=True):
         valid = np.arange(128)[None, :] < k[:, None]
         with np.errstate(divide="ignore"):
             x = np.where(valid, np.log(u["visits"].astype(np.float64)) / temperature, -np.inf)
+        x = np.where(valid & ~u["visits"].any(axis=1, keepdims=True), 0.0, x)   # no visit at all: 1 / k each, as visit_policy
         e = np.exp(x - x.max(axis=1, keepdims=True))
         p = e / e.sum(axis=1, keepdims=True)
         lab = u["labels"].astype(np.int64)
@@ -126,10 +136,22 @@ class SelfPlay:
 
     continuous=True : a finished game's slot starts a new game at once (the production loop: the batch never decays);
     continuous=False: finished games are parked — play() returns when every game has ended (one game per slot).
+    rules: "capture" — the reference's games: pseudo-legal moves, a game ends when a king is taken; "xiangqi" — the move is
+    chosen and recorded among the king-safe root children, and a mover without one loses (checkmate or stalemate).
+    repetition (rules="xiangqi" only): 0 — no repetition rule; 2..8 — a game ends when its position occurs for that many times
+    since the last capture: a draw, or a loss for the side that alone checked with every move of the cycle.
     """
 
     def __init__(self, engine, net, playouts, exploration=True, temperature=1.0, seed=0, max_plies=512, ring_records=None,
-                 continuous=True, eval_cache=False, xcache_log2=0):
+                 continuous=True, eval_cache=False, xcache_log2=0, rules="capture", repetition=0):
+        if rules not in RULES:
+            raise ValueError("SelfPlay: rules is 'capture' or 'xiangqi', not %r" % (rules,))
+        if isinstance(repetition, bool) or not isinstance(repetition, (int, np.integer)) or not (repetition == 0 or 2 <= repetition <= 8):
+            raise ValueError("SelfPlay: repetition is 0 (off) or 2..8, not %r" % (repetition,))
+        if repetition and rules != "xiangqi":
+            raise ValueError("SelfPlay: repetition needs rules='xiangqi' (the check flags come from the king-safe moves)")
+        self.rules = rules
+        self.repetition = int(repetition)
         self.eng, self.net = engine, net
         self.playouts = int(playouts)
         self.exploration = bool(exploration)
@@ -160,6 +182,10 @@ class SelfPlay:
         eng.compact = not self.continuous   # parked games drop out of the net's batch; a full batch needs no compaction
         G = eng.G
         check(lib().cz_selfplay_begin(eng.ctx.h, self.max_plies, None, None, None), "cz_selfplay_begin")
+        if RULES[self.rules]:
+            check(lib().cz_selfplay_set_rules(eng.ctx.h, RULES[self.rules]), "cz_selfplay_set_rules")
+        if self.repetition:
+            check(lib().cz_selfplay_set_repetition(eng.ctx.h, self.repetition), "cz_selfplay_set_repetition")
         p = C.c_void_p()
         check(lib().cz_selfplay_active(eng.ctx.h, C.byref(p)), "cz_selfplay_active")
         self._active_ptr = p
@@ -172,6 +198,7 @@ class SelfPlay:
         self.fin_n = torch.zeros(G, dtype=torch.int32, device=self.dev)
         self._alpha = torch.full((G, MAXMOVES), 0.3, dtype=torch.float32, device=self.dev)
         self._stats = torch.zeros(len(SP_STATS), dtype=torch.int64, device=self.dev)
+        self._rules_stats = torch.zeros(len(SP_RULES_STATS), dtype=torch.int64, device=self.dev)
         self.plies = 0
         self.lock_steps = 0
         self._dropped_seen = 0
@@ -276,6 +303,18 @@ class SelfPlay:
         check(lib().cz_download(self.eng.ctx.h, buf.ctypes.data_as(C.c_void_p), self._active_ptr, self.eng.G), "cz_download")
         return torch.from_numpy(buf)
 
+    def history(self):
+        """(keys u64 [G, 64], checks u8 [G, 64]) on the host: the slots' position rings (cz_selfplay_history; repetition != 0),
+        position i of a slot's game at [i & 63]."""
+        G, L, h = self.eng.G, lib(), self.eng.ctx.h
+        self.eng.ctx.bind_stream()
+        pk, pc = C.c_void_p(), C.c_void_p()
+        check(L.cz_selfplay_history(h, C.byref(pk), C.byref(pc)), "cz_selfplay_history")
+        keys, checks = np.zeros((G, 64), np.uint64), np.zeros((G, 64), np.uint8)
+        for o, p in ((keys, pk), (checks, pc)):
+            check(L.cz_download(h, o.ctypes.data_as(C.c_void_p), p, o.nbytes), "cz_download")
+        return keys, checks
+
     def drain_device(self, on_overflow="raise"):
         """-> uint8 [n, REC_BYTES] DEVICE tensor with the records finished since the last drain (synchronises on the
         cursor and the drop counter).  The returned rows stay valid until the ring wraps over them.
@@ -317,11 +356,16 @@ class SelfPlay:
         return self.drain_device().cpu().numpy().reshape(-1, REC_BYTES)
 
     def stats(self):
-        """Running totals since start(): games, red_wins, black_wins, draws, plies (records), stalled, dropped, sims."""
+        """Running totals since start(): games, red_wins, black_wins, draws, plies (records), stalled, dropped, sims; with
+        rules="xiangqi" also mates, repetitions, perpetuals — the games among them that ended by mate (a win), by a repetition
+        draw, by perpetual check (a win)."""
         self.eng.ctx.bind_stream()
         check(lib().cz_selfplay_stats(self.eng.ctx.h, C.c_void_p(self._stats.data_ptr())), "cz_selfplay_stats")
         s = self._stats.cpu().numpy()
         d = {k: int(v) for k, v in zip(SP_STATS, s)}
+        if RULES[self.rules]:
+            check(lib().cz_selfplay_rules_stats(self.eng.ctx.h, C.c_void_p(self._rules_stats.data_ptr())), "cz_selfplay_rules_stats")
+            d.update((k, int(v)) for k, v in zip(SP_RULES_STATS, self._rules_stats.cpu().numpy()))
         d["sims"] += int(self.eng.status()[2].sum().item())   # + the simulations of the searches in progress
         d["plies_played"] = self.plies          # lock-step plies (step_ply)
         d["lock_steps"] = self.lock_steps       # select / net / expand steps of the asynchronous loop (run_async)

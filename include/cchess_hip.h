@@ -368,6 +368,37 @@ int cz_selfplay_adjudicate(cz_ctx *, int reseed, const uint16_t *played, int32_t
 int cz_selfplay_flush(cz_ctx *, const int32_t *fin_n, const long long *offset, uint8_t *ring, long long ring_records,
                       const long long *read_cursor);
 int cz_selfplay_stats(cz_ctx *, long long *stats_dev);
+/* cz_selfplay_set_rules: 0 = king capture (the default: the reference's games, everything above, launch for launch), 1 = xiangqi,
+ *   as cz_match_set_rules.  The rules act AT THE ROOT ONLY: the search below it is untouched, so the trees stay the reference's
+ *   (in the tree a mate is a king capture two plies down, which the search already sees).  With 1, cz_selfplay_choose first
+ *   computes the king-safe set (cz_movegen_kingsafe) of every active slot's root position and then does everything above ON
+ *   THE ROOT CHILDREN WHOSE MOVE IS IN THAT SET, compacted in generation order: pi = softmax(log N / T) over them alone, the noise
+ *   of compacted child j is gamma[g][j] (a Dirichlet over len(probs) entries), the same inverse CDF with u[g], and the record holds
+ *   only them (labels / visits in generation order, count = their number, padding 0xFFFF / 0): pi has no mass on a move that
+ *   leaves the king en prise (when every simulation went to children outside the set, the record's visits are all 0: the move
+ *   is picked uniformly among them, as for a root without a visit).  A forced label is played as given.  A root with children, none of them king-safe: played = 0xFFFF,
+ *   no record, and cz_selfplay_adjudicate ends the game as a loss for the side to move (checkmate or stalemate), z = +1 / -1 as for
+ *   a king capture, fin_n = min(plies played, max_plies).  A root without children stalls as above.
+ *   Both setters: after cz_selfplay_begin — which returns the context to rules 0, fold 0 and zeroes the counters below and the
+ *   rings — and before the first cz_selfplay_choose that follows it; CZ_EINVAL otherwise.
+ * cz_selfplay_set_repetition: fold 0 = no repetition rule (the default), 2 <= fold <= 8 = a game ends when its position occurs
+ *   for the fold-th time (cz_repetition's rule, as cz_match_set_repetition; 3 is the usual value).  Needs cz_selfplay_set_rules(ctx,
+ *   1) first — the check flags are the king-safe pass's; cz_selfplay_set_rules(ctx, 0) is refused while the fold is not 0.  With
+ *   it, cz_selfplay_choose also takes every root position's CZ_POS_* flags and cz_hash, writes them into the slot's ring of 64
+ *   positions at entry ply & 63 (after the parked / min_sims / stalled tests, every index masked) and evaluates the rule with
+ *   w = min(restrict_round of the root, ply, 63): w <= ply keeps every read inside the slot's current game, so a re-seeded slot
+ *   never reads its previous game's ring.  Order: stalled, then repetition, then mate.  On a verdict played = 0xFFFF, no record is
+ *   written, the ply stays, and cz_selfplay_adjudicate — before the mate and before every test above, also for a slot its `played`
+ *   argument would skip — ends the game: CZ_REP_DRAW a draw (z = 0, CZ_SP_DRAWS), CZ_REP_RED_LOSES / CZ_REP_BLACK_LOSES a loss for
+ *   that side (z as for a king capture, CZ_SP_BLACK_WINS / CZ_SP_RED_WINS); fin_n = min(plies played, max_plies).
+ * cz_selfplay_history: the device pointers of the two rings, owned by the context — keys uint64 [G][64], checks uint8 [G][64]:
+ *   position i of the game in slot g at [g][i & 63]; either may be NULL.  CZ_EINVAL while the repetition rule is off.
+ * cz_selfplay_rules_stats: device int64 [3] <- games ended by mate, by a repetition draw, by perpetual check since
+ *   cz_selfplay_begin.  They are counted in the cz_selfplay_stats slots too (wins / draws, games, plies). */
+int cz_selfplay_set_rules(cz_ctx *, int rules);
+int cz_selfplay_set_repetition(cz_ctx *, int fold);
+int cz_selfplay_history(cz_ctx *, const uint64_t **keys, const uint8_t **checks);
+int cz_selfplay_rules_stats(cz_ctx *, long long *stats_dev /* [3]: mates, repetitions, perpetuals */);
 
 /* ---- device-resident evaluation matches between two players (one wave per game slot; no host round trip per ply) -------
  * replaces: cchess_main.policy_evaluate (main.py:1207-1222, commented out in the reference) — many games of player A

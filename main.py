@@ -339,6 +339,7 @@ class cchess_main(object):
         self.eval_every = 0           # run(): policy_evaluate every this many batches (0 = off; --eval_every)
         self.eval_games = 256
         self.last_evaluation = None
+        self.rules, self.repetition = "capture", 0   # the batched self-play games and the evaluation matches (--rules, --repetition)
 
     @staticmethod
     def flip_policy(prob):
@@ -504,7 +505,8 @@ class cchess_main(object):
         cap = pool_nodes(self.playout_counts)
         net = self.policy_value_netowrk.net
         sp = getattr(self, "_sp", None)
-        if sp is None or sp.eng.G != G or sp.eng.ctx.cap < cap or sp.playouts != self.playout_counts or sp.net is not net:
+        if (sp is None or sp.eng.G != G or sp.eng.ctx.cap < cap or sp.playouts != self.playout_counts or sp.net is not net
+                or sp.rules != self.rules or sp.repetition != self.repetition):
             # planes are written by the select kernel straight in the fused net's input format (16 channels of its 16-bit type)
             plane_dtype, channels = plane_format(net)
             eng = SearchEngine(G, cap, torch.cuda.current_device(), plane_dtype=plane_dtype, channels=channels)
@@ -523,7 +525,7 @@ class cchess_main(object):
                           # 4.16 M, 2**24 entries 4.38 M (+21.6 %); the write-once table is full either way
                           xcache_log2=min(24, max(18, (G * 2048 - 1).bit_length())) if self.playout_counts >= 400 else 0,
                           # a drain interval can end every game of every slot in the worst case: room for ~160 plies per slot
-                          ring_records=max(65536, 160 * G))
+                          ring_records=max(65536, 160 * G), rules=self.rules, repetition=self.repetition)
             b0 = np.tile(state_to_board(START_STATE), (G, 1))
             sp.start(b0, np.zeros(G, np.uint8), np.zeros(G, np.int32))
             self._sp, self._batch_eng = sp, eng
@@ -546,7 +548,8 @@ class cchess_main(object):
             st = sp.stats()
             if st["games"] - before["games"] >= target or (max_plies is not None and plies >= max_plies):
                 break
-        self.last_selfplay_stats = {k: (st[k] - before[k] if k in ("games", "red_wins", "black_wins", "draws", "plies", "sims", "lock_steps") else st[k]) for k in st}
+        self.last_selfplay_stats = {k: (st[k] - before[k] if k in ("games", "red_wins", "black_wins", "draws", "plies", "sims", "lock_steps", "mates", "repetitions", "perpetuals") else st[k])
+                                    for k in st}
         self.last_selfplay_sims = self.last_selfplay_stats["sims"]
         rec = torch.cat(chunks, 0) if chunks else sp.ring[:0]
         return parallel.gather_records(rec)
@@ -573,7 +576,7 @@ class cchess_main(object):
         self._eval_round = getattr(self, "_eval_round", 0) + 1
         openings = random_openings(pairs, 4, seed=self.update_seed + self._eval_round)
         res = Match((live, self.playout_counts), (opp, self.playout_counts), openings, slots=max(2, min(2 * pairs, self.games)),
-                    seed=self.update_seed + self._eval_round).play()
+                    seed=self.update_seed + self._eval_round, rules=self.rules, repetition=self.repetition).play()
         self.last_evaluation = res
         if opponent is None and res.score is not None and res.score >= 0.55:
             self._eval_snapshot = self._snapshot_net()
@@ -616,8 +619,9 @@ class cchess_main(object):
                 dt = time.time() - t0
                 st = self.last_selfplay_stats
                 n = len(rec)
-                print("batch i:{}, game slots:{}, games finished:{}, samples:{}, sims/s:{:.0f}".format(
-                    batch_iter, self.games, st["games"], n, self.last_selfplay_sims / max(dt, 1e-9)))
+                by_rules = ", mates:{mates}, repetitions:{repetitions}, perpetuals:{perpetuals}".format(**st) if "mates" in st else ""
+                print("batch i:{}, game slots:{}, games finished:{}, samples:{}, sims/s:{:.0f}{}".format(
+                    batch_iter, self.games, st["games"], n, self.last_selfplay_sims / max(dt, 1e-9), by_rules))
                 if self.data_buffer.maxlen < 2 * n:
                     self.data_buffer = deque(self.data_buffer, maxlen=2 * n)
                 # the buffer keeps the PACKED records (608 B each; the reference's dense tuple is 22 KB): policy_update
@@ -704,11 +708,19 @@ if __name__ == '__main__':
     parser.add_argument('--eval_every', default=0, type=int,
                         help='every this many batches, a match of the live net against a frozen snapshot (policy_evaluate); 0 = off')
     parser.add_argument('--eval_games', default=256, type=int, help='games of each evaluation match')
+    parser.add_argument('--rules', default='capture', choices=['capture', 'xiangqi'], type=str,
+                        help='batched self-play and evaluation matches: capture = the reference\'s games (a king is taken); xiangqi = '
+                             'king-safe moves only, a side without one is mated')
+    parser.add_argument('--repetition', default=0, type=int,
+                        help='with --rules xiangqi: a game ends when its position occurs for the N-th time (3 is the usual value): a draw, '
+                             'or a loss for the side that checked perpetually; 0 = no repetition rule')
     parser.add_argument('--net_precision', default=None, choices=['strict', 'mx6', 'fp16x2', 'fp16', 'bf16', 'bf16x2', 'fp32'], type=str,
                         help='net engine (policy_value_network.PRECISIONS): strict (default) = measured within 5e-4 absolute of the '
                              'fp32 graph on 64 positions with the LIVE weights after every weight change, falling over mx6 -> fp16x2 -> '
                              'fp32 otherwise (mx6: ~4e-5 of the largest logit; fp16x2: ~6e-6); fp16 = 2x faster, ~1e-3 of the largest logit')
     args = parser.parse_args()
+    if not (args.repetition == 0 or 2 <= args.repetition <= 8) or (args.repetition and args.rules != 'xiangqi'):
+        parser.error("--repetition is 0 or 2..8 and needs --rules xiangqi")
 
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:   # launched by torch.distributed.run: one rank per GPU
         import torch
@@ -733,6 +745,7 @@ if __name__ == '__main__':
         train_main = cchess_main(args.train_playout, args.batch_size, True, args.search_threads, args.processor, args.num_gpus,
                                  args.res_block_nums, args.human_color, games=args.games)
         train_main.eval_every, train_main.eval_games = args.eval_every, args.eval_games
+        train_main.rules, train_main.repetition = args.rules, args.repetition
         train_main.run(args.max_batches)
         if os.environ.get("CCHESS_WEIGHT_DIGEST_DIR"):   # tests: every rank leaves a digest of its replica (they must be equal)
             import hashlib
