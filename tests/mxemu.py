@@ -5,7 +5,9 @@ Every product of a tower conv is  a*w ~= a_hi*w_hi (fp16 MFMA)  +  2^-11 * [ q6(
 by the 32 slots of a block = both cross-term operands of 16 channels {32 t + 8 q + 4 h + i} of one cell (activations) / one
 (output channel, tap) (weights); scale = 2^(exponent(amax) - 2), so amax lands in [4, 8).  The block input of a residual
 block is added in fp32; the heads read the last layer's fp32 values.  Accumulation order differs from the MFMA's (fp32
-either way), so the kernel is held to this emulation with a small tolerance, and both to the fp32 graph with north_star's.
+either way), so on real weights the kernel is held to this emulation with a small tolerance, and both to the fp32 graph with
+north_star's; on the exact-arithmetic nets of tests/exactnets.py, where every partial sum is an exact fp32 number, the kernel
+must equal this emulation evaluated in float64 (the dtype arguments) bit for bit (tests/test_net_exact.py).
 Used by tests/test_net.py, tools/precision_mx_schemes.py and the packing test of cchess_zero_amd.net.mx_pack_layer."""
 import numpy as np
 import torch
@@ -39,7 +41,7 @@ def block_scale(amax):
     """2^(biased exponent(amax) - 2 - 127), the E8M0 byte clamped at 1 as the kernel does"""
     m, e = torch.frexp(amax.clamp(min=1e-45))                      # amax = m 2^e, m in [0.5, 1)
     byte = (e - 1 + 127 - 2).clamp(min=1)
-    return torch.exp2((byte - 127).float()), byte
+    return torch.exp2((byte - 127).to(amax.dtype)), byte
 
 
 def mxq_pair(p0, p1, cdim, scale_from=None):
@@ -62,39 +64,47 @@ def mxq_pair(p0, p1, cdim, scale_from=None):
     return da, db
 
 
-def split16(t):
-    hi = t.to(f16).float()
+def split16(t, dtype=torch.float32):
+    """dtype: the type the halves are handed out (and the difference is taken) in; torch.float64 for the exact tier"""
+    t = t.to(dtype)
+    hi = t.to(f16).to(dtype)
     return hi, t - hi
 
 
-def mx_conv(v, w):
+def mx_conv(v, w, dtype=torch.float32):
     """one 3x3 tower conv the way the kernel computes it.  v: post-ReLU fp32 activations [B,128,9,10] (clamped at 65504),
-    w: folded fp32 weights [128,128,3,3]"""
-    a_hi, a_lo = split16(v)
-    w_hi, w_lo = split16(w)
-    w_lo = w_lo.to(f16).float()            # the host stores lo as fp16 before it is quantised (as the strict engine's pack)
-    a_h6, a_l6 = mxq_pair(a_hi, a_lo * S_LO, 1, scale_from=v)
+    w: folded fp32 weights [128,128,3,3]; dtype: the arithmetic of the emulation (torch.float64: tests/exactnets.py)"""
+    a_hi, a_lo = split16(v, dtype)
+    w_hi, w_lo = split16(w, dtype)
+    w_lo = w_lo.to(f16).to(dtype)          # the host stores lo as fp16 before it is quantised (as the strict engine's pack)
+    a_h6, a_l6 = mxq_pair(a_hi, a_lo * S_LO, 1, scale_from=v.to(dtype))
     w_l6, w_h6 = mxq_pair(w_lo * S_LO, w_hi, 1)
     y = F.conv2d(a_hi, w_hi, None, padding=1)
     y = y + (F.conv2d(a_h6, w_l6, None, padding=1) + F.conv2d(a_l6, w_h6, None, padding=1)) / S_LO
     return y
 
 
-def forward_mx(m, x_nchw):
-    """PolicyValueModule m, planes [B,14,9,10] f32 -> (logits, value) as the mx engine computes them"""
+def forward_mx(m, x_nchw, dtype=torch.float32):
+    """PolicyValueModule m, planes [B,14,9,10] f32 -> (logits, value, trunk) as the mx engine computes them; dtype: the
+    arithmetic of the emulation (torch.float64 evaluates the folded fp32 weights and the FC layers in double)"""
     relu = lambda t: t.clamp(min=0.0, max=65504.0)
+    cast = lambda t: t.to(dtype)
+    lin = lambda fc, t: t @ cast(fc.weight).t() + cast(fc.bias)
+    x_nchw = cast(x_nchw)
     w, b = m.conv_in.folded()
-    w_hi, w_lo = split16(w)
-    w_lo = w_lo.to(f16).float()
-    v = relu(F.conv2d(x_nchw, w_hi, None, padding=1) + F.conv2d(x_nchw, w_lo, None, padding=1) + b.view(1, -1, 1, 1))
+    w_hi, w_lo = split16(w, dtype)
+    w_lo = w_lo.to(f16).to(dtype)
+    v = relu(F.conv2d(x_nchw, w_hi, None, padding=1) + F.conv2d(x_nchw, w_lo, None, padding=1) + cast(b).view(1, -1, 1, 1))
     for a, b2 in m.blocks:
         wa, ba = a.folded(); wb, bb = b2.folded()
-        t = relu(mx_conv(v, wa) + ba.view(1, -1, 1, 1))
-        v = relu(mx_conv(t, wb) + bb.view(1, -1, 1, 1) + v)
+        t = relu(mx_conv(v, wa, dtype) + cast(ba).view(1, -1, 1, 1))
+        v = relu(mx_conv(t, wb, dtype) + cast(bb).view(1, -1, 1, 1) + v)
     wp, bp = m.policy_conv.folded(); wv, bv = m.value_conv.folded()
-    p = torch.relu(F.conv2d(v, wp, bp)).permute(0, 2, 3, 1).reshape(v.shape[0], 180)
-    u = torch.relu(F.conv2d(v, wv, bv)).permute(0, 2, 3, 1).reshape(v.shape[0], 90)
-    return m.policy_fc(p), torch.tanh(m.value_fc2(torch.relu(m.value_fc1(u)))), v
+    p = torch.relu(F.conv2d(v, cast(wp), cast(bp))).permute(0, 2, 3, 1).reshape(v.shape[0], 180)
+    u = torch.relu(F.conv2d(v, cast(wv), cast(bv))).permute(0, 2, 3, 1).reshape(v.shape[0], 90)
+    if dtype == torch.float32:
+        return m.policy_fc(p), torch.tanh(m.value_fc2(torch.relu(m.value_fc1(u)))), v
+    return lin(m.policy_fc, p), torch.tanh(lin(m.value_fc2, torch.relu(lin(m.value_fc1, u)))), v
 
 
 def e2m3_codes(x_scaled):
