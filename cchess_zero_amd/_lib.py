@@ -20,10 +20,14 @@ F32, BF16, F16 = 0, 1, 2
 REC_BYTES, REC_SIDE, REC_COUNT, REC_Z, REC_FLAGS, REC_PLY, REC_LABELS, REC_VISITS = 608, 90, 91, 92, 93, 94, 96, 352
 SP_STATS = ("games", "red_wins", "black_wins", "draws", "plies", "stalled", "dropped", "sims")
 SP_RULES_STATS = ("mates", "repetitions", "perpetuals")   # cz_selfplay_rules_stats
+SP_CHASE_STATS = ("chases",)                               # cz_selfplay_chase_stats
 # why a match game ended (include/cchess_hip.h: CZ_MATCH_*); 0 = not finished
 MATCH_KING, MATCH_RR60, MATCH_PLY_CAP, MATCH_ABORTED, MATCH_MATE, MATCH_REPETITION, MATCH_PERPETUAL = 1, 2, 3, 4, 5, 6, 7
+MATCH_CHASE = 9   # 8 is not assigned
 # verdicts of cz_repetition (include/cchess_hip.h: CZ_REP_*)
 REP_NONE, REP_DRAW, REP_RED_LOSES, REP_BLACK_LOSES = 0, 1, 2, 3
+# why cz_repetition_chase gave its verdict (include/cchess_hip.h: CZ_CAUSE_*)
+CAUSE_NONE, CAUSE_CHECK, CAUSE_CHASE = 0, 1, 2
 # position flags of cz_movegen_kingsafe (include/cchess_hip.h: CZ_POS_*)
 POS_IN_CHECK, POS_CAN_TAKE_KING, POS_NO_SAFE_MOVE = 1, 2, 4
 
@@ -47,6 +51,8 @@ _SIGS = {
     "cz_movegen_ex": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_int, _u16p, _u16p, _vp, C.c_int]),
     "cz_movegen_kingsafe": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_int, _u16p, _u16p, _vp, _u8p, C.c_int]),
     "cz_repetition": (C.c_int, [C.c_void_p, _vp, _u8p, C.c_int, _i32p, _i32p, _u8p, C.c_int, C.c_int, _u8p, _i32p]),
+    "cz_threats": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_int, _vp]),
+    "cz_repetition_chase": (C.c_int, [C.c_void_p, _vp, _u8p, _vp, C.c_int, _i32p, _i32p, _u8p, C.c_int, C.c_int, _u8p, _i32p, _u8p]),
     "cz_apply_move": (C.c_int, [C.c_void_p, _u8p, _u8p, _u16p, C.c_int, _vp, _u8p, _vp]),
     "cz_hash": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_int, _vp]),
     "cz_encode_planes": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_int, _vp, C.c_int, C.c_int, C.c_int]),
@@ -93,12 +99,17 @@ _SIGS = {
     "cz_selfplay_set_repetition": (C.c_int, [C.c_void_p, C.c_int]),
     "cz_selfplay_history": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "cz_selfplay_rules_stats": (C.c_int, [C.c_void_p, _vp]),
+    "cz_selfplay_set_chase": (C.c_int, [C.c_void_p, C.c_int]),
+    "cz_selfplay_chase_history": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    "cz_selfplay_chase_stats": (C.c_int, [C.c_void_p, _vp]),
     "cz_match_create": (C.c_int, [C.c_void_p, C.c_void_p, _u8p, _u8p, _i32p, C.c_int, C.c_longlong, C.c_longlong, C.c_int,
                                   C.POINTER(C.c_void_p)]),
     "cz_match_destroy": (None, [C.c_void_p]),
     "cz_match_set_rules": (C.c_int, [C.c_void_p, C.c_int]),
     "cz_match_set_repetition": (C.c_int, [C.c_void_p, C.c_int]),
     "cz_match_history": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "cz_match_set_chase": (C.c_int, [C.c_void_p, C.c_int]),
+    "cz_match_chase_history": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "cz_match_active": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
     "cz_match_choose": (C.c_int, [C.c_void_p, C.c_int, C.c_ulonglong, _u16p]),
     "cz_match_adjudicate": (C.c_int, [C.c_void_p, _u16p]),

@@ -27,21 +27,22 @@ import time
 import numpy as np
 import torch
 
-from ._lib import (MATCH_ABORTED, MATCH_KING, MATCH_MATE, MATCH_PERPETUAL, MATCH_PLY_CAP, MATCH_REPETITION, MATCH_RR60, NSQ, check, lib,
-                   tables)
+from ._lib import (MATCH_ABORTED, MATCH_CHASE, MATCH_KING, MATCH_MATE, MATCH_PERPETUAL, MATCH_PLY_CAP, MATCH_REPETITION, MATCH_RR60, NSQ, check,
+                   lib, tables)
 from .engine import SearchEngine, _ptr, plane_format, pool_nodes
 from .notation import player_to_side, state_to_board
 
 REASONS = {0: "unfinished", MATCH_KING: "king", MATCH_RR60: "rr60", MATCH_PLY_CAP: "ply_cap", MATCH_ABORTED: "aborted", MATCH_MATE: "mate",
-           MATCH_REPETITION: "repetition", MATCH_PERPETUAL: "perpetual"}
+           MATCH_REPETITION: "repetition", MATCH_PERPETUAL: "perpetual", MATCH_CHASE: "chase"}
 RULES = {"capture": 0, "xiangqi": 1}   # cz_match_set_rules
 
 
 def is_scored(reason):
     """A finished game that counts: every ending but "aborted" (a mate, rules="xiangqi", is a loss for the mated side; with
-    repetition != 0 a repetition is a draw and a perpetual check a loss for the checking side)."""
+    repetition != 0 a repetition is a draw and a perpetual check a loss for the checking side; with chase a perpetual chase is
+    a loss for the chasing side)."""
     reason = np.asarray(reason, np.int64)
-    return ((reason >= MATCH_KING) & (reason <= MATCH_PLY_CAP)) | ((reason >= MATCH_MATE) & (reason <= MATCH_PERPETUAL))
+    return ((reason >= MATCH_KING) & (reason <= MATCH_PLY_CAP)) | ((reason >= MATCH_MATE) & (reason <= MATCH_PERPETUAL)) | (reason == MATCH_CHASE)
 
 
 # ---- openings ------------------------------------------------------------------------------------------------------------
@@ -171,9 +172,10 @@ class MatchResult:
     W / D / L for A overall and by colour over the scored games (aborted games excluded), score = (W + D / 2) / scored,
     elo and its 95 % interval from the pentanomial distribution of the opening pairs, simulations, seconds, sims_per_s;
     rules ("capture" / "xiangqi") and mates: the games that ended because the mover had no king-safe move; repetition (the
-    fold, 0 = no such rule), repetitions: the games drawn by it, perpetuals: the games lost by perpetual check."""
+    fold, 0 = no such rule), repetitions: the games drawn by it, perpetuals: the games lost by perpetual check; chase (the
+    perpetual-chase rule was on), chases: the games lost by perpetual chase."""
 
-    def __init__(self, result, a_red, plies, reason, moves, simulations, seconds, players, rules="capture", repetition=0):
+    def __init__(self, result, a_red, plies, reason, moves, simulations, seconds, players, rules="capture", repetition=0, chase=False):
         self.result = np.asarray(result, np.int8)
         self.a_red = np.asarray(a_red, np.uint8)
         self.plies = np.asarray(plies, np.int32)
@@ -187,6 +189,8 @@ class MatchResult:
         self.repetition = int(repetition)
         self.repetitions = int((self.reason == MATCH_REPETITION).sum())
         self.perpetuals = int((self.reason == MATCH_PERPETUAL).sum())
+        self.chase = bool(chase)
+        self.chases = int((self.reason == MATCH_CHASE).sum())
         self.aborted = int((self.reason == MATCH_ABORTED).sum())
         self.unfinished = int((self.reason == 0).sum())
         self.scored = int(scored.sum())
@@ -212,7 +216,7 @@ class MatchResult:
         """The summary (no per-game arrays): what `python -m cchess_zero_amd.arena` prints.  elo None = infinite (every
         scored game won or lost) or no scored game; an interval end None = unbounded on that side."""
         return dict(rules=self.rules, mates=self.mates, repetition=self.repetition, repetitions=self.repetitions, perpetuals=self.perpetuals,
-                    games=self.games, scored=self.scored, aborted=self.aborted, unfinished=self.unfinished, W=self.wins,
+                    chase=self.chase, chases=self.chases, games=self.games, scored=self.scored, aborted=self.aborted, unfinished=self.unfinished, W=self.wins,
                     D=self.draws, L=self.losses, by_colour=self.by_colour, score=self.score, elo=self.elo,
                     elo_95=None if self.elo_95 is None else list(self.elo_95), pentanomial=self.pentanomial.tolist(),
                     mean_plies=float(self.plies.mean()) if self.games else 0.0,
@@ -285,18 +289,24 @@ class Match:
     chosen among the king-safe root children only (cz_movegen_kingsafe), and a mover without one has lost ("mate").
     repetition (rules="xiangqi" only): 0 — no repetition rule; 2..8 — a game ends when its position occurs for that many
     times since the last capture (3 is the usual value): a draw ("repetition"), or a loss for the side that alone checked with
-    every move of the cycle ("perpetual"); perpetual chase is not judged (cz_match_set_repetition)."""
+    every move of the cycle ("perpetual") (cz_match_set_repetition).
+    chase (with a repetition fold only): False — a chase that repeats is a draw by repetition; True — when neither side checked
+    perpetually, a side that alone threatened one and the same unprotected piece after every one of its moves of the cycle has
+    lost ("chase"; cz_match_set_chase, Rules.threats)."""
 
     def __init__(self, player_a, player_b, openings, slots, max_plies=512, sample_plies=0, seed=0, check_every=8,
-                 nodes_per_tree=None, rules="capture", repetition=0):
+                 nodes_per_tree=None, rules="capture", repetition=0, chase=False):
         if rules not in RULES:
             raise ValueError("Match: rules is 'capture' or 'xiangqi', not %r" % (rules,))
         if isinstance(repetition, bool) or not isinstance(repetition, (int, np.integer)) or not (repetition == 0 or 2 <= repetition <= 8):
             raise ValueError("Match: repetition is 0 (off) or 2..8, not %r" % (repetition,))
         if repetition and rules != "xiangqi":
             raise ValueError("Match: repetition needs rules='xiangqi' (the check flags come from the king-safe moves)")
+        if chase and not repetition:
+            raise ValueError("Match: chase needs a repetition fold (a chase is judged on a repeated position)")
         self.rules = rules
         self.repetition = int(repetition)
+        self.chase = bool(chase)
         self.players = [_player(player_a), _player(player_b)]
         self.openings = as_openings(openings)
         self.slots = int(slots)
@@ -323,7 +333,8 @@ class Match:
         if multi:
             local = merge_ranks(local, n_pairs, rank, world)
         return MatchResult(local["result"], local["a_red"], local["plies"], local["reason"], local["moves"], local["simulations"],
-                           local["seconds"], [_describe(p) for p in self.players], rules=self.rules, repetition=self.repetition)
+                           local["seconds"], [_describe(p) for p in self.players], rules=self.rules, repetition=self.repetition,
+                           chase=self.chase)
 
     def _play_local(self, op, pair_base, pair_stride):
         self.start(op, pair_base, pair_stride)
@@ -376,6 +387,8 @@ class Match:
             check(L.cz_match_set_rules(self._h, RULES[self.rules]), "cz_match_set_rules")
         if self.repetition:
             check(L.cz_match_set_repetition(self._h, self.repetition), "cz_match_set_repetition")
+        if self.chase:
+            check(L.cz_match_set_chase(self._h, 1), "cz_match_set_chase")
         self.masks = []
         for player in (0, 1):
             p = C.c_void_p()
@@ -435,6 +448,16 @@ class Match:
             check(L.cz_download(h, o.ctypes.data_as(C.c_void_p), p, o.nbytes), "cz_download")
         return keys, checks
 
+    def chase_history(self):
+        """chase u64 [G, 64, 4] on the host: the slots' rings of chase records (cz_match_chase_history; chase=True), position i
+        of a slot's game at [i & 63] — Rules.threats of that position."""
+        G, L, h = self.G, lib(), self.engines[0].ctx.h
+        p = C.c_void_p()
+        check(L.cz_match_chase_history(self._h, C.byref(p)), "cz_match_chase_history")
+        out = np.zeros((G, 64, 4), np.uint64)
+        check(L.cz_download(h, out.ctypes.data_as(C.c_void_p), p, out.nbytes), "cz_download")
+        return out
+
     def results(self):
         """The per-game arrays on the host: result, a_red, plies, reason, moves [games, max_plies] (0xFFFF past the end)."""
         n, L, h = self.n_games, lib(), self.engines[0].ctx.h
@@ -488,15 +511,19 @@ def main(argv=None):
     ap.add_argument("--repetition", type=int, default=0,
                     help="with --rules xiangqi: a game ends when its position occurs for the N-th time (3 is the usual value): a draw, "
                          "or a loss for the side that checked perpetually; 0 = no repetition rule")
+    ap.add_argument("--chase", action="store_true",
+                    help="with --repetition: a side that alone chased one unprotected piece with every move of the cycle loses")
     args = ap.parse_args(argv)
     if not (args.repetition == 0 or 2 <= args.repetition <= 8) or (args.repetition and args.rules != "xiangqi"):
         ap.error("--repetition is 0 or 2..8 and needs --rules xiangqi")
+    if args.chase and not args.repetition:
+        ap.error("--chase needs --repetition")
     a = load_player(args.a, args.blocks)
     b = a if args.b == args.a else load_player(args.b, args.blocks)
     pairs = (args.games + 1) // 2
     op = random_openings(pairs, args.opening_plies, args.seed)
     res = Match((a, args.playout), (b, args.playout_b or args.playout), op, slots=args.slots or 2 * pairs, max_plies=args.max_plies,
-                sample_plies=args.sample_plies, seed=args.seed, rules=args.rules, repetition=args.repetition).play()
+                sample_plies=args.sample_plies, seed=args.seed, rules=args.rules, repetition=args.repetition, chase=args.chase).play()
     d = res.to_dict()
     d.update(a=args.a, b=args.b, blocks=args.blocks, opening_plies=args.opening_plies, slots=min(args.slots or 2 * pairs, 2 * pairs),
              seed=args.seed)

@@ -177,6 +177,7 @@ void cz_destroy(cz_ctx *c) {
     if (c->tree_block) (void)hipFree(c->tree_block);
     if (c->pool_block) (void)hipFree(c->pool_block);
     if (c->sp_block) (void)hipFree(c->sp_block);
+    if (c->sp_chase_block) (void)hipFree(c->sp_chase_block);
     if (c->ec_block) (void)hipFree(c->ec_block);
 #if defined(CZ_EXPERIMENT_MX2) || defined(CZ_EXPERIMENT_MX12)
     if (c->mx_xbuf) (void)hipFree(c->mx_xbuf);
@@ -251,6 +252,22 @@ int cz_repetition(cz_ctx *c, const uint64_t *keys, const uint8_t *in_check, int 
     if (G == 0) return CZ_OK;
     CZ_REQUIRE(keys && in_check && len && side && verdict, "cz_repetition: keys, in_check, len, side, verdict required");
     return czk_repetition(c, keys, in_check, stride, len, window, side, G, fold, verdict, first);
+}
+int cz_threats(cz_ctx *c, const uint8_t *boards, const uint8_t *side, int G, uint64_t *chase) {
+    CZ_REQUIRE(c && G >= 0, "cz_threats: null ctx / negative G");
+    if (G == 0) return CZ_OK;
+    CZ_REQUIRE(boards && side && chase, "cz_threats: boards, side, chase required");
+    CZ_REQUIRE((reinterpret_cast<uintptr_t>(chase) & 7u) == 0, "cz_threats: chase must be 8-byte aligned");
+    return czk_threats(c, boards, side, G, chase);
+}
+int cz_repetition_chase(cz_ctx *c, const uint64_t *keys, const uint8_t *in_check, const uint64_t *chase, int stride, const int32_t *len,
+                        const int32_t *window, const uint8_t *side, int G, int fold, uint8_t *verdict, int32_t *first, uint8_t *cause) {
+    CZ_REQUIRE(c && G >= 0, "cz_repetition_chase: null ctx / negative G");
+    CZ_REQUIRE(fold >= 2 && fold <= 8, "cz_repetition_chase: 2 <= fold <= 8");
+    CZ_REQUIRE(stride >= 1, "cz_repetition_chase: stride >= 1");
+    if (G == 0) return CZ_OK;
+    CZ_REQUIRE(keys && in_check && chase && len && side && verdict, "cz_repetition_chase: keys, in_check, chase, len, side, verdict required");
+    return czk_repetition_chase(c, keys, in_check, chase, stride, len, window, side, G, fold, verdict, first, cause);
 }
 int cz_apply_move(cz_ctx *c, uint8_t *boards, uint8_t *side, const uint16_t *label, int G, uint64_t *hash, uint8_t *captured, int8_t *terminal) {
     CZ_REQUIRE(c && G >= 0, "cz_apply_move: null ctx / negative G");
@@ -582,7 +599,7 @@ int cz_selfplay_begin(cz_ctx *c, int max_plies, const uint8_t *boards, const uin
         carve(k, c->sp);
         c->sp.max_plies = max_plies;
     }
-    c->sp_rules = 0; c->sp_fold = 0; c->sp_state = 1;
+    c->sp_rules = 0; c->sp_fold = 0; c->sp_chase = 0; c->sp_state = 1;
     return czk_selfplay_seed(c, boards, side, rr);
 }
 int cz_selfplay_set_rules(cz_ctx *c, int rules) {
@@ -598,6 +615,7 @@ int cz_selfplay_set_repetition(cz_ctx *c, int fold) {
     CZ_REQUIRE(fold == 0 || (fold >= 2 && fold <= 8), "cz_selfplay_set_repetition: fold 0 (off) or 2..8");
     CZ_REQUIRE(c->sp_state == 1, "cz_selfplay_set_repetition: before the first cz_selfplay_choose only (the history starts at the games' first positions)");
     CZ_REQUIRE(fold == 0 || c->sp_rules == 1, "cz_selfplay_set_repetition: cz_selfplay_set_rules(ctx, 1) first (the check flags are the king-safe pass's)");
+    CZ_REQUIRE(fold != 0 || c->sp_chase == 0, "cz_selfplay_set_repetition: the chase rule needs a fold: cz_selfplay_set_chase(ctx, 0) first");
     c->sp_fold = fold;
     return CZ_OK;
 }
@@ -605,6 +623,44 @@ int cz_selfplay_history(cz_ctx *c, const uint64_t **keys, const uint8_t **checks
     CZ_REQUIRE(c && c->sp_block && c->sp_fold != 0, "cz_selfplay_history: cz_selfplay_set_repetition first");
     if (keys) *keys = c->sp.ring_key;
     if (checks) *checks = c->sp.ring_check;
+    return CZ_OK;
+}
+int cz_selfplay_set_chase(cz_ctx *c, int on) {
+    CZ_REQUIRE(c && c->sp_block && c->sp_state != 0, "cz_selfplay_set_chase: call cz_selfplay_begin first");
+    CZ_REQUIRE(on == 0 || on == 1, "cz_selfplay_set_chase: on 0 or 1");
+    CZ_REQUIRE(c->sp_state == 1, "cz_selfplay_set_chase: before the first cz_selfplay_choose only (the history starts at the games' first positions)");
+    CZ_REQUIRE(on == 0 || c->sp_fold != 0, "cz_selfplay_set_chase: cz_selfplay_set_repetition(ctx, fold) first (a chase is judged on a repeated position)");
+    if (on) {
+        const size_t G = (size_t)c->max_games;
+        auto carve = [&](Carver &k, CzSelfplay &sp) {
+            sp.ring_chase = k.take<uint64_t>(G * 64 * 4);
+            sp.root_chase = k.take<uint64_t>(G * 4);
+            sp.chase_stat = k.take<long long>(1);
+        };
+        Carver m{nullptr};
+        CzSelfplay dummy;
+        carve(m, dummy);
+        if (!c->sp_chase_block && hipMalloc(&c->sp_chase_block, m.off) != hipSuccess) {
+            c->sp_chase_block = nullptr;
+            cz_set_error("cz_selfplay_set_chase: hipMalloc(%zu B) failed", m.off);
+            return CZ_ENOMEM;
+        }
+        Carver k{(char *)c->sp_chase_block};
+        carve(k, c->sp);
+        CZ_HIP(hipMemsetAsync(c->sp_chase_block, 0, m.off, c->stream));   // the counter starts with the games, as cz_selfplay_begin's
+    }
+    c->sp_chase = on;
+    return CZ_OK;
+}
+int cz_selfplay_chase_history(cz_ctx *c, const uint64_t **chase) {
+    CZ_REQUIRE(c && c->sp_block && c->sp_chase != 0, "cz_selfplay_chase_history: cz_selfplay_set_chase first");
+    if (chase) *chase = c->sp.ring_chase;
+    return CZ_OK;
+}
+int cz_selfplay_chase_stats(cz_ctx *c, long long *stats_dev) {
+    CZ_REQUIRE(c && c->sp_block && stats_dev, "cz_selfplay_chase_stats: call cz_selfplay_begin first / null argument");
+    if (c->sp_chase) CZ_HIP(hipMemcpyAsync(stats_dev, c->sp.chase_stat, sizeof(long long), hipMemcpyDeviceToDevice, c->stream));
+    else CZ_HIP(hipMemsetAsync(stats_dev, 0, sizeof(long long), c->stream));
     return CZ_OK;
 }
 int cz_selfplay_rules_stats(cz_ctx *c, long long *stats_dev) {

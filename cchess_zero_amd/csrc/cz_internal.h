@@ -74,7 +74,12 @@ struct CzSelfplay {
     uint8_t *rep;                // [max_games] CZ_REP_* of the last choose: the game ends by repetition
     uint8_t *flags;              // [max_games] CZ_POS_* of the root position (cz_movegen_kingsafe)
     uint64_t *root_key;          // [max_games] its cz_hash
+    // cz_selfplay_set_chase(1): the chase records (cz_threats), in an allocation of their own; NULL while the rule is off
+    uint64_t *ring_chase;        // [max_games][64][4] the record of position i of the slot's game at [i & 63]
+    uint64_t *root_chase;        // [max_games][4] the record of the root position
+    long long *chase_stat;       // [1] games ended by perpetual chase (cz_selfplay_chase_stats)
 };
+#define CZ_REP_BY_CHASE 0x10     /* in CzSelfplay::rep beside the CZ_REP_* verdict: the loss is a chase, not a perpetual check */
 
 #define CZ_EC_BUCKETS 128
 // cross-tree table: the bit that marks an entry whose payload is being written (claimed as key | CZ_XC_BUSY, not yet published);
@@ -201,6 +206,8 @@ struct cz_ctx {
     void *sp_block;
     int sp_rules;      // cz_selfplay_set_rules: 0 king capture, 1 xiangqi
     int sp_fold;       // cz_selfplay_set_repetition: 0 off, 2..8
+    int sp_chase;      // cz_selfplay_set_chase: 0 off, 1 on (needs sp_fold != 0)
+    void *sp_chase_block;
     int sp_state;      // 0: no cz_selfplay_begin yet, 1: begun (the setters may be called), 2: a cz_selfplay_choose has run since
     void *ec_block;    // cz_search_set_eval_cache
 };
@@ -398,6 +405,9 @@ __device__ __forceinline__ int wave_pick_inverse_cdf(const double p[2], double u
 int czk_movegen(cz_ctx *, const uint8_t *, const uint8_t *, int, uint16_t *, uint16_t *, uint32_t *, int flags);
 int czk_movegen_kingsafe(cz_ctx *, const uint8_t *, const uint8_t *, int, uint16_t *, uint16_t *, uint32_t *, uint8_t *, int flags);   // cz_kingsafe.hip
 int czk_repetition(cz_ctx *, const uint64_t *, const uint8_t *, int, const int32_t *, const int32_t *, const uint8_t *, int, int, uint8_t *, int32_t *);   // cz_repetition.hip
+int czk_threats(cz_ctx *, const uint8_t *, const uint8_t *, int, uint64_t *);   // cz_chase.hip
+int czk_repetition_chase(cz_ctx *, const uint64_t *, const uint8_t *, const uint64_t *, int, const int32_t *, const int32_t *, const uint8_t *, int, int, uint8_t *, int32_t *,
+                         uint8_t *);   // cz_chase.hip
 int czk_apply_move(cz_ctx *, uint8_t *, uint8_t *, const uint16_t *, int, uint64_t *, uint8_t *, int8_t *);
 int czk_hash(cz_ctx *, const uint8_t *, const uint8_t *, int, uint64_t *);
 int czk_encode_planes(cz_ctx *, const uint8_t *, const uint8_t *, int, void *, int, int, int);

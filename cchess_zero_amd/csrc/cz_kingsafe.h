@@ -34,7 +34,11 @@ CZM_FN CzkPieces czk_without(const CzkPieces &p, int q) {
 }
 
 // Is square k attacked by the pieces `a` of side `as` (0 = red) on the occupancy `occ`?  knon = CzmTables::knon[k].
-CZM_FN bool czk_attacked(const CzmSet &occ, const CzkPieces &a, int as, int k, uint32_t knon) {
+// fly (the default, and what every king-safe caller asks): k holds a king, so the attacker's king anywhere on k's file with
+// nothing between takes it (the flying general).  fly = false is the question for ANY occupied square (cz_chase.h: is a piece
+// protected, does a piece reach its attacker): the attacker's king reaches k by one step inside its palace and in no other way.
+// (A run-time flag, wave-uniform where it is not a constant: cz_chase.h asks both questions from ONE copy of this function.)
+CZM_FN bool czk_attacked(const CzmSet &occ, const CzkPieces &a, int as, int k, uint32_t knon, bool fly = true) {
     const int y = k / 9, x = k - y * 9;
     // rank and file: czm_line_dests with every square an enemy is the run up to and including the first occupied square (rook),
     // resp. the second occupied square behind one screen (cannon); the king's own bit is part of occ, as a slider's is
@@ -42,7 +46,8 @@ CZM_FN bool czk_attacked(const CzmSet &occ, const CzkPieces &a, int as, int k, u
     const uint32_t r1 = czm_line_dests<false>(ro, ~0u, x, 9) & ro, f1 = czm_line_dests<false>(fo, ~0u, y, 10) & fo;
     const uint32_t r2 = czm_line_dests<true>(ro, ~0u, x, 9) & ro, f2 = czm_line_dests<true>(fo, ~0u, y, 10) & fo;
     const uint32_t kr = czm_rank(a.K, y);
-    uint32_t hit = (r1 & czm_rank(a.R, y)) | (f1 & (czm_file(a.R, x) | czm_file(a.K, x))) |   // a king on the file with nothing between: the flying general
+    const uint32_t kf = czm_file(a.K, x);
+    uint32_t hit = (r1 & czm_rank(a.R, y)) | (f1 & (czm_file(a.R, x) | (fly ? kf : 0u))) |   // a king on the file with nothing between: the flying general
                    (r2 & czm_rank(a.C, y)) | (f2 & czm_file(a.C, x));
     // knight on k + (dx, dy): bit 19 + 9 dy + dx of the window at k - 19 (czm_knight_good's positions); its leg is k's diagonal
     // neighbour on that side: bits 9, 11, 27, 29
@@ -68,7 +73,8 @@ CZM_FN bool czk_attacked(const CzmSet &occ, const CzkPieces &a, int as, int k, u
         const bool palace = (as ? y >= 7 : y <= 2) & (x >= 3) & (x <= 5);
         const uint64_t aw = czm_window(a.A, k - 10);   // bit 0: k - 10, 2: k - 8, 18: k + 8, 20: k + 10; x is 3 .. 5: no wrap
         const uint32_t adv = czm_wbit(aw, 0) | czm_wbit(aw, 2) | czm_wbit(aw, 18) | czm_wbit(aw, 20);
-        const uint32_t kst = ((kr << 1) | (kr >> 1)) >> x & 1u;   // the attacker's king on k - 1 or k + 1 (k +- 9 is on the file: above)
+        uint32_t kst = ((kr << 1) | (kr >> 1)) >> x & 1u;   // the attacker's king on k - 1 or k + 1 (k +- 9 is on the file: above)
+        if (!fly) kst |= ((kf << 1) | (kf >> 1)) >> y & 1u;  // without the flying general k +- 9 is a step like the other two
         hit |= (uint32_t)palace & (adv | kst);
         const uint64_t bw = czm_window(a.B, k - 20), ew = ~czm_window(occ, k - 20);   // bishop: bit 20 + 2 (9 sy + sx), eye: bit 20 + 9 sy + sx
         const uint32_t bl = (czm_wbit(bw, 0) & czm_wbit(ew, 10)) | (czm_wbit(bw, 36) & czm_wbit(ew, 28));   // dx = -2

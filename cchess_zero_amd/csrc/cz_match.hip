@@ -22,6 +22,8 @@ struct cz_match {
     int fold;                           // 0: no repetition rule, 2..8: a fold-th occurrence ends the game (cz_match_set_repetition)
     void *rep_block;                    // fold != 0: the slots' position rings and verdicts
     bool chosen;                        // a cz_match_choose has run: the repetition rule can no longer be switched on
+    int chase;                          // 1: perpetual chase is judged too (cz_match_set_chase; needs fold != 0)
+    void *chase_block;                  // chase != 0: the slots' rings of chase records
 };
 
 namespace {
@@ -109,6 +111,13 @@ struct CzMatchRep {
     int fold;
 };
 
+// chase != 0 (cz_match_set_chase): the chase record (cz_threats) of every position of the slot's game, a third ring
+struct CzMatchChase {
+    uint64_t *ring;       // [G][64][4] the record of position i of the slot's game at [i & 63]
+    uint64_t *root;       // [G][4] the record of the mover's root position
+};
+#define CZM_REP_BY_CHASE 0x10   /* in CzMatchRep::rep beside the CZ_REP_* verdict: the loss is a chase, not a perpetual check */
+
 // the first maximum of N over children 0 .. n - 1 (N[r] of child lane + 64 r), wave-uniform: wave_most_visited on registers
 __device__ __forceinline__ int wave_first_max(const int N[2], int n, int lane) {
     int bn = -1, bi = 0x7fffffff;
@@ -129,10 +138,12 @@ __device__ __forceinline__ int wave_first_max(const int N[2], int n, int lane) {
 // REP (with XQ only): the root position goes into the slot's ring at the game's ply, and a fold-th occurrence inside the last
 // min(restrict_round, ply, 63) positions — a capture makes the earlier ones unreachable, and no read leaves the slot's current
 // game — ends the game before a move is chosen: no move is logged, the ply stays (k_match_adjudicate_rep)
-template <bool XQ, bool REP>
+// CHASE (with REP only): the root position's chase record goes into the slot's third ring the same way, and the verdict is
+// wave_repetition_chase's: a repetition that is a draw by checks may be a loss for the side that alone chased one piece
+template <bool XQ, bool REP, bool CHASE = false>
 __device__ __forceinline__ void choose_on(const CzTrees &t, const CzMatch &m, int g, int game, int sample_plies,
                                           unsigned long long seed, uint16_t *__restrict__ played, int lane, const CzMatchXq &x,
-                                          const CzMatchRep &r) {
+                                          const CzMatchRep &r, const CzMatchChase &c = CzMatchChase{}) {
     if (lane == 0) atomicAdd(m.sims, (unsigned long long)t.sims[g]);
     const TreeView v = view_of(t, g);
     int cb, n;
@@ -150,8 +161,17 @@ __device__ __forceinline__ void choose_on(const CzTrees &t, const CzMatch &m, in
         const uint8_t *ring_check = r.check + (size_t)g * 64;
         if (lane == 0) { r.key[(size_t)g * 64 + (ply & 63)] = key; r.check[(size_t)g * 64 + (ply & 63)] = chk ? 1 : 0; }
         const int w = max(0, min(min(t.root_rr[g], ply), 63));   // entry ply & 63, just written, is never among the w read
-        int first;
-        const int verdict = wave_repetition(ring_key, ring_check, 63, ply, w, key, chk, x.side[g] ? 1 : 0, r.fold, lane, first);
+        int first, verdict;
+        if constexpr (CHASE) {
+            uint64_t *ring = c.ring + (size_t)g * 64 * 4;
+            const uint64_t rec[4] = {c.root[(size_t)g * 4], c.root[(size_t)g * 4 + 1], c.root[(size_t)g * 4 + 2], c.root[(size_t)g * 4 + 3]};
+            if (lane < 4) ring[(ply & 63) * 4 + lane] = c.root[(size_t)g * 4 + lane];   // as the key: never among the positions read below
+            int cause;
+            verdict = wave_repetition_chase(ring_key, ring_check, ring, 63, ply, w, key, chk, rec, x.side[g] ? 1 : 0, r.fold, lane, first, cause);
+            if (cause == CZ_CAUSE_CHASE) verdict |= CZM_REP_BY_CHASE;
+        } else {
+            verdict = wave_repetition(ring_key, ring_check, 63, ply, w, key, chk, x.side[g] ? 1 : 0, r.fold, lane, first);
+        }
         if (verdict != CZ_REP_NONE) {
             if (lane == 0) { played[g] = 0xFFFF; r.rep[g] = (uint8_t)verdict; }
             return;
@@ -237,13 +257,24 @@ __global__ __launch_bounds__(64) void k_match_choose_rep(CzTrees ta, CzTrees tb,
     else choose_on<true, true>(tb, m, g, game, sample_plies, seed, played, lane, x, r);
 }
 
+__global__ __launch_bounds__(64) void k_match_choose_chase(CzTrees ta, CzTrees tb, CzMatch m, int sample_plies, unsigned long long seed,
+                                                           uint16_t *__restrict__ played, CzMatchXq x, CzMatchRep r, CzMatchChase c) {
+    const int g = blockIdx.x, lane = threadIdx.x;
+    if (g >= m.G) return;
+    const int game = m.game[g];
+    if (game < 0) { if (lane == 0) played[g] = 0xFFFF; return; }   // a parked slot: before the rings are touched
+    if (m.mover_a[g]) choose_on<true, true, true>(ta, m, g, game, sample_plies, seed, played, lane, x, r, c);
+    else choose_on<true, true, true>(tb, m, g, game, sample_plies, seed, played, lane, x, r, c);
+}
+
 // After cz_search_advance(played) on both contexts: the follower's failed advance (its root was never expanded, so it has no
 // child for the move) is its normal case — it starts a fresh root on the new position; then check_end (main.py:1380-1392)
 // plus the match's own endings (ply cap, aborted game), the result, and the slot's next game.
 // mated (rules = 1 only, else nullptr): the slot's mover had no king-safe move — CZ_MATCH_MATE, before every other ending
 // rep (fold != 0 only, else nullptr): the slot's choose found a fold-th occurrence — CZ_MATCH_REPETITION (a draw) or
 // CZ_MATCH_PERPETUAL (the side that checked with every move of the cycle loses), before mate and everything else
-template <bool XQ, bool REP>
+// CHASE: rep may carry CZM_REP_BY_CHASE — CZ_MATCH_CHASE, lost by the side that chased, scored like a perpetual check
+template <bool XQ, bool REP, bool CHASE = false>
 __device__ __forceinline__ void adjudicate_body(const CzTrees &ta, const CzTrees &tb, const CzMatch &m, const uint16_t *__restrict__ played, uint8_t *mated,
                                                 uint8_t *rep) {
     const int g = blockIdx.x, lane = threadIdx.x;
@@ -257,8 +288,10 @@ __device__ __forceinline__ void adjudicate_body(const CzTrees &ta, const CzTrees
     wave_kings_missing(mv.root_board + (size_t)g * CZD_BOARD_LDS, lane, Kmiss, kmiss);
     const int ply = m.ply[g];
     int reason = 0, verdict = CZ_REP_NONE;
+    bool by_chase = false;
     if constexpr (REP) verdict = rep[g];
-    if (verdict != CZ_REP_NONE) reason = verdict == CZ_REP_DRAW ? CZ_MATCH_REPETITION : CZ_MATCH_PERPETUAL;
+    if constexpr (CHASE) { by_chase = (verdict & CZM_REP_BY_CHASE) != 0; verdict &= ~CZM_REP_BY_CHASE; }
+    if (verdict != CZ_REP_NONE) reason = verdict == CZ_REP_DRAW ? CZ_MATCH_REPETITION : (by_chase ? CZ_MATCH_CHASE : CZ_MATCH_PERPETUAL);
     else if (XQ && mated[g]) reason = CZ_MATCH_MATE;
     else if (aborted) reason = CZ_MATCH_ABORTED;
     else if (Kmiss || kmiss) reason = CZ_MATCH_KING;
@@ -275,7 +308,7 @@ __device__ __forceinline__ void adjudicate_body(const CzTrees &ta, const CzTrees
         const bool a_wins = (king_capture_winner(Kmiss) == 0) == a_red;
         int8_t result = (int8_t)(reason == CZ_MATCH_KING ? (a_wins ? 1 : -1) : (reason == CZ_MATCH_MATE ? (ma ? -1 : 1) : 0));
         if constexpr (REP) {
-            if (reason == CZ_MATCH_PERPETUAL) result = (int8_t)(((verdict == CZ_REP_RED_LOSES) == a_red) ? -1 : 1);   // A has the losing colour
+            if (reason == CZ_MATCH_PERPETUAL || reason == CZ_MATCH_CHASE) result = (int8_t)(((verdict == CZ_REP_RED_LOSES) == a_red) ? -1 : 1);   // A has the losing colour
         }
         m.result[game] = result;
         if (XQ) mated[g] = 0;
@@ -298,6 +331,10 @@ __global__ __launch_bounds__(64) void k_match_adjudicate_xq(CzTrees ta, CzTrees 
 __global__ __launch_bounds__(64) void k_match_adjudicate_rep(CzTrees ta, CzTrees tb, CzMatch m, const uint16_t *__restrict__ played, uint8_t *mated,
                                                              uint8_t *rep) {
     adjudicate_body<true, true>(ta, tb, m, played, mated, rep);
+}
+__global__ __launch_bounds__(64) void k_match_adjudicate_chase(CzTrees ta, CzTrees tb, CzMatch m, const uint16_t *__restrict__ played, uint8_t *mated,
+                                                               uint8_t *rep) {
+    adjudicate_body<true, true, true>(ta, tb, m, played, mated, rep);
 }
 
 }  // namespace
@@ -351,6 +388,16 @@ static size_t carve_rep(const cz_match *mh, char *base, CzMatchRep &r) {
     r.flags = (uint8_t *)take(G);
     r.root_key = (uint64_t *)take(G * 8);
     r.fold = mh->fold;
+    return off;
+}
+
+// chase != 0: the chase rings inside their own allocation
+static size_t carve_chase(const cz_match *mh, char *base, CzMatchChase &c) {
+    size_t off = 0;
+    auto take = [&](size_t bytes) { char *q = base ? base + off : nullptr; off += (bytes + 255) & ~(size_t)255; return q; };
+    const size_t G = (size_t)mh->G;
+    c.ring = (uint64_t *)take(G * 64 * 4 * 8);
+    c.root = (uint64_t *)take(G * 4 * 8);
     return off;
 }
 
@@ -430,6 +477,7 @@ int cz_match_set_repetition(cz_match *mh, int fold) {
     CZ_REQUIRE(mh && (fold == 0 || (fold >= 2 && fold <= 8)), "cz_match_set_repetition: fold 0 (off) or 2..8");
     CZ_REQUIRE(fold == 0 || mh->rules == 1, "cz_match_set_repetition: cz_match_set_rules(match, 1) first (the check flags are the king-safe pass's)");
     CZ_REQUIRE(!mh->chosen,"cz_match_set_repetition: before the first cz_match_choose only (the history starts at the openings)");
+    CZ_REQUIRE(fold != 0 || mh->chase == 0, "cz_match_set_repetition: the chase rule needs a fold: cz_match_set_chase(match, 0) first");
     if (fold != 0 && !mh->rep_block) {
         CzMatchRep sizing;
         const size_t bytes = carve_rep(mh, nullptr, sizing);
@@ -453,12 +501,39 @@ int cz_match_history(cz_match *mh, const uint64_t **keys, const uint8_t **checks
     return CZ_OK;
 }
 
+int cz_match_set_chase(cz_match *mh, int on) {
+    CZ_REQUIRE(mh && (on == 0 || on == 1), "cz_match_set_chase: on 0 or 1");
+    CZ_REQUIRE(on == 0 || mh->fold != 0, "cz_match_set_chase: cz_match_set_repetition(match, fold) first (a chase is judged on a repeated position)");
+    CZ_REQUIRE(!mh->chosen, "cz_match_set_chase: before the first cz_match_choose only (the history starts at the openings)");
+    if (on && !mh->chase_block) {
+        CzMatchChase sizing;
+        const size_t bytes = carve_chase(mh, nullptr, sizing);
+        if (hipMalloc(&mh->chase_block, bytes) != hipSuccess) {
+            mh->chase_block = nullptr;
+            cz_set_error("cz_match_set_chase: hipMalloc(%zu B) failed", bytes);
+            return CZ_ENOMEM;
+        }
+        CZ_HIP(hipMemsetAsync(mh->chase_block, 0, bytes, mh->a->stream));
+    }
+    mh->chase = on;
+    return CZ_OK;
+}
+
+int cz_match_chase_history(cz_match *mh, const uint64_t **chase) {
+    CZ_REQUIRE(mh && mh->chase != 0 && mh->chase_block, "cz_match_chase_history: cz_match_set_chase first");
+    CzMatchChase c;
+    carve_chase(mh, (char *)mh->chase_block, c);
+    if (chase) *chase = c.ring;
+    return CZ_OK;
+}
+
 void cz_match_destroy(cz_match *mh) {
     if (!mh) return;
     (void)hipStreamSynchronize(mh->a->stream);
     (void)hipFree(mh->block);
     if (mh->xq_block) (void)hipFree(mh->xq_block);
     if (mh->rep_block) (void)hipFree(mh->rep_block);
+    if (mh->chase_block) (void)hipFree(mh->chase_block);
     delete mh;
 }
 
@@ -483,6 +558,14 @@ int cz_match_choose(cz_match *mh, int sample_plies, unsigned long long seed, uin
         int rc = czk_movegen_kingsafe(mh->a, x.board, x.side, mh->G, nullptr, nullptr, x.safe, r.flags, 0);
         if (rc != CZ_OK) return rc;
         if ((rc = czk_hash(mh->a, x.board, x.side, mh->G, r.root_key)) != CZ_OK) return rc;
+        if (mh->chase) {   // and their chase records, for the third ring
+            CzMatchChase c;
+            carve_chase(mh, (char *)mh->chase_block, c);
+            if ((rc = czk_threats(mh->a, x.board, x.side, mh->G, c.root)) != CZ_OK) return rc;
+            hipLaunchKernelGGL(k_match_choose_chase, dim3(mh->G), dim3(64), 0, mh->a->stream, mh->a->t, mh->b->t, device_view(mh), sample_plies, seed, played, x, r, c);
+            CZ_HIP(hipGetLastError());
+            return CZ_OK;
+        }
         hipLaunchKernelGGL(k_match_choose_rep, dim3(mh->G), dim3(64), 0, mh->a->stream, mh->a->t, mh->b->t, device_view(mh), sample_plies, seed, played, x, r);
         CZ_HIP(hipGetLastError());
         return CZ_OK;
@@ -511,7 +594,8 @@ int cz_match_adjudicate(cz_match *mh, const uint16_t *played) {
         CzMatchRep r;
         carve_xq(mh, (char *)mh->xq_block, x);
         carve_rep(mh, (char *)mh->rep_block, r);
-        hipLaunchKernelGGL(k_match_adjudicate_rep, dim3(mh->G), dim3(64), 0, mh->a->stream, mh->a->t, mh->b->t, device_view(mh), played, x.mated, r.rep);
+        if (mh->chase) hipLaunchKernelGGL(k_match_adjudicate_chase, dim3(mh->G), dim3(64), 0, mh->a->stream, mh->a->t, mh->b->t, device_view(mh), played, x.mated, r.rep);
+        else hipLaunchKernelGGL(k_match_adjudicate_rep, dim3(mh->G), dim3(64), 0, mh->a->stream, mh->a->t, mh->b->t, device_view(mh), played, x.mated, r.rep);
     } else if (mh->rules == 1) {
         CzMatchXq x;
         carve_xq(mh, (char *)mh->xq_block, x);

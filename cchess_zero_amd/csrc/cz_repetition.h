@@ -14,8 +14,12 @@
 // Lane l of a chunk looks at position n - 1 - (base + l): the lanes with the current key are the earlier occurrences, most
 // recent first, and the (fold - 1)-th of them is `first` = j; the cycle is j + 1 .. n.  Side X checked perpetually when every
 // position of the cycle with side 1 - X to move (at least one) is a check.  -> CZ_REP_*, wave-uniform; first = -1 without a verdict.
-__device__ __forceinline__ int wave_repetition(const uint64_t *__restrict__ keys, const uint8_t *__restrict__ in_check, int imask,
-                                               int n, int w, uint64_t key_n, bool chk_n, int side_n, int fold, int lane, int &first) {
+// wave_repetition_ex also says which sides checked perpetually (red / black), which CZ_REP_DRAW folds together: the chase
+// verdict below runs only when neither did.
+__device__ __forceinline__ int wave_repetition_ex(const uint64_t *__restrict__ keys, const uint8_t *__restrict__ in_check, int imask,
+                                                  int n, int w, uint64_t key_n, bool chk_n, int side_n, int fold, int lane, int &first,
+                                                  bool &red, bool &black) {
+    red = black = false;
     first = -1;
     int need = fold - 1;
     // quiet[s]: a position of the cycle with side s to move is no check; seen[s]: the cycle has a position with side s to move
@@ -45,6 +49,86 @@ __device__ __forceinline__ int wave_repetition(const uint64_t *__restrict__ keys
         need -= cnt;
     }
     if (first < 0) return CZ_REP_NONE;
-    const bool red = seen[1] && !quiet[1], black = seen[0] && !quiet[0];   // red checked with every move / black did
+    red = seen[1] && !quiet[1]; black = seen[0] && !quiet[0];   // red checked with every move / black did
     return red == black ? CZ_REP_DRAW : (red ? CZ_REP_RED_LOSES : CZ_REP_BLACK_LOSES);
+}
+__device__ __forceinline__ int wave_repetition(const uint64_t *__restrict__ keys, const uint8_t *__restrict__ in_check, int imask,
+                                               int n, int w, uint64_t key_n, bool chk_n, int side_n, int fold, int lane, int &first) {
+    bool red, black;
+    return wave_repetition_ex(keys, in_check, imask, n, w, key_n, chk_n, side_n, fold, lane, first, red, black);
+}
+
+// ---- perpetual chase (tests/chase_model.py: verdict).  A position's CHASE RECORD is four 64-bit words (cz_threats): the
+// threatened set of the side to move (squares 0 .. 63, 64 .. 89) and that side's squares in the same layout.  Position i's
+// record is at chase[(i & imask) * 4]; the current position's is passed in rec_n (the match writes it in the same kernel).
+// Side X chases perpetually when one and the same piece of 1 - X is threatened in every position of the cycle j + 1 .. n that
+// X's moves led to (1 - X to move; at least one): C = T(first such position); from one such position to the next the victim
+// side's squares differ by exactly one "from" and one "to" square (a cycle holds no capture) — a threatened piece on "from" is
+// followed to "to", any other difference empties C — and C &= T(next).  -> bit X set: X chases perpetually.
+// The walk is serial and wave-uniform: a chunk of 64 positions is loaded one per lane (ascending: lane l holds position
+// j + 1 + base + l) and read back lane by lane with __shfl; it stops when neither side has a candidate left.
+struct CzChaseSet { uint64_t lo, hi; };
+__device__ __forceinline__ int wave_chase(const uint64_t *__restrict__ chase, int imask, int n, int j, const uint64_t (&rec_n)[4],
+                                          int side_n, int lane) {
+    // state per victim side v (the side TO MOVE in the positions walked); the loop over v is unrolled: no array is indexed at run time
+    CzChaseSet C[2] = {{0ull, 0ull}, {0ull, 0ull}}, prev[2] = {{0ull, 0ull}, {0ull, 0ull}};
+    bool started[2] = {false, false}, dead[2] = {false, false};
+    const int len = n - j;   // positions j + 1 .. n
+    const int v0 = (side_n ^ (len - 1)) & 1;   // the side to move at j + 1 (and at every chunk's lane 0: 64 is even)
+    for (int base = 0; base < len; base += 64) {
+        if (dead[0] && dead[1]) break;
+        const int i = j + 1 + base + lane;
+        uint64_t r0 = 0ull, r1 = 0ull, r2 = 0ull, r3 = 0ull;
+        if (i < n) {
+            const uint64_t *p = chase + (size_t)(i & imask) * 4;
+            r0 = p[0]; r1 = p[1]; r2 = p[2]; r3 = p[3];
+        } else if (i == n) {
+            r0 = rec_n[0]; r1 = rec_n[1]; r2 = rec_n[2]; r3 = rec_n[3];
+        }
+        const int cnt = min(64, len - base);
+#pragma unroll
+        for (int v = 0; v < 2; ++v) {
+            for (int l = v == v0 ? 0 : 1; l < cnt && !dead[v]; l += 2) {
+                const CzChaseSet T = {__shfl(r0, l, 64), __shfl(r1, l, 64)}, own = {__shfl(r2, l, 64), __shfl(r3, l, 64)};
+                if (!started[v]) {
+                    C[v] = T;
+                    started[v] = true;
+                } else {
+                    const CzChaseSet from = {prev[v].lo & ~own.lo, prev[v].hi & ~own.hi}, to = {own.lo & ~prev[v].lo, own.hi & ~prev[v].hi};
+                    const bool one = __popcll(from.lo) + __popcll(from.hi) == 1 && __popcll(to.lo) + __popcll(to.hi) == 1;
+                    if (!one) {
+                        C[v] = CzChaseSet{0ull, 0ull};
+                    } else if ((C[v].lo & from.lo) | (C[v].hi & from.hi)) {
+                        C[v].lo = (C[v].lo & ~from.lo) | to.lo;
+                        C[v].hi = (C[v].hi & ~from.hi) | to.hi;
+                    }
+                    C[v].lo &= T.lo;
+                    C[v].hi &= T.hi;
+                }
+                prev[v] = own;
+                dead[v] = (C[v].lo | C[v].hi) == 0ull;
+            }
+        }
+    }
+    // the chaser of victim v is 1 - v
+    return ((started[1] && !dead[1]) ? 1 : 0) | ((started[0] && !dead[0]) ? 2 : 0);
+}
+
+// The repetition rule with the chase verdict behind it: wave_repetition's code and first; *cause = CZ_CAUSE_*.  Exactly one
+// side checked perpetually: as wave_repetition, cause check (it outranks a chase by the other side).  Both: a draw.  Neither:
+// exactly one side chases perpetually -> that side loses, cause chase; else a draw.
+__device__ __forceinline__ int wave_repetition_chase(const uint64_t *__restrict__ keys, const uint8_t *__restrict__ in_check,
+                                                     const uint64_t *__restrict__ chase, int imask, int n, int w, uint64_t key_n,
+                                                     bool chk_n, const uint64_t (&rec_n)[4], int side_n, int fold, int lane, int &first,
+                                                     int &cause) {
+    bool red, black;
+    const int v = wave_repetition_ex(keys, in_check, imask, n, w, key_n, chk_n, side_n, fold, lane, first, red, black);
+    cause = CZ_CAUSE_NONE;
+    if (v == CZ_REP_NONE) return v;
+    if (v != CZ_REP_DRAW) { cause = CZ_CAUSE_CHECK; return v; }
+    if (red) return v;   // both checked
+    const int ch = wave_chase(chase, imask, n, first, rec_n, side_n, lane);
+    if (ch == 0 || ch == 3) return CZ_REP_DRAW;
+    cause = CZ_CAUSE_CHASE;
+    return ch == 1 ? CZ_REP_RED_LOSES : CZ_REP_BLACK_LOSES;
 }

@@ -61,7 +61,9 @@ __global__ __launch_bounds__(64) void k_sp_roots_xq(CzTrees t, CzSelfplay sp, in
 // fold != 0 (XQ only): the root position goes into the slot's ring at the game's ply first, and a fold-th occurrence inside the
 // last min(restrict_round, ply, 63) positions ends the game (choose_on<XQ, REP> of cz_match.hip).  On either ending played =
 // 0xFFFF, no record is written and the ply stays; k_sp_adjudicate_xq ends the game.  A forced label is played as given.
-template <bool XQ>
+// CHASE (cz_selfplay_set_chase; XQ with a fold only): the root position's chase record goes into the slot's third ring, and the
+// verdict is wave_repetition_chase's (choose_on<XQ, REP, CHASE> of cz_match.hip).
+template <bool XQ, bool CHASE = false>
 __device__ __forceinline__ void sp_choose(const CzTrees &t, const CzSelfplay &sp, int G, const float *__restrict__ gamma,
                                           const float *__restrict__ u, const uint16_t *__restrict__ forced, double inv_temp,
                                           float eps, int min_sims, uint16_t *__restrict__ played, int fold) {
@@ -95,8 +97,18 @@ __device__ __forceinline__ void sp_choose(const CzTrees &t, const CzSelfplay &sp
             uint8_t *ring_check = sp.ring_check + (size_t)g * 64;
             if (lane == 0) { ring_key[ply & 63] = key; ring_check[ply & 63] = chk ? 1 : 0; }
             const int w = max(0, min(min(t.root_rr[g], ply), 63));   // entry ply & 63, just written, is never among the w read
-            int first;
-            const int verdict = wave_repetition(ring_key, ring_check, 63, ply, w, key, chk, sp.xq_side[g] ? 1 : 0, fold, lane, first);
+            int first, verdict;
+            if constexpr (CHASE) {
+                uint64_t *ring = sp.ring_chase + (size_t)g * 64 * 4;
+                const uint64_t *root = sp.root_chase + (size_t)g * 4;
+                const uint64_t rec[4] = {root[0], root[1], root[2], root[3]};
+                if (lane < 4) ring[(ply & 63) * 4 + lane] = root[lane];   // as the key: never among the positions read below
+                int cause;
+                verdict = wave_repetition_chase(ring_key, ring_check, ring, 63, ply, w, key, chk, rec, sp.xq_side[g] ? 1 : 0, fold, lane, first, cause);
+                if (cause == CZ_CAUSE_CHASE) verdict |= CZ_REP_BY_CHASE;
+            } else {
+                verdict = wave_repetition(ring_key, ring_check, 63, ply, w, key, chk, sp.xq_side[g] ? 1 : 0, fold, lane, first);
+            }
             if (verdict != CZ_REP_NONE) {
                 if (lane == 0) { played[g] = 0xFFFF; sp.rep[g] = (uint8_t)verdict; }
                 return;
@@ -173,19 +185,28 @@ __global__ __launch_bounds__(64) void k_sp_choose_xq(CzTrees t, CzSelfplay sp, i
                                                      double inv_temp, float eps, int min_sims, uint16_t *__restrict__ played, int fold) {
     sp_choose<true>(t, sp, G, gamma, u, forced, inv_temp, eps, min_sims, played, fold);
 }
+__global__ __launch_bounds__(64) void k_sp_choose_chase(CzTrees t, CzSelfplay sp, int G, const float *__restrict__ gamma,
+                                                        const float *__restrict__ u, const uint16_t *__restrict__ forced,
+                                                        double inv_temp, float eps, int min_sims, uint16_t *__restrict__ played, int fold) {
+    sp_choose<true, true>(t, sp, G, gamma, u, forced, inv_temp, eps, min_sims, played, fold);
+}
 
 // The game-end tests of selfplay (main.py:1532-1545) on the position after the move, z for every recorded ply, and —
 // reseed != 0 — MCTS_tree.reload / GameBoard.reload for the next game of the slot (:1549-1551, :1494).
 // fin_n[g] = number of records the finished game hands to the ring (0: not finished, or dropped).
 // XQ: before those tests, the endings the last choose found on the root it left untouched — a repetition verdict (a draw, or a
 // loss for the side that checked perpetually), then a mated mover (the side to move loses); z as for a king capture.
-template <bool XQ>
+// CHASE: the verdict may carry CZ_REP_BY_CHASE — a loss for the side that chased, z as for perpetual check, counted in
+// chase_stat and not among the perpetuals.
+template <bool XQ, bool CHASE = false>
 __device__ __forceinline__ void sp_adjudicate(const CzTrees &t, const CzSelfplay &sp, int G, int reseed, const uint16_t *__restrict__ played,
                                               int32_t *__restrict__ fin_n) {
     const int g = blockIdx.x, lane = threadIdx.x;
     if (g >= G) return;
     if (!sp.active[g]) { if (lane == 0) fin_n[g] = 0; return; }
-    const int verdict = XQ ? (int)sp.rep[g] : CZ_REP_NONE;
+    const int stored = XQ ? (int)sp.rep[g] : CZ_REP_NONE;
+    const bool by_chase = CHASE && (stored & CZ_REP_BY_CHASE) != 0;
+    const int verdict = CHASE ? (stored & ~CZ_REP_BY_CHASE) : stored;
     const bool mated = XQ && verdict == CZ_REP_NONE && sp.mated[g] != 0;
     const bool by_rules = verdict != CZ_REP_NONE || mated;
     // asynchronous plies: only the slots that just moved (or stalled, or ended by the rules) can have ended their game
@@ -213,7 +234,8 @@ __device__ __forceinline__ void sp_adjudicate(const CzTrees &t, const CzSelfplay
         else atomicAdd((unsigned long long *)&sp.stats[CZ_SP_DRAWS], 1ull);
         atomicAdd((unsigned long long *)&sp.stats[CZ_SP_PLIES], (unsigned long long)n);
         if constexpr (XQ) {
-            if (by_rules) atomicAdd((unsigned long long *)&sp.xq_stats[mated ? 0 : (verdict == CZ_REP_DRAW ? 1 : 2)], 1ull);
+            if (by_chase) atomicAdd((unsigned long long *)sp.chase_stat, 1ull);
+            else if (by_rules) atomicAdd((unsigned long long *)&sp.xq_stats[mated ? 0 : (verdict == CZ_REP_DRAW ? 1 : 2)], 1ull);
             sp.mated[g] = 0; sp.rep[g] = CZ_REP_NONE;
         }
     }
@@ -229,6 +251,10 @@ __global__ __launch_bounds__(64) void k_sp_adjudicate(CzTrees t, CzSelfplay sp, 
 __global__ __launch_bounds__(64) void k_sp_adjudicate_xq(CzTrees t, CzSelfplay sp, int G, int reseed, const uint16_t *__restrict__ played,
                                                          int32_t *__restrict__ fin_n) {
     sp_adjudicate<true>(t, sp, G, reseed, played, fin_n);
+}
+__global__ __launch_bounds__(64) void k_sp_adjudicate_chase(CzTrees t, CzSelfplay sp, int G, int reseed, const uint16_t *__restrict__ played,
+                                                            int32_t *__restrict__ fin_n) {
+    sp_adjudicate<true, true>(t, sp, G, reseed, played, fin_n);
 }
 
 // Copies the records of the games k_sp_adjudicate finished to ring[(offset[g] + j) % ring_records].  The offsets are an
@@ -269,6 +295,13 @@ int czk_selfplay_choose(cz_ctx *c, const float *gamma, const float *u, const uin
         int rc = czk_movegen_kingsafe(c, sp.xq_board, sp.xq_side, c->G, nullptr, nullptr, sp.safe, c->sp_fold ? sp.flags : nullptr, 0);
         if (rc != CZ_OK) return rc;
         if (c->sp_fold && (rc = czk_hash(c, sp.xq_board, sp.xq_side, c->G, sp.root_key)) != CZ_OK) return rc;
+        if (c->sp_fold && c->sp_chase) {   // and its chase record, for the third ring
+            if ((rc = czk_threats(c, sp.xq_board, sp.xq_side, c->G, sp.root_chase)) != CZ_OK) return rc;
+            hipLaunchKernelGGL(k_sp_choose_chase, dim3(c->G), dim3(64), 0, c->stream, c->t, sp, c->G, gamma, u, forced, 1.0 / temperature, eps, min_sims,
+                               played, c->sp_fold);
+            CZ_HIP(hipGetLastError());
+            return CZ_OK;
+        }
         hipLaunchKernelGGL(k_sp_choose_xq, dim3(c->G), dim3(64), 0, c->stream, c->t, sp, c->G, gamma, u, forced, 1.0 / temperature, eps, min_sims, played,
                            c->sp_fold);
         CZ_HIP(hipGetLastError());
@@ -280,7 +313,8 @@ int czk_selfplay_choose(cz_ctx *c, const float *gamma, const float *u, const uin
 }
 
 int czk_selfplay_adjudicate(cz_ctx *c, int reseed, const uint16_t *played, int32_t *fin_n) {
-    if (c->sp_rules == 1) hipLaunchKernelGGL(k_sp_adjudicate_xq, dim3(c->G), dim3(64), 0, c->stream, c->t, c->sp, c->G, reseed, played, fin_n);
+    if (c->sp_rules == 1 && c->sp_fold && c->sp_chase) hipLaunchKernelGGL(k_sp_adjudicate_chase, dim3(c->G), dim3(64), 0, c->stream, c->t, c->sp, c->G, reseed, played, fin_n);
+    else if (c->sp_rules == 1) hipLaunchKernelGGL(k_sp_adjudicate_xq, dim3(c->G), dim3(64), 0, c->stream, c->t, c->sp, c->G, reseed, played, fin_n);
     else hipLaunchKernelGGL(k_sp_adjudicate, dim3(c->G), dim3(64), 0, c->stream, c->t, c->sp, c->G, reseed, played, fin_n);
     CZ_HIP(hipGetLastError());
     return CZ_OK;

@@ -119,6 +119,39 @@ class Rules:
                                   _ptr(verdict), _ptr(first)), "cz_repetition")
         return verdict, first
 
+    def threats(self, boards, side):
+        """The chase record of G positions (cz_threats) -> [G, 4] i64 (u64 bits): words 0, 1 the pieces of the side to move that
+        the other side threatens (squares 0 .. 63, 64 .. 89: an unprotected or more valuable piece under a king-safe attack by
+        a rook, cannon, knight, advisor or bishop that is no exchange offer), words 2, 3 the squares of the side to move.  A
+        board movegen refuses answers four zero words."""
+        self.ctx.bind_stream()   # torch's current stream
+        boards = self._dev(boards, torch.uint8).reshape(-1, NSQ)
+        side = self._dev(side, torch.uint8)
+        chase = torch.empty((boards.shape[0], 4), dtype=torch.int64, device=self.dev)
+        check(lib().cz_threats(self.ctx.h, _ptr(boards), _ptr(side), boards.shape[0], _ptr(chase)), "cz_threats")
+        return chase
+
+    def repetition_chase(self, keys, in_check, chase, side, length=None, window=None, fold=3):
+        """repetition() with the perpetual-chase verdict behind it (cz_repetition_chase): chase [G, stride, 4] i64 is
+        threats() of every position -> (verdict [G] u8, first [G] i32, cause [G] u8: CAUSE_NONE / CAUSE_CHECK / CAUSE_CHASE).
+        Perpetual check by one side outranks a chase by the other; a side that alone chases one piece with every move of the
+        cycle loses."""
+        self.ctx.bind_stream()   # torch's current stream
+        keys = self._dev(keys, torch.int64)
+        keys = keys.reshape(-1, keys.shape[-1])
+        G, stride = keys.shape
+        in_check = self._dev(in_check, torch.uint8).reshape(G, stride)
+        chase = self._dev(chase, torch.int64).reshape(G, stride, 4)
+        side = self._dev(side, torch.uint8).reshape(G)
+        length = torch.full((G,), stride, dtype=torch.int32, device=self.dev) if length is None else self._dev(length, torch.int32).reshape(G)
+        window = None if window is None else self._dev(window, torch.int32).reshape(G)
+        verdict = torch.empty(G, dtype=torch.uint8, device=self.dev)
+        first = torch.empty(G, dtype=torch.int32, device=self.dev)
+        cause = torch.empty(G, dtype=torch.uint8, device=self.dev)
+        check(lib().cz_repetition_chase(self.ctx.h, _ptr(keys), _ptr(in_check), _ptr(chase), stride, _ptr(length), _ptr(window), _ptr(side), G,
+                                        int(fold), _ptr(verdict), _ptr(first), _ptr(cause)), "cz_repetition_chase")
+        return verdict, first, cause
+
     @staticmethod
     def check_counts(count):
         """Raises if any position answered count 0xFFFF (k_movegen_list / k_movegen_mask refuse boards that are not a Xiangqi

@@ -27,7 +27,7 @@ import numpy as np
 import torch
 
 from ._lib import (MAXMOVES, NLABELS, NSQ, REC_BYTES, REC_COUNT, REC_FLAGS, REC_LABELS, REC_PLY, REC_SIDE, REC_VISITS, REC_Z,
-                   SP_RULES_STATS, SP_STATS, check, lib, tables)
+                   SP_CHASE_STATS, SP_RULES_STATS, SP_STATS, check, lib, tables)
 
 REC_MAXMOVES = MAXMOVES
 RULES = {"capture": 0, "xiangqi": 1}   # cz_selfplay_set_rules (arena.RULES)
@@ -140,18 +140,24 @@ class SelfPlay:
     chosen and recorded among the king-safe root children, and a mover without one loses (checkmate or stalemate).
     repetition (rules="xiangqi" only): 0 — no repetition rule; 2..8 — a game ends when its position occurs for that many times
     since the last capture: a draw, or a loss for the side that alone checked with every move of the cycle.
+    chase (with a repetition fold only): True — when neither side checked so, a side that alone chased one and the same
+    unprotected piece with every move of the cycle has lost (cz_selfplay_set_chase, as arena.Match(chase=True)); z as for
+    perpetual check.
     """
 
     def __init__(self, engine, net, playouts, exploration=True, temperature=1.0, seed=0, max_plies=512, ring_records=None,
-                 continuous=True, eval_cache=False, xcache_log2=0, rules="capture", repetition=0):
+                 continuous=True, eval_cache=False, xcache_log2=0, rules="capture", repetition=0, chase=False):
         if rules not in RULES:
             raise ValueError("SelfPlay: rules is 'capture' or 'xiangqi', not %r" % (rules,))
         if isinstance(repetition, bool) or not isinstance(repetition, (int, np.integer)) or not (repetition == 0 or 2 <= repetition <= 8):
             raise ValueError("SelfPlay: repetition is 0 (off) or 2..8, not %r" % (repetition,))
         if repetition and rules != "xiangqi":
             raise ValueError("SelfPlay: repetition needs rules='xiangqi' (the check flags come from the king-safe moves)")
+        if chase and not repetition:
+            raise ValueError("SelfPlay: chase needs a repetition fold (a chase is judged on a repeated position)")
         self.rules = rules
         self.repetition = int(repetition)
+        self.chase = bool(chase)
         self.eng, self.net = engine, net
         self.playouts = int(playouts)
         self.exploration = bool(exploration)
@@ -186,6 +192,8 @@ class SelfPlay:
             check(lib().cz_selfplay_set_rules(eng.ctx.h, RULES[self.rules]), "cz_selfplay_set_rules")
         if self.repetition:
             check(lib().cz_selfplay_set_repetition(eng.ctx.h, self.repetition), "cz_selfplay_set_repetition")
+        if self.chase:
+            check(lib().cz_selfplay_set_chase(eng.ctx.h, 1), "cz_selfplay_set_chase")
         p = C.c_void_p()
         check(lib().cz_selfplay_active(eng.ctx.h, C.byref(p)), "cz_selfplay_active")
         self._active_ptr = p
@@ -199,6 +207,7 @@ class SelfPlay:
         self._alpha = torch.full((G, MAXMOVES), 0.3, dtype=torch.float32, device=self.dev)
         self._stats = torch.zeros(len(SP_STATS), dtype=torch.int64, device=self.dev)
         self._rules_stats = torch.zeros(len(SP_RULES_STATS), dtype=torch.int64, device=self.dev)
+        self._chase_stats = torch.zeros(len(SP_CHASE_STATS), dtype=torch.int64, device=self.dev)
         self.plies = 0
         self.lock_steps = 0
         self._dropped_seen = 0
@@ -315,6 +324,16 @@ class SelfPlay:
             check(L.cz_download(h, o.ctypes.data_as(C.c_void_p), p, o.nbytes), "cz_download")
         return keys, checks
 
+    def chase_history(self):
+        """chase u64 [G, 64, 4] on the host: the slots' rings of chase records (cz_selfplay_chase_history; chase=True)."""
+        G, L, h = self.eng.G, lib(), self.eng.ctx.h
+        self.eng.ctx.bind_stream()
+        p = C.c_void_p()
+        check(L.cz_selfplay_chase_history(h, C.byref(p)), "cz_selfplay_chase_history")
+        out = np.zeros((G, 64, 4), np.uint64)
+        check(L.cz_download(h, out.ctypes.data_as(C.c_void_p), p, out.nbytes), "cz_download")
+        return out
+
     def drain_device(self, on_overflow="raise"):
         """-> uint8 [n, REC_BYTES] DEVICE tensor with the records finished since the last drain (synchronises on the
         cursor and the drop counter).  The returned rows stay valid until the ring wraps over them.
@@ -358,7 +377,8 @@ class SelfPlay:
     def stats(self):
         """Running totals since start(): games, red_wins, black_wins, draws, plies (records), stalled, dropped, sims; with
         rules="xiangqi" also mates, repetitions, perpetuals — the games among them that ended by mate (a win), by a repetition
-        draw, by perpetual check (a win)."""
+        draw, by perpetual check (a win); with chase=True also chases — the games that ended by perpetual chase (a win; not
+        among the perpetuals)."""
         self.eng.ctx.bind_stream()
         check(lib().cz_selfplay_stats(self.eng.ctx.h, C.c_void_p(self._stats.data_ptr())), "cz_selfplay_stats")
         s = self._stats.cpu().numpy()
@@ -366,6 +386,9 @@ class SelfPlay:
         if RULES[self.rules]:
             check(lib().cz_selfplay_rules_stats(self.eng.ctx.h, C.c_void_p(self._rules_stats.data_ptr())), "cz_selfplay_rules_stats")
             d.update((k, int(v)) for k, v in zip(SP_RULES_STATS, self._rules_stats.cpu().numpy()))
+        if self.chase:
+            check(lib().cz_selfplay_chase_stats(self.eng.ctx.h, C.c_void_p(self._chase_stats.data_ptr())), "cz_selfplay_chase_stats")
+            d.update((k, int(v)) for k, v in zip(SP_CHASE_STATS, self._chase_stats.cpu().numpy()))
         d["sims"] += int(self.eng.status()[2].sum().item())   # + the simulations of the searches in progress
         d["plies_played"] = self.plies          # lock-step plies (step_ply)
         d["lock_steps"] = self.lock_steps       # select / net / expand steps of the asynchronous loop (run_async)

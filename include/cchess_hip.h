@@ -142,7 +142,7 @@ int cz_movegen_ex(cz_ctx *, const uint8_t *boards, const uint8_t *side, int G, u
  *     pos_flags (and / or count) this is the "in check?" query and neither list nor set rows are built.
  *     Alignment as for cz_movegen: `moves` 16-byte aligned, everything else at any address.  A board cz_movegen answers with
  *     count 0xFFFF answers count 0xFFFF here too (its rows are undefined, its flags 0).  Repetition and perpetual check
- *     are judged by cz_repetition below, on a game's history; perpetual chase is not a rule of this library. */
+ *     are judged by cz_repetition below, on a game's history; perpetual chase by cz_threats and cz_repetition_chase. */
 #define CZ_POS_IN_CHECK 1        /* the side to move is attacked */
 #define CZ_POS_CAN_TAKE_KING 2   /* the other side is attacked: the side to move can take its king */
 #define CZ_POS_NO_SAFE_MOVE 4    /* no king-safe move: checkmate or stalemate, both lost in Xiangqi */
@@ -159,7 +159,7 @@ int cz_movegen_kingsafe(cz_ctx *, const uint8_t *boards, const uint8_t *side, in
  *       4. side X checked perpetually when every position of the cycle with side 1 - X to move — the positions X's moves
  *          led to — has in_check set, and there is at least one such position;
  *       5. exactly one side checked perpetually: that side loses; neither or both: a draw.
- *     Perpetual CHASE is not judged (it needs an attack-and-protection analysis of its own): a chase that repeats is a draw here.
+ *     Perpetual CHASE is not judged by this call: a chase that repeats is a draw here (cz_repetition_chase below judges it).
  *     keys uint64 [G][stride], in_check uint8 [G][stride]: position i of game g at g * stride + i; len int32 [G]: 1 <= len[g] <=
  *     stride, the current position is len[g] - 1 (a length outside that range answers CZ_REP_NONE / -1: nothing is read);
  *     window int32 [G]: w, clamped to 0 .. len[g] - 1, or NULL = every earlier position; side uint8 [G]: the side to move in the
@@ -172,6 +172,40 @@ int cz_movegen_kingsafe(cz_ctx *, const uint8_t *boards, const uint8_t *side, in
 #define CZ_REP_BLACK_LOSES 3   /* black checked with every move of the cycle, red did not */
 int cz_repetition(cz_ctx *, const uint64_t *keys, const uint8_t *in_check, int stride, const int32_t *len, const int32_t *window,
                   const uint8_t *side, int G, int fold, uint8_t *verdict, int32_t *first);
+/* K1t THREATS: the attack-and-protection analysis of the perpetual-chase rule.  No reference function.  s is the side to
+ *     move (the possible victim), X = 1 - s the side that just moved.  Square t is THREATENED when it holds a piece of s and
+ *     some pseudo-legal move a -> t of X on this board (cz_movegen's list for X) passes all of:
+ *       1. the attacker on a is a rook, cannon, knight, advisor or bishop (kings and pawns may chase freely);
+ *       2. the victim on t is not the king and not a pawn on its own side of the river (a crossed pawn counts);
+ *       3. the capture is king-safe for X (cz_movegen_kingsafe's rule: a pinned piece threatens nothing);
+ *       4. it is no exchange offer: attacker and victim are of one kind and s has the pseudo-legal move t -> a;
+ *       5. the victim is not protected, unless it is worth more than the attacker (R 3, N = C 2, A = B = P 1).  PROTECTED:
+ *          after a x t, s has a pseudo-legal move onto t — pseudo-legal on purpose (a pinned protector protects): this is
+ *          the library's definition.
+ *     chase uint64 [G][4] out, 8-byte aligned: words 0, 1 the threatened set (bit q of word 0 = square q < 64, bit q - 64 of
+ *     word 1 = square 64 .. 89), words 2, 3 the squares of the side to move in the same layout: a position's CHASE RECORD.  A
+ *     board cz_movegen refuses for either side (not a Xiangqi set, an advisor / bishop step without a label) answers four
+ *     zero words.  boards and side at any address.  One lane per position. */
+int cz_threats(cz_ctx *, const uint8_t *boards, const uint8_t *side, int G, uint64_t *chase);
+/* K1c REPETITION, PERPETUAL CHECK AND PERPETUAL CHASE: cz_repetition (same records, lengths, windows, fold and refusals; its
+ *     steps 1 - 5) with the chase record of every position beside its key, chase uint64 [G][stride][4] (cz_threats):
+ *       6. exactly one side checked perpetually: cz_repetition's verdict, cause CZ_CAUSE_CHECK — perpetual check outranks a
+ *          chase by the other side; both sides checked perpetually: a draw;
+ *       7. otherwise side X CHASES perpetually when one and the same piece of 1 - X is threatened in every position of the cycle
+ *          that X's moves led to (at least one).  The piece is followed from such a position to the next by the one "from" and
+ *          one "to" square in which the squares of 1 - X differ (a cycle holds no capture; records that differ in another way
+ *          follow nothing).  A threat that merely stands while X moves something else counts: the rule looks at the position
+ *          after each of X's moves;
+ *       8. exactly one side chases perpetually: that side loses, cause CZ_CAUSE_CHASE; neither or both: a draw.
+ *     NOT judged: a cycle that mixes checks and chases move by move is a draw, and two pieces of one kind that swap places over
+ *     a cycle are not told apart.
+ *     verdict uint8 [G] out: CZ_REP_*; first int32 [G] out (may be NULL) as in cz_repetition; cause uint8 [G] out (may be NULL):
+ *     CZ_CAUSE_* (NONE without a verdict and for a draw). */
+#define CZ_CAUSE_NONE 0
+#define CZ_CAUSE_CHECK 1
+#define CZ_CAUSE_CHASE 2
+int cz_repetition_chase(cz_ctx *, const uint64_t *keys, const uint8_t *in_check, const uint64_t *chase, int stride, const int32_t *len,
+                        const int32_t *window, const uint8_t *side, int G, int fold, uint8_t *verdict, int32_t *first, uint8_t *cause);
 /* K2  replaces GameBoard.sim_do_action (main.py:647-702), is_kill_move (:226) and the king test
  *     (:409-413).  Updates boards/side in place.  hash: in/out incremental Zobrist (may be NULL);
  *     captured [G] = captured piece code or 0; terminal [G]: bit0 'K' missing, bit1 'k' missing.
@@ -394,11 +428,25 @@ int cz_selfplay_stats(cz_ctx *, long long *stats_dev);
  * cz_selfplay_history: the device pointers of the two rings, owned by the context — keys uint64 [G][64], checks uint8 [G][64]:
  *   position i of the game in slot g at [g][i & 63]; either may be NULL.  CZ_EINVAL while the repetition rule is off.
  * cz_selfplay_rules_stats: device int64 [3] <- games ended by mate, by a repetition draw, by perpetual check since
- *   cz_selfplay_begin.  They are counted in the cz_selfplay_stats slots too (wins / draws, games, plies). */
+ *   cz_selfplay_begin.  They are counted in the cz_selfplay_stats slots too (wins / draws, games, plies).
+ * cz_selfplay_set_chase: 0 = perpetual chase is not judged (the default: everything above, launch for launch and byte for
+ *   byte), 1 = it is, as cz_match_set_chase.  Needs a non-zero fold (CZ_EINVAL otherwise; cz_selfplay_set_repetition(ctx, 0) is
+ *   refused while it is on) and is set like the other two, between cz_selfplay_begin — which switches it off — and the first
+ *   cz_selfplay_choose.  With it, cz_selfplay_choose also takes every root position's chase record (one cz_threats launch on
+ *   the boards it already copies out), writes it into a third ring, chase uint64 [G][64][4], at entry ply & 63, and evaluates
+ *   cz_repetition_chase's rule instead of cz_repetition's: a repetition that cz_repetition calls a draw is a loss for the
+ *   side that alone chased one piece with every move of the cycle — z as for perpetual check.  Such a game counts in
+ *   cz_selfplay_chase_stats and NOT among cz_selfplay_rules_stats' perpetuals (whose signature and meaning stay).
+ * cz_selfplay_chase_history: the device pointer of the third ring; CZ_EINVAL while the rule is off.
+ * cz_selfplay_chase_stats: device int64 [1] <- games ended by perpetual chase since cz_selfplay_set_chase(ctx, 1) (0 while
+ *   the rule is off). */
 int cz_selfplay_set_rules(cz_ctx *, int rules);
 int cz_selfplay_set_repetition(cz_ctx *, int fold);
 int cz_selfplay_history(cz_ctx *, const uint64_t **keys, const uint8_t **checks);
 int cz_selfplay_rules_stats(cz_ctx *, long long *stats_dev /* [3]: mates, repetitions, perpetuals */);
+int cz_selfplay_set_chase(cz_ctx *, int on);
+int cz_selfplay_chase_history(cz_ctx *, const uint64_t **chase);
+int cz_selfplay_chase_stats(cz_ctx *, long long *stats_dev /* [1]: chases */);
 
 /* ---- device-resident evaluation matches between two players (one wave per game slot; no host round trip per ply) -------
  * replaces: cchess_main.policy_evaluate (main.py:1207-1222, commented out in the reference) — many games of player A
@@ -437,6 +485,8 @@ int cz_selfplay_rules_stats(cz_ctx *, long long *stats_dev /* [3]: mates, repeti
 #define CZ_MATCH_MATE 5      /* rules = 1: the mover had no king-safe move (checkmate or stalemate): it loses */
 #define CZ_MATCH_REPETITION 6   /* cz_match_set_repetition: the position occurred for the fold-th time: a draw */
 #define CZ_MATCH_PERPETUAL 7    /* ... and one side alone checked with every move of the cycle: that side loses */
+#define CZ_MATCH_CHASE 9        /* cz_match_set_chase: ... neither side checked so, and one side alone chased one piece with every
+                                   move of the cycle: that side loses (8 is not assigned) */
 typedef struct cz_match cz_match;
 int cz_match_create(cz_ctx *a, cz_ctx *b, const uint8_t *open_boards, const uint8_t *open_side, const int32_t *open_rr,
                     int n_openings, long long pair_base, long long pair_stride, int max_plies, cz_match **out);
@@ -462,9 +512,19 @@ int cz_match_set_rules(cz_match *, int rules);
  *   CZ_MATCH_REPETITION (result 0) or CZ_MATCH_PERPETUAL (result -1 when the losing side is A's colour in that game, else +1),
  *   plies = the plies actually played.
  * cz_match_history: the device pointers of the two rings, owned by the match — keys uint64 [G][64], checks uint8 [G][64]:
- *   position i of the game in slot g at [g][i & 63]; either may be NULL.  CZ_EINVAL while the repetition rule is off. */
+ *   position i of the game in slot g at [g][i & 63]; either may be NULL.  CZ_EINVAL while the repetition rule is off.
+ * cz_match_set_chase: 0 = perpetual chase is not judged (the default: everything above, launch for launch), 1 = it is.  Needs
+ *   a non-zero fold (CZ_EINVAL otherwise), is set before the first cz_match_choose, and cz_match_set_repetition(match, 0) is
+ *   refused while it is on.  With it, cz_match_choose adds one cz_threats launch on the root boards it already copies out,
+ *   writes every root position's chase record into a third ring, chase uint64 [G][64][4], at entry ply & 63, and evaluates
+ *   cz_repetition_chase's rule with the same window: a verdict whose cause is CZ_CAUSE_CHASE ends the game as CZ_MATCH_CHASE, a
+ *   scored game like CZ_MATCH_PERPETUAL (result -1 when the chaser is A's colour in that game, else +1); every other verdict
+ *   ends it as before.
+ * cz_match_chase_history: the device pointer of the third ring, owned by the match; CZ_EINVAL while the rule is off. */
 int cz_match_set_repetition(cz_match *, int fold);
 int cz_match_history(cz_match *, const uint64_t **keys, const uint8_t **checks);
+int cz_match_set_chase(cz_match *, int on);
+int cz_match_chase_history(cz_match *, const uint64_t **chase);
 int cz_match_active(cz_match *, int player, const uint8_t **mask_dev);
 int cz_match_choose(cz_match *, int sample_plies, unsigned long long seed, uint16_t *played);
 int cz_match_adjudicate(cz_match *, const uint16_t *played);

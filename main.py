@@ -340,6 +340,7 @@ class cchess_main(object):
         self.eval_games = 256
         self.last_evaluation = None
         self.rules, self.repetition = "capture", 0   # the batched self-play games and the evaluation matches (--rules, --repetition)
+        self.chase = False                            # ... and whether they judge perpetual chase (--chase)
 
     @staticmethod
     def flip_policy(prob):
@@ -506,7 +507,7 @@ class cchess_main(object):
         net = self.policy_value_netowrk.net
         sp = getattr(self, "_sp", None)
         if (sp is None or sp.eng.G != G or sp.eng.ctx.cap < cap or sp.playouts != self.playout_counts or sp.net is not net
-                or sp.rules != self.rules or sp.repetition != self.repetition):
+                or sp.rules != self.rules or sp.repetition != self.repetition or sp.chase != self.chase):
             # planes are written by the select kernel straight in the fused net's input format (16 channels of its 16-bit type)
             plane_dtype, channels = plane_format(net)
             eng = SearchEngine(G, cap, torch.cuda.current_device(), plane_dtype=plane_dtype, channels=channels)
@@ -525,7 +526,7 @@ class cchess_main(object):
                           # 4.16 M, 2**24 entries 4.38 M (+21.6 %); the write-once table is full either way
                           xcache_log2=min(24, max(18, (G * 2048 - 1).bit_length())) if self.playout_counts >= 400 else 0,
                           # a drain interval can end every game of every slot in the worst case: room for ~160 plies per slot
-                          ring_records=max(65536, 160 * G), rules=self.rules, repetition=self.repetition)
+                          ring_records=max(65536, 160 * G), rules=self.rules, repetition=self.repetition, chase=self.chase)
             b0 = np.tile(state_to_board(START_STATE), (G, 1))
             sp.start(b0, np.zeros(G, np.uint8), np.zeros(G, np.int32))
             self._sp, self._batch_eng = sp, eng
@@ -548,7 +549,7 @@ class cchess_main(object):
             st = sp.stats()
             if st["games"] - before["games"] >= target or (max_plies is not None and plies >= max_plies):
                 break
-        self.last_selfplay_stats = {k: (st[k] - before[k] if k in ("games", "red_wins", "black_wins", "draws", "plies", "sims", "lock_steps", "mates", "repetitions", "perpetuals") else st[k])
+        self.last_selfplay_stats = {k: (st[k] - before[k] if k in ("games", "red_wins", "black_wins", "draws", "plies", "sims", "lock_steps", "mates", "repetitions", "perpetuals", "chases") else st[k])
                                     for k in st}
         self.last_selfplay_sims = self.last_selfplay_stats["sims"]
         rec = torch.cat(chunks, 0) if chunks else sp.ring[:0]
@@ -576,7 +577,7 @@ class cchess_main(object):
         self._eval_round = getattr(self, "_eval_round", 0) + 1
         openings = random_openings(pairs, 4, seed=self.update_seed + self._eval_round)
         res = Match((live, self.playout_counts), (opp, self.playout_counts), openings, slots=max(2, min(2 * pairs, self.games)),
-                    seed=self.update_seed + self._eval_round, rules=self.rules, repetition=self.repetition).play()
+                    seed=self.update_seed + self._eval_round, rules=self.rules, repetition=self.repetition, chase=self.chase).play()
         self.last_evaluation = res
         if opponent is None and res.score is not None and res.score >= 0.55:
             self._eval_snapshot = self._snapshot_net()
@@ -620,6 +621,8 @@ class cchess_main(object):
                 st = self.last_selfplay_stats
                 n = len(rec)
                 by_rules = ", mates:{mates}, repetitions:{repetitions}, perpetuals:{perpetuals}".format(**st) if "mates" in st else ""
+                if "chases" in st:
+                    by_rules += ", chases:{chases}".format(**st)
                 print("batch i:{}, game slots:{}, games finished:{}, samples:{}, sims/s:{:.0f}{}".format(
                     batch_iter, self.games, st["games"], n, self.last_selfplay_sims / max(dt, 1e-9), by_rules))
                 if self.data_buffer.maxlen < 2 * n:
@@ -642,6 +645,8 @@ class cchess_main(object):
                           "policy_updates": updates, "policy_update_seconds": round(time.time() - t1, 3),
                           "net_engine": getattr(self.policy_value_netowrk.net, "engine_name", None), "strict_check": rep,
                           "eval_cache": bool(getattr(self._sp, "eval_cache", False)), "xcache_log2": int(getattr(self._sp, "xcache_log2", 0))}
+                if "chases" in st:
+                    timing["chases"] = int(st["chases"])
                 msg = "batch_timing: " + json.dumps(timing)
                 print(msg, flush=True)
                 self.log_file.write(msg + '\n')
@@ -714,6 +719,8 @@ if __name__ == '__main__':
     parser.add_argument('--repetition', default=0, type=int,
                         help='with --rules xiangqi: a game ends when its position occurs for the N-th time (3 is the usual value): a draw, '
                              'or a loss for the side that checked perpetually; 0 = no repetition rule')
+    parser.add_argument('--chase', action='store_true',
+                        help='with --repetition: a side that alone chased one unprotected piece with every move of the cycle loses')
     parser.add_argument('--net_precision', default=None, choices=['strict', 'mx6', 'fp16x2', 'fp16', 'bf16', 'bf16x2', 'fp32'], type=str,
                         help='net engine (policy_value_network.PRECISIONS): strict (default) = measured within 5e-4 absolute of the '
                              'fp32 graph on 64 positions with the LIVE weights after every weight change, falling over mx6 -> fp16x2 -> '
@@ -721,6 +728,8 @@ if __name__ == '__main__':
     args = parser.parse_args()
     if not (args.repetition == 0 or 2 <= args.repetition <= 8) or (args.repetition and args.rules != 'xiangqi'):
         parser.error("--repetition is 0 or 2..8 and needs --rules xiangqi")
+    if args.chase and not args.repetition:
+        parser.error("--chase needs --repetition")
 
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:   # launched by torch.distributed.run: one rank per GPU
         import torch
@@ -745,7 +754,7 @@ if __name__ == '__main__':
         train_main = cchess_main(args.train_playout, args.batch_size, True, args.search_threads, args.processor, args.num_gpus,
                                  args.res_block_nums, args.human_color, games=args.games)
         train_main.eval_every, train_main.eval_games = args.eval_every, args.eval_games
-        train_main.rules, train_main.repetition = args.rules, args.repetition
+        train_main.rules, train_main.repetition, train_main.chase = args.rules, args.repetition, args.chase
         train_main.run(args.max_batches)
         if os.environ.get("CCHESS_WEIGHT_DIGEST_DIR"):   # tests: every rank leaves a digest of its replica (they must be equal)
             import hashlib

@@ -5,7 +5,9 @@ a nibble board + mask; this ABI moves 90 B board + 1 B side in, 256 B ordered li
 usage: python tools/rules_bench.py [N positions, default 1048576]
        python tools/rules_bench.py --kingsafe [N]     the king-safe generator (cz_movegen_kingsafe) on N positions of
            rules.random_positions against (a) the pseudo-legal kernels on the same positions and (b) the same answer composed from
-           cz_movegen + cz_apply_move + cz_movegen + torch; one JSON line at the end"""
+           cz_movegen + cz_apply_move + cz_movegen + torch; one JSON line at the end
+       python tools/rules_bench.py --threats [N]      the threat kernel of the chase rule (cz_threats) beside the king-safe
+           generator's flags-only and list forms on the same N positions, in the same run; one JSON line at the end"""
 import os
 import sys
 import time
@@ -19,7 +21,8 @@ from cchess_zero_amd.engine import Context  # noqa: E402
 from cchess_zero_amd.rules import Rules  # noqa: E402
 
 KINGSAFE = "--kingsafe" in sys.argv
-_args = [a for a in sys.argv[1:] if a != "--kingsafe"]
+THREATS = "--threats" in sys.argv
+_args = [a for a in sys.argv[1:] if a not in ("--kingsafe", "--threats")]
 N = int(_args[0]) if _args else 1 << 20
 ctx = Context(1, 2, 0)
 rules = Rules(ctx)
@@ -106,8 +109,43 @@ def kingsafe_leg():
     print(json.dumps(out), flush=True)
 
 
+def threats_leg():
+    """Median of 25 launches (device events, 3 warm-up launches) per kernel, all on the same positions of random_positions."""
+    import json
+    from cchess_zero_amd.rules import random_positions
+    boards, side, _ = random_positions(rules, N, seed=17)
+    forms = {
+        "kingsafe_flags_only": lambda: rules.in_check(boards, side),
+        "threats": lambda: rules.threats(boards, side),
+        "kingsafe_list": lambda: rules.movegen_kingsafe(boards, side, want_mask=False, pad=False),
+        "kingsafe_list_and_set": lambda: rules.movegen_kingsafe(boards, side, pad=False),
+    }
+    out = {"positions": N}
+    for name, fn in forms.items():
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize()
+        ts = []
+        for _ in range(25):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            ts.append(e0.elapsed_time(e1))
+        ts.sort()
+        out[name] = dict(ms=round(ts[12], 4), min_ms=round(ts[0], 4), max_ms=round(ts[-1], 4), positions_per_s=round(N / ts[12] * 1e3))
+        print("%-24s: median %.3f ms (min %.3f, max %.3f) = %.3f G positions/s" % (name, ts[12], ts[0], ts[-1], N / ts[12] / 1e6))
+    rec = rules.threats(boards, side)
+    out["positions_with_a_threat"] = int(((rec[:, 0] | rec[:, 1]) != 0).sum().item())
+    print(json.dumps(out), flush=True)
+
+
 if KINGSAFE:
     kingsafe_leg()
+    sys.exit(0)
+if THREATS:
+    threats_leg()
     sys.exit(0)
 b0, s0, _ = bench.synth_positions(rules, 8192, seed=5)
 rep = (N + 8191) // 8192
