@@ -31,10 +31,10 @@ from ._lib import (MATCH_ABORTED, MATCH_CHASE, MATCH_KING, MATCH_MATE, MATCH_PER
                    lib, tables)
 from .engine import SearchEngine, _ptr, plane_format, pool_nodes
 from .notation import player_to_side, state_to_board
+from .rules import RULES, check_rule_options, set_rule_options   # noqa: F401 (RULES: re-exported)
 
 REASONS = {0: "unfinished", MATCH_KING: "king", MATCH_RR60: "rr60", MATCH_PLY_CAP: "ply_cap", MATCH_ABORTED: "aborted", MATCH_MATE: "mate",
            MATCH_REPETITION: "repetition", MATCH_PERPETUAL: "perpetual", MATCH_CHASE: "chase"}
-RULES = {"capture": 0, "xiangqi": 1}   # cz_match_set_rules
 
 
 def is_scored(reason):
@@ -296,14 +296,7 @@ class Match:
 
     def __init__(self, player_a, player_b, openings, slots, max_plies=512, sample_plies=0, seed=0, check_every=8,
                  nodes_per_tree=None, rules="capture", repetition=0, chase=False):
-        if rules not in RULES:
-            raise ValueError("Match: rules is 'capture' or 'xiangqi', not %r" % (rules,))
-        if isinstance(repetition, bool) or not isinstance(repetition, (int, np.integer)) or not (repetition == 0 or 2 <= repetition <= 8):
-            raise ValueError("Match: repetition is 0 (off) or 2..8, not %r" % (repetition,))
-        if repetition and rules != "xiangqi":
-            raise ValueError("Match: repetition needs rules='xiangqi' (the check flags come from the king-safe moves)")
-        if chase and not repetition:
-            raise ValueError("Match: chase needs a repetition fold (a chase is judged on a repeated position)")
+        check_rule_options("Match", rules, repetition, chase)
         self.rules = rules
         self.repetition = int(repetition)
         self.chase = bool(chase)
@@ -383,12 +376,7 @@ class Match:
         self._h = C.c_void_p()
         check(L.cz_match_create(ea.ctx.h, eb.ctx.h, *[_ptr(x) for x in self._op_dev], len(op), int(pair_base), int(pair_stride),
                                 self.max_plies, C.byref(self._h)), "cz_match_create")
-        if RULES[self.rules]:
-            check(L.cz_match_set_rules(self._h, RULES[self.rules]), "cz_match_set_rules")
-        if self.repetition:
-            check(L.cz_match_set_repetition(self._h, self.repetition), "cz_match_set_repetition")
-        if self.chase:
-            check(L.cz_match_set_chase(self._h, 1), "cz_match_set_chase")
+        set_rule_options("cz_match", self._h, self.rules, self.repetition, self.chase)
         self.masks = []
         for player in (0, 1):
             p = C.c_void_p()
@@ -514,10 +502,10 @@ def main(argv=None):
     ap.add_argument("--chase", action="store_true",
                     help="with --repetition: a side that alone chased one unprotected piece with every move of the cycle loses")
     args = ap.parse_args(argv)
-    if not (args.repetition == 0 or 2 <= args.repetition <= 8) or (args.repetition and args.rules != "xiangqi"):
-        ap.error("--repetition is 0 or 2..8 and needs --rules xiangqi")
-    if args.chase and not args.repetition:
-        ap.error("--chase needs --repetition")
+    try:
+        check_rule_options("arena", args.rules, args.repetition, args.chase)
+    except ValueError as e:
+        ap.error(str(e))
     a = load_player(args.a, args.blocks)
     b = a if args.b == args.a else load_player(args.b, args.blocks)
     pairs = (args.games + 1) // 2

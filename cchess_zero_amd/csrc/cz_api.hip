@@ -17,19 +17,6 @@ void cz_set_error(const char *fmt, ...) {
 
 namespace {
 
-size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
-
-// carve helper over one device allocation
-struct Carver {
-    char *base;
-    size_t off = 0;
-    template <typename T> T *take(size_t n) {
-        T *p = base ? (T *)(base + off) : nullptr;
-        off = align_up(off + n * sizeof(T));
-        return p;
-    }
-};
-
 void carve_pool(Carver &c, CzPool &p, size_t n) {
     p.P = c.take<float>(n); p.W = c.take<float>(n); p.Q = c.take<float>(n);
     p.N = c.take<int32_t>(n); p.parent = c.take<int32_t>(n); p.child_begin = c.take<int32_t>(n);
@@ -580,16 +567,8 @@ int cz_selfplay_begin(cz_ctx *c, int max_plies, const uint8_t *boards, const uin
             sp.start_side = k.take<uint8_t>(G);
             sp.start_rr = k.take<int32_t>(G);
             sp.stats = k.take<long long>(CZ_SP_NSTATS);
-            sp.xq_board = k.take<uint8_t>(G * CZ_NSQ);
-            sp.xq_side = k.take<uint8_t>(G);
-            sp.safe = k.take<uint32_t>(G * CZ_MASK_WORDS);
-            sp.mated = k.take<uint8_t>(G);
             sp.xq_stats = k.take<long long>(3);
-            sp.ring_key = k.take<uint64_t>(G * 64);
-            sp.ring_check = k.take<uint8_t>(G * 64);
-            sp.rep = k.take<uint8_t>(G);
-            sp.flags = k.take<uint8_t>(G);
-            sp.root_key = k.take<uint64_t>(G);
+            carve_root_rules(k, sp.rr, G, false);
         };
         Carver m{nullptr};
         CzSelfplay dummy;
@@ -599,62 +578,52 @@ int cz_selfplay_begin(cz_ctx *c, int max_plies, const uint8_t *boards, const uin
         carve(k, c->sp);
         c->sp.max_plies = max_plies;
     }
-    c->sp_rules = 0; c->sp_fold = 0; c->sp_chase = 0; c->sp_state = 1;
+    c->sp_rules = 0; c->sp.rr.fold = 0; c->sp_chase = 0; c->sp_state = 1;
     return czk_selfplay_seed(c, boards, side, rr);
+}
+// the setters' order (cz_root_rules_order), in self-play's names
+static int sp_order(const cz_ctx *c, int what, int value) {
+    return cz_root_rules_order("cz_selfplay", "ctx", "the history starts at the games' first positions", what, value, c->sp_rules, c->sp.rr.fold,
+                               c->sp_chase, c->sp_state != 1);
 }
 int cz_selfplay_set_rules(cz_ctx *c, int rules) {
     CZ_REQUIRE(c && c->sp_block && c->sp_state != 0, "cz_selfplay_set_rules: call cz_selfplay_begin first");
-    CZ_REQUIRE(rules == 0 || rules == 1, "cz_selfplay_set_rules: rules 0 (king capture) or 1 (xiangqi)");
-    CZ_REQUIRE(c->sp_state == 1, "cz_selfplay_set_rules: before the first cz_selfplay_choose only (a game is played under one set of rules)");
-    CZ_REQUIRE(rules == 1 || c->sp_fold == 0, "cz_selfplay_set_rules: the repetition rule needs rules 1: cz_selfplay_set_repetition(ctx, 0) first");
+    if (const int rc = sp_order(c, CZ_SET_RULES, rules)) return rc;
     c->sp_rules = rules;
     return CZ_OK;
 }
 int cz_selfplay_set_repetition(cz_ctx *c, int fold) {
     CZ_REQUIRE(c && c->sp_block && c->sp_state != 0, "cz_selfplay_set_repetition: call cz_selfplay_begin first");
-    CZ_REQUIRE(fold == 0 || (fold >= 2 && fold <= 8), "cz_selfplay_set_repetition: fold 0 (off) or 2..8");
-    CZ_REQUIRE(c->sp_state == 1, "cz_selfplay_set_repetition: before the first cz_selfplay_choose only (the history starts at the games' first positions)");
-    CZ_REQUIRE(fold == 0 || c->sp_rules == 1, "cz_selfplay_set_repetition: cz_selfplay_set_rules(ctx, 1) first (the check flags are the king-safe pass's)");
-    CZ_REQUIRE(fold != 0 || c->sp_chase == 0, "cz_selfplay_set_repetition: the chase rule needs a fold: cz_selfplay_set_chase(ctx, 0) first");
-    c->sp_fold = fold;
+    if (const int rc = sp_order(c, CZ_SET_REPETITION, fold)) return rc;
+    c->sp.rr.fold = fold;
     return CZ_OK;
 }
 int cz_selfplay_history(cz_ctx *c, const uint64_t **keys, const uint8_t **checks) {
-    CZ_REQUIRE(c && c->sp_block && c->sp_fold != 0, "cz_selfplay_history: cz_selfplay_set_repetition first");
-    if (keys) *keys = c->sp.ring_key;
-    if (checks) *checks = c->sp.ring_check;
+    CZ_REQUIRE(c && c->sp_block && c->sp.rr.fold != 0, "cz_selfplay_history: cz_selfplay_set_repetition first");
+    if (keys) *keys = c->sp.rr.ring_key;
+    if (checks) *checks = c->sp.rr.ring_check;
     return CZ_OK;
 }
 int cz_selfplay_set_chase(cz_ctx *c, int on) {
     CZ_REQUIRE(c && c->sp_block && c->sp_state != 0, "cz_selfplay_set_chase: call cz_selfplay_begin first");
-    CZ_REQUIRE(on == 0 || on == 1, "cz_selfplay_set_chase: on 0 or 1");
-    CZ_REQUIRE(c->sp_state == 1, "cz_selfplay_set_chase: before the first cz_selfplay_choose only (the history starts at the games' first positions)");
-    CZ_REQUIRE(on == 0 || c->sp_fold != 0, "cz_selfplay_set_chase: cz_selfplay_set_repetition(ctx, fold) first (a chase is judged on a repeated position)");
+    if (const int rc = sp_order(c, CZ_SET_CHASE, on)) return rc;
     if (on) {
-        const size_t G = (size_t)c->max_games;
-        auto carve = [&](Carver &k, CzSelfplay &sp) {
-            sp.ring_chase = k.take<uint64_t>(G * 64 * 4);
-            sp.root_chase = k.take<uint64_t>(G * 4);
-            sp.chase_stat = k.take<long long>(1);
+        auto carve = [&](Carver &k) {
+            carve_root_rules(k, c->sp.rr, (size_t)c->max_games, true);
+            c->sp.chase_stat = k.take<long long>(1);
         };
         Carver m{nullptr};
-        CzSelfplay dummy;
-        carve(m, dummy);
-        if (!c->sp_chase_block && hipMalloc(&c->sp_chase_block, m.off) != hipSuccess) {
-            c->sp_chase_block = nullptr;
-            cz_set_error("cz_selfplay_set_chase: hipMalloc(%zu B) failed", m.off);
-            return CZ_ENOMEM;
-        }
+        carve(m);
+        if (const int rc = alloc_zeroed(&c->sp_chase_block, m.off, c->stream, "cz_selfplay_set_chase")) return rc;   // the counter starts with the games, as cz_selfplay_begin's
         Carver k{(char *)c->sp_chase_block};
-        carve(k, c->sp);
-        CZ_HIP(hipMemsetAsync(c->sp_chase_block, 0, m.off, c->stream));   // the counter starts with the games, as cz_selfplay_begin's
+        carve(k);
     }
     c->sp_chase = on;
     return CZ_OK;
 }
 int cz_selfplay_chase_history(cz_ctx *c, const uint64_t **chase) {
     CZ_REQUIRE(c && c->sp_block && c->sp_chase != 0, "cz_selfplay_chase_history: cz_selfplay_set_chase first");
-    if (chase) *chase = c->sp.ring_chase;
+    if (chase) *chase = c->sp.rr.ring_chase;
     return CZ_OK;
 }
 int cz_selfplay_chase_stats(cz_ctx *c, long long *stats_dev) {

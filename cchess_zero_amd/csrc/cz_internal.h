@@ -9,6 +9,7 @@
 
 #include "../../include/cchess_hip.h"
 #include "cz_device.h"
+#include "cz_rootrules.h"
 
 // ---- error plumbing -------------------------------------------------------------------------
 void cz_set_error(const char *fmt, ...);
@@ -24,6 +25,27 @@ void cz_set_error(const char *fmt, ...);
     do {                                                     \
         if (!(cond)) { cz_set_error("%s", msg); return CZ_EINVAL; } \
     } while (0)
+
+// ---- carving one device allocation into arrays (base NULL: only the size, in off) --------------
+struct Carver {
+    char *base;
+    size_t off = 0;
+    template <typename T> T *take(size_t n) {
+        T *p = base ? (T *)(base + off) : nullptr;
+        off = (off + n * sizeof(T) + 255) / 256 * 256;
+        return p;
+    }
+};
+// *block (allocated here unless it already is) of `bytes` zeros, in stream order; who: the API call the error text names
+inline int alloc_zeroed(void **block, size_t bytes, hipStream_t stream, const char *who) {
+    if (!*block && hipMalloc(block, bytes) != hipSuccess) {
+        *block = nullptr;
+        cz_set_error("%s: hipMalloc(%zu B) failed", who, bytes);
+        return CZ_ENOMEM;
+    }
+    CZ_HIP(hipMemsetAsync(*block, 0, bytes, stream));
+    return CZ_OK;
+}
 
 // ---- host tables (cz_tables.hip) --------------------------------------------------------------
 struct CzHostTables {
@@ -62,24 +84,12 @@ struct CzSelfplay {
     uint8_t *start_side;         // [max_games]
     int32_t *start_rr;           // [max_games]
     long long *stats;            // [CZ_SP_NSTATS]
-    // cz_selfplay_set_rules(1): what the xiangqi kernels keep beside the games (the arrays of cz_match.hip's CzMatchXq / CzMatchRep)
-    uint8_t *xq_board;           // [max_games][90] the root position of every slot at the last choose (an empty board for a parked slot)
-    uint8_t *xq_side;            // [max_games]
-    uint32_t *safe;              // [max_games][66] its king-safe set (cz_movegen_kingsafe)
-    uint8_t *mated;              // [max_games] the last choose found children, none of them king-safe
+    // cz_selfplay_set_rules(1): what the rules at the root keep beside the games (cz_rootrules.h); the chase part is an allocation
+    // of its own, chase_stat behind it, NULL while cz_selfplay_set_chase is off
+    CzRootRules rr;
     long long *xq_stats;         // [3] games ended by mate, by a repetition draw, by perpetual check (cz_selfplay_rules_stats)
-    // cz_selfplay_set_repetition(fold != 0): the history of every slot's game, a ring over the position index
-    uint64_t *ring_key;          // [max_games][64] cz_hash of position i of the slot's game at [i & 63]
-    uint8_t *ring_check;         // [max_games][64] its side to move is in check
-    uint8_t *rep;                // [max_games] CZ_REP_* of the last choose: the game ends by repetition
-    uint8_t *flags;              // [max_games] CZ_POS_* of the root position (cz_movegen_kingsafe)
-    uint64_t *root_key;          // [max_games] its cz_hash
-    // cz_selfplay_set_chase(1): the chase records (cz_threats), in an allocation of their own; NULL while the rule is off
-    uint64_t *ring_chase;        // [max_games][64][4] the record of position i of the slot's game at [i & 63]
-    uint64_t *root_chase;        // [max_games][4] the record of the root position
     long long *chase_stat;       // [1] games ended by perpetual chase (cz_selfplay_chase_stats)
 };
-#define CZ_REP_BY_CHASE 0x10     /* in CzSelfplay::rep beside the CZ_REP_* verdict: the loss is a chase, not a perpetual check */
 
 #define CZ_EC_BUCKETS 128
 // cross-tree table: the bit that marks an entry whose payload is being written (claimed as key | CZ_XC_BUSY, not yet published);
@@ -205,8 +215,7 @@ struct cz_ctx {
     CzSelfplay sp;     // cz_selfplay_begin
     void *sp_block;
     int sp_rules;      // cz_selfplay_set_rules: 0 king capture, 1 xiangqi
-    int sp_fold;       // cz_selfplay_set_repetition: 0 off, 2..8
-    int sp_chase;      // cz_selfplay_set_chase: 0 off, 1 on (needs sp_fold != 0)
+    int sp_chase;      // cz_selfplay_set_chase: 0 off, 1 on (needs a fold, sp.rr.fold: cz_selfplay_set_repetition)
     void *sp_chase_block;
     int sp_state;      // 0: no cz_selfplay_begin yet, 1: begun (the setters may be called), 2: a cz_selfplay_choose has run since
     void *ec_block;    // cz_search_set_eval_cache
@@ -325,14 +334,13 @@ __device__ __forceinline__ int wave_kingsafe_children(const TreeView &v, int cb,
 }
 
 // ---- move choice at a root (k_pick_ready, k_sp_choose, k_match_choose) ---------------------------
-// get_action in its T -> 0 limit (main.py:1332-1341): the first maximum of N over the root's n children at cb, in
-// generation order (Python max() over root.child.items()); the index is wave-uniform, 0 when n == 0
-__device__ __forceinline__ int wave_most_visited(const TreeView &v, int cb, int n, int lane) {
+// get_action in its T -> 0 limit (main.py:1332-1341): the first maximum of N over a root's n <= 128 children, in generation
+// order (Python max() over root.child.items()) — N[r] is the visit count of child lane + 64 r; the index is wave-uniform
+__device__ __forceinline__ int wave_most_visited(const int N[2], int n, int lane) {
     int bn = -1, bi = 0x7fffffff;
-    for (int i = lane; i < n; i += 64) {
-        const int x = v.N[cb + i];
-        if (x > bn) { bn = x; bi = i; }
-    }
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+        if (lane + 64 * r < n && N[r] > bn) { bn = N[r]; bi = lane + 64 * r; }
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) {
         const int on = __shfl_xor(bn, d, 64), oi = __shfl_xor(bi, d, 64);
@@ -424,6 +432,62 @@ int czk_search_reload_finished(cz_ctx *, const uint8_t *, const uint16_t *, cons
 int czk_search_select_k(cz_ctx *, int, int, const uint8_t *, void *, int, int, uint8_t *);
 int czk_search_expand_backup_k(cz_ctx *, int, const void *, const void *, int);
 int czk_selfplay_seed(cz_ctx *, const uint8_t *, const uint8_t *, const int32_t *);
-int czk_selfplay_choose(cz_ctx *, const float *, const float *, const uint16_t *, double, float, int, uint16_t *);   // by c->sp_rules / c->sp_fold
+int czk_selfplay_choose(cz_ctx *, const float *, const float *, const uint16_t *, double, float, int, uint16_t *);   // by c->sp_rules / sp.rr.fold / c->sp_chase
 int czk_selfplay_adjudicate(cz_ctx *, int, const uint16_t *, int32_t *);
 int czk_selfplay_flush(cz_ctx *, const int32_t *, const long long *, uint8_t *, long long, const long long *);
+
+// ---- the rules at the root, host side (cz_rootrules.h; cz_match.hip, cz_selfplay.hip / cz_api.hip) ----
+// the arrays of G slots inside the carver's allocation: the chase rings (chase_part), or everything else
+inline void carve_root_rules(Carver &k, CzRootRules &rr, size_t G, bool chase_part) {
+    if (chase_part) {
+        rr.ring_chase = k.take<uint64_t>(G * 64 * 4);
+        rr.root_chase = k.take<uint64_t>(G * 4);
+        return;
+    }
+    rr.board = k.take<uint8_t>(G * CZ_NSQ);
+    rr.side = k.take<uint8_t>(G);
+    rr.safe = k.take<uint32_t>(G * CZ_MASK_WORDS);
+    rr.mated = k.take<uint8_t>(G);
+    rr.ring_key = k.take<uint64_t>(G * 64);
+    rr.ring_check = k.take<uint8_t>(G * 64);
+    rr.rep = k.take<uint8_t>(G);
+    rr.flags = k.take<uint8_t>(G);
+    rr.root_key = k.take<uint64_t>(G);
+}
+
+// Between a consumer's root gather (wave_gather_root) and its choose kernel, level >= CZ_RULES_KINGSAFE: the king-safe sets of
+// the G root positions; from CZ_RULES_REPETITION their check flags and keys; at CZ_RULES_CHASE their chase records
+inline int czk_root_rules_prepare(cz_ctx *c, const CzRootRules &rr, int G, int level) {
+    int rc = czk_movegen_kingsafe(c, rr.board, rr.side, G, nullptr, nullptr, rr.safe, level >= CZ_RULES_REPETITION ? rr.flags : nullptr, 0);
+    if (rc == CZ_OK && level >= CZ_RULES_REPETITION) rc = czk_hash(c, rr.board, rr.side, G, rr.root_key);
+    if (rc == CZ_OK && level >= CZ_RULES_CHASE) rc = czk_threats(c, rr.board, rr.side, G, rr.root_chase);
+    return rc;
+}
+
+// The order a consumer's three setters keep — rules before the fold, the fold before the chase rule, off in the reverse order,
+// nothing after the first choose (started) — for the call `what` with argument `value` on a consumer in state (rules, fold,
+// chase).  api ("cz_match" / "cz_selfplay") and handle ("match" / "ctx") are the names the error texts speak of, since: where
+// the consumer's history starts.
+enum CzRuleSetter { CZ_SET_RULES, CZ_SET_REPETITION, CZ_SET_CHASE };
+inline int cz_root_rules_order(const char *api, const char *handle, const char *since, int what, int value, int rules, int fold, int chase,
+                               bool started) {
+    const std::string a(api), h(handle), late = "before the first " + a + "_choose only (";
+    std::string e;
+    if (what == CZ_SET_RULES) {
+        if (value != 0 && value != 1) e = a + "_set_rules: rules 0 (king capture) or 1 (xiangqi)";
+        else if (started) e = a + "_set_rules: " + late + "a game is played under one set of rules)";
+        else if (value == 0 && fold != 0) e = a + "_set_rules: the repetition rule needs rules 1: " + a + "_set_repetition(" + h + ", 0) first";
+    } else if (what == CZ_SET_REPETITION) {
+        if (value != 0 && (value < 2 || value > 8)) e = a + "_set_repetition: fold 0 (off) or 2..8";
+        else if (started) e = a + "_set_repetition: " + late + since + ")";
+        else if (value != 0 && rules != 1) e = a + "_set_repetition: " + a + "_set_rules(" + h + ", 1) first (the check flags are the king-safe pass's)";
+        else if (value == 0 && chase != 0) e = a + "_set_repetition: the chase rule needs a fold: " + a + "_set_chase(" + h + ", 0) first";
+    } else {
+        if (value != 0 && value != 1) e = a + "_set_chase: on 0 or 1";
+        else if (started) e = a + "_set_chase: " + late + since + ")";
+        else if (value != 0 && fold == 0) e = a + "_set_chase: " + a + "_set_repetition(" + h + ", fold) first (a chase is judged on a repeated position)";
+    }
+    if (e.empty()) return CZ_OK;
+    cz_set_error("%s", e.c_str());
+    return CZ_EINVAL;
+}

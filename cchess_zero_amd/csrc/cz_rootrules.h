@@ -1,0 +1,86 @@
+// cz_rootrules.h — the Xiangqi rules that act at the root of a game slot, shared by the match (cz_match.hip) and self-play
+// (cz_selfplay.hip): the king-safe set of the root position, the slot's rings of position keys, check flags and chase records,
+// and the repetition / perpetual-check / perpetual-chase verdict on them.  The search below the root is untouched.
+// The host side (carve_root_rules, czk_root_rules_prepare, cz_root_rules_order) is in cz_internal.h.
+#pragma once
+#include <type_traits>
+
+#include "cz_device.h"
+#include "cz_repetition.h"
+
+// What the rules need per slot, beside the consumer's own game state.  The chase part is an allocation of its own in both
+// consumers (NULL while that rule is off).
+struct CzRootRules {
+    uint8_t *board;         // [G][90] the mover's root position of every slot at the last choose (an empty board for a parked slot)
+    uint8_t *side;          // [G]
+    uint32_t *safe;         // [G][66] its king-safe set (cz_movegen_kingsafe)
+    uint8_t *mated;         // [G] the last choose found children, none of them king-safe
+    uint64_t *ring_key;     // [G][64] cz_hash of position i of the slot's game at [i & 63]
+    uint8_t *ring_check;    // [G][64] its side to move is in check
+    uint8_t *rep;           // [G] CZ_REP_* of the last choose, CZ_REP_BY_CHASE beside it: the game ends by repetition
+    uint8_t *flags;         // [G] CZ_POS_* of the root position (cz_movegen_kingsafe)
+    uint64_t *root_key;     // [G] its cz_hash
+    uint64_t *ring_chase;   // [G][64][4] the chase record (cz_threats) of position i of the slot's game at [i & 63]
+    uint64_t *root_chase;   // [G][4] the record of the root position
+    int fold;               // 0: no repetition rule, 2..8: a fold-th occurrence ends the game
+};
+#define CZ_REP_BY_CHASE 0x10   /* in CzRootRules::rep beside the CZ_REP_* verdict: the loss is a chase, not a perpetual check */
+
+// The rule level of a consumer; every level includes the ones below it.
+enum CzRulesLevel {
+    CZ_RULES_CAPTURE = 0,      // the reference's games: a king is captured
+    CZ_RULES_KINGSAFE = 1,     // moves are king-safe, a mover without one is mated
+    CZ_RULES_REPETITION = 2,   // and a fold-th occurrence of the root position ends the game
+    CZ_RULES_CHASE = 3,        // and a perpetual chase is judged on it
+};
+inline int cz_rules_level(int rules, int fold, int chase) {
+    return rules != 1 ? CZ_RULES_CAPTURE : (fold == 0 ? CZ_RULES_KINGSAFE : (chase ? CZ_RULES_CHASE : CZ_RULES_REPETITION));
+}
+
+// f(std::integral_constant<int, level>): the one place a run-time level picks a kernel instantiation
+template <typename F>
+inline void cz_by_rules_level(int level, F &&f) {
+    switch (level) {
+    case CZ_RULES_CHASE: f(std::integral_constant<int, CZ_RULES_CHASE>{}); break;
+    case CZ_RULES_REPETITION: f(std::integral_constant<int, CZ_RULES_REPETITION>{}); break;
+    case CZ_RULES_KINGSAFE: f(std::integral_constant<int, CZ_RULES_KINGSAFE>{}); break;
+    default: f(std::integral_constant<int, CZ_RULES_CAPTURE>{}); break;
+    }
+}
+
+// Before the choice: slot g's root position of tree set t (CzTrees), for cz_movegen_kingsafe / cz_hash / cz_threats, by one wave64
+template <typename Trees>
+__device__ __forceinline__ void wave_gather_root(const CzRootRules &rr, const Trees &t, int g, bool live, int lane) {
+    for (int j = lane; j < CZ_NSQ; j += 64) rr.board[(size_t)g * CZ_NSQ + j] = live ? t.root_board[(size_t)g * CZD_BOARD_LDS + j] : (uint8_t)0;
+    if (lane == 0) rr.side[g] = live ? t.root_side[g] : (uint8_t)0;
+}
+
+// The root position of slot g's game goes into the slot's rings at the game's ply, and a fold-th occurrence inside the last
+// min(root_rr, ply, 63) positions — a capture makes the earlier ones unreachable, and no read leaves the slot's current game —
+// ends the game.  CHASE: its chase record goes into the third ring the same way, and the verdict is wave_repetition_chase's: a
+// repetition that is a draw by checks may be a loss for the side that alone chased one piece.
+// -> CZ_REP_* (| CZ_REP_BY_CHASE), wave-uniform, also left in rr.rep[g] when it is a verdict.  A parked slot never gets here.
+template <bool CHASE>
+__device__ __forceinline__ int wave_root_history(const CzRootRules &rr, int g, int ply, int root_rr, int lane) {
+    const uint64_t key = rr.root_key[g];
+    const bool chk = (rr.flags[g] & CZ_POS_IN_CHECK) != 0;
+    uint64_t *ring_key = rr.ring_key + (size_t)g * 64;
+    uint8_t *ring_check = rr.ring_check + (size_t)g * 64;
+    if (lane == 0) { ring_key[ply & 63] = key; ring_check[ply & 63] = chk ? 1 : 0; }
+    const int w = max(0, min(min(root_rr, ply), 63));   // entry ply & 63, just written, is never among the w read
+    const int side = rr.side[g] ? 1 : 0;
+    int first, verdict;
+    if constexpr (CHASE) {
+        uint64_t *ring = rr.ring_chase + (size_t)g * 64 * 4;
+        const uint64_t *root = rr.root_chase + (size_t)g * 4;
+        const uint64_t rec[4] = {root[0], root[1], root[2], root[3]};
+        if (lane < 4) ring[(ply & 63) * 4 + lane] = root[lane];   // as the key: never among the positions read below
+        int cause;
+        verdict = wave_repetition_chase(ring_key, ring_check, ring, 63, ply, w, key, chk, rec, side, rr.fold, lane, first, cause);
+        if (cause == CZ_CAUSE_CHASE) verdict |= CZ_REP_BY_CHASE;
+    } else {
+        verdict = wave_repetition(ring_key, ring_check, 63, ply, w, key, chk, side, rr.fold, lane, first);
+    }
+    if (verdict != CZ_REP_NONE && lane == 0) rr.rep[g] = (uint8_t)verdict;
+    return verdict;
+}

@@ -41,7 +41,11 @@ __global__ __launch_bounds__(64) void k_pick_ready(CzTrees t, int G, int32_t *__
         int cb, n;
         root_children(t, g, v, cb, n);
         // first maximum of N in generation order (Python max() over root.child.items())
-        const int bi = wave_most_visited(v, cb, n, lane);
+        int N[2] = {0, 0};
+#pragma unroll
+        for (int r = 0; r < 2; ++r)
+            if (lane + 64 * r < n) N[r] = v.N[cb + lane + 64 * r];
+        const int bi = wave_most_visited(N, n, lane);
         if (n > 0) label = v.move[cb + bi];
         if (lane == 0) {
             thr[g] = next_thr;

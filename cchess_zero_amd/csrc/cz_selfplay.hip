@@ -17,7 +17,6 @@
 // without one is mated; with a fold, a fold-th occurrence of the root position ends the game.  The search below the root is
 // untouched: in the tree a mate is a king capture two plies down, which it already sees.
 #include "cz_internal.h"
-#include "cz_repetition.h"
 
 #include <math.h>
 
@@ -35,38 +34,36 @@ __global__ __launch_bounds__(64) void k_sp_seed(CzTrees t, CzSelfplay sp, int G,
         sp.start_side[g] = boards ? (side[g] ? 1 : 0) : t.root_side[g];
         sp.start_rr[g] = boards ? (rr ? rr[g] : 0) : t.root_rr[g];
         sp.ply[g] = 0; sp.stalled[g] = 0; sp.active[g] = 1;
-        sp.mated[g] = 0; sp.rep[g] = CZ_REP_NONE;
+        sp.rr.mated[g] = 0; sp.rr.rep[g] = CZ_REP_NONE;
         if (g == 0) {
             for (int k = 0; k < CZ_SP_NSTATS; ++k) sp.stats[k] = 0;
             for (int k = 0; k < 3; ++k) sp.xq_stats[k] = 0;
         }
     }
-    sp.ring_key[(size_t)g * 64 + lane] = 0ull;
-    sp.ring_check[(size_t)g * 64 + lane] = 0;
+    sp.rr.ring_key[(size_t)g * 64 + lane] = 0ull;
+    sp.rr.ring_check[(size_t)g * 64 + lane] = 0;
 }
 
-// rules = 1, before the choice: the root position of every slot, for cz_movegen_kingsafe (k_match_roots_xq)
+// level >= CZ_RULES_KINGSAFE, before the choice: the root position of every slot, for czk_root_rules_prepare
 __global__ __launch_bounds__(64) void k_sp_roots_xq(CzTrees t, CzSelfplay sp, int G) {
     const int g = blockIdx.x, lane = threadIdx.x;
     if (g >= G) return;
-    const bool live = sp.active[g] != 0;
-    for (int j = lane; j < CZ_NSQ; j += 64) sp.xq_board[(size_t)g * CZ_NSQ + j] = live ? t.root_board[(size_t)g * CZD_BOARD_LDS + j] : (uint8_t)0;
-    if (lane == 0) sp.xq_side[g] = live ? t.root_side[g] : (uint8_t)0;
+    wave_gather_root(sp.rr, t, g, sp.active[g] != 0, lane);
 }
 
-// get_action (main.py:1337-1351) + the record append of selfplay (:1504-1518) for every active game.
-// XQ (cz_selfplay_set_rules(1)): over the root children whose move is in the slot's king-safe set — they are compacted, in
-// generation order, and pi, the noise (gamma[g][j] of compacted child j: a Dirichlet over len(probs) entries), the pick and the
-// record run on the ns compacted children exactly as they run on all n under king-capture rules.  ns = 0: the mover is mated.
-// fold != 0 (XQ only): the root position goes into the slot's ring at the game's ply first, and a fold-th occurrence inside the
-// last min(restrict_round, ply, 63) positions ends the game (choose_on<XQ, REP> of cz_match.hip).  On either ending played =
-// 0xFFFF, no record is written and the ply stays; k_sp_adjudicate_xq ends the game.  A forced label is played as given.
-// CHASE (cz_selfplay_set_chase; XQ with a fold only): the root position's chase record goes into the slot's third ring, and the
-// verdict is wave_repetition_chase's (choose_on<XQ, REP, CHASE> of cz_match.hip).
-template <bool XQ, bool CHASE = false>
-__device__ __forceinline__ void sp_choose(const CzTrees &t, const CzSelfplay &sp, int G, const float *__restrict__ gamma,
-                                          const float *__restrict__ u, const uint16_t *__restrict__ forced, double inv_temp,
-                                          float eps, int min_sims, uint16_t *__restrict__ played, int fold) {
+// get_action (main.py:1337-1351) + the record append of selfplay (:1504-1518) for every active game, at rule level LEVEL
+// (CzRulesLevel, cz_rootrules.h).
+// From CZ_RULES_KINGSAFE (cz_selfplay_set_rules(1)): over the root children whose move is in the slot's king-safe set — they are
+// compacted, in generation order, and pi, the noise (gamma[g][j] of compacted child j: a Dirichlet over len(probs) entries), the
+// pick and the record run on the compacted children exactly as they run on all n under king-capture rules.  None: the mover is mated.
+// From CZ_RULES_REPETITION: first the root position goes through the slot's history (wave_root_history), whose verdict ends the
+// game.  On either ending played = 0xFFFF, no record is written and the ply stays; k_sp_adjudicate ends the game.  A forced
+// label is played as given.
+template <int LEVEL>
+__global__ __launch_bounds__(64) void k_sp_choose(CzTrees t, CzSelfplay sp, int G, const float *__restrict__ gamma,
+                                                  const float *__restrict__ u, const uint16_t *__restrict__ forced,
+                                                  double inv_temp, float eps, int min_sims, uint16_t *__restrict__ played) {
+    constexpr bool XQ = LEVEL >= CZ_RULES_KINGSAFE;
     const int g = blockIdx.x, lane = threadIdx.x;
     if (g >= G) return;
     if (!sp.active[g]) { if (lane == 0) played[g] = 0xFFFF; return; }
@@ -80,7 +77,7 @@ __device__ __forceinline__ void sp_choose(const CzTrees &t, const CzSelfplay &sp
     const TreeView v = view_of(t, g);
     int cb, n;
     root_children(t, g, v, cb, n);
-    if (XQ && lane == 0) { sp.mated[g] = 0; sp.rep[g] = CZ_REP_NONE; }
+    if (XQ && lane == 0) { sp.rr.mated[g] = 0; sp.rr.rep[g] = CZ_REP_NONE; }
     if (root_cannot_move(t.status[g], n)) {   // the adjudication drops the game and re-seeds the slot
         if (lane == 0) { played[g] = 0xFFFF; sp.stalled[g] = 1; }
         return;
@@ -90,34 +87,16 @@ __device__ __forceinline__ void sp_choose(const CzTrees &t, const CzSelfplay &sp
     uint16_t lab[2] = {0xFFFF, 0xFFFF};
     double pi[2], p[2];
     if constexpr (XQ) {
-        if (fold != 0) {
-            const uint64_t key = sp.root_key[g];
-            const bool chk = (sp.flags[g] & CZ_POS_IN_CHECK) != 0;
-            uint64_t *ring_key = sp.ring_key + (size_t)g * 64;
-            uint8_t *ring_check = sp.ring_check + (size_t)g * 64;
-            if (lane == 0) { ring_key[ply & 63] = key; ring_check[ply & 63] = chk ? 1 : 0; }
-            const int w = max(0, min(min(t.root_rr[g], ply), 63));   // entry ply & 63, just written, is never among the w read
-            int first, verdict;
-            if constexpr (CHASE) {
-                uint64_t *ring = sp.ring_chase + (size_t)g * 64 * 4;
-                const uint64_t *root = sp.root_chase + (size_t)g * 4;
-                const uint64_t rec[4] = {root[0], root[1], root[2], root[3]};
-                if (lane < 4) ring[(ply & 63) * 4 + lane] = root[lane];   // as the key: never among the positions read below
-                int cause;
-                verdict = wave_repetition_chase(ring_key, ring_check, ring, 63, ply, w, key, chk, rec, sp.xq_side[g] ? 1 : 0, fold, lane, first, cause);
-                if (cause == CZ_CAUSE_CHASE) verdict |= CZ_REP_BY_CHASE;
-            } else {
-                verdict = wave_repetition(ring_key, ring_check, 63, ply, w, key, chk, sp.xq_side[g] ? 1 : 0, fold, lane, first);
-            }
-            if (verdict != CZ_REP_NONE) {
-                if (lane == 0) { played[g] = 0xFFFF; sp.rep[g] = (uint8_t)verdict; }
+        if constexpr (LEVEL >= CZ_RULES_REPETITION) {
+            if (wave_root_history<LEVEL >= CZ_RULES_CHASE>(sp.rr, g, ply, t.root_rr[g], lane) != CZ_REP_NONE) {
+                if (lane == 0) played[g] = 0xFFFF;
                 return;
             }
         }
         __shared__ int sN[128], sI[128];
-        n = wave_kingsafe_children(v, cb, n, sp.safe + (size_t)g * CZ_MASK_WORDS, lane, sN, sI);
+        n = wave_kingsafe_children(v, cb, n, sp.rr.safe + (size_t)g * CZ_MASK_WORDS, lane, sN, sI);
         if (n == 0) {   // children, none of them king-safe: checkmate or stalemate, the mover loses
-            if (lane == 0) { played[g] = 0xFFFF; sp.mated[g] = 1; }
+            if (lane == 0) { played[g] = 0xFFFF; sp.rr.mated[g] = 1; }
             return;
         }
 #pragma unroll
@@ -175,39 +154,25 @@ __device__ __forceinline__ void sp_choose(const CzTrees &t, const CzSelfplay &sp
     }
     if (lane == 0) { played[g] = (uint16_t)mv; sp.ply[g] = ply + 1; }
 }
-__global__ __launch_bounds__(64) void k_sp_choose(CzTrees t, CzSelfplay sp, int G, const float *__restrict__ gamma,
-                                                  const float *__restrict__ u, const uint16_t *__restrict__ forced,
-                                                  double inv_temp, float eps, int min_sims, uint16_t *__restrict__ played) {
-    sp_choose<false>(t, sp, G, gamma, u, forced, inv_temp, eps, min_sims, played, 0);
-}
-__global__ __launch_bounds__(64) void k_sp_choose_xq(CzTrees t, CzSelfplay sp, int G, const float *__restrict__ gamma,
-                                                     const float *__restrict__ u, const uint16_t *__restrict__ forced,
-                                                     double inv_temp, float eps, int min_sims, uint16_t *__restrict__ played, int fold) {
-    sp_choose<true>(t, sp, G, gamma, u, forced, inv_temp, eps, min_sims, played, fold);
-}
-__global__ __launch_bounds__(64) void k_sp_choose_chase(CzTrees t, CzSelfplay sp, int G, const float *__restrict__ gamma,
-                                                        const float *__restrict__ u, const uint16_t *__restrict__ forced,
-                                                        double inv_temp, float eps, int min_sims, uint16_t *__restrict__ played, int fold) {
-    sp_choose<true, true>(t, sp, G, gamma, u, forced, inv_temp, eps, min_sims, played, fold);
-}
 
 // The game-end tests of selfplay (main.py:1532-1545) on the position after the move, z for every recorded ply, and —
 // reseed != 0 — MCTS_tree.reload / GameBoard.reload for the next game of the slot (:1549-1551, :1494).
 // fin_n[g] = number of records the finished game hands to the ring (0: not finished, or dropped).
-// XQ: before those tests, the endings the last choose found on the root it left untouched — a repetition verdict (a draw, or a
-// loss for the side that checked perpetually), then a mated mover (the side to move loses); z as for a king capture.
-// CHASE: the verdict may carry CZ_REP_BY_CHASE — a loss for the side that chased, z as for perpetual check, counted in
-// chase_stat and not among the perpetuals.
-template <bool XQ, bool CHASE = false>
-__device__ __forceinline__ void sp_adjudicate(const CzTrees &t, const CzSelfplay &sp, int G, int reseed, const uint16_t *__restrict__ played,
-                                              int32_t *__restrict__ fin_n) {
+// From CZ_RULES_KINGSAFE: before those tests, the endings the last choose found on the root it left untouched — a repetition
+// verdict (a draw, or a loss for the side that checked perpetually), then a mated mover (the side to move loses); z as for a king
+// capture.  At CZ_RULES_CHASE the verdict may carry CZ_REP_BY_CHASE — a loss for the side that chased, z as for perpetual check,
+// counted in chase_stat and not among the perpetuals.
+template <int LEVEL>
+__global__ __launch_bounds__(64) void k_sp_adjudicate(CzTrees t, CzSelfplay sp, int G, int reseed, const uint16_t *__restrict__ played,
+                                                      int32_t *__restrict__ fin_n) {
+    constexpr bool XQ = LEVEL >= CZ_RULES_KINGSAFE, CHASE = LEVEL >= CZ_RULES_CHASE;
     const int g = blockIdx.x, lane = threadIdx.x;
     if (g >= G) return;
     if (!sp.active[g]) { if (lane == 0) fin_n[g] = 0; return; }
-    const int stored = XQ ? (int)sp.rep[g] : CZ_REP_NONE;
+    const int stored = XQ ? (int)sp.rr.rep[g] : CZ_REP_NONE;
     const bool by_chase = CHASE && (stored & CZ_REP_BY_CHASE) != 0;
     const int verdict = CHASE ? (stored & ~CZ_REP_BY_CHASE) : stored;
-    const bool mated = XQ && verdict == CZ_REP_NONE && sp.mated[g] != 0;
+    const bool mated = XQ && verdict == CZ_REP_NONE && sp.rr.mated[g] != 0;
     const bool by_rules = verdict != CZ_REP_NONE || mated;
     // asynchronous plies: only the slots that just moved (or stalled, or ended by the rules) can have ended their game
     if (played && played[g] == 0xFFFF && !sp.stalled[g] && !by_rules) { if (lane == 0) fin_n[g] = 0; return; }
@@ -236,7 +201,7 @@ __device__ __forceinline__ void sp_adjudicate(const CzTrees &t, const CzSelfplay
         if constexpr (XQ) {
             if (by_chase) atomicAdd((unsigned long long *)sp.chase_stat, 1ull);
             else if (by_rules) atomicAdd((unsigned long long *)&sp.xq_stats[mated ? 0 : (verdict == CZ_REP_DRAW ? 1 : 2)], 1ull);
-            sp.mated[g] = 0; sp.rep[g] = CZ_REP_NONE;
+            sp.rr.mated[g] = 0; sp.rr.rep[g] = CZ_REP_NONE;
         }
     }
     if (reseed) {   // the slot's next game: a fresh root on its start position
@@ -244,19 +209,6 @@ __device__ __forceinline__ void sp_adjudicate(const CzTrees &t, const CzSelfplay
         if (lane == 0) { sp.ply[g] = 0; sp.stalled[g] = 0; }
     } else if (lane == 0) sp.active[g] = 0;
 }
-__global__ __launch_bounds__(64) void k_sp_adjudicate(CzTrees t, CzSelfplay sp, int G, int reseed, const uint16_t *__restrict__ played,
-                                                      int32_t *__restrict__ fin_n) {
-    sp_adjudicate<false>(t, sp, G, reseed, played, fin_n);
-}
-__global__ __launch_bounds__(64) void k_sp_adjudicate_xq(CzTrees t, CzSelfplay sp, int G, int reseed, const uint16_t *__restrict__ played,
-                                                         int32_t *__restrict__ fin_n) {
-    sp_adjudicate<true>(t, sp, G, reseed, played, fin_n);
-}
-__global__ __launch_bounds__(64) void k_sp_adjudicate_chase(CzTrees t, CzSelfplay sp, int G, int reseed, const uint16_t *__restrict__ played,
-                                                            int32_t *__restrict__ fin_n) {
-    sp_adjudicate<true, true>(t, sp, G, reseed, played, fin_n);
-}
-
 // Copies the records of the games k_sp_adjudicate finished to ring[(offset[g] + j) % ring_records].  The offsets are an
 // exclusive prefix sum of fin_n computed by the caller (record order = game order: deterministic, no atomics).
 __global__ __launch_bounds__(64) void k_sp_flush(CzSelfplay sp, int G, const int32_t *__restrict__ fin_n,
@@ -288,34 +240,24 @@ int czk_selfplay_seed(cz_ctx *c, const uint8_t *boards, const uint8_t *side, con
 
 int czk_selfplay_choose(cz_ctx *c, const float *gamma, const float *u, const uint16_t *forced, double temperature, float eps,
                         int min_sims, uint16_t *played) {
-    if (c->sp_rules == 1) {   // the king-safe set of every slot's root position (with a fold: its check flag and key), then the choice
-        const CzSelfplay &sp = c->sp;
-        hipLaunchKernelGGL(k_sp_roots_xq, dim3(c->G), dim3(64), 0, c->stream, c->t, sp, c->G);
+    const int level = cz_rules_level(c->sp_rules, c->sp.rr.fold, c->sp_chase);
+    if (level >= CZ_RULES_KINGSAFE) {   // what the rules need of every slot's root position, then the choice
+        hipLaunchKernelGGL(k_sp_roots_xq, dim3(c->G), dim3(64), 0, c->stream, c->t, c->sp, c->G);
         CZ_HIP(hipGetLastError());
-        int rc = czk_movegen_kingsafe(c, sp.xq_board, sp.xq_side, c->G, nullptr, nullptr, sp.safe, c->sp_fold ? sp.flags : nullptr, 0);
-        if (rc != CZ_OK) return rc;
-        if (c->sp_fold && (rc = czk_hash(c, sp.xq_board, sp.xq_side, c->G, sp.root_key)) != CZ_OK) return rc;
-        if (c->sp_fold && c->sp_chase) {   // and its chase record, for the third ring
-            if ((rc = czk_threats(c, sp.xq_board, sp.xq_side, c->G, sp.root_chase)) != CZ_OK) return rc;
-            hipLaunchKernelGGL(k_sp_choose_chase, dim3(c->G), dim3(64), 0, c->stream, c->t, sp, c->G, gamma, u, forced, 1.0 / temperature, eps, min_sims,
-                               played, c->sp_fold);
-            CZ_HIP(hipGetLastError());
-            return CZ_OK;
-        }
-        hipLaunchKernelGGL(k_sp_choose_xq, dim3(c->G), dim3(64), 0, c->stream, c->t, sp, c->G, gamma, u, forced, 1.0 / temperature, eps, min_sims, played,
-                           c->sp_fold);
-        CZ_HIP(hipGetLastError());
-        return CZ_OK;
+        if (const int rc = czk_root_rules_prepare(c, c->sp.rr, c->G, level)) return rc;
     }
-    hipLaunchKernelGGL(k_sp_choose, dim3(c->G), dim3(64), 0, c->stream, c->t, c->sp, c->G, gamma, u, forced, 1.0 / temperature, eps, min_sims, played);
+    cz_by_rules_level(level, [&](auto L) {
+        hipLaunchKernelGGL(k_sp_choose<decltype(L)::value>, dim3(c->G), dim3(64), 0, c->stream, c->t, c->sp, c->G, gamma, u, forced, 1.0 / temperature, eps,
+                           min_sims, played);
+    });
     CZ_HIP(hipGetLastError());
     return CZ_OK;
 }
 
 int czk_selfplay_adjudicate(cz_ctx *c, int reseed, const uint16_t *played, int32_t *fin_n) {
-    if (c->sp_rules == 1 && c->sp_fold && c->sp_chase) hipLaunchKernelGGL(k_sp_adjudicate_chase, dim3(c->G), dim3(64), 0, c->stream, c->t, c->sp, c->G, reseed, played, fin_n);
-    else if (c->sp_rules == 1) hipLaunchKernelGGL(k_sp_adjudicate_xq, dim3(c->G), dim3(64), 0, c->stream, c->t, c->sp, c->G, reseed, played, fin_n);
-    else hipLaunchKernelGGL(k_sp_adjudicate, dim3(c->G), dim3(64), 0, c->stream, c->t, c->sp, c->G, reseed, played, fin_n);
+    cz_by_rules_level(cz_rules_level(c->sp_rules, c->sp.rr.fold, c->sp_chase), [&](auto L) {
+        hipLaunchKernelGGL(k_sp_adjudicate<decltype(L)::value>, dim3(c->G), dim3(64), 0, c->stream, c->t, c->sp, c->G, reseed, played, fin_n);
+    });
     CZ_HIP(hipGetLastError());
     return CZ_OK;
 }

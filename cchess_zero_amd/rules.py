@@ -8,6 +8,31 @@ from ._lib import BF16, F16, F32, MASK_WORDS, MAXMOVES, NLABELS, NSQ, check, lib
 from .engine import Context, _ptr
 
 
+RULES = {"capture": 0, "xiangqi": 1}   # cz_match_set_rules / cz_selfplay_set_rules
+
+
+def check_rule_options(who, rules, repetition, chase):
+    """The rule options of arena.Match and selfplay.SelfPlay (`who` names the caller in the text): rules before a repetition
+    fold, a fold before the chase rule.  Raises ValueError."""
+    if rules not in RULES:
+        raise ValueError("%s: rules is 'capture' or 'xiangqi', not %r" % (who, rules))
+    if isinstance(repetition, bool) or not isinstance(repetition, (int, np.integer)) or not (repetition == 0 or 2 <= repetition <= 8):
+        raise ValueError("%s: repetition is 0 (off) or 2..8, not %r" % (who, repetition))
+    if repetition and rules != "xiangqi":
+        raise ValueError("%s: repetition needs rules='xiangqi' (the check flags come from the king-safe moves)" % who)
+    if chase and not repetition:
+        raise ValueError("%s: chase needs a repetition fold (a chase is judged on a repeated position)" % who)
+
+
+def set_rule_options(prefix, handle, rules, repetition, chase):
+    """<prefix>_set_rules / _set_repetition / _set_chase on a match or a self-play context, in the order the library asks for;
+    an option that is off is left alone."""
+    for name, value in (("rules", RULES[rules]), ("repetition", int(repetition)), ("chase", int(bool(chase)))):
+        if value:
+            fn = "%s_set_%s" % (prefix, name)
+            check(getattr(lib(), fn)(handle, value), fn)
+
+
 # the start position (main.py:585: RNBAKABNR/9/1C5C1/P1P1P1P1P/9/9/p1p1p1p1p/1c5c1/9/rnbakabnr) as piece codes, sq = 9 y + x
 START_BOARD = np.array([3, 5, 4, 2, 1, 2, 4, 5, 3] + [0] * 9 + [0, 7, 0, 0, 0, 0, 0, 7, 0] + [6, 0, 6, 0, 6, 0, 6, 0, 6] + [0] * 18 +
                        [13, 0, 13, 0, 13, 0, 13, 0, 13] + [0, 14, 0, 0, 0, 0, 0, 14, 0] + [0] * 9 + [10, 12, 11, 9, 8, 9, 11, 12, 10], np.uint8)

@@ -28,9 +28,9 @@ import torch
 
 from ._lib import (MAXMOVES, NLABELS, NSQ, REC_BYTES, REC_COUNT, REC_FLAGS, REC_LABELS, REC_PLY, REC_SIDE, REC_VISITS, REC_Z,
                    SP_CHASE_STATS, SP_RULES_STATS, SP_STATS, check, lib, tables)
+from .rules import RULES, check_rule_options, set_rule_options
 
 REC_MAXMOVES = MAXMOVES
-RULES = {"capture": 0, "xiangqi": 1}   # cz_selfplay_set_rules (arena.RULES)
 
 
 def pack_records(boards, side, labels, visits, counts, z, ply=None):
@@ -147,14 +147,7 @@ class SelfPlay:
 
     def __init__(self, engine, net, playouts, exploration=True, temperature=1.0, seed=0, max_plies=512, ring_records=None,
                  continuous=True, eval_cache=False, xcache_log2=0, rules="capture", repetition=0, chase=False):
-        if rules not in RULES:
-            raise ValueError("SelfPlay: rules is 'capture' or 'xiangqi', not %r" % (rules,))
-        if isinstance(repetition, bool) or not isinstance(repetition, (int, np.integer)) or not (repetition == 0 or 2 <= repetition <= 8):
-            raise ValueError("SelfPlay: repetition is 0 (off) or 2..8, not %r" % (repetition,))
-        if repetition and rules != "xiangqi":
-            raise ValueError("SelfPlay: repetition needs rules='xiangqi' (the check flags come from the king-safe moves)")
-        if chase and not repetition:
-            raise ValueError("SelfPlay: chase needs a repetition fold (a chase is judged on a repeated position)")
+        check_rule_options("SelfPlay", rules, repetition, chase)
         self.rules = rules
         self.repetition = int(repetition)
         self.chase = bool(chase)
@@ -188,12 +181,7 @@ class SelfPlay:
         eng.compact = not self.continuous   # parked games drop out of the net's batch; a full batch needs no compaction
         G = eng.G
         check(lib().cz_selfplay_begin(eng.ctx.h, self.max_plies, None, None, None), "cz_selfplay_begin")
-        if RULES[self.rules]:
-            check(lib().cz_selfplay_set_rules(eng.ctx.h, RULES[self.rules]), "cz_selfplay_set_rules")
-        if self.repetition:
-            check(lib().cz_selfplay_set_repetition(eng.ctx.h, self.repetition), "cz_selfplay_set_repetition")
-        if self.chase:
-            check(lib().cz_selfplay_set_chase(eng.ctx.h, 1), "cz_selfplay_set_chase")
+        set_rule_options("cz_selfplay", eng.ctx.h, self.rules, self.repetition, self.chase)
         p = C.c_void_p()
         check(lib().cz_selfplay_active(eng.ctx.h, C.byref(p)), "cz_selfplay_active")
         self._active_ptr = p
