@@ -415,7 +415,7 @@ int czk_movegen_kingsafe(cz_ctx *, const uint8_t *, const uint8_t *, int, uint16
 int czk_repetition(cz_ctx *, const uint64_t *, const uint8_t *, int, const int32_t *, const int32_t *, const uint8_t *, int, int, uint8_t *, int32_t *);   // cz_repetition.hip
 int czk_threats(cz_ctx *, const uint8_t *, const uint8_t *, int, uint64_t *);   // cz_chase.hip
 int czk_repetition_chase(cz_ctx *, const uint64_t *, const uint8_t *, const uint64_t *, int, const int32_t *, const int32_t *, const uint8_t *, int, int, uint8_t *, int32_t *,
-                         uint8_t *);   // cz_chase.hip
+                         uint8_t *);   // cz_repetition.hip
 int czk_apply_move(cz_ctx *, uint8_t *, uint8_t *, const uint16_t *, int, uint64_t *, uint8_t *, int8_t *);
 int czk_hash(cz_ctx *, const uint8_t *, const uint8_t *, int, uint64_t *);
 int czk_encode_planes(cz_ctx *, const uint8_t *, const uint8_t *, int, void *, int, int, int);

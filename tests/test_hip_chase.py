@@ -54,10 +54,11 @@ def test_golden_positions(rules, rules_golden):
     assert len(ref[0]) == 4381 and _hold(rules, ref) >= 400
 
 
-@pytest.mark.parametrize("G", [1, 63, 64, 65, 4097])
+@pytest.mark.parametrize("G", [1, 63, 64, 65, 4097, 400011])
 def test_ragged_sizes_and_odd_addresses_raw_abi(rules, rules_golden, G):
     """Batch sizes around the wave's 64 positions; boards and side at a 16-byte aligned, an even and an odd byte address, the
-    records at a 16-byte and at an 8-byte boundary; rows beyond the batch are not touched."""
+    records at a 16-byte and at an 8-byte boundary; rows beyond the batch are not touched.  400 011 positions are 6 251 groups
+    with a last one of 11, on a grid of 3 072 waves: every wave walks two or three groups, the next one prefetched."""
     from cchess_zero_amd._lib import check, lib
     boards, side, recs = CM.golden_reference(rules_golden)
     idx = (np.arange(G) * 37) % len(boards)

@@ -142,14 +142,20 @@ def test_every_combination_of_null_outputs(rules, golden_model):
             assert np.array_equal(pf[:G], flags[:G]) and (pf[G:] == 0x5A).all() if want[3] else (pf == 0x5A).all()
 
 
-@pytest.mark.parametrize("G", [1, 63, 64, 65, 4097])
+@pytest.mark.parametrize("G", [1, 63, 64, 65, 4097, 400011])
 def test_ragged_sizes_and_odd_addresses_raw_abi(rules, golden_model, G):
     """Batch sizes around the wave's 64 positions; boards, side, count, mask and pos_flags at a 16-byte aligned, an even and an ODD
-    byte address (`moves` alone must be aligned); rows beyond the batch are not touched."""
+    byte address (`moves` alone must be aligned); rows beyond the batch are not touched.  400 011 positions (all four outputs and
+    the flags alone, the 16-byte and the byte path of the boards) are 6 251 groups with a last one of 11, on grids of 1 536 and
+    2 560 waves: every wave walks several groups, the next one prefetched."""
     boards, side, lists, counts, masks, flags, _ = golden_model
     idx = (np.arange(G) * 37) % len(counts)
-    for off in (0, 2, 1, 7):
-        for want in ((True, True, True, True), (False, True, True, True), (False, False, False, True)):
+    rows = np.full((len(counts), 128), 0xFFFF, np.uint16)          # a position's list with the ABI's padding behind it
+    for i, l in enumerate(lists):
+        rows[i, :len(l)] = l
+    many = G > 100000
+    for off in (0, 1) if many else (0, 2, 1, 7):
+        for want in ((True, True, True, True), (False, False, False, True)) if many else ((True, True, True, True), (False, True, True, True), (False, False, False, True)):
             mv, cnt, mask, pf = _raw(rules, boards[idx], side[idx], G, want, off=off)
             assert np.array_equal(pf[:G], flags[idx]) and (pf[G:] == 0x5A).all()
             if want[1]:
@@ -157,8 +163,7 @@ def test_ragged_sizes_and_odd_addresses_raw_abi(rules, golden_model, G):
             if want[2]:
                 assert np.array_equal(mask[:G], masks[idx]) and (mask[G:] == 0x5A5A5A5A).all()
             if want[0]:
-                for i in range(G):
-                    assert np.array_equal(mv[i, :counts[idx[i]]], lists[idx[i]]) and (mv[i, counts[idx[i]]:] == 0xFFFF).all(), (off, i)
+                assert np.array_equal(mv[:G], rows[idx]), off
                 assert (mv[G:] == 0x5A5A).all()
 
 

@@ -214,15 +214,61 @@ def test_rules_edge_sizes(rules):
     assert int(_u16(c)[0]) == 44
 
 
-@pytest.mark.parametrize("G", [1, 3, 4, 5, 63, 64, 65, 130, 4097])
+def _list_kernel_many_groups(rules, g, G):
+    """The list kernel on G positions cut from the goldens, whole buffers compared on the device: list + mask, list only, and
+    list + mask with CZ_MOVES_NO_PAD (cz_movegen_ex), the boards at a 16-byte aligned and at an odd address."""
+    from cchess_zero_amd._lib import check, lib
+    from cchess_zero_amd.engine import _ptr
+    n0 = len(g["boards"])
+    idx = (np.arange(G) * 37) % n0
+    valid0 = np.arange(128)[None, :] < g["counts"][:, None]
+    r, c = np.nonzero(valid0)
+    lab = g["moves"][r, c].astype(np.int64)
+    masks0 = np.zeros((n0, 66), np.uint32)
+    np.bitwise_or.at(masks0, (r, lab >> 5), (np.uint32(1) << (lab & 31).astype(np.uint32)))
+    ti = torch.from_numpy(idx).cuda()
+    exp_mv = torch.from_numpy(g["moves"].view(np.int16)).cuda()[ti]
+    exp_ct = torch.from_numpy(g["counts"].astype(np.uint16).view(np.int16)).cuda()[ti]
+    exp_mk = torch.from_numpy(masks0.view(np.int32)).cuda()[ti]
+    col = torch.arange(128, device="cuda")[None, :]
+    cnt = torch.from_numpy(g["counts"].astype(np.int64)).cuda()[ti][:, None]
+    valid, behind = col < cnt, col >= (cnt + 7) // 8 * 8             # a row's labels / behind its last 16-byte piece
+    side = torch.from_numpy(g["side"][idx]).cuda()
+    for off in (0, 1):
+        raw = torch.zeros(G * 90 + 16, dtype=torch.uint8, device="cuda")
+        raw[off:off + G * 90] = torch.from_numpy(g["boards"][idx].reshape(-1)).cuda()
+        boards = raw[off:off + G * 90]
+        for want_mask, no_pad in ((True, 0), (False, 0), (True, 1)):
+            moves = torch.full((G + 2, 128), 0x1234, dtype=torch.int16, device="cuda")
+            count = torch.full((G + 2,), 0x1234, dtype=torch.int16, device="cuda")
+            mask = torch.full((G + 2, 66), 0x55, dtype=torch.int32, device="cuda")
+            rules.ctx.bind_stream()
+            check(lib().cz_movegen_ex(rules.ctx.h, _ptr(boards), _ptr(side), G, _ptr(moves), _ptr(count), _ptr(mask) if want_mask else None,
+                                      no_pad), "cz_movegen_ex")
+            assert torch.equal(count[:G], exp_ct) and bool((count[G:] == 0x1234).all())
+            if no_pad:
+                assert torch.equal(moves[:G][valid], exp_mv[valid]) and bool((moves[:G][behind] == 0x1234).all())
+            else:
+                assert torch.equal(moves[:G], exp_mv)
+            assert bool((moves[G:] == 0x1234).all())
+            if want_mask:
+                assert torch.equal(mask[:G], exp_mk) and bool((mask[G:] == 0x55).all())
+            else:
+                assert bool((mask == 0x55).all())
+
+
+@pytest.mark.parametrize("G", [1, 3, 4, 5, 63, 64, 65, 130, 4097, 400011])
 def test_movegen_ragged_sizes_and_alignment_raw_abi(rules, rules_golden, G):
     """cz_movegen through the raw C-ABI on batch sizes around the kernels' group sizes (4 positions per wave for the list
     kernel, 64 for the mask-only kernel), with the boards at a 16-byte-aligned, an even and an ODD byte address (the ABI promises
     byte alignment only), and the mask at a 16-byte-aligned and a 4-byte-aligned address: list + mask, list only, mask only,
-    count only — against the golden lists; rows beyond the batch are not touched."""
+    count only — against the golden lists; rows beyond the batch are not touched.  400 011 positions are 6 251 groups with a last
+    one of 11, on the list kernel's grids of 2 048 and 2 304 waves: every wave walks two to four groups, the next one prefetched."""
     from cchess_zero_amd._lib import check, lib
     from cchess_zero_amd.engine import _ptr
     g = rules_golden
+    if G > 100000:
+        return _list_kernel_many_groups(rules, g, G)
     idx = (np.arange(G) * 37) % len(g["boards"])
     exp = np.zeros((G, 66), np.uint32)
     for i in range(G):
