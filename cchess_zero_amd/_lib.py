@@ -54,6 +54,7 @@ _SIGS = {
     "cz_threats": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_int, _vp]),
     "cz_repetition_chase": (C.c_int, [C.c_void_p, _vp, _u8p, _vp, C.c_int, _i32p, _i32p, _u8p, C.c_int, C.c_int, _u8p, _i32p, _u8p]),
     "cz_apply_move": (C.c_int, [C.c_void_p, _u8p, _u8p, _u16p, C.c_int, _vp, _u8p, _vp]),
+    "cz_successors": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_int, _u16p, _i32p, C.c_int, _u8p, _u8p, _u8p, _i32p, _u16p]),
     "cz_hash": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_int, _vp]),
     "cz_encode_planes": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_int, _vp, C.c_int, C.c_int, C.c_int]),
     "cz_search_reset": (C.c_int, [C.c_void_p, _u8p, _u8p, _i32p, C.c_int]),

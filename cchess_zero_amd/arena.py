@@ -125,6 +125,30 @@ def random_openings(n, plies, seed, device=None):
     return Openings(np.stack(out_b), out_s, out_r, out_m, np.array(out_k, np.uint64))
 
 
+def exhaustive_openings(plies, device=None):
+    """EVERY distinct position (distinct by Zobrist key, side to move included; the first occurrence in generation order)
+    after `plies` king-safe plies from the start position, on the GPU (movegen_kingsafe -> successors, ply by ply, -> hash).
+    moves holds the line that led to the first occurrence, rebuilt from the successors' parents and labels.  King-safe moves
+    take no king: both kings are on the board by construction.  1 920 openings at 2 plies, under 79 666 at 3."""
+    from .rules import START_BOARD, Rules
+    dev = torch.device("cuda", torch.cuda.current_device() if device is None else int(device))
+    rules = Rules(device=dev.index)
+    boards = torch.from_numpy(START_BOARD[None].copy()).to(dev)
+    side = torch.zeros(1, dtype=torch.uint8, device=dev)
+    rr = torch.zeros(1, dtype=torch.int32, device=dev)
+    lines = torch.zeros((1, 0), dtype=torch.int64, device=dev)
+    for _ in range(int(plies)):
+        mv, cnt, _, _ = rules.movegen_kingsafe(boards, side, want_mask=False, pad=False)
+        boards, side, cap, par, label = rules.successors(boards, side, mv, cnt)
+        par = par.to(torch.int64)
+        rr = torch.where(cap != 0, torch.zeros_like(rr[par]), rr[par] + 1)
+        lines = torch.cat([lines[par], (label.to(torch.int64) & 0xFFFF).unsqueeze(1)], 1)
+    keys = rules.hash(boards, side).cpu().numpy().view(np.uint64)
+    first = np.sort(np.unique(keys, return_index=True)[1])
+    return Openings(boards.cpu().numpy()[first], side.cpu().numpy()[first], rr.cpu().numpy()[first],
+                    [[int(x) for x in l] for l in lines.cpu().numpy()[first]], keys[first])
+
+
 def as_openings(openings):
     if isinstance(openings, Openings):
         return openings
@@ -486,10 +510,13 @@ def main(argv=None):
     ap.add_argument("--a", default=None, help="checkpoint of player A (own .pt, reference TF bundle, .npz); none = fresh weights")
     ap.add_argument("--b", default=None, help="checkpoint of player B; none = fresh weights")
     ap.add_argument("--blocks", type=int, default=7, help="residual blocks of both nets")
-    ap.add_argument("--games", type=int, default=256, help="games (rounded up to an even number: each opening with both colours)")
+    ap.add_argument("--games", type=int, default=None,
+                    help="games (rounded up to an even number: each opening with both colours); default 256, with --all_openings twice their number")
     ap.add_argument("--playout", type=int, default=400, help="playouts per move of A (and of B without --playout_b)")
     ap.add_argument("--playout_b", type=int, default=None, help="playouts per move of B")
     ap.add_argument("--opening_plies", type=int, default=4, help="random plies of the openings")
+    ap.add_argument("--all_openings", action="store_true",
+                    help="every distinct position after --opening_plies king-safe plies (exhaustive_openings) instead of a random sample")
     ap.add_argument("--slots", type=int, default=None, help="concurrent games (default: all)")
     ap.add_argument("--seed", type=int, default=0, help="openings and sampled plies")
     ap.add_argument("--max_plies", type=int, default=512, help="a game reaching it is a draw")
@@ -508,8 +535,15 @@ def main(argv=None):
         ap.error(str(e))
     a = load_player(args.a, args.blocks)
     b = a if args.b == args.a else load_player(args.b, args.blocks)
-    pairs = (args.games + 1) // 2
-    op = random_openings(pairs, args.opening_plies, args.seed)
+    if args.all_openings:
+        op = exhaustive_openings(args.opening_plies)
+        pairs = len(op) if args.games is None else (args.games + 1) // 2
+        if pairs > len(op):
+            ap.error("--all_openings: %d plies give %d openings, --games %d asks for %d" % (args.opening_plies, len(op), args.games, pairs))
+        op = op.subset(np.arange(pairs))
+    else:
+        pairs = ((256 if args.games is None else args.games) + 1) // 2
+        op = random_openings(pairs, args.opening_plies, args.seed)
     res = Match((a, args.playout), (b, args.playout_b or args.playout), op, slots=args.slots or 2 * pairs, max_plies=args.max_plies,
                 sample_plies=args.sample_plies, seed=args.seed, rules=args.rules, repetition=args.repetition, chase=args.chase).play()
     d = res.to_dict()

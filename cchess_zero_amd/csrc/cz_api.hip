@@ -262,6 +262,13 @@ int cz_apply_move(cz_ctx *c, uint8_t *boards, uint8_t *side, const uint16_t *lab
     CZ_REQUIRE(boards && side && label, "cz_apply_move: boards, side, move_label required");
     return czk_apply_move(c, boards, side, label, G, hash, captured, terminal);
 }
+int cz_successors(cz_ctx *c, const uint8_t *boards, const uint8_t *side, int G, const uint16_t *moves, const int32_t *offsets, int total,
+                  uint8_t *out_boards, uint8_t *out_side, uint8_t *out_captured, int32_t *out_parent, uint16_t *out_label) {
+    CZ_REQUIRE(c && G >= 0 && total >= 0, "cz_successors: null ctx / negative G or total");
+    if (G == 0 || total == 0) return CZ_OK;
+    CZ_REQUIRE(boards && side && moves && offsets && out_boards, "cz_successors: boards, side, moves, offsets, out_boards required");
+    return czk_successors(c, boards, side, G, moves, offsets, total, out_boards, out_side, out_captured, out_parent, out_label);
+}
 int cz_hash(cz_ctx *c, const uint8_t *boards, const uint8_t *side, int G, uint64_t *hash) {
     CZ_REQUIRE(c && G >= 0, "cz_hash: null ctx / negative G");
     if (G == 0) return CZ_OK;

@@ -418,6 +418,8 @@ int czk_repetition_chase(cz_ctx *, const uint64_t *, const uint8_t *, const uint
                          uint8_t *);   // cz_repetition.hip
 int czk_apply_move(cz_ctx *, uint8_t *, uint8_t *, const uint16_t *, int, uint64_t *, uint8_t *, int8_t *);
 int czk_hash(cz_ctx *, const uint8_t *, const uint8_t *, int, uint64_t *);
+int czk_successors(cz_ctx *, const uint8_t *, const uint8_t *, int, const uint16_t *, const int32_t *, int, uint8_t *, uint8_t *, uint8_t *, int32_t *,
+                   uint16_t *);   // cz_successors.hip
 int czk_encode_planes(cz_ctx *, const uint8_t *, const uint8_t *, int, void *, int, int, int);
 int czk_search_reset(cz_ctx *, const uint8_t *, const uint8_t *, const int32_t *, int, const uint8_t *which);
 int czk_search_status(cz_ctx *, int32_t *, int32_t *, int32_t *, int32_t *);

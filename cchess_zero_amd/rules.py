@@ -198,6 +198,114 @@ class Rules:
         check(lib().cz_apply_move(self.ctx.h, _ptr(boards), _ptr(side), _ptr(labels), G, _ptr(hash_), _ptr(cap), _ptr(term)), "cz_apply_move")
         return cap, term
 
+    def successors(self, boards, side, moves, count):
+        """Every successor of G positions (cz_successors): moves [G,128] i16 and count [G] i16 as movegen / movegen_kingsafe
+        return them (padded or not; count -1, a refused board, has no children) -> (boards [T,90] u8, side [T] u8, captured
+        [T] u8, parent [T] i32, label [T] i16), T the sum of the counts: child offsets[g] + j is parent g after moves[g][j], in
+        list order.  Reading T back is the call's only synchronisation."""
+        self.ctx.bind_stream()   # torch's current stream
+        boards = self._dev(boards, torch.uint8).reshape(-1, NSQ)
+        side = self._dev(side, torch.uint8)
+        G = boards.shape[0]
+        moves = self._dev(moves, torch.int16).reshape(G, MAXMOVES)
+        offsets = torch.zeros(G + 1, dtype=torch.int64, device=self.dev)
+        torch.cumsum(self._dev(count, torch.int16).reshape(G).clamp(min=0), 0, out=offsets[1:])
+        T = int(offsets[-1].item())
+        if T >= 2 ** 31:
+            raise ValueError("Rules.successors: %d children do not fit one call (offsets are int32): pass fewer parents" % T)
+        offsets = offsets.to(torch.int32)
+        out = torch.empty((T, NSQ), dtype=torch.uint8, device=self.dev)
+        cside = torch.empty(T, dtype=torch.uint8, device=self.dev)
+        cap = torch.empty(T, dtype=torch.uint8, device=self.dev)
+        parent = torch.empty(T, dtype=torch.int32, device=self.dev)
+        label = torch.empty(T, dtype=torch.int16, device=self.dev)
+        check(lib().cz_successors(self.ctx.h, _ptr(boards), _ptr(side), G, _ptr(moves), _ptr(offsets), T, _ptr(out), _ptr(cside), _ptr(cap),
+                                  _ptr(parent), _ptr(label)), "cz_successors")
+        return out, cside, cap, parent, label
+
+    PERFT_CHUNK = 1 << 17
+
+    def perft(self, boards, side, depth, stats=False, chunk=None):
+        """Perft under Xiangqi rules (king-safe moves, movegen_kingsafe) of N root positions, all in one pass -> a dict of int64
+        numpy arrays [N, depth + 1], column d the tally over the move sequences of length d: `nodes` their number, and with
+        stats=True `captures` (sequences whose last move takes a piece), `checks` (positions with POS_IN_CHECK) and `mates`
+        (POS_NO_SAFE_MOVE).  Column 0 is the root itself.  A root movegen refuses raises CchessHipError.
+        The tree is walked depth first in slices of at most `chunk` parents (default PERFT_CHUNK = 131 072: 2 048 groups, eight
+        waves on every CU); a slice's lists and children live until its subtree is done, so the peak is bounded by
+        depth x chunk x (256 + 128 x 106) bytes — 128 children of 90 + 16 bytes per parent, 1.8 GB per level at the default,
+        never reached: ~40 children per parent make it ~0.6 GB — not by the tree (133 M positions, 12 GB, at depth 5).
+        Without stats the last ply is counted, not made: the count-only form of movegen_kingsafe on the frontier of depth - 1."""
+        from ._lib import POS_IN_CHECK, POS_NO_SAFE_MOVE
+        boards = self._dev(boards, torch.uint8).reshape(-1, NSQ)
+        side = self._dev(side, torch.uint8).reshape(-1)
+        N, depth, chunk = boards.shape[0], int(depth), int(chunk or self.PERFT_CHUNK)
+        if depth < 0 or chunk < 1:
+            raise ValueError("Rules.perft: depth >= 0 and chunk >= 1")
+        names = ("nodes", "captures", "checks", "mates") if stats else ("nodes",)
+        tally = {k: torch.zeros((N, depth + 1), dtype=torch.int64, device=self.dev) for k in names}
+        tally["nodes"][:, 0] = 1
+
+        def add(name, d, root, w):   # tally[name][root, d] += w, position by position
+            if N == 1:
+                tally[name][0, d] += w.sum(dtype=torch.int64)
+            else:
+                tally[name][:, d] += torch.bincount(root, weights=w.to(torch.float64), minlength=N).to(torch.int64)   # exact below 2^53
+
+        def flags_of(d, root, pf):
+            add("checks", d, root, pf & POS_IN_CHECK != 0)
+            add("mates", d, root, pf & POS_NO_SAFE_MOVE != 0)
+
+        def walk(b, s, root, d):   # the positions of depth d < depth, a root index each
+            for lo in range(0, b.shape[0], chunk):
+                bb, ss, rr = b[lo:lo + chunk], s[lo:lo + chunk], root[lo:lo + chunk]
+                if d == depth - 1 and not stats:
+                    _, cnt, _, _ = self.movegen_kingsafe(bb, ss, want_mask=False, want_moves=False)
+                    if d == 0:
+                        self.check_counts(cnt)
+                    add("nodes", d + 1, rr, cnt.clamp(min=0))
+                    continue
+                mv, cnt, _, pf = self.movegen_kingsafe(bb, ss, want_mask=False, pad=False)
+                if d == 0:
+                    self.check_counts(cnt)
+                if stats:
+                    flags_of(d, rr, pf)
+                cb, cs, cap, par, _ = self.successors(bb, ss, mv, cnt)
+                del mv
+                cr = rr[par.to(torch.int64)]
+                add("nodes", d + 1, cr, torch.ones_like(cr))
+                if stats:
+                    add("captures", d + 1, cr, cap != 0)
+                del cap, par
+                if d + 1 < depth:
+                    walk(cb, cs, cr, d + 1)
+                elif stats and cb.shape[0]:
+                    flags_of(depth, cr, self.in_check(cb, cs))
+
+        root = torch.arange(N, dtype=torch.int64, device=self.dev)
+        if depth == 0:
+            _, cnt, _, pf = self.movegen_kingsafe(boards, side, want_mask=False, want_moves=False)
+            self.check_counts(cnt)
+            if stats:
+                flags_of(0, root, pf)
+        elif N:
+            walk(boards, side, root, 0)
+        return {k: v.cpu().numpy() for k, v in tally.items()}
+
+    def divide(self, board, side, depth):
+        """Perft of ONE position split by its first move -> {ICCS label: the move sequences of length `depth` that start with
+        it}, in list order: perft(depth - 1) over the root's successors, one pass."""
+        from ._lib import tables
+        if int(depth) < 1:
+            raise ValueError("Rules.divide: depth >= 1")
+        board = self._dev(board, torch.uint8).reshape(1, NSQ)
+        side = self._dev(side, torch.uint8).reshape(1)
+        mv, cnt, _, _ = self.movegen_kingsafe(board, side, want_mask=False, pad=False)
+        self.check_counts(cnt)
+        cb, cs, _, _, label = self.successors(board, side, mv, cnt)
+        nodes = self.perft(cb, cs, int(depth) - 1)["nodes"][:, -1] if cb.shape[0] else []
+        names = tables()["labels"]
+        return {names[int(l)]: int(n) for l, n in zip(label.cpu().numpy().view(np.uint16), nodes)}
+
     def hash(self, boards, side):
         self.ctx.bind_stream()   # torch's current stream
         boards = self._dev(boards, torch.uint8).reshape(-1, NSQ)

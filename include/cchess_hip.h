@@ -213,6 +213,22 @@ int cz_repetition_chase(cz_ctx *, const uint64_t *keys, const uint8_t *in_check,
 int cz_apply_move(cz_ctx *, uint8_t *boards, uint8_t *side, const uint16_t *move_label, int G,
                   uint64_t *hash, uint8_t *captured, int8_t *terminal);
 int cz_hash(cz_ctx *, const uint8_t *boards, const uint8_t *side, int G, uint64_t *hash);
+/* K2s SUCCESSORS: every position one move away from G positions.  No reference function (the reference plays one move per
+ *     game, sim_do_action, main.py:647-702); the move is made as cz_apply_move makes it.
+ *     moves [G][128]: a move list as cz_movegen / cz_movegen_ex / cz_movegen_kingsafe write it, padded or CZ_MOVES_NO_PAD; the
+ *     kernel generates no move itself, so pseudo-legal and king-safe lists serve alike.  offsets int32 [G + 1]: the exclusive
+ *     prefix sum of the per-position counts, offsets[G] == total — the only source of how many children a parent has: parent
+ *     g has offsets[g + 1] - offsets[g] of them, 0 .. 128 (the caller gives a board with count 0xFFFF none).
+ *     Child offsets[g] + j is parent g after moves[g][j], in list order: the output is a pure function of the input (no
+ *     atomics).  Per child: out_boards [total][90]; out_side = 1 - the parent's side; out_captured = the piece code taken or
+ *     0, as cz_apply_move reports it; out_parent int32 = g; out_label = the move.  Every output but out_boards may be NULL.  A
+ *     label >= 2086 in the list leaves the child the parent's board (captured 0).
+ *     Alignment: out_boards must be 16-byte aligned (the children leave as 16-byte stores; CZ_EINVAL otherwise); everything
+ *     else may sit at any address its element type allows.  G == 0 or total == 0: CZ_OK, no launch.  Offsets outside
+ *     [0, total] are clamped: no access leaves the arrays whatever they hold. */
+int cz_successors(cz_ctx *, const uint8_t *boards, const uint8_t *side, int G, const uint16_t *moves /* [G][128] */,
+                  const int32_t *offsets /* [G + 1] */, int total, uint8_t *out_boards /* [total][90] */, uint8_t *out_side,
+                  uint8_t *out_captured, int32_t *out_parent, uint16_t *out_label);
 /* K3  replaces MCTS_tree.generate_inputs = try_flip + state_to_positions, main.py:531-574.
  *     planes [G][9][10][channels] of dtype CZ_F32 / CZ_BF16.  quirk_q1 = 1 reproduces the
  *     reference bit for bit; 0 gives the transposed encoding its shapes suggest. */

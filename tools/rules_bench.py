@@ -7,7 +7,9 @@ usage: python tools/rules_bench.py [N positions, default 1048576]
            rules.random_positions against (a) the pseudo-legal kernels on the same positions and (b) the same answer composed from
            cz_movegen + cz_apply_move + cz_movegen + torch; one JSON line at the end
        python tools/rules_bench.py --threats [N]      the threat kernel of the chase rule (cz_threats) beside the king-safe
-           generator's flags-only and list forms on the same N positions, in the same run; one JSON line at the end"""
+           generator's flags-only and list forms on the same N positions, in the same run; one JSON line at the end
+       python tools/rules_bench.py --successors [N]   cz_successors on the first N positions of the start position's depth-4
+           frontier (3 290 240 positions) with their king-safe lists: time and achieved store bandwidth; one JSON line at the end"""
 import os
 import sys
 import time
@@ -22,7 +24,8 @@ from cchess_zero_amd.rules import Rules  # noqa: E402
 
 KINGSAFE = "--kingsafe" in sys.argv
 THREATS = "--threats" in sys.argv
-_args = [a for a in sys.argv[1:] if a not in ("--kingsafe", "--threats")]
+SUCCESSORS = "--successors" in sys.argv
+_args = [a for a in sys.argv[1:] if a not in ("--kingsafe", "--threats", "--successors")]
 N = int(_args[0]) if _args else 1 << 20
 ctx = Context(1, 2, 0)
 rules = Rules(ctx)
@@ -141,6 +144,53 @@ def threats_leg():
     print(json.dumps(out), flush=True)
 
 
+def successors_leg():
+    """Median of 25 launches (device events, 3 warm-up launches) of the bare C call into buffers allocated once: all five outputs,
+    and the boards alone.  The lists, the offsets and their sum are made before the clock starts."""
+    import json
+    from cchess_zero_amd._lib import check, lib
+    from cchess_zero_amd.engine import _ptr
+    from cchess_zero_amd.rules import START_BOARD
+    boards, side = torch.from_numpy(START_BOARD[None].copy()).cuda(), torch.zeros(1, dtype=torch.uint8, device="cuda")
+    for _ in range(4):
+        mv, cnt, _, _ = rules.movegen_kingsafe(boards, side, want_mask=False, pad=False)
+        boards, side = rules.successors(boards, side, mv, cnt)[:2]
+    boards, side = boards[:N].contiguous(), side[:N].contiguous()
+    n = boards.shape[0]
+    mv, cnt, _, _ = rules.movegen_kingsafe(boards, side, want_mask=False, pad=False)
+    offsets = torch.zeros(n + 1, dtype=torch.int64, device="cuda")
+    offsets[1:] = torch.cumsum(cnt.to(torch.int64), 0)
+    T = int(offsets[-1].item())
+    offsets = offsets.to(torch.int32)
+    ob = torch.empty((T, 90), dtype=torch.uint8, device="cuda")
+    o1, o2 = torch.empty(T, dtype=torch.uint8, device="cuda"), torch.empty(T, dtype=torch.uint8, device="cuda")
+    o4, o5 = torch.empty(T, dtype=torch.int32, device="cuda"), torch.empty(T, dtype=torch.int16, device="cuda")
+    ctx.bind_stream()
+    out = {"parents": n, "children": T}
+    for name, rest, width in (("all_outputs", (o1, o2, o4, o5), 98), ("boards_only", (None,) * 4, 90)):
+        fn = lambda: check(lib().cz_successors(ctx.h, _ptr(boards), _ptr(side), n, _ptr(mv), _ptr(offsets), T, _ptr(ob), *[_ptr(x) for x in rest]))
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize()
+        ts = []
+        for _ in range(25):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            ts.append(e0.elapsed_time(e1))
+        ts.sort()
+        out[name] = dict(ms=round(ts[12], 4), min_ms=round(ts[0], 4), max_ms=round(ts[-1], 4), children_per_s=round(T / ts[12] * 1e3),
+                         store_TB_per_s=round(T * width / ts[12] / 1e9, 3))
+        print("%-12s: median %.3f ms (min %.3f, max %.3f) for %d parents, %d children = %.2f G children/s, %.2f TB/s of stores"
+              % (name, ts[12], ts[0], ts[-1], n, T, T / ts[12] / 1e6, T * width / ts[12] / 1e9))
+    print(json.dumps(out), flush=True)
+
+
+if SUCCESSORS:
+    successors_leg()
+    sys.exit(0)
 if KINGSAFE:
     kingsafe_leg()
     sys.exit(0)
