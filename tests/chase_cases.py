@@ -3,6 +3,7 @@ sets and the four-move chase line, shared by the CPU and the GPU tests."""
 import numpy as np
 
 import chase_model as CM
+import fakenet
 from oracle import oracle as O
 
 CODE = {c: i + 1 for i, c in enumerate("KARBNPC")}
@@ -42,6 +43,7 @@ TABLE = [
 CHASE_BOARD = board(["Ra5", "cb6"])
 CHASE_LINE = ["a5a6", "b6b5", "a6a5", "b5b6"] * 2
 CHASE_THREATS = [[], [55], [], [46]] * 2 + [[]]
+CHASE_PLAYOUTS = 30          # of a search that steering_forward leads along the line
 
 
 def label_of(move, lut=None):
@@ -90,3 +92,31 @@ def synthetic_cycle(threat_even, threat_odd, check_even=0, check_odd=0, plies=8)
         chk.append(check_odd if odd else check_even)
         recs.append([t & CM.MASK64, t >> 64, own & CM.MASK64, own >> 64])
     return keys, chk, recs
+
+
+def steering_forward():
+    """A numpy forward on planes [B, 9, 10, 14] that makes a search play CHASE_LINE.  The reference's root never counts its
+    own visits, so at the root U = 0 and the choice among the root children is by Q alone: a policy cannot steer it, the values
+    do.  Value 0 on the four positions of the line (keyed by fakenet.position_key of their planes), +0.9 for the side to move
+    everywhere else: whoever leaves the line hands the other side a good position, so the line's move is every root's only child
+    with Q >= 0 and takes the visits left once each child has been tried.  Logits all 1."""
+    boards, sides, _ = play_line(CHASE_BOARD, 0, CHASE_LINE[:4])
+    keys = np.array([fakenet.position_key(O.encode_planes(boards[i], int(sides[i]))[None])[0] for i in range(4)], np.uint64)
+
+    def forward(planes):
+        planes = np.asarray(planes, np.float32)
+        if planes.ndim == 3:
+            planes = planes[None]
+        hit = np.isin(fakenet.position_key(planes), keys)
+        return np.ones((planes.shape[0], 2086), np.float32), np.where(hit, np.float32(0.0), np.float32(0.9)).astype(np.float32).reshape(-1, 1)
+    return forward
+
+
+def steering_device_forward():
+    import torch
+    f = steering_forward()
+
+    def forward(planes):
+        lg, v = f(planes.float().cpu().numpy())
+        return torch.from_numpy(lg).to(planes.device), torch.from_numpy(v).to(planes.device)
+    return forward

@@ -1,5 +1,5 @@
 """Evaluation matches with the perpetual-chase rule (cz_match_set_chase: on a repeated position, a side that alone chased one
-piece with every move of the cycle loses) against tests/match_chase_model.py, the third ring (cz_match_chase_history) against
+piece with every move of the cycle loses) against tests/match_model.py at the chase level, the third ring (cz_match_chase_history) against
 Rules.threats, chase=False against the match as it was, and the setter's refusals."""
 import ctypes as C
 import functools
@@ -9,8 +9,7 @@ import pytest
 import torch
 
 import chase_cases as CC
-import match_chase_model as MCM
-import repetition_cases as RC
+import match_model as MM
 from test_match_gpu import _fake_players, _one_opening
 
 pytestmark = pytest.mark.gpu
@@ -18,53 +17,38 @@ KEYS = ("result", "a_red", "plies", "reason")
 
 
 @functools.lru_cache(maxsize=None)
-def _openings():
-    from cchess_zero_amd.arena import Openings
-    boards, side = RC.cpu_openings(8, 4, 11)
-    return Openings(boards, side)
-
-
-@functools.lru_cache(maxsize=None)
 def _play(sample_plies, slots, chase):
     """One match per (sample_plies, slots, chase), shared by the tests below; read-only."""
     from cchess_zero_amd.arena import Match
     extra = dict(chase=True) if chase else {}
-    return Match(*_fake_players(), _openings(), slots=slots, max_plies=160, sample_plies=sample_plies, seed=5, nodes_per_tree=1 << 15,
-                 rules="xiangqi", repetition=3, **extra).play()
-
-
-def _moves(want):
-    from cchess_zero_amd._lib import tables
-    lab = tables()["labels"]
-    return [[lab[int(x)] for x in row if x != 0xFFFF] for row in want["moves"]]
+    return Match(*_fake_players(), MM.fakenet_openings(), slots=slots, max_plies=160, sample_plies=sample_plies, seed=5,
+                 nodes_per_tree=1 << 15, rules="xiangqi", repetition=3, **extra).play()
 
 
 # ---- 1. the model's replay -------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("slots", [16, 6])        # 6 slots: the queue re-seeds slots as games end, the rings are not reset
 @pytest.mark.parametrize("sample_plies", [0, 6])
 def test_chase_match_equals_the_models_replay(sample_plies, slots):
-    want = MCM.fakenet_match(sample_plies)
+    want = MM.fakenet_match(sample_plies)
     print("model: reasons", want["reason"].tolist(), "plies", want["plies"].tolist())
-    assert int((want["reason"] == MCM.CHASE).sum()) >= 5 and int((want["reason"] == MCM.REPETITION).sum()) >= 4
+    assert int((want["reason"] == MM.CHASE).sum()) >= 5 and int((want["reason"] == MM.REPETITION).sum()) >= 4
     res = _play(sample_plies, slots, True)
-    for k in KEYS:
-        assert np.array_equal(getattr(res, k), want[k]), (k, getattr(res, k), want[k])
-    assert res.moves == _moves(want)
-    assert res.unfinished == 0 and res.aborted == 0
+    MM.assert_equals_model(res, want, (sample_plies, slots))
+    assert res.aborted == 0
     d = res.to_dict()
     assert res.chase is True and d["chase"] is True
-    assert res.chases == int((want["reason"] == MCM.CHASE).sum()) == d["chases"] == d["reasons"]["chase"]
-    assert res.repetitions == int((want["reason"] == MCM.REPETITION).sum()) and res.perpetuals == int((want["reason"] == MCM.PERPETUAL).sum())
-    lost_by_a = (want["reason"] == MCM.CHASE) & (want["result"] == -1)
+    assert res.chases == int((want["reason"] == MM.CHASE).sum()) == d["chases"] == d["reasons"]["chase"]
+    assert res.repetitions == int((want["reason"] == MM.REPETITION).sum()) and res.perpetuals == int((want["reason"] == MM.PERPETUAL).sum())
+    lost_by_a = (want["reason"] == MM.CHASE) & (want["result"] == -1)
     assert res.scored == 16 and res.losses >= int(lost_by_a.sum())
 
 
 @pytest.mark.parametrize("sample_plies", [0, 6])
 def test_against_the_same_match_without_the_rule_only_the_chase_games_differ(sample_plies):
     on, off = _play(sample_plies, 16, True), _play(sample_plies, 16, False)
-    chase = on.reason == MCM.CHASE
+    chase = on.reason == MM.CHASE
     assert chase.sum() >= 5 and off.chase is False and off.chases == 0
-    assert (off.reason[chase] == MCM.REPETITION).all() and (off.result[chase] == 0).all()
+    assert (off.reason[chase] == MM.REPETITION).all() and (off.result[chase] == 0).all()
     assert np.array_equal(on.plies, off.plies) and np.array_equal(on.a_red, off.a_red) and on.moves == off.moves
     assert np.array_equal(on.reason[~chase], off.reason[~chase]) and np.array_equal(on.result[~chase], off.result[~chase])
 
@@ -72,22 +56,23 @@ def test_against_the_same_match_without_the_rule_only_the_chase_games_differ(sam
 # ---- 2. the constructed chase ------------------------------------------------------------------------------------------------
 def test_the_constructed_chase_is_lost_by_red_in_both_colour_assignments():
     from cchess_zero_amd.arena import Match
-    f = (MCM.steering_device_forward(), MCM.CHASE_PLAYOUTS)
+    f = (CC.steering_device_forward(), CC.CHASE_PLAYOUTS)
     op = _one_opening(CC.CHASE_BOARD, 0)
     res = Match(f, f, op, slots=2, max_plies=64, rules="xiangqi", repetition=3, chase=True).play()
-    assert res.reason.tolist() == [MCM.CHASE, MCM.CHASE] and res.plies.tolist() == [8, 8]
+    assert res.reason.tolist() == [MM.CHASE, MM.CHASE] and res.plies.tolist() == [8, 8]
     assert res.result.tolist() == [-1, 1]            # red chases: game 0 has A red, game 1 B red
     assert res.moves == [CC.CHASE_LINE] * 2
     assert (res.chases, res.perpetuals, res.repetitions, res.scored, res.losses, res.wins, res.score) == (2, 0, 0, 2, 1, 1, 0.5)
     res = Match(f, f, op, slots=2, max_plies=64, rules="xiangqi", repetition=3).play()       # without the rule: a draw
-    assert res.reason.tolist() == [MCM.REPETITION] * 2 and res.result.tolist() == [0, 0] and res.moves == [CC.CHASE_LINE] * 2
+    assert res.reason.tolist() == [MM.REPETITION] * 2 and res.result.tolist() == [0, 0] and res.moves == [CC.CHASE_LINE] * 2
 
 
 # ---- 3. the ring -------------------------------------------------------------------------------------------------------------
 def test_the_third_ring_holds_the_threats_of_every_root_position():
     from cchess_zero_amd.arena import Match
     from cchess_zero_amd.rules import Rules
-    m = Match(*_fake_players(), _openings(), slots=16, max_plies=160, seed=5, nodes_per_tree=1 << 15, rules="xiangqi", repetition=3, chase=True)
+    m = Match(*_fake_players(), MM.fakenet_openings(), slots=16, max_plies=160, seed=5, nodes_per_tree=1 << 15, rules="xiangqi",
+              repetition=3, chase=True)
     m.start()
     rules = Rules()
     nonempty = 0
@@ -119,7 +104,7 @@ def test_chase_false_is_the_repetition_match_as_it_was():
     kw = dict(slots=6, max_plies=60, sample_plies=6, seed=5, nodes_per_tree=1 << 15, rules="xiangqi", repetition=3)
     rows = []
     for extra in ({}, dict(chase=False)):
-        m = Match(*_fake_players(), _openings(), **kw, **extra)
+        m = Match(*_fake_players(), MM.fakenet_openings(), **kw, **extra)
         m.start()
         fin = 0
         while fin < m.n_games:
@@ -132,7 +117,7 @@ def test_chase_false_is_the_repetition_match_as_it_was():
         m.close()
     for k in KEYS + ("moves",):        # per game; which slot a queued game runs in is not fixed, so the rings are not compared
         assert rows[0][k].tobytes() == rows[1][k].tobytes(), k
-    assert not (rows[0]["reason"] == MCM.CHASE).any() and (rows[0]["reason"] == MCM.REPETITION).any()
+    assert not (rows[0]["reason"] == MM.CHASE).any() and (rows[0]["reason"] == MM.REPETITION).any()
 
 
 # ---- 5. the switch -----------------------------------------------------------------------------------------------------------

@@ -31,10 +31,6 @@ def openings8():
     return random_openings(8, 4, seed=11)
 
 
-def _arrays(res):
-    return dict(result=res.result, a_red=res.a_red, plies=res.plies, reason=res.reason)
-
-
 # ---- 1. oracle replay ------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("sample_plies", [0, 6])
 def test_match_equals_oracle_replay(openings8, sample_plies):
@@ -43,13 +39,8 @@ def test_match_equals_oracle_replay(openings8, sample_plies):
     for slots in (16, 6):   # 6 slots: the queue re-seeds slots as games end
         m = Match(*_fake_players(), openings8, slots=slots, max_plies=160, sample_plies=sample_plies, seed=5, nodes_per_tree=1 << 15)
         res = m.play()
-        got = _arrays(res)
-        for k in ("a_red", "plies", "reason", "result"):
-            assert np.array_equal(got[k], want[k]), (slots, k, got[k], want[k])
-        lab = __import__("cchess_zero_amd._lib", fromlist=["tables"]).tables()["labels"]
-        for g in range(16):
-            assert res.moves[g] == [lab[int(x)] for x in want["moves"][g] if x != 0xFFFF], (slots, g)
-        assert res.unfinished == 0 and res.simulations > 0 and res.sims_per_s > 0
+        MM.assert_equals_model(res, want, slots)
+        assert res.simulations > 0 and res.sims_per_s > 0
 
 
 # ---- 2. a real net against itself ----------------------------------------------------------------------------------------

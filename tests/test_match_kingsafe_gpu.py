@@ -1,10 +1,9 @@
 """Evaluation matches under rules="xiangqi" (cz_match_set_rules(1): the move is chosen among the king-safe root children, a
-mover without one is mated) against tests/match_kingsafe_model.py, and rules="capture" against the match as it was."""
+mover without one is mated) against tests/match_model.py at the king-safe level, and rules="capture" against the match as it was."""
 import numpy as np
 import pytest
 
 import kingsafe_model as KM
-import match_kingsafe_model as XM
 import match_model as MM
 from test_match_gpu import _const_forward, _fake_players, _host_players, _one_opening
 
@@ -24,21 +23,16 @@ def _board(rows):
 
 @pytest.mark.parametrize("sample_plies", [0, 6])
 def test_xiangqi_match_equals_the_models_replay(openings8, sample_plies):
-    from cchess_zero_amd._lib import tables
     from cchess_zero_amd.arena import Match
-    want = XM.play_match(_host_players(), openings8, max_plies=160, sample_plies=sample_plies, seed=5)
-    lab = tables()["labels"]
+    want = MM.play_match(_host_players(), openings8, max_plies=160, sample_plies=sample_plies, seed=5, rules="xiangqi")
     for slots in (16, 6):   # 6 slots: the queue re-seeds slots as games end
         res = Match(*_fake_players(), openings8, slots=slots, max_plies=160, sample_plies=sample_plies, seed=5, nodes_per_tree=1 << 15,
                     rules="xiangqi").play()
-        for k in ("a_red", "plies", "reason", "result"):
-            assert np.array_equal(getattr(res, k), want[k]), (slots, k, getattr(res, k), want[k])
-        for g in range(16):
-            assert res.moves[g] == [lab[int(x)] for x in want["moves"][g] if x != 0xFFFF], (slots, g)
-        assert res.unfinished == 0 and res.aborted == 0
+        MM.assert_equals_model(res, want, slots)
+        assert res.aborted == 0
         # a legal opening and king-safe moves only: no king is ever taken
         assert not (res.reason == MM.KING).any()
-        assert res.rules == "xiangqi" and res.mates == int((want["reason"] == XM.MATE).sum()) == res.to_dict()["mates"]
+        assert res.rules == "xiangqi" and res.mates == int((want["reason"] == MM.MATE).sum()) == res.to_dict()["mates"]
         assert res.to_dict()["rules"] == "xiangqi" and res.to_dict()["reasons"]["mate"] == res.mates
 
 
@@ -51,7 +45,7 @@ def test_a_mated_root_loses_at_ply_0_in_both_colour_assignments():
     assert len(O.legal_moves(b, 0)) == 3 and KM.kingsafe(b, 0)[1] == KM.IN_CHECK | KM.NO_SAFE_MOVE
     f = (_const_forward(0.0), 6)
     res = Match(f, f, _one_opening(b, 0), slots=2, max_plies=8, rules="xiangqi").play()
-    assert res.reason.tolist() == [XM.MATE, XM.MATE] and res.plies.tolist() == [0, 0]
+    assert res.reason.tolist() == [MM.MATE, MM.MATE] and res.plies.tolist() == [0, 0]
     assert res.result.tolist() == [-1, 1]            # game 0: A is red and mated; game 1: B is red and mated
     assert res.moves == [[], []] and res.mates == 2 and res.scored == 2 and res.aborted == 0 and res.score == 0.5
     # under king-capture rules the same root is played on: red moves, and black takes the king
@@ -82,7 +76,7 @@ def test_the_most_visited_child_is_not_played_when_it_is_unsafe():
         vis, lab = N[mover]["N"][g, :n], N[mover]["label"][g, :n]
         top = int(np.argmax(vis))
         assert int(lab[top]) == unsafe and (vis[top] > np.delete(vis, top)).all()       # not vacuous: the unsafe child leads
-        want = int(lab[XM.choose(b, 0, lab, vis, 9, 0, 0, g)])
+        want = int(lab[MM.choose_safe(b, 0, lab, vis, 9, 0, 0, g)])
         assert int(played[g]) == want and want in safe and want != unsafe
         best_safe = max(int(v) for v, l in zip(vis, lab) if int(l) in safe)
         assert int(vis[list(lab).index(want)]) == best_safe

@@ -1,70 +1,48 @@
 """Evaluation matches with the repetition rule (cz_match_set_repetition: a fold-th occurrence of a position ends the game, a
-draw or a loss for the side that checked perpetually) against tests/match_repetition_model.py, the ring of positions
+draw or a loss for the side that checked perpetually) against tests/match_model.py at the repetition level, the ring of positions
 (cz_match_history) against the rules kernels, and repetition=0 against the match as it was."""
 import ctypes as C
-import functools
 
 import numpy as np
 import pytest
 import torch
 
-import match_kingsafe_model as XM
-import match_repetition_model as RMM
+import match_model as MM
 import repetition_cases as RC
-from test_match_gpu import _fake_players, _host_players, _one_opening
+from test_match_gpu import _fake_players, _one_opening
 
 pytestmark = pytest.mark.gpu
 
 
-@functools.lru_cache(maxsize=None)
-def _openings():
-    from cchess_zero_amd.arena import Openings
-    boards, side = RC.cpu_openings(8, 4, 11)
-    return Openings(boards, side)
-
-
-@functools.lru_cache(maxsize=None)
-def _model(sample_plies, fold):
-    """The CPU replay of the 16-game match, once per (sample_plies, fold); fold 0: the match without the rule."""
-    if fold == 0:
-        return XM.play_match(_host_players(), _openings(), max_plies=160, sample_plies=sample_plies, seed=5)
-    return RMM.play_match(_host_players(), _openings(), max_plies=160, sample_plies=sample_plies, seed=5, fold=fold)
-
-
 def _play(sample_plies, slots, fold):
     from cchess_zero_amd.arena import Match
-    return Match(*_fake_players(), _openings(), slots=slots, max_plies=160, sample_plies=sample_plies, seed=5, nodes_per_tree=1 << 15,
-                 rules="xiangqi", repetition=fold).play()
+    return Match(*_fake_players(), MM.fakenet_openings(), slots=slots, max_plies=160, sample_plies=sample_plies, seed=5,
+                 nodes_per_tree=1 << 15, rules="xiangqi", repetition=fold).play()
 
 
 def _assert_equals_model(res, want, tag):
-    from cchess_zero_amd._lib import tables
-    lab = tables()["labels"]
-    for k in ("a_red", "plies", "reason", "result"):
-        assert np.array_equal(getattr(res, k), want[k]), (tag, k, getattr(res, k), want[k])
-    for g in range(16):
-        assert res.moves[g] == [lab[int(x)] for x in want["moves"][g] if x != 0xFFFF], (tag, g)
-    assert res.unfinished == 0 and res.aborted == 0
+    MM.assert_equals_model(res, want, tag)
+    assert res.aborted == 0
 
 
 # ---- 1. the model's replay ---------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("slots", [16, 6])        # 6 slots: the queue re-seeds slots as games end, the rings are not reset
 @pytest.mark.parametrize("sample_plies", [0, 6])
 def test_repetition_match_equals_the_models_replay(sample_plies, slots):
-    want = _model(sample_plies, 3)
+    want = MM.fakenet_match(sample_plies, fold=3, chase=False)
     print("model: reasons", np.bincount(want["reason"], minlength=8).tolist(), "plies", want["plies"].tolist())
-    assert int((want["reason"] == RMM.REPETITION).sum()) >= 12          # the rule decides most games: the comparison is not vacuous
-    assert int((want["reason"] != RMM.REPETITION).sum()) >= 1           # and the ply cap or a mate ends the others
+    assert int((want["reason"] == MM.REPETITION).sum()) >= 12          # the rule decides most games: the comparison is not vacuous
+    assert int((want["reason"] != MM.REPETITION).sum()) >= 1           # and the ply cap or a mate ends the others
     res = _play(sample_plies, slots, 3)
     _assert_equals_model(res, want, (sample_plies, slots))
     d = res.to_dict()
-    assert res.repetition == 3 and res.repetitions == int((want["reason"] == RMM.REPETITION).sum()) == d["reasons"]["repetition"]
-    assert res.perpetuals == int((want["reason"] == RMM.PERPETUAL).sum()) == d["perpetuals"] and d["repetition"] == 3
+    assert res.repetition == 3 and res.repetitions == int((want["reason"] == MM.REPETITION).sum()) == d["reasons"]["repetition"]
+    assert res.perpetuals == int((want["reason"] == MM.PERPETUAL).sum()) == d["perpetuals"] and d["repetition"] == 3
 
 
 def test_twofold_repetition_ends_every_repeating_game_earlier():
-    want2, want3 = _model(0, 2), _model(0, 3)
-    rep2 = want2["reason"] == RMM.REPETITION
+    want2, want3 = MM.fakenet_match(0, fold=2, chase=False), MM.fakenet_match(0, fold=3, chase=False)
+    rep2 = want2["reason"] == MM.REPETITION
     assert int(rep2.sum()) >= 12 and (want2["plies"][rep2] < want3["plies"][rep2]).all()
     _assert_equals_model(_play(0, 6, 2), want2, "fold 2")
 
@@ -75,13 +53,13 @@ def test_perpetual_check_loses_in_both_colour_assignments():
     f = (RC.steering_device_forward(), RC.PERPETUAL_PLAYOUTS)
     op = _one_opening(RC.perpetual_board(), 0)
     res = Match(f, f, op, slots=2, max_plies=64, rules="xiangqi", repetition=3).play()
-    assert res.reason.tolist() == [RMM.PERPETUAL, RMM.PERPETUAL] and res.plies.tolist() == [8, 8]
+    assert res.reason.tolist() == [MM.PERPETUAL, MM.PERPETUAL] and res.plies.tolist() == [8, 8]
     assert res.result.tolist() == [-1, 1]            # red checks with every move: game 0 has A red, game 1 B red
     assert res.moves == [RC.PERPETUAL_LINE * 2] * 2
     assert (res.perpetuals, res.repetitions, res.scored, res.losses, res.wins, res.score) == (2, 0, 2, 1, 1, 0.5)
     # without the rule the same players walk the loop on
     res = Match(f, f, op, slots=2, max_plies=24, rules="xiangqi").play()
-    assert not np.isin(res.reason, (RMM.REPETITION, RMM.PERPETUAL)).any() and (res.plies > 8).all()
+    assert not np.isin(res.reason, (MM.REPETITION, MM.PERPETUAL)).any() and (res.plies > 8).all()
     assert res.repetition == 0 and res.perpetuals == 0
 
 
@@ -89,7 +67,8 @@ def test_perpetual_check_loses_in_both_colour_assignments():
 def test_the_ring_holds_the_movers_root_position_of_every_ply():
     from cchess_zero_amd.arena import Match
     from cchess_zero_amd.rules import Rules
-    m = Match(*_fake_players(), _openings(), slots=16, max_plies=160, seed=5, nodes_per_tree=1 << 15, rules="xiangqi", repetition=3)
+    m = Match(*_fake_players(), MM.fakenet_openings(), slots=16, max_plies=160, seed=5, nodes_per_tree=1 << 15, rules="xiangqi",
+              repetition=3)
     m.start()
     rules = Rules()
     for ply in range(10):
@@ -119,7 +98,7 @@ def test_repetition_0_is_the_xiangqi_match_as_it_was():
     kw = dict(slots=6, max_plies=60, sample_plies=6, seed=5, nodes_per_tree=1 << 15, rules="xiangqi")
     rows = []
     for extra in ({}, dict(repetition=0)):
-        m = Match(*_fake_players(), _openings(), **kw, **extra)
+        m = Match(*_fake_players(), MM.fakenet_openings(), **kw, **extra)
         m.start()
         fin = 0
         while fin < m.n_games:
@@ -134,7 +113,7 @@ def test_repetition_0_is_the_xiangqi_match_as_it_was():
         m.close()
     for k in ("result", "a_red", "plies", "reason", "moves"):
         assert np.array_equal(rows[0][k], rows[1][k]), k
-    assert not np.isin(rows[0]["reason"], (RMM.REPETITION, RMM.PERPETUAL)).any()
+    assert not np.isin(rows[0]["reason"], (MM.REPETITION, MM.PERPETUAL)).any()
 
 
 # ---- 5. the switch -------------------------------------------------------------------------------------------------------

@@ -1,10 +1,10 @@
 """The repetition rule without a GPU: the model (tests/repetition_model.py) on hand-written histories, the arena's scoring of
 the two new endings, Match's argument checks, and the constructed perpetual check replayed with the match model
-(tests/match_repetition_model.py) on the CPU oracle."""
+(tests/match_model.py at the repetition level) on the CPU oracle."""
 import numpy as np
 import pytest
 
-import match_repetition_model as RMM
+import match_model as MM
 import repetition_cases as RC
 import repetition_model as RM
 
@@ -64,7 +64,7 @@ def test_four_occurrences_under_fold_3_use_the_second_most_recent():
 # ---- 2. the arena's scores -----------------------------------------------------------------------------------------------
 def test_the_arena_scores_repetition_as_a_draw_and_perpetual_check_as_a_loss():
     from cchess_zero_amd import _lib, arena
-    assert (_lib.MATCH_REPETITION, _lib.MATCH_PERPETUAL) == (6, 7) == (RMM.REPETITION, RMM.PERPETUAL)
+    assert (_lib.MATCH_REPETITION, _lib.MATCH_PERPETUAL) == (6, 7) == (MM.REPETITION, MM.PERPETUAL)
     assert (_lib.REP_NONE, _lib.REP_DRAW, _lib.REP_RED_LOSES, _lib.REP_BLACK_LOSES) == (RM.NONE, RM.DRAW, RM.RED_LOSES, RM.BLACK_LOSES)
     assert arena.REASONS[6] == "repetition" and arena.REASONS[7] == "perpetual"
     assert arena.is_scored([0, 1, 2, 3, 4, 5, 6, 7, 8]).tolist() == [False, True, True, True, False, True, True, True, False]
@@ -109,10 +109,10 @@ def test_the_constructed_perpetual_check_is_lost_by_the_checking_side(playouts):
     want_moves = RC.PERPETUAL_LINE * 2
     for game, result in ((0, -1), (1, 1)):       # game 0: A is red, the checking side; game 1: B is red
         trace = []
-        g = RMM.play_game(players, b, 0, 0, game, 64, fold=3, trace=trace)
-        assert (g["reason"], g["plies"], g["result"], g["a_red"]) == (RMM.PERPETUAL, 8, result, 1 - game)
+        g = MM.play_game(players, b, 0, 0, game, 64, rules="xiangqi", fold=3, trace=trace)
+        assert (g["reason"], g["plies"], g["result"], g["a_red"]) == (MM.PERPETUAL, 8, result, 1 - game)
         assert [lab[m] for m in g["moves"]] == want_moves
         assert trace == [(8, 0)]                 # the third occurrence at ply 8, the cycle starts from the opening
     # with the rule off the same players walk the loop on
-    g = RMM.play_game(players, b, 0, 0, 0, 24, fold=0)
-    assert g["reason"] not in (RMM.REPETITION, RMM.PERPETUAL) and g["plies"] > 8
+    g = MM.play_game(players, b, 0, 0, 0, 24, rules="xiangqi", fold=0)
+    assert g["reason"] not in (MM.REPETITION, MM.PERPETUAL) and g["plies"] > 8

@@ -1,11 +1,13 @@
-"""tests/selfplay_chase_model.py (self-play with the perpetual-chase rule, on the CPU oracle): the constructed chase as a forced
+"""tests/selfplay_rules_model.py with the perpetual-chase rule (self-play on the CPU oracle): the constructed chase as a forced
 line — it ends at ply 8 as a loss for red, the chaser — and whole games in which every kind of ending occurs."""
+import functools
+
 import numpy as np
 
 import chase_cases as CC
 import fakenet
 import repetition_cases as RC
-import selfplay_chase_model as SC
+import selfplay_rules_model as XS
 
 # whole games: 16 openings, pos/11 at 16 playouts, 81 lock-step plies at temperature 0.01 without noise, max_plies 80
 WHOLE = dict(G=16, T=81, playouts=16, max_plies=80, temperature=0.01)
@@ -16,9 +18,11 @@ def whole_games_stream():
     return [(None, rng.random(WHOLE["G"]).astype(np.float32)) for _ in range(WHOLE["T"])]
 
 
+@functools.lru_cache(maxsize=None)
 def whole_games_model(chase=True):
+    """The whole games on the CPU oracle, once per process and setting; read-only."""
     boards, side = RC.cpu_openings(WHOLE["G"], 4, 11)
-    return SC.play_games(fakenet.make_forward("pos", 11), WHOLE["playouts"], boards, side, None, whole_games_stream(),
+    return XS.play_games(fakenet.make_forward("pos", 11), WHOLE["playouts"], boards, side, None, whole_games_stream(),
                          max_plies=WHOLE["max_plies"], temperature=WHOLE["temperature"], eps=0.0, fold=3, chase=chase)
 
 
@@ -27,7 +31,7 @@ def test_the_constructed_chase_ends_at_ply_8_as_a_loss_for_red():
     forced = [np.array([l], np.uint16) for l in line]
     stream = [(None, np.full(1, 0.5, np.float32))] * 9
     for chase, how, z in ((True, "chase", [-1, 1] * 4), (False, "repetition", [0] * 8)):
-        out = SC.play_games(fakenet.make_forward("pos", 11), 8, CC.CHASE_BOARD[None], [0], None, stream, max_plies=64, eps=0.0, fold=3,
+        out = XS.play_games(fakenet.make_forward("pos", 11), 8, CC.CHASE_BOARD[None], [0], None, stream, max_plies=64, eps=0.0, fold=3,
                             forced=forced, chase=chase)
         (t, g, o), = out["outcomes"]
         assert (t, g, o.how, o.fin_n) == (8, 0, how, 8) and o.z.tolist() == z

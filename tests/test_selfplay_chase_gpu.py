@@ -1,5 +1,5 @@
 """Self-play with the perpetual-chase rule on the GPU (cz_selfplay_set_chase, csrc/cz_selfplay.hip) against
-tests/selfplay_chase_model.py: whole games byte for byte, the constructed chase (ply 8, a loss for red, counted as a chase and
+tests/selfplay_rules_model.py: whole games byte for byte, the constructed chase (ply 8, a loss for red, counted as a chase and
 not as a perpetual check), chase off as self-play was, and the setter's refusals."""
 import ctypes as C
 
@@ -12,7 +12,6 @@ import chase_model as CM
 import fakenet
 import match_model as MM
 import repetition_cases as RC
-import selfplay_chase_model as SC
 from test_selfplay_chase_cpu import WHOLE, whole_games_model, whole_games_stream
 
 pytestmark = pytest.mark.gpu
