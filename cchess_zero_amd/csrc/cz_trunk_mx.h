@@ -61,6 +61,8 @@ struct MXGeo {
 };
 static_assert(MXGeo::HI_OFF % 256 == 0 && MXGeo::W_OFF % 16 == 0, "hi rows are swizzled by their absolute 256-byte row");
 static_assert(MXGeo::Y_OFF == 28672 && MXGeo::S_OFF == 43008, "tools/gen_tower_asm.py: MX_Y_OFF / MX_S_OFF");
+static_assert(MXGeo::SLABS_PER_LAYER % 4 == 0 && MXGeo::SLAB_BYTES == 16384 && 3 * MXGeo::SLAB_BYTES + 14336 < 65536,
+              "tools/gen_tower_asm.py: slab g of a layer sits in ring slot g & 3 = its quarter, an immediate of the slab bodies (MX_SLAB)");
 static_assert(MXGeo::ROWS * MXGeo::F32_ROWB <= MXGeo::HEADW_OFF, "fp32 trunk rows must leave the head weights alone");
 constexpr int MX_P = MXGeo::P, MX_THREADS = MXGeo::THREADS, MX_LDS_BYTES = MXGeo::LDS_TOTAL;
 
@@ -165,6 +167,7 @@ __global__ __launch_bounds__(512, 2) void k_trunk_mx_c128(const unsigned char *_
     const int vb0 = Geo::W_OFF + khalf * 2048 + ((ct * 32 + l31) << 4);
     const int vy0 = Geo::W_OFF + 12288 + khalf * 1024 + ((ct * 32 + l31) << 3);
     const int vs0 = Geo::W_OFF + 14336 + khalf * 512 + ((ct * 32 + l31) << 2);
+    const int ldst0 = Geo::W_OFF + (wave_u << 10);   // the wave's DMA destination in ring slot 0
     int keep;
 
     int rkk[3];
@@ -281,12 +284,13 @@ __global__ __launch_bounds__(512, 2) void k_trunk_mx_c128(const unsigned char *_
             : [ab0] "v"(ab[0]), [ab1] "v"(ab[1]), [ab2] "v"(ab[2]), [key0] "v"(key[0]), [key1] "v"(key[1]),            \
               [key2] "v"(key[2]), [nab0] "v"(NAB[0]), [nab1] "v"(NAB[1]), [nab2] "v"(NAB[2]), [nkey0] "v"(NKEY[0]),     \
               [nkey1] "v"(NKEY[1]), [nkey2] "v"(NKEY[2]), [xr0] "v"(xr[0]), [xr1] "v"(xr[1]), [xr2] "v"(xr[2]),        \
-              [yr0] "v"(yr[0]), [yr1] "v"(yr[1]), [yr2] "v"(yr[2]), [vb] "v"(vb), [vy] "v"(vy), [vs] "v"(vs),          \
-              [vbn] "v"(vbn), [voff0] "v"(voff0), [voff1] "v"(voff1), [sbase] "s"(sbase), [ldst] "s"(ldst)
+              [yr0] "v"(yr[0]), [yr1] "v"(yr[1]), [yr2] "v"(yr[2]), [vb] "v"(vb0), [vy] "v"(vy0), [vs] "v"(vs0),       \
+              [voff0] "v"(voff0), [voff1] "v"(voff1), [sbase] "s"(sbase), [ldst] "s"(ldst0)
 #define MX_CLOBBERS "memory", "scc", "v232", "v233", "v234", "v235", "v236", "v237", "v238", "v239", "v240", "v241", "v242", "v243", \
                     "v244", "v245", "v246", "v247", "v248", "v249", "v250", "v251", "v252", "v253", "v254", "v255"
-#define MX_ARGS()                                                                                                    \
-            TRUNK_SLAB_ARGS(wpk, const int vy = vy0 + slot; const int vs = vs0 + slot;)   /* + the fp6 blocks' last 8 bytes and their scale dwords */
+#define MX_ARGS()   /* slab g sits in ring slot g & 3 = the body's quarter: the bodies carry the slots as immediates, and all that */ \
+            const int gn = g + 3 < nslabs ? g + 3 : nslabs - 1;   /* moves from slab to slab is the global source of the DMA (slab g + 3) */ \
+            const unsigned char *sbase = wpk + (size_t)gn * Geo::SLAB_BYTES;
 #define MX_RUN(ASMSTR, NAB, NKEY)                                                                                    \
         {                                                                                                            \
             MX_ARGS()                                                                                                \
@@ -311,6 +315,11 @@ __global__ __launch_bounds__(512, 2) void k_trunk_mx_c128(const unsigned char *_
     int g = 0;
     int skipm;   // cell group 0 (waves 0..3): its first row tile skips the dy = -1 taps
     asm volatile("s_cmp_lt_u32 %1, 4\n\ts_cselect_b32 %0, 1, 0" : "=s"(skipm) : "s"(wave_u) : "scc");
+    // The two waves of a SIMD (w and w + 4) run the same body between the same barriers and ask for the same issue slots at the same
+    // time.  One static priority for one of them, set once for the whole tower (no per-step flips), settles every such tie the same
+    // way: 742 -> 728 cycles per slab and -0.9 % per launch together with the immediates.  Either half gains; this one measured
+    // 0.2 % better than waves 4-7 on two boxes.  Every offset of the partners' BARRIERS lost (profiles/mx_partner_offset_ab.txt).
+    if (wave_u < 4) __builtin_amdgcn_s_setprio(1);
 #pragma unroll 1
     for (int layer = 0; layer < nlayers; ++layer) {
         f32x16 acc[3];
@@ -320,7 +329,7 @@ __global__ __launch_bounds__(512, 2) void k_trunk_mx_c128(const unsigned char *_
         MxFrag fa, fb;
         tap_addr(0, ab, key, xr, yr);
         {   // the first slab's two fp16 operand sets (waited for by its steps A and B)
-            const int vb = vb0 + (((unsigned)g & 3u) << Geo::SLAB_SHIFT);
+            const int vb = vb0;   // a layer starts in ring slot 0
 #pragma unroll
             for (int i = 0; i < 3; ++i) {
                 fa.a[i] = *reinterpret_cast<const bf16x8 *>(smem + ab[i] + ((0 ^ key[i]) << 4));

@@ -119,6 +119,7 @@ XS_LO_OFF = 181 * 256   # cz_trunk_split.h: XSGeo::LO_OFF (180 activation rows +
 # channels on ONE block-scaled fp6 MFMA (v_mfma_scale_f32_32x32x64_f8f6f4, 8 passes): 9 MFMAs per slab and wave instead of 18.
 MX_XPLANE, MX_YPLANE = 224 * 16, 224 * 8      # MXGeo: one plane per 16-channel group, 224 entries (180 cells + the zero aliases)
 MX_Y_OFF, MX_S_OFF = 8 * MX_XPLANE, 8 * MX_XPLANE + 8 * MX_YPLANE
+MX_SLAB = 16384                               # MXGeo::SLAB_BYTES: one slot of the ring of four
 MX_AX = ["v[232:237]", "v[238:243]", "v[244:249]"]   # fp6 activation blocks of the three cell tiles: loaded and consumed inside
 MX_WX = "v[250:255]"                                  # one slab body, so they are hard registers (the body clobbers v232..v255)
 
@@ -130,6 +131,9 @@ def slabMX(hs, layer_last=False):
       B (k-step 1, set a1*/w1)  vmcnt(2) + barrier first (slab g+1 published, slab g-1's buffer free), requests the NEXT slab's
                                 set A (after the fourth slab of a tap: at the next tap's addresses)
       C (fp6, hard registers)   requests the next slab's set B, issues the wave's 2 DMA pieces of slab g+3.
+    36 slabs per layer = a multiple of 4: slab g lives in ring slot g & 3 = hs, so the slots are immediates: the weight reads carry
+    them in their offset fields (vb / vy / vs are the wave's addresses in slot 0), the DMA adds its slot to ldst (slot 0 + 1 KB per
+    wave); from slab to slab only the DMA's global source moves (tests/test_mx_slab_plan_cpu.py walks a layer of these bodies).
     layer_last (round 6): the LAST slab of a layer requests no operands (the activations are about to be replaced) and waits
     for all of its LDS reads in front of its barrier — behind it no wave reads the activation planes any more, so the epilogue
     needs no barrier of its own in front."""
@@ -140,6 +144,7 @@ def slabMX(hs, layer_last=False):
                     % (i, MX_WX, MX_AX[i], i, i, hs & 1, hs >> 1))
     sub = lambda r, lo, hi: "v[%d:%d]" % (int(r[2:].split(":")[0]) + lo, int(r[2:].split(":")[0]) + hi)
     xo, yo = hs * 2 * MX_XPLANE, MX_Y_OFF + hs * 2 * MX_YPLANE
+    slot, nslot, dslot = hs * MX_SLAB, ((hs + 1) % 4) * MX_SLAB, ((hs + 3) % 4) * MX_SLAB     # this slab's, the next slab's, the DMA's
     L = ["s_mov_b32 %[keep], m0"]
     # step A
     L += ["s_waitcnt lgkmcnt(4)", f(0, "w0", "a0h")]
@@ -154,7 +159,8 @@ def slabMX(hs, layer_last=False):
         L += ["ds_read_b32 %%[sb%d], %%[t%d] offset:%d" % (i, i, MX_S_OFF) for i in range(3)]
         nc = 12
     L += [f(2, "w0", "a0h")]
-    L += ["ds_read_b128 %s, %%[vb] offset:8192" % sub(MX_WX, 0, 3), "ds_read_b64 %s, %%[vy]" % sub(MX_WX, 4, 5), "ds_read_b32 %[ws], %[vs]"]
+    L += ["ds_read_b128 %s, %%[vb] offset:%d" % (sub(MX_WX, 0, 3), slot + 8192), "ds_read_b64 %s, %%[vy] offset:%d" % (sub(MX_WX, 4, 5), slot),
+          "ds_read_b32 %%[ws], %%[vs] offset:%d" % slot]
     # step B
     if layer_last:
         L += ["s_waitcnt vmcnt(2) lgkmcnt(0)", "s_barrier"]
@@ -167,10 +173,10 @@ def slabMX(hs, layer_last=False):
         L += [f(1, "w1", "a1h")]
         L += ["ds_read_b128 %[a0h0], %[t0]", "ds_read_b128 %[a0h1], %[t1]"]
         L += [f(2, "w1", "a1h")]
-        L += ["ds_read_b128 %[a0h2], %[t2]", "ds_read_b128 %[w0], %[vbn]"]
+        L += ["ds_read_b128 %[a0h2], %[t2]", "ds_read_b128 %%[w0], %%[vb] offset:%d" % nslot]
     # step C
-    dma1 = ["s_mov_b32 m0, %[ldst]", "s_nop 0", "global_load_lds_dwordx4 %[voff0], %[sbase]"]
-    dma2 = ["s_add_u32 m0, %[ldst], 0x2000", "s_nop 0", "global_load_lds_dwordx4 %[voff1], %[sbase]"]
+    dma1 = ["s_add_u32 m0, %%[ldst], 0x%x" % dslot, "s_nop 0", "global_load_lds_dwordx4 %[voff0], %[sbase]"]
+    dma2 = ["s_add_u32 m0, %%[ldst], 0x%x" % (dslot + 0x2000), "s_nop 0", "global_load_lds_dwordx4 %[voff1], %[sbase]"]
     place = os.environ.get("MX_DMA_PLACE", "C")     # experiment knob: where the wave's two LDS-DMA pieces go
     if place == "B0":       # both right behind the barrier
         i = L.index("s_barrier") + 1
@@ -192,7 +198,7 @@ def slabMX(hs, layer_last=False):
     if place == "C":
         L += dma2
     L += [mx(2)]
-    L += [] if layer_last else ["ds_read_b128 %[a1h2], %[t2]", "ds_read_b128 %[w1], %[vbn] offset:4096"]
+    L += [] if layer_last else ["ds_read_b128 %[a1h2], %[t2]", "ds_read_b128 %%[w1], %%[vb] offset:%d" % (nslot + 4096)]
     if place == "Cend":
         L += dma1 + dma2
     L += ["s_mov_b32 m0, %[keep]"]
