@@ -160,6 +160,29 @@ def check(rc, what=""):
         raise CchessHipError("%s failed (%d): %s" % (what or "cchess_hip call", rc, msg.decode() if msg else "?"))
 
 
+def _ptr(t):
+    """tensor -> c_void_p for a direct lib() call (tests, tools); None and a raw device pointer pass through."""
+    if t is None or isinstance(t, C.c_void_p):
+        return t
+    return C.c_void_p(t.data_ptr())
+
+
+def call(name, *args):
+    """lib().<name>(*args): anything with a data_ptr() (a tensor) goes as that address, None / ctypes objects / Python scalars
+    as they are.  Raises CchessHipError on a negative return, else returns the value (0, or the count a dump hands back)."""
+    rc = getattr(lib(), name)(*[a.data_ptr() if hasattr(a, "data_ptr") else a for a in args])
+    if rc < 0:
+        check(rc, name)
+    return rc
+
+
+def out_pointers(name, handle, n, *args):
+    """The n device pointers the getter <name>(handle, *args, &p0 .. &p[n-1]) hands back, as c_void_p."""
+    ptrs = [C.c_void_p() for _ in range(n)]
+    call(name, handle, *args, *[C.byref(p) for p in ptrs])
+    return ptrs
+
+
 _tables = None
 
 
@@ -167,9 +190,8 @@ def tables():
     """Host copies of the static tables: dict(lut[90,90] i16, unflip[2086] i16, labels[2086] str, srcdst[2086] u16)."""
     global _tables
     if _tables is None:
-        L = lib()
         p = [C.c_void_p() for _ in range(4)]
-        check(L.cz_tables(*[C.byref(x) for x in p]), "cz_tables")
+        call("cz_tables", *[C.byref(x) for x in p])
         lut = np.ctypeslib.as_array(C.cast(p[0], C.POINTER(C.c_int16)), shape=(NSQ * NSQ,)).reshape(NSQ, NSQ).copy()
         unflip = np.ctypeslib.as_array(C.cast(p[1], C.POINTER(C.c_int16)), shape=(NLABELS,)).copy()
         raw = C.string_at(p[2], NLABELS * 5)
@@ -177,7 +199,7 @@ def tables():
         srcdst = np.ctypeslib.as_array(C.cast(p[3], C.POINTER(C.c_uint16)), shape=(NLABELS,)).copy()
         zk = C.c_void_p()
         sk = C.c_uint64()
-        check(L.cz_zobrist(C.byref(zk), C.byref(sk)), "cz_zobrist")
+        call("cz_zobrist", C.byref(zk), C.byref(sk))
         zob = np.ctypeslib.as_array(C.cast(zk, C.POINTER(C.c_uint64)), shape=(15 * NSQ,)).reshape(15, NSQ).copy()
         _tables = dict(lut=lut, unflip=unflip, labels=labels, srcdst=srcdst, zobrist=zob, zobrist_side=int(sk.value),
                        label2i={s: i for i, s in enumerate(labels)})

@@ -27,11 +27,11 @@ import time
 import numpy as np
 import torch
 
-from ._lib import (MATCH_ABORTED, MATCH_CHASE, MATCH_KING, MATCH_MATE, MATCH_PERPETUAL, MATCH_PLY_CAP, MATCH_REPETITION, MATCH_RR60, NSQ, check,
-                   lib, tables)
-from .engine import SearchEngine, _ptr, plane_format, pool_nodes
+from ._lib import (MATCH_ABORTED, MATCH_CHASE, MATCH_KING, MATCH_MATE, MATCH_PERPETUAL, MATCH_PLY_CAP, MATCH_REPETITION, MATCH_RR60, NSQ, call,
+                   lib, out_pointers, tables)
+from .engine import SearchEngine, plane_format, pool_nodes
 from .notation import player_to_side, state_to_board
-from .rules import RULES, check_rule_options, set_rule_options   # noqa: F401 (RULES: re-exported)
+from .rules import RULES, check_rule_options, root_rules_chase_history, root_rules_history, set_rule_options   # noqa: F401 (RULES: re-exported)
 
 REASONS = {0: "unfinished", MATCH_KING: "king", MATCH_RR60: "rr60", MATCH_PLY_CAP: "ply_cap", MATCH_ABORTED: "aborted", MATCH_MATE: "mate",
            MATCH_REPETITION: "repetition", MATCH_PERPETUAL: "perpetual", MATCH_CHASE: "chase"}
@@ -394,18 +394,12 @@ class Match:
             self.engines.append(eng)
         ea, eb = self.engines
         self._op_dev = [torch.from_numpy(x).to(dev) for x in (op.boards, op.side, op.rr)]
-        L = lib()
         ea.ctx.bind_stream()
         eb.ctx.bind_stream()
         self._h = C.c_void_p()
-        check(L.cz_match_create(ea.ctx.h, eb.ctx.h, *[_ptr(x) for x in self._op_dev], len(op), int(pair_base), int(pair_stride),
-                                self.max_plies, C.byref(self._h)), "cz_match_create")
+        call("cz_match_create", ea.ctx.h, eb.ctx.h, *self._op_dev, len(op), int(pair_base), int(pair_stride), self.max_plies, C.byref(self._h))
         set_rule_options("cz_match", self._h, self.rules, self.repetition, self.chase)
-        self.masks = []
-        for player in (0, 1):
-            p = C.c_void_p()
-            check(L.cz_match_active(self._h, player, C.byref(p)), "cz_match_active")
-            self.masks.append(p)
+        self.masks = [out_pointers("cz_match_active", self._h, 1, player)[0] for player in (0, 1)]
         self.played = torch.empty(G, dtype=torch.int16, device=dev)
 
     def search(self, player):
@@ -415,7 +409,7 @@ class Match:
 
     def choose(self):
         self.engines[0].ctx.bind_stream()
-        check(lib().cz_match_choose(self._h, self.sample_plies, C.c_ulonglong(self.seed), _ptr(self.played)), "cz_match_choose")
+        call("cz_match_choose", self._h, self.sample_plies, C.c_ulonglong(self.seed), self.played)
 
     def follow(self):
         for eng in self.engines:
@@ -423,7 +417,7 @@ class Match:
 
     def adjudicate(self):
         self.engines[0].ctx.bind_stream()
-        check(lib().cz_match_adjudicate(self._h, _ptr(self.played)), "cz_match_adjudicate")
+        call("cz_match_adjudicate", self._h, self.played)
 
     def step_ply(self):
         """One ply of every live game: search A over its movers, search B over its movers, choose, advance both, adjudicate."""
@@ -436,50 +430,29 @@ class Match:
     def finished(self):
         """(games finished, simulations of the searches whose move was chosen) — synchronises."""
         fin, sims = C.c_int32(0), C.c_ulonglong(0)
-        check(lib().cz_match_finished(self._h, C.byref(fin), C.byref(sims)), "cz_match_finished")
+        call("cz_match_finished", self._h, C.byref(fin), C.byref(sims))
         return int(fin.value), int(sims.value)
 
     def active(self):
         """(mask of A, mask of B, game of each slot) as host arrays."""
-        G, L, h = self.G, lib(), self.engines[0].ctx.h
-        out = [np.zeros(G, np.uint8), np.zeros(G, np.uint8), np.zeros(G, np.int32)]
-        ptrs = [C.c_void_p() for _ in range(6)]
-        check(L.cz_match_results(self._h, *[C.byref(p) for p in ptrs]), "cz_match_results")
-        for o, p in zip(out, self.masks + [ptrs[5]]):
-            check(L.cz_download(h, o.ctypes.data_as(C.c_void_p), p, o.nbytes), "cz_download")
-        return tuple(out)
+        ptrs = self.masks + [out_pointers("cz_match_results", self._h, 6)[5]]
+        return tuple(self.engines[0].ctx.download(p, dt, self.G) for p, dt in zip(ptrs, (np.uint8, np.uint8, np.int32)))
 
     def history(self):
         """(keys u64 [G, 64], checks u8 [G, 64]) on the host: the slots' position rings (cz_match_history; repetition != 0),
         position i of a slot's game at [i & 63]."""
-        G, L, h = self.G, lib(), self.engines[0].ctx.h
-        pk, pc = C.c_void_p(), C.c_void_p()
-        check(L.cz_match_history(self._h, C.byref(pk), C.byref(pc)), "cz_match_history")
-        keys, checks = np.zeros((G, 64), np.uint64), np.zeros((G, 64), np.uint8)
-        for o, p in ((keys, pk), (checks, pc)):
-            check(L.cz_download(h, o.ctypes.data_as(C.c_void_p), p, o.nbytes), "cz_download")
-        return keys, checks
+        return root_rules_history("cz_match", self._h, self.engines[0].ctx, self.G)
 
     def chase_history(self):
         """chase u64 [G, 64, 4] on the host: the slots' rings of chase records (cz_match_chase_history; chase=True), position i
         of a slot's game at [i & 63] — Rules.threats of that position."""
-        G, L, h = self.G, lib(), self.engines[0].ctx.h
-        p = C.c_void_p()
-        check(L.cz_match_chase_history(self._h, C.byref(p)), "cz_match_chase_history")
-        out = np.zeros((G, 64, 4), np.uint64)
-        check(L.cz_download(h, out.ctypes.data_as(C.c_void_p), p, out.nbytes), "cz_download")
-        return out
+        return root_rules_chase_history("cz_match", self._h, self.engines[0].ctx, self.G)
 
     def results(self):
         """The per-game arrays on the host: result, a_red, plies, reason, moves [games, max_plies] (0xFFFF past the end)."""
-        n, L, h = self.n_games, lib(), self.engines[0].ctx.h
-        ptrs = [C.c_void_p() for _ in range(6)]
-        check(L.cz_match_results(self._h, *[C.byref(p) for p in ptrs]), "cz_match_results")
-        out = dict(result=np.zeros(n, np.int8), a_red=np.zeros(n, np.uint8), plies=np.zeros(n, np.int32),
-                   reason=np.zeros(n, np.uint8), moves=np.zeros((n, self.max_plies), np.uint16))
-        for k, p in zip(("result", "a_red", "plies", "reason", "moves"), ptrs):
-            check(L.cz_download(h, out[k].ctypes.data_as(C.c_void_p), p, out[k].nbytes), "cz_download")
-        return out
+        n, ptrs = self.n_games, out_pointers("cz_match_results", self._h, 6)
+        what = (("result", np.int8, n), ("a_red", np.uint8, n), ("plies", np.int32, n), ("reason", np.uint8, n), ("moves", np.uint16, (n, self.max_plies)))
+        return {k: self.engines[0].ctx.download(p, dt, shape) for (k, dt, shape), p in zip(what, ptrs)}
 
     def close(self):
         if getattr(self, "_h", None):

@@ -266,7 +266,16 @@ def mx_pack_layer(w):
 STRICT_CHECK_TOL = 5e-4        # precision "strict": the engine's MEASURED |dlogit| / |dvalue| against fp32 on the live weights must
 STRICT_CHECK_POSITIONS = 64    # stay below this on this many distinct positions (half of north_star's 1e-3), else the next engine
 _STRICT_LADDER = ("mx6", "fp16x2", "fp32")
+# the fused trunk launch by engine: (entry point, first-layer weights, tower weights, the trunk comes out as fp32 = hi + lo)
+_TRUNK_ENGINES = {"16": ("cz_net_trunk_%s", "hip_w0", "hip_tower_w", False),
+                  "x2": ("cz_net_trunk_split", "hip_split_w0", "hip_split_w", True),     # + a trailing halves_dtype argument
+                  "mx6": ("cz_net_trunk_mx", "hip_split_w0", "hip_mx_w", True)}
 _probe_planes = {}
+
+
+def _planes_f32(planes, device):
+    """a planes argument (ndarray or tensor, wherever it lives) -> float32 tensor on `device`"""
+    return torch.as_tensor(np.asarray(planes.cpu() if torch.is_tensor(planes) else planes, dtype=np.float32)).to(device)
 
 
 def strict_probe_planes(ctx):
@@ -379,7 +388,7 @@ class PolicyValueNet:
         import warnings
         tol = STRICT_CHECK_TOL if tol is None else float(tol)
         self._check_pending = False
-        x = strict_probe_planes(self._hip_ctx()) if planes_nhwc is None else torch.as_tensor(np.asarray(planes_nhwc.cpu() if torch.is_tensor(planes_nhwc) else planes_nhwc, dtype=np.float32)).to(self.device)
+        x = strict_probe_planes(self._hip_ctx()) if planes_nhwc is None else _planes_f32(planes_nhwc, self.device)
         lr, vr = self.module.float()(x.permute(0, 3, 1, 2).contiguous())
         lr, vr = lr.double(), vr.double().reshape(-1)
         failed = []
@@ -458,30 +467,26 @@ class PolicyValueNet:
         self.head_w_rows = torch.cat([wp.view(2, FILTERS), wv.view(1, FILTERS)], 0).contiguous()  # [3,128]
         self.head_w = self.head_w_rows.t().contiguous()  # [128,3]
         self.head_b = torch.cat([bp, bv], 0).contiguous()
-        self.pfc_w = m.policy_fc.weight.float().t().contiguous()
-        self.pfc_b = m.policy_fc.bias.float()
-        self.v1_w = m.value_fc1.weight.float().t().contiguous()
-        self.v1_b = m.value_fc1.bias.float()
-        self.v2_w = m.value_fc2.weight.float().t().contiguous()
-        self.v2_b = m.value_fc2.bias.float()
+        # FC layers, each tensor once: [in,out] for the torch heads; the hip_* names are what cz_fc_heads_f32 reads
+        self.pfc_w_rows = m.policy_fc.weight.detach().float().contiguous()   # [2086,180]: rows the expansion kernel gathers
+        self.pfc_w = self.pfc_w_rows.t().contiguous()
+        self.pfc_b = self.pfc_b_f32 = self.hip_pfc_b = m.policy_fc.bias.detach().float().contiguous()
+        self.v1_w = self.hip_v1_wt = m.value_fc1.weight.detach().float().t().contiguous()      # [90,256]
+        self.v1_b = self.hip_v1_b = m.value_fc1.bias.detach().float().contiguous()
+        self.v2_w = m.value_fc2.weight.detach().float().t().contiguous()      # [256,1]
+        self.hip_v2_w = self.v2_w.view(-1)                                    # the same 256 floats
+        self.v2_b = self.hip_v2_b = m.value_fc2.bias.detach().float().contiguous()
         if self.backend.startswith("hip"):
             # policy FC weight [2086,180] split into bf16 hi + lo and packed in MFMA B-fragment order
             # [label/32][k/16][lane = (k%16)/8*32 + label%32][k%8] (cz_fc_heads_f32)
             wpad = torch.zeros((66 * 32, 192), dtype=torch.float32, device=self.device)
-            wpad[:PROB_SIZE, :180] = m.policy_fc.weight.float()
+            wpad[:PROB_SIZE, :180] = self.pfc_w_rows
             hi = wpad.to(torch.bfloat16)
             lo = (wpad - hi.float()).to(torch.bfloat16)
 
             def frag(w):
                 return w.view(66, 32, 12, 2, 8).permute(0, 2, 3, 1, 4).contiguous()
             self.hip_pfc_hi, self.hip_pfc_lo = frag(hi), frag(lo)
-            self.hip_pfc_b = m.policy_fc.bias.detach().float().contiguous()
-            self.pfc_w_rows = m.policy_fc.weight.detach().float().contiguous()   # [2086,180]: rows the expansion kernel gathers
-            self.pfc_b_f32 = self.hip_pfc_b
-            self.hip_v1_wt = m.value_fc1.weight.float().t().contiguous()      # [90,256]
-            self.hip_v1_b = m.value_fc1.bias.float().contiguous()
-            self.hip_v2_w = m.value_fc2.weight.float().reshape(-1).contiguous()  # [256]
-            self.hip_v2_b = m.value_fc2.bias.float().contiguous()
 
     def _hip_ctx(self):
         if self._ctx is None:
@@ -489,113 +494,64 @@ class PolicyValueNet:
             self._ctx = Context(1, 2, self.device.index or 0)
         return self._ctx
 
-    def _hip_conv(self, x, wb, res, out, relu=True):
-        """x, res, out: [B,90,128] bf16 contiguous device tensors; one launch = one fused layer."""
-        import ctypes as C
-        from ._lib import check, lib
-        wp, b = wb
+    def _launch(self, name, *args):
+        """One launch of the library on this net's context, between a pair of HIP events while conv_events collects them."""
         ev = None
         if self.conv_events is not None:
             ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
             ev[0].record()
-        check(lib().cz_conv3x3_c128_bf16(self._hip_ctx().h, C.c_void_p(x.data_ptr()), C.c_void_p(wp.data_ptr()),
-                                         C.c_void_p(b.data_ptr()), C.c_void_p(res.data_ptr()) if res is not None else None,
-                                         C.c_void_p(out.data_ptr()), x.shape[0], 1 if relu else 0), "cz_conv3x3_c128_bf16")
+        self._hip_ctx().call(name, *args)
         if ev is not None:
             ev[1].record()
             self.conv_events.append(ev)
+
+    def _hip_conv(self, x, wb, res, out, relu=True):
+        """x, res, out: [B,90,128] bf16 contiguous device tensors; one launch = one fused layer."""
+        self._launch("cz_conv3x3_c128_bf16", x, wb[0], wb[1], res, out, x.shape[0], 1 if relu else 0)
         return out
 
     def _hip_net_forward(self, planes, trunk=False):
         """planes [B,9,10,C] (C = 16 in the net's 16-bit dtype: zero-copy; anything else is repacked) -> z [B,90,3] f32
         (post-ReLU head conv outputs), or with trunk=True the trunk activations [B,90,128] in the net's dtype.
-        First conv + residual tower + head 1x1 convs in ONE launch (cz_net_trunk_bf16 / cz_net_trunk_f16)."""
-        import ctypes as C
-        from ._lib import check, lib
+        First conv + residual tower + head 1x1 convs in ONE launch (_TRUNK_ENGINES)."""
         B = planes.shape[0]
-        hdt = torch.float16 if self.dtype == torch.float16 else torch.bfloat16
-        fn = lib().cz_net_trunk_f16 if hdt == torch.float16 else lib().cz_net_trunk_bf16
+        f16 = self.dtype == torch.float16
+        hdt = torch.float16 if f16 else torch.bfloat16
         if planes.dtype == hdt and planes.shape[-1] == 16 and planes.is_contiguous():
             p16 = planes
         else:
             p16 = torch.zeros((B, 9, 10, 16), dtype=hdt, device=self.device)
             p16[..., :14] = planes[..., :14].to(hdt)
-        tdt = torch.float32 if self.split else hdt     # the strict engine hands the trunk out as fp32 = hi + lo
+        engine = "mx6" if self.mx else "x2" if self.split else "16"
+        name, w0, tower_w, strict = _TRUNK_ENGINES[engine]
+        if engine == "16":
+            name %= "f16" if f16 else "bf16"
+        tdt = torch.float32 if strict else hdt     # the strict engines hand the trunk out as fp32 = hi + lo
         z = torch.empty((B, 90, FILTERS), dtype=tdt, device=self.device) if trunk else torch.empty((B, 90, 3), dtype=torch.float32, device=self.device)
-        self._hip_ctx().bind_stream()
-        ev = None
-        if self.conv_events is not None:
-            ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-            ev[0].record()
-        if self.mx:
-            check(lib().cz_net_trunk_mx(self._hip_ctx().h, C.c_void_p(p16.data_ptr()), C.c_void_p(self.hip_split_w0.data_ptr()),
-                                        C.c_void_p(self.hip_b0.data_ptr()), C.c_void_p(self.hip_mx_w.data_ptr()),
-                                        C.c_void_p(self.hip_tower_b.data_ptr()), C.c_void_p(z.data_ptr()) if trunk else None,
-                                        C.c_void_p(self.head_w_rows.data_ptr()), C.c_void_p(self.head_b.data_ptr()),
-                                        None if trunk else C.c_void_p(z.data_ptr()), B, self.res_block_nums), "cz_net_trunk_mx")
-        elif self.split:
-            check(lib().cz_net_trunk_split(self._hip_ctx().h, C.c_void_p(p16.data_ptr()), C.c_void_p(self.hip_split_w0.data_ptr()),
-                                           C.c_void_p(self.hip_b0.data_ptr()), C.c_void_p(self.hip_split_w.data_ptr()),
-                                           C.c_void_p(self.hip_tower_b.data_ptr()), C.c_void_p(z.data_ptr()) if trunk else None,
-                                           C.c_void_p(self.head_w_rows.data_ptr()), C.c_void_p(self.head_b.data_ptr()),
-                                           None if trunk else C.c_void_p(z.data_ptr()), B, self.res_block_nums,
-                                           2 if hdt == torch.float16 else 1), "cz_net_trunk_split")
-        else:
-            check(fn(self._hip_ctx().h, C.c_void_p(p16.data_ptr()), C.c_void_p(self.hip_w0.data_ptr()),
-                     C.c_void_p(self.hip_b0.data_ptr()), C.c_void_p(self.hip_tower_w.data_ptr()),
-                     C.c_void_p(self.hip_tower_b.data_ptr()), C.c_void_p(z.data_ptr()) if trunk else None,
-                     C.c_void_p(self.head_w_rows.data_ptr()), C.c_void_p(self.head_b.data_ptr()),
-                     None if trunk else C.c_void_p(z.data_ptr()), B, self.res_block_nums), "cz_net_trunk")
-        if ev is not None:
-            ev[1].record()
-            self.conv_events.append(ev)
+        self._launch(name, p16, getattr(self, w0), self.hip_b0, getattr(self, tower_w), self.hip_tower_b, z if trunk else None,
+                     self.head_w_rows, self.head_b, None if trunk else z, B, self.res_block_nums, *((2 if f16 else 1,) if engine == "x2" else ()))
         return z
 
     def _hip_tower_heads_forward(self, h):
         """h: [B,128,9,10] channels_last bf16 -> z [B,90,3] f32: residual tower + both head 1x1 convs (+BN+ReLU) in
         one launch; the trunk never leaves the CU."""
-        import ctypes as C
-        from ._lib import check, lib
         B = h.shape[0]
         if not h.is_contiguous(memory_format=torch.channels_last):
             h = h.contiguous(memory_format=torch.channels_last)
         x = h.permute(0, 2, 3, 1).reshape(B, 90, FILTERS)
         z = torch.empty((B, 90, 3), dtype=torch.float32, device=self.device)
-        self._hip_ctx().bind_stream()
-        ev = None
-        if self.conv_events is not None:
-            ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-            ev[0].record()
-        check(lib().cz_tower_heads_c128_bf16(self._hip_ctx().h, C.c_void_p(x.data_ptr()), C.c_void_p(self.hip_tower_w.data_ptr()),
-                                             C.c_void_p(self.hip_tower_b.data_ptr()), None, C.c_void_p(self.head_w_rows.data_ptr()),
-                                             C.c_void_p(self.head_b.data_ptr()), C.c_void_p(z.data_ptr()), B, self.res_block_nums),
-              "cz_tower_heads_c128_bf16")
-        if ev is not None:
-            ev[1].record()
-            self.conv_events.append(ev)
+        self._launch("cz_tower_heads_c128_bf16", x, self.hip_tower_w, self.hip_tower_b, None, self.head_w_rows, self.head_b, z, B, self.res_block_nums)
         return z
 
     def _hip_tower_forward(self, h):
         """h: [B,128,9,10] channels_last bf16 -> all residual blocks in one launch (activations stay in LDS)."""
-        import ctypes as C
-        from ._lib import check, lib
         B = h.shape[0]
         if not h.is_contiguous(memory_format=torch.channels_last):
             h = h.contiguous(memory_format=torch.channels_last)
         x = h.permute(0, 2, 3, 1).reshape(B, 90, FILTERS)
         if self.res_block_nums == 0:
             return h
-        self._hip_ctx().bind_stream()
-        ev = None
-        if self.conv_events is not None:
-            ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-            ev[0].record()
-        check(lib().cz_tower_c128_bf16(self._hip_ctx().h, C.c_void_p(x.data_ptr()), C.c_void_p(self.hip_tower_w.data_ptr()),
-                                       C.c_void_p(self.hip_tower_b.data_ptr()), C.c_void_p(x.data_ptr()), B, self.res_block_nums),
-              "cz_tower_c128_bf16")
-        if ev is not None:
-            ev[1].record()
-            self.conv_events.append(ev)
+        self._launch("cz_tower_c128_bf16", x, self.hip_tower_w, self.hip_tower_b, x, B, self.res_block_nums)
         return x.reshape(B, 9, 10, FILTERS).permute(0, 3, 1, 2)
 
     def _hip_blocks_forward(self, h):
@@ -606,7 +562,6 @@ class PolicyValueNet:
         cur = h.permute(0, 2, 3, 1).reshape(B, 90, FILTERS)  # same memory viewed as NHWC rows
         if self._bufs is None or self._bufs[0].shape[0] != B:
             self._bufs = [torch.empty((B, 90, FILTERS), dtype=torch.bfloat16, device=self.device) for _ in range(3)]
-        self._hip_ctx().bind_stream()
         t = self._bufs[0]
         for i, (w1, w2) in enumerate(self.hip_blocks):
             y = self._bufs[1 + (i & 1)]           # never the buffer `cur` lives in
@@ -667,16 +622,11 @@ class PolicyValueNet:
     def _hip_fc_heads(self, z):
         """z [B,90,3] f32 -> (logits [B,2086] f32, value [B,1] f32): policy FC on MFMA (split-bf16, fp32
         accumulate) + value FCs on the fp32 VALU, cz_fc_heads_f32."""
-        import ctypes as C
-        from ._lib import check, lib
         B = z.shape[0]
         logits = torch.empty((B, PROB_SIZE), dtype=torch.float32, device=self.device)
         value = torch.empty((B, 1), dtype=torch.float32, device=self.device)
-        self._hip_ctx().bind_stream()
-        vp = lambda t: C.c_void_p(t.data_ptr())
-        check(lib().cz_fc_heads_f32(self._hip_ctx().h, vp(z), vp(self.hip_pfc_hi), vp(self.hip_pfc_lo), vp(self.hip_pfc_b),
-                                    vp(self.hip_v1_wt), vp(self.hip_v1_b), vp(self.hip_v2_w), vp(self.hip_v2_b),
-                                    vp(logits), vp(value), B), "cz_fc_heads_f32")
+        self._hip_ctx().call("cz_fc_heads_f32", z, self.hip_pfc_hi, self.hip_pfc_lo, self.hip_pfc_b, self.hip_v1_wt, self.hip_v1_b,
+                             self.hip_v2_w, self.hip_v2_b, logits, value, B)
         return logits, value
 
     @torch.no_grad()
@@ -693,7 +643,7 @@ class PolicyValueNet:
             x[0, 0, 4, 0] = 1.0   # any plane pattern will do; the check is about the weights' scale
             x[0, 8, 4, 7] = 1.0
         else:
-            x = torch.as_tensor(np.asarray(planes_nhwc, dtype=np.float32)).to(self.device)
+            x = _planes_f32(planes_nhwc, self.device)
         logits, v = self.forward_device(x)
         finite = bool(torch.isfinite(logits).all()) and bool(torch.isfinite(v).all())
         peak = float(self.tower(x).float().abs().max())
@@ -714,22 +664,18 @@ class PolicyValueNet:
         """Device planes -> (z [B,90,3] f32 head-conv outputs, value [B,1] f32): what the search needs when the policy
         FC is evaluated inside the expansion kernel (cz_search_expand_backup_fc).  n_rows: device address of an int
         (SearchEngine.select_compact) — only the first *n_rows rows are computed, the rest of z / value is undefined."""
-        import ctypes as C
-        from ._lib import check, lib
         self._ensure_checked()
-        h = self._hip_ctx().h
+        call = self._hip_ctx().call
         if n_rows is not None:
-            check(lib().cz_set_batch_count(h, n_rows), "cz_set_batch_count")
+            call("cz_set_batch_count", n_rows)
         try:
             z = self._hip_net_forward(planes)
             B = z.shape[0]
             value = torch.empty((B, 1), dtype=torch.float32, device=self.device)
-            vp = lambda t: C.c_void_p(t.data_ptr())
-            check(lib().cz_fc_heads_f32(h, vp(z), None, None, None, vp(self.hip_v1_wt), vp(self.hip_v1_b),
-                                        vp(self.hip_v2_w), vp(self.hip_v2_b), None, vp(value), B), "cz_fc_heads_f32")
+            call("cz_fc_heads_f32", z, None, None, None, self.hip_v1_wt, self.hip_v1_b, self.hip_v2_w, self.hip_v2_b, None, value, B)
         finally:
             if n_rows is not None:
-                check(lib().cz_set_batch_count(h, None), "cz_set_batch_count")
+                call("cz_set_batch_count", None)
         return z, value
 
     @torch.no_grad()
@@ -771,7 +717,7 @@ def trained_like_(net, planes_nhwc, seed=5):
         # both heads are calibrated on the given positions, whatever the depth of the tower: the policy FC is scaled so
         # that the largest logit of a position averages 10; the last value layer so that tanh's argument has mean 0 and
         # std 0.6 (a Glorot-initialised head answers ~-0.65 +- 0.03 for every position: no value signal for a search)
-        x = torch.as_tensor(np.asarray(planes_nhwc.cpu() if torch.is_tensor(planes_nhwc) else planes_nhwc, dtype=np.float32)).to(w.device).permute(0, 3, 1, 2)
+        x = _planes_f32(planes_nhwc, w.device).permute(0, 3, 1, 2)
         feats, vconv = [], []
         hook = m.value_fc2.register_forward_hook(lambda mod, inp, out: feats.append(inp[0].detach()))
         hook2 = m.value_conv.register_forward_hook(lambda mod, inp, out: vconv.append(out.detach()))

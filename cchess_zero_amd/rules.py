@@ -1,11 +1,10 @@
 """Batched rules ops K1-K3 over device tensors (host side of cz_movegen / cz_apply_move / cz_encode_planes)."""
-import ctypes as C
-
 import numpy as np
 import torch
 
-from ._lib import BF16, F16, F32, MASK_WORDS, MAXMOVES, NLABELS, NSQ, check, lib
-from .engine import Context, _ptr
+from ._lib import (BF16, F16, F32, MASK_WORDS, MAXMOVES, NLABELS, NSQ, POS_IN_CHECK, POS_NO_SAFE_MOVE, CchessHipError, call, out_pointers,
+                   tables)
+from .engine import Context
 
 
 RULES = {"capture": 0, "xiangqi": 1}   # cz_match_set_rules / cz_selfplay_set_rules
@@ -29,8 +28,20 @@ def set_rule_options(prefix, handle, rules, repetition, chase):
     an option that is off is left alone."""
     for name, value in (("rules", RULES[rules]), ("repetition", int(repetition)), ("chase", int(bool(chase)))):
         if value:
-            fn = "%s_set_%s" % (prefix, name)
-            check(getattr(lib(), fn)(handle, value), fn)
+            call("%s_set_%s" % (prefix, name), handle, value)
+
+
+def root_rules_history(prefix, handle, ctx, G):
+    """(keys u64 [G, 64], checks u8 [G, 64]) on the host: the slots' position rings of a match or a self-play context
+    (<prefix>_history; repetition != 0), position i of a slot's game at [i & 63]."""
+    pk, pc = out_pointers(prefix + "_history", handle, 2)
+    return ctx.download(pk, np.uint64, (G, 64)), ctx.download(pc, np.uint8, (G, 64))
+
+
+def root_rules_chase_history(prefix, handle, ctx, G):
+    """chase u64 [G, 64, 4] on the host: the slots' rings of chase records (<prefix>_chase_history; chase=True), position i of a
+    slot's game at [i & 63] — Rules.threats of that position."""
+    return ctx.download(out_pointers(prefix + "_chase_history", handle, 1)[0], np.uint64, (G, 64, 4))
 
 
 # the start position (main.py:585: RNBAKABNR/9/1C5C1/P1P1P1P1P/9/9/p1p1p1p1p/1c5c1/9/rnbakabnr) as piece codes, sq = 9 y + x
@@ -72,9 +83,7 @@ class Rules:
         self.dev = self.ctx.device
 
     def _dev(self, a, dtype):
-        if torch.is_tensor(a):
-            return a.to(self.dev).to(dtype).contiguous()
-        return torch.as_tensor(np.ascontiguousarray(a)).to(self.dev).to(dtype).contiguous()
+        return self.ctx.tensor(a, dtype)
 
     def movegen(self, boards, side, want_mask=True, want_moves=True, pad=True, strict=False):
         """GameBoard.get_legal_moves for G positions -> (moves [G,128] i16(u16 bits), count [G], mask [G,66] i32).
@@ -82,7 +91,6 @@ class Rules:
         pad=False (CZ_MOVES_NO_PAD): rows are valid up to their count only, the rest of the (uninitialised) buffer is not written.
         strict=True: raise if a board answered count 0xFFFF (not a Xiangqi set: its list / mask row is undefined; include/
         cchess_hip.h) — synchronises; without it a caller checks `count == -1` (0xFFFF as int16) itself before it reads rows."""
-        self.ctx.bind_stream()   # torch's current stream
         boards = self._dev(boards, torch.uint8).reshape(-1, NSQ)
         side = self._dev(side, torch.uint8)
         G = boards.shape[0]
@@ -90,9 +98,9 @@ class Rules:
         count = torch.empty(G, dtype=torch.int16, device=self.dev)
         mask = torch.empty((G, MASK_WORDS), dtype=torch.int32, device=self.dev) if want_mask else None
         if pad:
-            check(lib().cz_movegen(self.ctx.h, _ptr(boards), _ptr(side), G, _ptr(moves), _ptr(count), _ptr(mask)), "cz_movegen")
+            self.ctx.call("cz_movegen", boards, side, G, moves, count, mask)
         else:
-            check(lib().cz_movegen_ex(self.ctx.h, _ptr(boards), _ptr(side), G, _ptr(moves), _ptr(count), _ptr(mask), 1), "cz_movegen_ex")
+            self.ctx.call("cz_movegen_ex", boards, side, G, moves, count, mask, 1)
         if strict:
             self.check_counts(count)
         return moves, count, mask
@@ -102,7 +110,6 @@ class Rules:
         mover's king attacked) -> (moves [G,128] i16(u16 bits) or None, count [G], mask [G,66] i32 or None, pos_flags [G] u8:
         POS_IN_CHECK | POS_CAN_TAKE_KING | POS_NO_SAFE_MOVE).  pad=False: CZ_MOVES_NO_PAD, as in movegen.  A board movegen
         refuses answers count -1 (0xFFFF) here too."""
-        self.ctx.bind_stream()   # torch's current stream
         boards = self._dev(boards, torch.uint8).reshape(-1, NSQ)
         side = self._dev(side, torch.uint8)
         G = boards.shape[0]
@@ -110,18 +117,16 @@ class Rules:
         count = torch.empty(G, dtype=torch.int16, device=self.dev)
         mask = torch.empty((G, MASK_WORDS), dtype=torch.int32, device=self.dev) if want_mask else None
         pos_flags = torch.empty(G, dtype=torch.uint8, device=self.dev)
-        check(lib().cz_movegen_kingsafe(self.ctx.h, _ptr(boards), _ptr(side), G, _ptr(moves), _ptr(count), _ptr(mask), _ptr(pos_flags), 0 if pad else 1),
-              "cz_movegen_kingsafe")
+        self.ctx.call("cz_movegen_kingsafe", boards, side, G, moves, count, mask, pos_flags, 0 if pad else 1)
         return moves, count, mask, pos_flags
 
     def in_check(self, boards, side):
         """-> pos_flags [G] u8 alone (bit 0: the side to move is in check, bit 1: it can take the king, bit 2: it has no
         king-safe move): the launch that builds neither list nor set."""
-        self.ctx.bind_stream()   # torch's current stream
         boards = self._dev(boards, torch.uint8).reshape(-1, NSQ)
         side = self._dev(side, torch.uint8)
         pos_flags = torch.empty(boards.shape[0], dtype=torch.uint8, device=self.dev)
-        check(lib().cz_movegen_kingsafe(self.ctx.h, _ptr(boards), _ptr(side), boards.shape[0], None, None, None, _ptr(pos_flags), 0), "cz_movegen_kingsafe")
+        self.ctx.call("cz_movegen_kingsafe", boards, side, boards.shape[0], None, None, None, pos_flags, 0)
         return pos_flags
 
     def repetition(self, keys, in_check, side, length=None, window=None, fold=3):
@@ -130,7 +135,6 @@ class Rules:
         (the side to move in the current position), length [G] i32 (positions recorded; None: stride), window [G] i32 (how
         many earlier positions count; None: all) -> (verdict [G] u8: REP_NONE / REP_DRAW / REP_RED_LOSES / REP_BLACK_LOSES,
         first [G] i32: the earlier occurrence the cycle starts from, -1 without a verdict)."""
-        self.ctx.bind_stream()   # torch's current stream
         keys = self._dev(keys, torch.int64)
         keys = keys.reshape(-1, keys.shape[-1])
         G, stride = keys.shape
@@ -140,8 +144,7 @@ class Rules:
         window = None if window is None else self._dev(window, torch.int32).reshape(G)
         verdict = torch.empty(G, dtype=torch.uint8, device=self.dev)
         first = torch.empty(G, dtype=torch.int32, device=self.dev)
-        check(lib().cz_repetition(self.ctx.h, _ptr(keys), _ptr(in_check), stride, _ptr(length), _ptr(window), _ptr(side), G, int(fold),
-                                  _ptr(verdict), _ptr(first)), "cz_repetition")
+        self.ctx.call("cz_repetition", keys, in_check, stride, length, window, side, G, int(fold), verdict, first)
         return verdict, first
 
     def threats(self, boards, side):
@@ -149,11 +152,10 @@ class Rules:
         the other side threatens (squares 0 .. 63, 64 .. 89: an unprotected or more valuable piece under a king-safe attack by
         a rook, cannon, knight, advisor or bishop that is no exchange offer), words 2, 3 the squares of the side to move.  A
         board movegen refuses answers four zero words."""
-        self.ctx.bind_stream()   # torch's current stream
         boards = self._dev(boards, torch.uint8).reshape(-1, NSQ)
         side = self._dev(side, torch.uint8)
         chase = torch.empty((boards.shape[0], 4), dtype=torch.int64, device=self.dev)
-        check(lib().cz_threats(self.ctx.h, _ptr(boards), _ptr(side), boards.shape[0], _ptr(chase)), "cz_threats")
+        self.ctx.call("cz_threats", boards, side, boards.shape[0], chase)
         return chase
 
     def repetition_chase(self, keys, in_check, chase, side, length=None, window=None, fold=3):
@@ -161,7 +163,6 @@ class Rules:
         threats() of every position -> (verdict [G] u8, first [G] i32, cause [G] u8: CAUSE_NONE / CAUSE_CHECK / CAUSE_CHASE).
         Perpetual check by one side outranks a chase by the other; a side that alone chases one piece with every move of the
         cycle loses."""
-        self.ctx.bind_stream()   # torch's current stream
         keys = self._dev(keys, torch.int64)
         keys = keys.reshape(-1, keys.shape[-1])
         G, stride = keys.shape
@@ -173,8 +174,7 @@ class Rules:
         verdict = torch.empty(G, dtype=torch.uint8, device=self.dev)
         first = torch.empty(G, dtype=torch.int32, device=self.dev)
         cause = torch.empty(G, dtype=torch.uint8, device=self.dev)
-        check(lib().cz_repetition_chase(self.ctx.h, _ptr(keys), _ptr(in_check), _ptr(chase), stride, _ptr(length), _ptr(window), _ptr(side), G,
-                                        int(fold), _ptr(verdict), _ptr(first), _ptr(cause)), "cz_repetition_chase")
+        self.ctx.call("cz_repetition_chase", keys, in_check, chase, stride, length, window, side, G, int(fold), verdict, first, cause)
         return verdict, first, cause
 
     @staticmethod
@@ -183,19 +183,17 @@ class Rules:
         set; their rows are undefined and must not be consumed)."""
         bad = (count == -1).nonzero().flatten()
         if bad.numel():
-            from ._lib import CchessHipError
             raise CchessHipError("cz_movegen: %d position(s) are not a Xiangqi set (count 0xFFFF), first at index %d: their move rows are undefined"
                                  % (int(bad.numel()), int(bad[0])))
 
     def apply_move(self, boards, side, labels, hash_=None):
         """In-place GameBoard.sim_do_action for G games -> (captured [G] u8, terminal [G] i8)."""
-        self.ctx.bind_stream()   # torch's current stream
         G = boards.shape[0]
         assert boards.is_cuda and side.is_cuda and boards.dtype == torch.uint8 and boards.is_contiguous()
-        labels = self._dev(labels, torch.int16) if not (torch.is_tensor(labels) and labels.dtype == torch.int16) else labels.to(self.dev).contiguous()
+        labels = self._dev(labels, torch.int16)
         cap = torch.empty(G, dtype=torch.uint8, device=self.dev)
         term = torch.empty(G, dtype=torch.int8, device=self.dev)
-        check(lib().cz_apply_move(self.ctx.h, _ptr(boards), _ptr(side), _ptr(labels), G, _ptr(hash_), _ptr(cap), _ptr(term)), "cz_apply_move")
+        self.ctx.call("cz_apply_move", boards, side, labels, G, hash_, cap, term)
         return cap, term
 
     def successors(self, boards, side, moves, count):
@@ -203,7 +201,6 @@ class Rules:
         return them (padded or not; count -1, a refused board, has no children) -> (boards [T,90] u8, side [T] u8, captured
         [T] u8, parent [T] i32, label [T] i16), T the sum of the counts: child offsets[g] + j is parent g after moves[g][j], in
         list order.  Reading T back is the call's only synchronisation."""
-        self.ctx.bind_stream()   # torch's current stream
         boards = self._dev(boards, torch.uint8).reshape(-1, NSQ)
         side = self._dev(side, torch.uint8)
         G = boards.shape[0]
@@ -219,8 +216,7 @@ class Rules:
         cap = torch.empty(T, dtype=torch.uint8, device=self.dev)
         parent = torch.empty(T, dtype=torch.int32, device=self.dev)
         label = torch.empty(T, dtype=torch.int16, device=self.dev)
-        check(lib().cz_successors(self.ctx.h, _ptr(boards), _ptr(side), G, _ptr(moves), _ptr(offsets), T, _ptr(out), _ptr(cside), _ptr(cap),
-                                  _ptr(parent), _ptr(label)), "cz_successors")
+        self.ctx.call("cz_successors", boards, side, G, moves, offsets, T, out, cside, cap, parent, label)
         return out, cside, cap, parent, label
 
     PERFT_CHUNK = 1 << 17
@@ -235,7 +231,6 @@ class Rules:
         depth x chunk x (256 + 128 x 106) bytes — 128 children of 90 + 16 bytes per parent, 1.8 GB per level at the default,
         never reached: ~40 children per parent make it ~0.6 GB — not by the tree (133 M positions, 12 GB, at depth 5).
         Without stats the last ply is counted, not made: the count-only form of movegen_kingsafe on the frontier of depth - 1."""
-        from ._lib import POS_IN_CHECK, POS_NO_SAFE_MOVE
         boards = self._dev(boards, torch.uint8).reshape(-1, NSQ)
         side = self._dev(side, torch.uint8).reshape(-1)
         N, depth, chunk = boards.shape[0], int(depth), int(chunk or self.PERFT_CHUNK)
@@ -294,7 +289,6 @@ class Rules:
     def divide(self, board, side, depth):
         """Perft of ONE position split by its first move -> {ICCS label: the move sequences of length `depth` that start with
         it}, in list order: perft(depth - 1) over the root's successors, one pass."""
-        from ._lib import tables
         if int(depth) < 1:
             raise ValueError("Rules.divide: depth >= 1")
         board = self._dev(board, torch.uint8).reshape(1, NSQ)
@@ -307,19 +301,16 @@ class Rules:
         return {names[int(l)]: int(n) for l, n in zip(label.cpu().numpy().view(np.uint16), nodes)}
 
     def hash(self, boards, side):
-        self.ctx.bind_stream()   # torch's current stream
         boards = self._dev(boards, torch.uint8).reshape(-1, NSQ)
         side = self._dev(side, torch.uint8)
         h = torch.empty(boards.shape[0], dtype=torch.int64, device=self.dev)
-        check(lib().cz_hash(self.ctx.h, _ptr(boards), _ptr(side), boards.shape[0], _ptr(h)), "cz_hash")
+        self.ctx.call("cz_hash", boards, side, boards.shape[0], h)
         return h
 
     def encode_planes(self, boards, side, dtype=torch.float32, channels=14, quirk_q1=True):
-        self.ctx.bind_stream()   # torch's current stream
         boards = self._dev(boards, torch.uint8).reshape(-1, NSQ)
         side = self._dev(side, torch.uint8)
         G = boards.shape[0]
         out = torch.empty((G, 9, 10, channels), dtype=dtype, device=self.dev)
-        check(lib().cz_encode_planes(self.ctx.h, _ptr(boards), _ptr(side), G, _ptr(out), {torch.bfloat16: BF16, torch.float16: F16}.get(dtype, F32),
-                                     channels, 1 if quirk_q1 else 0), "cz_encode_planes")
+        self.ctx.call("cz_encode_planes", boards, side, G, out, {torch.bfloat16: BF16, torch.float16: F16}.get(dtype, F32), channels, 1 if quirk_q1 else 0)
         return out

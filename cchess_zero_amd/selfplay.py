@@ -21,14 +21,12 @@ Records are packed (include/cchess_hip.h CZ_REC_*: board, mover, <=128 (label, v
 expands them to the reference's training tuples (planes [9,10,14] f32, pi [2086], z).  pi is recomputed from the
 visit counts with the reference's own float64 expression, so it is bit-identical to what get_action returns.
 """
-import ctypes as C
-
 import numpy as np
 import torch
 
 from ._lib import (MAXMOVES, NLABELS, NSQ, REC_BYTES, REC_COUNT, REC_FLAGS, REC_LABELS, REC_PLY, REC_SIDE, REC_VISITS, REC_Z,
-                   SP_CHASE_STATS, SP_RULES_STATS, SP_STATS, check, lib, tables)
-from .rules import RULES, check_rule_options, set_rule_options
+                   SP_CHASE_STATS, SP_RULES_STATS, SP_STATS, out_pointers, tables)
+from .rules import RULES, check_rule_options, root_rules_chase_history, root_rules_history, set_rule_options
 
 REC_MAXMOVES = MAXMOVES
 
@@ -180,11 +178,9 @@ class SelfPlay:
         eng.reset(boards, side, rr)
         eng.compact = not self.continuous   # parked games drop out of the net's batch; a full batch needs no compaction
         G = eng.G
-        check(lib().cz_selfplay_begin(eng.ctx.h, self.max_plies, None, None, None), "cz_selfplay_begin")
+        eng.ctx.call("cz_selfplay_begin", self.max_plies, None, None, None)
         set_rule_options("cz_selfplay", eng.ctx.h, self.rules, self.repetition, self.chase)
-        p = C.c_void_p()
-        check(lib().cz_selfplay_active(eng.ctx.h, C.byref(p)), "cz_selfplay_active")
-        self._active_ptr = p
+        self._active_ptr, = out_pointers("cz_selfplay_active", eng.ctx.h, 1)
         R = int(self.ring_records or max(65536, 64 * G))
         self.ring = torch.zeros((R, REC_BYTES), dtype=torch.uint8, device=self.dev)
         self.cursor = torch.zeros(1, dtype=torch.int64, device=self.dev)       # records ever handed to the ring
@@ -225,27 +221,19 @@ class SelfPlay:
     def _transition(self, min_sims, forced=None, rand=None):
         """choose / advance / adjudicate / flush for every game (min_sims = 0) or for the games whose search has completed
         min_sims simulations (asynchronous plies).  rand: (gamma, u) replacing random_inputs() (gamma may be None)."""
-        eng, h = self.eng, self.eng.ctx.h
+        eng, ctx = self.eng, self.eng.ctx
         if rand is None:
             gamma, u = self.random_inputs()
         else:
-            dev_f32 = lambda t: None if t is None else torch.as_tensor(t, dtype=torch.float32).to(self.dev).contiguous()
-            gamma, u = dev_f32(rand[0]), dev_f32(rand[1])
+            gamma, u = ctx.tensor(rand[0], torch.float32), ctx.tensor(rand[1], torch.float32)
             assert (gamma is None or gamma.shape == (eng.G, MAXMOVES)) and u.shape == (eng.G,)
-        f = None
-        if forced is not None:
-            f = torch.as_tensor(np.ascontiguousarray(forced).view(np.int16) if not torch.is_tensor(forced) else forced).to(self.dev).contiguous()
-        vp = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        eng.ctx.bind_stream()
-        check(lib().cz_selfplay_choose(h, vp(gamma), vp(u), vp(f), self.temperature, 0.25 if self.exploration else 0.0,
-                                       int(min_sims), vp(self.played)), "cz_selfplay_choose")
+        f = ctx.tensor(forced, torch.int16)
+        ctx.call("cz_selfplay_choose", gamma, u, f, self.temperature, 0.25 if self.exploration else 0.0, int(min_sims), self.played)
         eng.advance(self.played)
-        check(lib().cz_selfplay_adjudicate(h, 1 if self.continuous else 0, vp(self.played) if min_sims > 0 else None,
-                                           vp(self.fin_n)), "cz_selfplay_adjudicate")
+        ctx.call("cz_selfplay_adjudicate", 1 if self.continuous else 0, self.played if min_sims > 0 else None, self.fin_n)
         csum = torch.cumsum(self.fin_n, 0, dtype=torch.int64)
         offset = csum - self.fin_n + self.cursor
-        check(lib().cz_selfplay_flush(h, vp(self.fin_n), vp(offset), vp(self.ring), self.ring.shape[0], vp(self.read_cursor)),
-              "cz_selfplay_flush")
+        ctx.call("cz_selfplay_flush", self.fin_n, offset, self.ring, self.ring.shape[0], self.read_cursor)
         self.cursor += csum[-1:]
 
     def run(self, plies, forward=None):
@@ -295,32 +283,16 @@ class SelfPlay:
     # -- host side --------------------------------------------------------------------------------------
     def active(self):
         """uint8 [G] host tensor: 1 = game in progress (synchronises)."""
-        self.eng.ctx.bind_stream()
-        buf = np.empty(self.eng.G, np.uint8)
-        check(lib().cz_download(self.eng.ctx.h, buf.ctypes.data_as(C.c_void_p), self._active_ptr, self.eng.G), "cz_download")
-        return torch.from_numpy(buf)
+        return torch.from_numpy(self.eng.ctx.download(self._active_ptr, np.uint8, self.eng.G))
 
     def history(self):
         """(keys u64 [G, 64], checks u8 [G, 64]) on the host: the slots' position rings (cz_selfplay_history; repetition != 0),
         position i of a slot's game at [i & 63]."""
-        G, L, h = self.eng.G, lib(), self.eng.ctx.h
-        self.eng.ctx.bind_stream()
-        pk, pc = C.c_void_p(), C.c_void_p()
-        check(L.cz_selfplay_history(h, C.byref(pk), C.byref(pc)), "cz_selfplay_history")
-        keys, checks = np.zeros((G, 64), np.uint64), np.zeros((G, 64), np.uint8)
-        for o, p in ((keys, pk), (checks, pc)):
-            check(L.cz_download(h, o.ctypes.data_as(C.c_void_p), p, o.nbytes), "cz_download")
-        return keys, checks
+        return root_rules_history("cz_selfplay", self.eng.ctx.h, self.eng.ctx, self.eng.G)
 
     def chase_history(self):
         """chase u64 [G, 64, 4] on the host: the slots' rings of chase records (cz_selfplay_chase_history; chase=True)."""
-        G, L, h = self.eng.G, lib(), self.eng.ctx.h
-        self.eng.ctx.bind_stream()
-        p = C.c_void_p()
-        check(L.cz_selfplay_chase_history(h, C.byref(p)), "cz_selfplay_chase_history")
-        out = np.zeros((G, 64, 4), np.uint64)
-        check(L.cz_download(h, out.ctypes.data_as(C.c_void_p), p, out.nbytes), "cz_download")
-        return out
+        return root_rules_chase_history("cz_selfplay", self.eng.ctx.h, self.eng.ctx, self.eng.G)
 
     def drain_device(self, on_overflow="raise"):
         """-> uint8 [n, REC_BYTES] DEVICE tensor with the records finished since the last drain (synchronises on the
@@ -331,8 +303,7 @@ class SelfPlay:
         (default), a RuntimeError says so; on_overflow = "skip" counts it in self.overflow_intervals and returns no rows
         (a long training run prefers losing one interval of samples to stopping).  Drain more often or pass a larger
         ring_records to avoid it."""
-        self.eng.ctx.bind_stream()
-        check(lib().cz_selfplay_stats(self.eng.ctx.h, C.c_void_p(self._stats.data_ptr())), "cz_selfplay_stats")
+        self.eng.ctx.call("cz_selfplay_stats", self._stats)
         dropped = int(self._stats[SP_STATS.index("dropped")].item())
         c = int(self.cursor.item())
         if dropped > self._dropped_seen:
@@ -367,15 +338,14 @@ class SelfPlay:
         rules="xiangqi" also mates, repetitions, perpetuals — the games among them that ended by mate (a win), by a repetition
         draw, by perpetual check (a win); with chase=True also chases — the games that ended by perpetual chase (a win; not
         among the perpetuals)."""
-        self.eng.ctx.bind_stream()
-        check(lib().cz_selfplay_stats(self.eng.ctx.h, C.c_void_p(self._stats.data_ptr())), "cz_selfplay_stats")
+        self.eng.ctx.call("cz_selfplay_stats", self._stats)
         s = self._stats.cpu().numpy()
         d = {k: int(v) for k, v in zip(SP_STATS, s)}
         if RULES[self.rules]:
-            check(lib().cz_selfplay_rules_stats(self.eng.ctx.h, C.c_void_p(self._rules_stats.data_ptr())), "cz_selfplay_rules_stats")
+            self.eng.ctx.call("cz_selfplay_rules_stats", self._rules_stats)
             d.update((k, int(v)) for k, v in zip(SP_RULES_STATS, self._rules_stats.cpu().numpy()))
         if self.chase:
-            check(lib().cz_selfplay_chase_stats(self.eng.ctx.h, C.c_void_p(self._chase_stats.data_ptr())), "cz_selfplay_chase_stats")
+            self.eng.ctx.call("cz_selfplay_chase_stats", self._chase_stats)
             d.update((k, int(v)) for k, v in zip(SP_CHASE_STATS, self._chase_stats.cpu().numpy()))
         d["sims"] += int(self.eng.status()[2].sum().item())   # + the simulations of the searches in progress
         d["plies_played"] = self.plies          # lock-step plies (step_ply)

@@ -132,16 +132,13 @@ class ClockProbe:
         self.readings = []
 
     def arm(self):
-        import ctypes as C
-        from ._lib import check, lib
-        check(lib().cz_set_clock_probe(self.ctx.h, C.c_void_p(self.buf.data_ptr()), self.n), "cz_set_clock_probe")
+        self.ctx.call("cz_set_clock_probe", self.buf, self.n)
 
     def disarm(self, collect=True):
         """Switch the probe off; with collect=True read the stamps of the last probed launch (synchronises)."""
         import torch
-        from ._lib import check, lib
-        grid = lib().cz_clock_probe_last_grid(self.ctx.h)
-        check(lib().cz_set_clock_probe(self.ctx.h, None, 0), "cz_set_clock_probe")
+        grid = self.ctx.call("cz_clock_probe_last_grid")
+        self.ctx.call("cz_set_clock_probe", None, 0)
         if not collect or grid <= 0:
             return None
         torch.cuda.synchronize()

@@ -669,3 +669,47 @@ def test_advance_ready_device_driver_matches_host_logic():
         x, y = a["stats"][k], b["stats"][k]
         assert torch.equal(x.view(torch.int32) if x.dtype.is_floating_point else x, y.view(torch.int32) if y.dtype.is_floating_point else y), k
     print("advance_ready: %d simulations banked, %d games restarted, identical under both drivers" % (a["banked"], a["reloaded"]))
+
+
+def test_every_call_goes_to_torchs_current_stream():
+    """SearchEngine.reset / set_sim_target / status / root_state and Rules.hash inside `with torch.cuda.stream(side)`: every call
+    binds the context to torch's current stream (Context.call), so the side stream's results equal the default stream's and a
+    status() behind a reset() on the side stream sees the reset — no simulations — although the trees had some a moment before,
+    from launches on the default stream."""
+    from cchess_zero_amd.engine import SearchEngine
+    from cchess_zero_amd.rules import START_BOARD, Rules
+    G = 3
+    boards, side = np.tile(START_BOARD, (G, 1)), np.zeros(G, np.uint8)
+    eng = SearchEngine(G, 4096)
+    rules = Rules(eng.ctx)
+    fwd = fakenet.make_forward("pos", 3)
+
+    def simulate(n):
+        for step in range(n):
+            planes, _ = eng.select(0 if step == 0 else 1)
+            lg, v = fwd(planes.cpu().numpy())
+            eng.expand_backup(torch.from_numpy(lg).cuda(), torch.from_numpy(v).cuda())
+
+    def fresh():
+        eng.reset(boards, side, None)
+        eng.set_sim_target(5)
+        b, s, rr = eng.root_state()
+        return [x.cpu().numpy() for x in eng.status()] + [b.cpu().numpy(), s.cpu().numpy(), rr.cpu().numpy(), rules.hash(b, s).cpu().numpy()]
+
+    try:
+        eng.reset(boards, side, None)
+        simulate(4)
+        assert (eng.status()[2].cpu().numpy() > 0).all()
+        ref = fresh()
+        simulate(4)
+        assert (eng.status()[2].cpu().numpy() > 0).all()
+        stream = torch.cuda.Stream()
+        stream.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(stream):
+            got = fresh()
+        torch.cuda.current_stream().wait_stream(stream)
+    finally:
+        eng.set_sim_target(0)
+    assert len(got) == len(ref) == 8 and all(np.array_equal(a, b) for a, b in zip(got, ref))
+    assert not got[2].any() and not ref[2].any()                      # status(): no simulations behind a reset
+    assert np.array_equal(got[4], boards) and got[7][0] == got[7][1] == got[7][2] != 0
