@@ -38,6 +38,7 @@ _SIGS = {
     "cz_version": (C.c_int, []),
     "cz_crc32c": (C.c_uint, [C.c_char_p, C.c_size_t]),
     "cz_tables": (C.c_int, [C.POINTER(C.c_void_p)] * 4),
+    "cz_mirror_table": (C.c_int, [C.POINTER(C.c_void_p)]),
     "cz_zobrist": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
     "cz_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "cz_destroy": (None, [C.c_void_p]),
@@ -57,6 +58,7 @@ _SIGS = {
     "cz_successors": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_int, _u16p, _i32p, C.c_int, _u8p, _u8p, _u8p, _i32p, _u16p]),
     "cz_hash": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_int, _vp]),
     "cz_encode_planes": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_int, _vp, C.c_int, C.c_int, C.c_int]),
+    "cz_records_expand": (C.c_int, [C.c_void_p, _u8p, C.c_int, _u8p, C.c_double, _f32p, _f32p, _f32p]),
     "cz_search_reset": (C.c_int, [C.c_void_p, _u8p, _u8p, _i32p, C.c_int]),
     "cz_search_set_eval_cache": (C.c_int, [C.c_void_p, C.c_int]),
     "cz_search_eval_cache_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]),
@@ -187,7 +189,8 @@ _tables = None
 
 
 def tables():
-    """Host copies of the static tables: dict(lut[90,90] i16, unflip[2086] i16, labels[2086] str, srcdst[2086] u16)."""
+    """Host copies of the static tables: dict(lut[90,90] i16, unflip[2086] i16, mirror[2086] i16 — the label of the move mirrored
+    across the e-file —, labels[2086] str, srcdst[2086] u16)."""
     global _tables
     if _tables is None:
         p = [C.c_void_p() for _ in range(4)]
@@ -197,10 +200,13 @@ def tables():
         raw = C.string_at(p[2], NLABELS * 5)
         labels = [raw[i * 5:i * 5 + 4].decode() for i in range(NLABELS)]
         srcdst = np.ctypeslib.as_array(C.cast(p[3], C.POINTER(C.c_uint16)), shape=(NLABELS,)).copy()
+        mp = C.c_void_p()
+        call("cz_mirror_table", C.byref(mp))
+        mirror = np.ctypeslib.as_array(C.cast(mp, C.POINTER(C.c_int16)), shape=(NLABELS,)).copy()
         zk = C.c_void_p()
         sk = C.c_uint64()
         call("cz_zobrist", C.byref(zk), C.byref(sk))
         zob = np.ctypeslib.as_array(C.cast(zk, C.POINTER(C.c_uint64)), shape=(15 * NSQ,)).reshape(15, NSQ).copy()
-        _tables = dict(lut=lut, unflip=unflip, labels=labels, srcdst=srcdst, zobrist=zob, zobrist_side=int(sk.value),
+        _tables = dict(lut=lut, unflip=unflip, mirror=mirror, labels=labels, srcdst=srcdst, zobrist=zob, zobrist_side=int(sk.value),
                        label2i={s: i for i, s in enumerate(labels)})
     return _tables

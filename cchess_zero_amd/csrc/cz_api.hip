@@ -81,6 +81,11 @@ int cz_tables(const int16_t **lut, const int16_t **unflip, const char **labels, 
     return CZ_OK;
 }
 
+int cz_mirror_table(const int16_t **mirror) {
+    if (mirror) *mirror = cz_host_tables().mirror;
+    return CZ_OK;
+}
+
 int cz_zobrist(const uint64_t **keys, uint64_t *side_key) {
     const CzHostTables &t = cz_host_tables();
     if (keys) *keys = t.zob;
@@ -105,17 +110,21 @@ int cz_create(int device, int max_games, int max_nodes_per_tree, cz_ctx **out) {
     {
         Carver m{nullptr};
         m.take<int16_t>(CZ_NSQ * CZ_NSQ); m.take<int16_t>(CZ_NLABELS); m.take<uint16_t>(CZ_NLABELS); m.take<uint64_t>(15 * CZ_NSQ + 1);
+        m.take<int16_t>(CZ_NLABELS);
         if (hipMalloc(&c->tab_block, m.off) != hipSuccess) { cz_set_error("cz_create: hipMalloc(tables) failed"); delete c; return CZ_ENOMEM; }
         Carver k{(char *)c->tab_block};
         int16_t *lut = k.take<int16_t>(CZ_NSQ * CZ_NSQ);
         int16_t *unf = k.take<int16_t>(CZ_NLABELS);
         uint16_t *sd = k.take<uint16_t>(CZ_NLABELS);
         uint64_t *zb = k.take<uint64_t>(15 * CZ_NSQ + 1);
+        int16_t *mir = k.take<int16_t>(CZ_NLABELS);
         CZ_HIP(hipMemcpy(lut, ht.lut, sizeof(ht.lut), hipMemcpyHostToDevice));
         CZ_HIP(hipMemcpy(unf, ht.unflip, sizeof(ht.unflip), hipMemcpyHostToDevice));
         CZ_HIP(hipMemcpy(sd, ht.srcdst, sizeof(ht.srcdst), hipMemcpyHostToDevice));
         CZ_HIP(hipMemcpy(zb, ht.zob, sizeof(ht.zob), hipMemcpyHostToDevice));
+        CZ_HIP(hipMemcpy(mir, ht.mirror, sizeof(ht.mirror), hipMemcpyHostToDevice));
         c->tab.lut = lut; c->tab.unflip = unf; c->tab.srcdst = sd; c->tab.zob = zb;
+        c->tab_mirror = mir;
         CzmTables mt = {};   // the mask-only generator's per-square tables, derived from the label LUT
         czm_build_tables(ht.lut, &mt);
         CzmTables *dmt = nullptr;
@@ -282,6 +291,17 @@ int cz_encode_planes(cz_ctx *c, const uint8_t *boards, const uint8_t *side, int 
     CZ_REQUIRE(dtype == CZ_F32 || dtype == CZ_BF16 || dtype == CZ_F16, "cz_encode_planes: dtype must be CZ_F32, CZ_BF16 or CZ_F16");
     CZ_REQUIRE(channels >= 14 && channels <= 64, "cz_encode_planes: 14 <= channels <= 64");
     return czk_encode_planes(c, boards, side, G, planes, dtype, channels, quirk);
+}
+int cz_records_expand(cz_ctx *c, const uint8_t *records, int n, const uint8_t *mirror, double temperature, float *planes, float *pi, float *z) {
+    CZ_REQUIRE(c && n >= 0, "cz_records_expand: null ctx / negative n");
+    CZ_REQUIRE(temperature > 0.0, "cz_records_expand: temperature > 0 required");   // false for a NaN too
+    CZ_REQUIRE(planes && pi && z, "cz_records_expand: planes, pi, z required");
+    if (n == 0) return CZ_OK;
+    CZ_REQUIRE(records, "cz_records_expand: records required");
+    CZ_REQUIRE((reinterpret_cast<uintptr_t>(records) & 3u) == 0 && (reinterpret_cast<uintptr_t>(pi) & 7u) == 0 &&
+                   (reinterpret_cast<uintptr_t>(planes) & 3u) == 0 && (reinterpret_cast<uintptr_t>(z) & 3u) == 0,
+               "cz_records_expand: records 4-byte, pi 8-byte, planes and z 4-byte aligned");
+    return czk_records_expand(c, records, n, mirror, temperature, planes, pi, z);
 }
 
 int cz_search_set_width(cz_ctx *c, int width) {

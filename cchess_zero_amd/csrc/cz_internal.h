@@ -52,6 +52,7 @@ struct CzHostTables {
     char labels[CZ_NLABELS * 5];
     int16_t lut[CZ_NSQ * CZ_NSQ];
     int16_t unflip[CZ_NLABELS];
+    int16_t mirror[CZ_NLABELS];   // the label of the move mirrored across the e-file (an involution; cz_mirror_table)
     uint16_t srcdst[CZ_NLABELS];
     uint64_t zob[15 * CZ_NSQ + 1];  // [15*90] = side key
 };
@@ -189,6 +190,7 @@ struct cz_ctx {
     int max_games, cap, G;
     CzTables tab;      // device tables
     void *tab_block;   // single allocation behind `tab`
+    const int16_t *tab_mirror;   // [2086] device copy of CzHostTables::mirror, in tab_block (cz_records_expand alone reads it)
     CzTrees t;
     void *tree_block;  // single allocation behind the per-tree arrays
     void *pool_block;
@@ -437,6 +439,7 @@ int czk_selfplay_seed(cz_ctx *, const uint8_t *, const uint8_t *, const int32_t 
 int czk_selfplay_choose(cz_ctx *, const float *, const float *, const uint16_t *, double, float, int, uint16_t *);   // by c->sp_rules / sp.rr.fold / c->sp_chase
 int czk_selfplay_adjudicate(cz_ctx *, int, const uint16_t *, int32_t *);
 int czk_selfplay_flush(cz_ctx *, const int32_t *, const long long *, uint8_t *, long long, const long long *);
+int czk_records_expand(cz_ctx *, const uint8_t *, int, const uint8_t *, double, float *, float *, float *);   // cz_records.hip
 
 // ---- the rules at the root, host side (cz_rootrules.h; cz_match.hip, cz_selfplay.hip / cz_api.hip) ----
 // the arrays of G slots inside the carver's allocation: the chase rings (chase_part), or everything else

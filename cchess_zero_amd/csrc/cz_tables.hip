@@ -4,7 +4,8 @@
 // square (file-major: 'a'..'i' outer, rank 0..9 inner) all same-rank destinations, all same-file
 // destinations, then the on-board knight jumps in the fixed offset order; then 16 advisor and
 // 32 bishop literals.  label2i (main.py:217) becomes a 90x90 LUT; unflipped_index (main.py:214)
-// is the rank mirror (digit d -> 9-d, main.py:23-27) looked up through that LUT.
+// is the rank mirror (digit d -> 9-d, main.py:23-27) looked up through that LUT.  mirror is the FILE mirror (letter
+// a..i -> i..a, digits unchanged) looked up the same way: the board's left-right symmetry on the labels (cz_records.hip).
 #include "cz_internal.h"
 
 #include <mutex>
@@ -56,6 +57,8 @@ CzHostTables *build() {
         const int s = b.t.srcdst[i] & 0xFF, d = b.t.srcdst[i] >> 8;
         const int ms = (9 - s / 9) * 9 + s % 9, md = (9 - d / 9) * 9 + d % 9;
         b.t.unflip[i] = b.t.lut[ms * CZ_NSQ + md];
+        const int fs = s / 9 * 9 + (8 - s % 9), fd = d / 9 * 9 + (8 - d % 9);
+        b.t.mirror[i] = b.t.lut[fs * CZ_NSQ + fd];
     }
     // Zobrist keys: fixed seed, piece-major then square, side key last (format defined by this project).
     uint64_t st = 0xC0FFEE1234567ull;

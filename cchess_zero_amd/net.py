@@ -689,8 +689,11 @@ class PolicyValueNet:
     @torch.no_grad()
     def forward(self, positions):
         """Reference signature (policy_value_network.py:202-214): ndarray or list of [9,10,14] ->
-        (logits [B,2086] float32 ndarray, value [B,1] float32 ndarray)."""
-        x = torch.as_tensor(np.asarray(positions, dtype=np.float32)).to(self.device)
+        (logits [B,2086] float32 ndarray, value [B,1] float32 ndarray).  A tensor (on the device already) is taken as it is."""
+        if torch.is_tensor(positions):
+            x = positions.to(self.device, torch.float32)
+        else:
+            x = torch.as_tensor(np.asarray(positions, dtype=np.float32)).to(self.device)
         if x.dim() == 3:
             x = x.unsqueeze(0)
         logits, v = self.forward_device(x)

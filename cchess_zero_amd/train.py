@@ -68,10 +68,10 @@ class Trainer:
 
     def _tensors(self, positions, probs, winners):
         dev = self.device
-        x = torch.as_tensor(np.asarray(positions, dtype=np.float32)).to(dev).permute(0, 3, 1, 2)
-        pi = torch.as_tensor(np.asarray(probs, dtype=np.float32)).to(dev)
-        z = torch.as_tensor(np.asarray(winners, dtype=np.float32)).to(dev).reshape(-1, 1)
-        return x, pi, z
+
+        def f32(a):   # a tensor (records.RecordExpander's, already on the device) as it is; arrays and lists through numpy
+            return a.to(dev, torch.float32) if torch.is_tensor(a) else torch.as_tensor(np.asarray(a, dtype=np.float32)).to(dev)
+        return f32(positions).permute(0, 3, 1, 2), f32(probs), f32(winners).reshape(-1, 1)
 
     def loss(self, positions, probs, winners, training=True):
         """-> (loss, accuracy): policy_value_network.py:77-92,108-111.  training=True uses batch statistics in the
@@ -171,7 +171,7 @@ def kl_estimate_rows(old_probs, new_probs):
 
 
 def policy_update(net, data_buffer, batch_size, epochs, learning_rate, lr_multiplier, kl_targ, seed=0, log=print, temperature=1.0,
-                  save=True, sample=None):
+                  save=True, sample=None, mirror=False, expand=None):
     """cchess_main.policy_update (main.py:1157-1204).  net: forward(list of planes) -> (logits, value) ndarrays,
     train_step(...) -> (accuracy, loss, global_step), save(step), global_step.  Returns (lr_multiplier, info dict).
 
@@ -181,7 +181,13 @@ def policy_update(net, data_buffer, batch_size, epochs, learning_rate, lr_multip
     every rank because every rank holds the same gathered buffer —, rank r trains on elements r::world of it, and the
     KL estimate is averaged over the ranks before the early-stop / learning-rate decisions.
     save=False skips the checkpoint (the batched loop of main.py saves once per self-play batch, not once per update);
-    sample: explicit buffer indices instead of the seeded draw (tests)."""
+    sample: explicit buffer indices instead of the seeded draw (tests).
+    mirror=True (packed records only): every drawn sample is learnt from as it is or as its left-right mirror image
+    (records.mirror_records), one coin per drawn index from the same generator, after the index draw — so every rank flips
+    the same coins and takes its slice of them with its slice of the indices; info["mirrored"] counts this rank's mirrored samples.
+    expand: records.RecordExpander(...).expand (or any callable (records [n,608] u8, flags [n] u8 or None, temperature) ->
+    (planes, pi, z)): the mini-batch is built by it — on the device, nothing of the host expansion below runs — instead of
+    selfplay.to_dense.  With mirror=False and expand=None the path and the random draws are exactly the ones described above."""
     world = dist.get_world_size() if _dist_on() else 1
     rank = dist.get_rank() if _dist_on() else 0
     rng = random.Random((int(seed) << 32) ^ int(net.global_step))
@@ -189,12 +195,23 @@ def policy_update(net, data_buffer, batch_size, epochs, learning_rate, lr_multip
         raise ValueError("batch_size %d is smaller than the number of ranks %d: a rank would train on nothing" % (batch_size, world))
     # main.py:1159 (random.sample): indices are drawn, the buffer itself (possibly hundreds of thousands of records) is not copied
     idx = list(sample) if sample is not None else rng.sample(range(len(data_buffer)), batch_size)
+    flags = np.array([rng.getrandbits(1) for _ in idx], np.uint8)[rank::world] if mirror else None
     mini_batch = [data_buffer[i] for i in idx[rank::world]]
-    if isinstance(mini_batch[0], np.ndarray) and mini_batch[0].dtype == np.uint8 and mini_batch[0].ndim == 1:
+    packed = isinstance(mini_batch[0], np.ndarray) and mini_batch[0].dtype == np.uint8 and mini_batch[0].ndim == 1
+    if (mirror or expand is not None) and not packed:
+        raise ValueError("policy_update: mirror / expand work on packed self-play records, the buffer holds dense tuples")
+    if expand is not None:
+        state_batch, mcts_probs_batch, z = expand(np.stack(mini_batch), flags, temperature)
+        winner_batch = z.reshape(-1, 1)
+    elif packed:
         # the buffer holds PACKED records (608 bytes each instead of 22 KB of dense planes + pi): only the mini-batch is
         # expanded to the reference's (state planes, pi[2086], z) tuples, pi with the reference's exact float64 expression
         from .selfplay import to_dense
-        planes, pi, z = to_dense(np.stack(mini_batch), temperature, exact=True)
+        records = np.stack(mini_batch)
+        if mirror:
+            from .records import mirror_records
+            records = mirror_records(records, flags)
+        planes, pi, z = to_dense(records, temperature, exact=True)
         state_batch, mcts_probs_batch, winner_batch = list(planes), list(pi), np.expand_dims(z, 1)
     else:
         state_batch = [d[0] for d in mini_batch]
@@ -231,9 +248,10 @@ def policy_update(net, data_buffer, batch_size, epochs, learning_rate, lr_multip
         lr_multiplier *= 1.5
     # the figures the reference logs (main.py:1197-1198): winner_batch is [B,1] there and old_v.flatten() is [B], so the
     # difference broadcasts to a [B,B] matrix of z_i - v_j — reproduced as written (a report, nothing is decided on it)
-    wb = np.array(winner_batch)
+    wb = winner_batch.cpu().numpy() if torch.is_tensor(winner_batch) else np.array(winner_batch)
     with np.errstate(all="ignore"):
         info = dict(kl=kl, lr_multiplier=lr_multiplier, loss=loss, accuracy=accuracy, steps=steps,
                     explained_var_old=1 - np.var(wb - np.asarray(old_v).flatten()) / np.var(wb),
-                    explained_var_new=1 - np.var(wb - np.asarray(new_v).flatten()) / np.var(wb))
+                    explained_var_new=1 - np.var(wb - np.asarray(new_v).flatten()) / np.var(wb),
+                    mirrored=int(flags.sum()) if mirror else 0)
     return lr_multiplier, info

@@ -96,6 +96,11 @@ int cz_version(void);
  *   labels = 2086 x 5 chars ("a0a1\0");   srcdst[i] = src | dst << 8. */
 int cz_tables(const int16_t **lut90x90, const int16_t **unflip2086, const char **labels,
               const uint16_t **srcdst);
+/* The left-right symmetry of the board on the move vocabulary (host pointer, valid for the process lifetime; the reference has
+ * no such table): mirror2086[i] = the label of move i with both files mirrored across the e-file (a..i -> i..a, ranks
+ * unchanged), looked up through the 90x90 LUT like unflip2086.  A permutation and an involution; its 90 fixed points are the
+ * vertical moves on the e-file; it commutes with unflip2086. */
+int cz_mirror_table(const int16_t **mirror2086);
 /* Zobrist keys used by cz_hash / cz_apply_move: keys[15][90] (row 0 unused), side key.
  * The reference has no state hash (identity = the state string); this format is ours. */
 int cz_zobrist(const uint64_t **keys15x90, uint64_t *side_key);
@@ -234,6 +239,22 @@ int cz_successors(cz_ctx *, const uint8_t *boards, const uint8_t *side, int G, c
  *     reference bit for bit; 0 gives the transposed encoding its shapes suggest. */
 int cz_encode_planes(cz_ctx *, const uint8_t *boards, const uint8_t *side, int G, void *planes,
                      int dtype, int channels, int quirk_q1);
+/* Record expansion  replaces the host side of cchess_main.run's data_buffer.extend (main.py:1234-1240) for packed records: n
+ *     CZ_REC_* records on the device -> the training tuples, planes [n][9][10][14] f32 (generate_inputs of the record's board
+ *     for its mover, quirk Q1), pi [n][2086] f32 (softmax(1 / temperature * log(visits)) in float64 — get_action's expression,
+ *     main.py:1341; no visit at all: 1 / count each — rounded to float32 and scattered over the children's labels in canonical
+ *     orientation, main.py:1507-1512; 0 elsewhere; count 0: a zero row), z [n] f32.  mirror [n] (device; NULL = none): a record
+ *     with mirror[i] != 0 is expanded as its LEFT-RIGHT MIRROR IMAGE — the board read with its files reversed (cell (rank, f)
+ *     from (rank, 8 - f)) and every label mapped through cz_mirror_table — an equally valid sample of the same game.  The
+ *     mirror acts before try_flip / unflip and the encoding; it is not a flip of the plane tensor (the planes are read with a
+ *     9-stride).  The children of a mirrored record stay in the order they were generated for the unmirrored board.
+ *     Every element of planes, pi and z is written exactly once.  Records from anywhere are safe: a count above 128 is taken
+ *     as 128, a label >= 2086 has no cell in pi (its visits still count in the softmax), nothing outside the n records and the
+ *     three output arrays is touched.  n == 0: CZ_OK, no launch.  CZ_EINVAL: n < 0, temperature <= 0, a NULL output, records
+ *     or planes or z not 4-byte aligned, pi not 8-byte aligned. */
+int cz_records_expand(cz_ctx *, const uint8_t *records /* [n][CZ_REC_BYTES], device */, int n,
+                      const uint8_t *mirror /* [n] 0/1, or NULL = none */, double temperature,
+                      float *planes /* [n][9][10][14] */, float *pi /* [n][2086] */, float *z /* [n] */);
 
 /* ---- lock-step search over G trees, one wavefront per tree ---------------------------------
  * replaces: MCTS_tree.__init__/reload (main.py:235-259): fresh, unexpanded roots. */

@@ -341,6 +341,10 @@ class cchess_main(object):
         self.last_evaluation = None
         self.rules, self.repetition = "capture", 0   # the batched self-play games and the evaluation matches (--rules, --repetition)
         self.chase = False                            # ... and whether they judge perpetual chase (--chase)
+        # --mirror_augment: every sample a policy update draws is learnt from as it is or as its left-right mirror image, and the
+        # mini-batch is built on the GPU from the packed records (cchess_zero_amd/records.py)
+        self.mirror_augment = False
+        self.mirrored_samples = 0
 
     @staticmethod
     def flip_policy(prob):
@@ -593,9 +597,18 @@ class cchess_main(object):
 
     def policy_update(self, save=True):
         from cchess_zero_amd.train import policy_update
+        expand = None
+        if self.mirror_augment:
+            if getattr(self, "_expander", None) is None:
+                import torch
+                from cchess_zero_amd.records import RecordExpander
+                eng = getattr(self, "_batch_eng", None)   # the self-play engine's context: same device, same stream
+                self._expander = RecordExpander(ctx=eng.ctx) if eng is not None else RecordExpander(device=torch.cuda.current_device())
+            expand = self._expander.expand
         self.lr_multiplier, info = policy_update(self.policy_value_netowrk, self.data_buffer, self.batch_size, self.epochs,
                                                  self.learning_rate, self.lr_multiplier, self.kl_targ, seed=self.update_seed,
-                                                 temperature=self.temperature, save=save)
+                                                 temperature=self.temperature, save=save, mirror=self.mirror_augment, expand=expand)
+        self.mirrored_samples += info["mirrored"]
         self.global_step = self.policy_value_netowrk.global_step
         msg = "kl:{:.5f},lr_multiplier:{:.3f},loss:{},accuracy:{},explained_var_old:{:.3f},explained_var_new:{:.3f}".format(
             info["kl"], self.lr_multiplier, info["loss"], info["accuracy"], info["explained_var_old"], info["explained_var_new"])
@@ -632,7 +645,7 @@ class cchess_main(object):
                 order = np.random.RandomState(self.update_seed + batch_iter).permutation(n)   # same on every rank
                 self.data_buffer.extend(rec[i] for i in order)
                 t1 = time.time()
-                updates = 0
+                updates, mirrored_before = 0, self.mirrored_samples
                 if len(self.data_buffer) > self.batch_size:
                     updates = max(1, min(64, n // self.batch_size))
                     for u in range(updates):   # the reference saves after its one update per game (main.py:1188): once per batch here
@@ -647,6 +660,8 @@ class cchess_main(object):
                           "eval_cache": bool(getattr(self._sp, "eval_cache", False)), "xcache_log2": int(getattr(self._sp, "xcache_log2", 0))}
                 if "chases" in st:
                     timing["chases"] = int(st["chases"])
+                if self.mirror_augment:
+                    timing["mirrored_samples"] = int(self.mirrored_samples - mirrored_before)   # of this rank's slices of the batch's updates
                 msg = "batch_timing: " + json.dumps(timing)
                 print(msg, flush=True)
                 self.log_file.write(msg + '\n')
@@ -721,6 +736,9 @@ if __name__ == '__main__':
                              'or a loss for the side that checked perpetually; 0 = no repetition rule')
     parser.add_argument('--chase', action='store_true',
                         help='with --repetition: a side that alone chased one unprotected piece with every move of the cycle loses')
+    parser.add_argument('--mirror_augment', action='store_true',
+                        help='policy updates learn from every drawn sample as it is or as its left-right mirror image (one coin per '
+                             'sample), and build the mini-batch on the GPU from the packed records')
     parser.add_argument('--net_precision', default=None, choices=['strict', 'mx6', 'fp16x2', 'fp16', 'bf16', 'bf16x2', 'fp32'], type=str,
                         help='net engine (policy_value_network.PRECISIONS): strict (default) = measured within 5e-4 absolute of the '
                              'fp32 graph on 64 positions with the LIVE weights after every weight change, falling over mx6 -> fp16x2 -> '
@@ -755,6 +773,7 @@ if __name__ == '__main__':
                                  args.res_block_nums, args.human_color, games=args.games)
         train_main.eval_every, train_main.eval_games = args.eval_every, args.eval_games
         train_main.rules, train_main.repetition, train_main.chase = args.rules, args.repetition, args.chase
+        train_main.mirror_augment = args.mirror_augment
         train_main.run(args.max_batches)
         if os.environ.get("CCHESS_WEIGHT_DIGEST_DIR"):   # tests: every rank leaves a digest of its replica (they must be equal)
             import hashlib
