@@ -40,6 +40,36 @@ void carve_trees(Carver &c, CzTrees &t, size_t G, size_t words) {
 
 }  // namespace
 
+// Tree g's expansion records in pre-order (children in generation order, the root itself not numbered): the numbering of
+// cz_search_tree_dump's records, which cz_search_debug_eval_cache_dump reports its entries' nodes in.  A record that points
+// outside the tree's nodes ends the walk: what was numbered so far stands.
+int cz_tree_preorder(cz_ctx *c, int g, CzPreorder &o) {
+    int32_t root = 0;
+    CZ_HIP(hipMemcpy(&root, &c->t.root_node[g], 4, hipMemcpyDeviceToHost));
+    CZ_HIP(hipMemcpy(&o.n, &c->t.n_nodes[g], 4, hipMemcpyDeviceToHost));
+    const int n = o.n;
+    const size_t base = (size_t)g * (size_t)c->cap;
+    std::vector<int32_t> &cb = o.child_begin;
+    std::vector<uint16_t> &cc = o.child_count;
+    cb.resize(n); cc.resize(n);
+    CZ_HIP(hipMemcpy(cb.data(), c->t.pool.child_begin + base, 4 * (size_t)n, hipMemcpyDeviceToHost));
+    CZ_HIP(hipMemcpy(cc.data(), c->t.pool.child_count + base, 2 * (size_t)n, hipMemcpyDeviceToHost));
+    o.root = root >= 0 && root < n ? root : -1;
+    o.node.clear(); o.depth.clear();
+    struct Frame { int node, next, depth; };
+    std::vector<Frame> st;
+    if (o.root >= 0 && cb[root] >= 0) st.push_back({root, 0, 0});
+    while (!st.empty()) {
+        Frame &f = st.back();
+        if (f.next >= cc[f.node]) { st.pop_back(); continue; }
+        const int ch = cb[f.node] + f.next++, depth = f.depth;
+        if (ch < 0 || ch >= n) break;
+        o.node.push_back(ch); o.depth.push_back(depth);
+        if (cb[ch] >= 0) st.push_back({ch, 0, depth + 1});
+    }
+    return CZ_OK;
+}
+
 extern "C" {
 
 const char *cz_last_error(void) { return g_err; }
@@ -331,155 +361,9 @@ int cz_search_set_sim_target(cz_ctx *c, int target) {
     return CZ_OK;
 }
 
-int cz_search_set_eval_cache(cz_ctx *c, int on) {
-    CZ_REQUIRE(c, "cz_search_set_eval_cache: null ctx");
-    if (on && c->width != 1) { cz_set_error("cz_search_set_eval_cache: needs width 1 (one simulation in flight per tree)"); return CZ_EINVAL; }
-    const size_t per = (size_t)c->max_games * CZ_EC_ENTRIES;
-    if (on && !c->ec_block) {
-        // per entry: key 8 B, node 4 B, value 4 B, the packed position 48 B; per tree: the pending leaf's packed position
-        const size_t bytes = per * (8 + 4 + 4 + 48) + (size_t)c->max_games * 48;
-        CZ_HIP(hipSetDevice(c->device));
-        if (hipMalloc(&c->ec_block, bytes) != hipSuccess) { c->ec_block = nullptr; cz_set_error("cz_search_set_eval_cache: hipMalloc(%zu B) failed", bytes); return CZ_ENOMEM; }
-    }
-    if (on) {
-        char *b = (char *)c->ec_block;
-        c->t.ec_key = (unsigned long long *)b;
-        c->t.ec_node = (int32_t *)(b + per * 8);
-        c->t.ec_val = (float *)(b + per * 12);
-        c->t.ec_board = (uint32_t *)(b + per * 16);
-        c->t.pend_board = (uint32_t *)(b + per * 64);
-        if (!c->t.ec_key_mask) c->t.ec_key_mask = ~0ull;
-        // an empty cache: entries of an earlier use would point into trees that no longer exist
-        CZ_HIP(hipMemsetAsync(c->ec_block, 0, per * 8, c->stream));
-        czk_search_clear_cache_stats(c);
-        if (c->t.xc_base) CZ_HIP(hipMemsetAsync(c->xc_block, 0, ((size_t)1 << c->xc_log2_entries) * 16 + 64, c->stream));   // and the cross-tree level (keys, values, counts)
-    } else {
-        c->t.ec_key = nullptr; c->t.ec_node = nullptr; c->t.ec_val = nullptr; c->t.ec_board = nullptr; c->t.pend_board = nullptr;
-        if (c->xc_block) return cz_search_set_xcache(c, 0);   // the cross-tree level lives behind the per-tree probe
-    }
-    return CZ_OK;
-}
-int cz_search_set_xcache(cz_ctx *c, int log2_entries) {
-    CZ_REQUIRE(c && (log2_entries == 0 || (log2_entries >= 6 && log2_entries <= 24)), "cz_search_set_xcache: log2_entries must be 0 (off) or 6..24");
-    CZ_HIP(hipSetDevice(c->device));
-    if (log2_entries == 0 || (c->xc_block && c->xc_log2_entries != log2_entries)) {
-        if (c->xc_block) { CZ_HIP(hipStreamSynchronize(c->stream)); (void)hipFree(c->xc_block); }
-        c->xc_block = nullptr; c->xc_log2_entries = 0;
-        c->t.xc_base = nullptr; c->t.xc_mask = 0;
-        if (log2_entries == 0) return CZ_OK;
-    }
-    if (!c->t.ec_key) { cz_set_error("cz_search_set_xcache: switch the per-tree evaluation cache on first (cz_search_set_eval_cache(ctx, 1))"); return CZ_EINVAL; }
-    const size_t n = (size_t)1 << log2_entries;
-    // per entry: key 8, value 4, count 4, position 48, labels 256, (src, dst) 256, priors 512 = 1088 bytes; + 32 bytes of counters per tree
-    if (!c->xc_block) {
-        const size_t bytes = n * 1088 + 64 + (size_t)c->max_games * 32;
-        if (hipMalloc(&c->xc_block, bytes) != hipSuccess) { c->xc_block = nullptr; cz_set_error("cz_search_set_xcache: hipMalloc(%zu B) failed", bytes); return CZ_ENOMEM; }
-        c->xc_log2_entries = log2_entries;
-        c->t.xc_base = (char *)c->xc_block;
-        c->t.xc_mask = (uint32_t)(n / 64 - 1);
-    }
-    // an empty table (new weights => remembered evaluations are stale): keys, values and count | ply words (a full bucket's
-    // victim is chosen by the ply of every slot: no slot may carry a ply of an earlier use or uninitialised memory)
-    CZ_HIP(hipMemsetAsync(c->xc_block, 0, n * 16 + 64, c->stream));
-    CZ_HIP(hipMemsetAsync(czx_tree_stats(c->t), 0, (size_t)c->max_games * 32, c->stream));
-    return CZ_OK;
-}
-static int xcache_stats5(cz_ctx *c, unsigned long long *stats, int n) {
-    for (int k = 0; k < n; ++k) stats[k] = 0;
-    if (!c->t.xc_base) return CZ_OK;
-    std::vector<uint32_t> per((size_t)c->max_games * 8);     // per tree: hits, lookups, written, no room, replaced, 3 spare
-    CZ_HIP(hipMemcpyAsync(per.data(), czx_tree_stats(c->t), per.size() * 4, hipMemcpyDeviceToHost, c->stream));
-    CZ_HIP(hipStreamSynchronize(c->stream));
-    for (size_t g = 0; g < (size_t)c->max_games; ++g)
-        for (int k = 0; k < n; ++k) stats[k] += per[g * 8 + k];
-    return CZ_OK;
-}
-int cz_search_xcache_stats(cz_ctx *c, unsigned long long *stats4) {
-    CZ_REQUIRE(c && stats4, "cz_search_xcache_stats: null argument");
-    return xcache_stats5(c, stats4, 4);
-}
-int cz_search_xcache_stats5(cz_ctx *c, unsigned long long *stats5) {
-    CZ_REQUIRE(c && stats5, "cz_search_xcache_stats5: null argument");
-    return xcache_stats5(c, stats5, 5);
-}
-int cz_search_debug_xcache_dump(cz_ctx *c, void *host, size_t bytes) {
-    CZ_REQUIRE(c, "cz_search_debug_xcache_dump: null context");
-    if (!c->t.xc_base) { cz_set_error("cz_search_debug_xcache_dump: the cross-tree table is off"); return CZ_EINVAL; }
-    const size_t n = czx_n(c->t), need = n * 1088 + 64;
-    if (!host) return (int)n;
-    if (bytes < need) { cz_set_error("cz_search_debug_xcache_dump: %zu bytes < %zu", bytes, need); return CZ_EINVAL; }
-    CZ_HIP(hipStreamSynchronize(c->stream));
-    CZ_HIP(hipMemcpy(host, c->t.xc_base, need, hipMemcpyDeviceToHost));
-    return (int)n;
-}
-int cz_search_debug_eval_cache_dump(cz_ctx *c, int g, unsigned long long *key, int32_t *node, float *value, uint32_t *board,
-                                    int32_t *record) {
-    CZ_REQUIRE(c && c->G > 0 && g >= 0 && g < c->G, "cz_search_debug_eval_cache_dump: bad tree index");
-    if (!c->t.ec_key) { cz_set_error("cz_search_debug_eval_cache_dump: the evaluation cache is off"); return CZ_EINVAL; }
-    CZ_HIP(hipStreamSynchronize(c->stream));
-    const size_t e0 = (size_t)g * CZ_EC_ENTRIES;
-    std::vector<unsigned long long> k(CZ_EC_ENTRIES);
-    std::vector<int32_t> nd(CZ_EC_ENTRIES);
-    CZ_HIP(hipMemcpy(k.data(), c->t.ec_key + e0, 8 * (size_t)CZ_EC_ENTRIES, hipMemcpyDeviceToHost));
-    CZ_HIP(hipMemcpy(nd.data(), c->t.ec_node + e0, 4 * (size_t)CZ_EC_ENTRIES, hipMemcpyDeviceToHost));
-    if (key) memcpy(key, k.data(), 8 * (size_t)CZ_EC_ENTRIES);
-    if (node) memcpy(node, nd.data(), 4 * (size_t)CZ_EC_ENTRIES);
-    if (value) CZ_HIP(hipMemcpy(value, c->t.ec_val + e0, 4 * (size_t)CZ_EC_ENTRIES, hipMemcpyDeviceToHost));
-    if (board) CZ_HIP(hipMemcpy(board, c->t.ec_board + e0 * 12, 48 * (size_t)CZ_EC_ENTRIES, hipMemcpyDeviceToHost));
-    if (record) {
-        // the entry's node as cz_search_tree_dump numbers it: the same pre-order walk over the tree's expansion records
-        int32_t root = 0, n = 0;
-        CZ_HIP(hipMemcpy(&root, &c->t.root_node[g], 4, hipMemcpyDeviceToHost));
-        CZ_HIP(hipMemcpy(&n, &c->t.n_nodes[g], 4, hipMemcpyDeviceToHost));
-        const size_t base = (size_t)g * (size_t)c->cap;
-        std::vector<int32_t> cb(n), rec(n, -2);
-        std::vector<uint16_t> cc(n);
-        CZ_HIP(hipMemcpy(cb.data(), c->t.pool.child_begin + base, 4 * (size_t)n, hipMemcpyDeviceToHost));
-        CZ_HIP(hipMemcpy(cc.data(), c->t.pool.child_count + base, 2 * (size_t)n, hipMemcpyDeviceToHost));
-        std::vector<std::pair<int, int>> st;   // (node, next child)
-        int nrec = 0;
-        if (root >= 0 && root < n) { rec[root] = -1; if (cb[root] >= 0) st.push_back({root, 0}); }
-        while (!st.empty()) {
-            auto &f = st.back();
-            if (f.second >= cc[f.first]) { st.pop_back(); continue; }
-            const int ch = cb[f.first] + f.second++;
-            if (ch < 0 || ch >= n) break;   // a broken record: what was numbered so far stands, the rest stays "not in the tree"
-            rec[ch] = nrec++;
-            if (cb[ch] >= 0) st.push_back({ch, 0});
-        }
-        for (int i = 0; i < CZ_EC_ENTRIES; ++i) record[i] = (k[i] && nd[i] >= 0 && nd[i] < n) ? rec[nd[i]] : -2;
-    }
-    return CZ_EC_ENTRIES;
-}
-int cz_search_debug_eval_cache_key_bits(cz_ctx *c, int bits) {
-    CZ_REQUIRE(c && (bits == 64 || (bits >= 8 && bits <= 24)), "cz_search_debug_eval_cache_key_bits: bits must be 8..24 or 64");
-    // narrowed keys keep the 7-bit bucket field (bits 17..23) plus the bits - 7 lowest bits: entries still spread over the buckets
-    c->t.ec_key_mask = bits == 64 ? ~0ull : ((0x7Full << 17) | ((1ull << (bits - 7)) - 1ull));
-    return CZ_OK;
-}
 int cz_search_debug_advance_in_global_memory(cz_ctx *c, int on) {
     CZ_REQUIRE(c, "cz_search_debug_advance_in_global_memory: null context");
     c->adv_force_global = on != 0;
-    return CZ_OK;
-}
-int cz_search_eval_cache_collisions(cz_ctx *c, unsigned long long *collisions) {
-    CZ_REQUIRE(c && collisions, "cz_search_eval_cache_collisions: null argument");
-    *collisions = 0;
-    if (c->G <= 0) return CZ_OK;
-    std::vector<CzTreeRec> h((size_t)c->G);
-    CZ_HIP(hipMemcpyAsync(h.data(), c->t.rec, h.size() * sizeof(CzTreeRec), hipMemcpyDeviceToHost, c->stream));
-    CZ_HIP(hipStreamSynchronize(c->stream));
-    for (int g = 0; g < c->G; ++g) *collisions += h[(size_t)g].ec_collisions;
-    return CZ_OK;
-}
-int cz_search_eval_cache_stats(cz_ctx *c, unsigned long long *hits, unsigned long long *lookups) {
-    CZ_REQUIRE(c && hits && lookups, "cz_search_eval_cache_stats: null argument");
-    *hits = 0; *lookups = 0;
-    if (c->G <= 0) return CZ_OK;
-    std::vector<CzTreeRec> h((size_t)c->G);
-    CZ_HIP(hipMemcpyAsync(h.data(), c->t.rec, h.size() * sizeof(CzTreeRec), hipMemcpyDeviceToHost, c->stream));
-    CZ_HIP(hipStreamSynchronize(c->stream));
-    for (int g = 0; g < c->G; ++g) { *hits += h[(size_t)g].ec_hits; *lookups += h[(size_t)g].ec_lookups; }
     return CZ_OK;
 }
 int cz_search_set_terminal_extra(cz_ctx *c, int n) {
@@ -695,39 +579,26 @@ int cz_selfplay_stats(cz_ctx *c, long long *stats_dev) {
 int cz_search_tree_dump(cz_ctx *c, int g, int32_t *out, int max_records) {
     CZ_REQUIRE(c && c->G > 0 && g >= 0 && g < c->G, "cz_search_tree_dump: bad tree index");
     CZ_HIP(hipStreamSynchronize(c->stream));
-    int32_t root = 0, n = 0;
-    CZ_HIP(hipMemcpy(&root, &c->t.root_node[g], 4, hipMemcpyDeviceToHost));
-    CZ_HIP(hipMemcpy(&n, &c->t.n_nodes[g], 4, hipMemcpyDeviceToHost));
+    CzPreorder po;
+    if (const int rc = cz_tree_preorder(c, g, po)) return rc;
+    const int n = po.n, nrec = (int)po.node.size();
+    if (!out) return nrec;
     const CzPool &p = c->t.pool;
     const size_t base = (size_t)g * (size_t)c->cap;
     std::vector<float> P(n), W(n), Q(n);
-    std::vector<int32_t> N(n), cb(n);
-    std::vector<uint16_t> cc(n), mv(n);
+    std::vector<int32_t> N(n);
+    std::vector<uint16_t> mv(n);
     CZ_HIP(hipMemcpy(P.data(), p.P + base, 4 * (size_t)n, hipMemcpyDeviceToHost));
     CZ_HIP(hipMemcpy(W.data(), p.W + base, 4 * (size_t)n, hipMemcpyDeviceToHost));
     CZ_HIP(hipMemcpy(Q.data(), p.Q + base, 4 * (size_t)n, hipMemcpyDeviceToHost));
     CZ_HIP(hipMemcpy(N.data(), p.N + base, 4 * (size_t)n, hipMemcpyDeviceToHost));
-    CZ_HIP(hipMemcpy(cb.data(), p.child_begin + base, 4 * (size_t)n, hipMemcpyDeviceToHost));
-    CZ_HIP(hipMemcpy(cc.data(), p.child_count + base, 2 * (size_t)n, hipMemcpyDeviceToHost));
     CZ_HIP(hipMemcpy(mv.data(), p.move + base, 2 * (size_t)n, hipMemcpyDeviceToHost));
-    // iterative pre-order
-    struct Frame { int node, next; int depth; };
-    std::vector<Frame> st;
-    int nrec = 0;
-    if (cb[root] >= 0) st.push_back({root, 0, 0});
     auto bits = [](float f) { int32_t i; memcpy(&i, &f, 4); return i; };
-    while (!st.empty()) {
-        Frame &f = st.back();
-        if (f.next >= cc[f.node]) { st.pop_back(); continue; }
-        const int ch = cb[f.node] + f.next++;
-        const int depth = f.depth;
-        if (nrec < max_records && out) {
-            int32_t *r = out + (size_t)nrec * 7;
-            r[0] = depth; r[1] = mv[ch]; r[2] = N[ch]; r[3] = bits(W[ch]); r[4] = bits(Q[ch]); r[5] = bits(P[ch]);
-            r[6] = cb[ch] < 0 ? -1 : cc[ch];
-        }
-        ++nrec;
-        if (cb[ch] >= 0) st.push_back({ch, 0, depth + 1});
+    for (int k = 0; k < nrec && k < max_records; ++k) {
+        const int ch = po.node[k];
+        int32_t *r = out + (size_t)k * 7;
+        r[0] = po.depth[k]; r[1] = mv[ch]; r[2] = N[ch]; r[3] = bits(W[ch]); r[4] = bits(Q[ch]); r[5] = bits(P[ch]);
+        r[6] = po.child_begin[ch] < 0 ? -1 : po.child_count[ch];
     }
     return nrec;
 }

@@ -6,6 +6,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string>
+#include <vector>
 
 #include "../../include/cchess_hip.h"
 #include "cz_device.h"
@@ -92,15 +93,6 @@ struct CzSelfplay {
     long long *chase_stat;       // [1] games ended by perpetual chase (cz_selfplay_chase_stats)
 };
 
-#define CZ_EC_BUCKETS 128
-// cross-tree table: the bit that marks an entry whose payload is being written (claimed as key | CZ_XC_BUSY, not yet published);
-// no position's key has it (wave_position_key clears it), so a claim still tells the other trees which position it is for
-#define CZ_XC_BUSY (1ull << 63)
-#define CZ_EC_ENTRIES (CZ_EC_BUCKETS * 64)
-#ifndef CZ_EC_BUDGET
-#define CZ_EC_BUDGET 4   // evaluation-cache hits a tree may complete inside one select launch (its own budget, beside terminal_extra)
-#endif
-
 // Per-tree scalars: ONE 64-byte record per tree instead of sixteen arrays.  A wave owns a tree, so what it reads at entry
 // (root, counters, status) and leaves behind (the pending leaf) is one cache line, and the kernels hold one base pointer
 // instead of sixteen (the select kernels spilled 30-60 SGPRs keeping the array bases alive).  Kernel code keeps the array
@@ -154,28 +146,14 @@ struct CzTrees {
     float *pk_value;
     uint8_t *pk_side;
     uint16_t *pk_nmoves;
-    // evaluation cache (cz_search_set_eval_cache): per tree CZ_EC_BUCKETS buckets of 64 entries {Zobrist key of an expanded
-    // node's position, its node index, the value its evaluation backed up}.  The priors are the node's children's P.
+    // evaluation cache (cz_evalcache.h: what it is, its layout, the kernels' helpers).  Per-tree level, cz_search_set_eval_cache:
     unsigned long long *ec_key;       // [max_games][CZ_EC_ENTRIES]  0 = empty      (NULL: cache off)
     int32_t *ec_node;                 // [max_games][CZ_EC_ENTRIES]
     float *ec_val;                    // [max_games][CZ_EC_ENTRIES]
     uint32_t *ec_board;               // [max_games][CZ_EC_ENTRIES][12] the entry's position, packed (wave_pack_board): checked on every hit
     uint32_t *pend_board;             // [max_games][12] packed position of the pending leaf (select -> expand_backup)
     unsigned long long ec_key_mask;   // ~0; tests narrow it (cz_search_debug_eval_cache_key_bits) to force key collisions
-    // cross-tree level of the evaluation cache (cz_search_set_xcache): ONE table per context, shared by all of its trees.  An
-    // entry cannot lend node indices (the lender tree's nodes move at its next re-root), so it is self-contained: key, packed
-    // position, the value the evaluation backed up, the move count, the <= 128 labels / (src, dst) pairs / priors.  Entries are
-    // claimed by k_expand_backup with an atomic compare-and-swap on the key — an empty slot of the key's 64-entry bucket, or,
-    // when the bucket is full (round 6), the entry whose position lies DEEPEST in its game (game ply = re-roots of the filing tree
-    // + depth of the leaf, kept in the upper half of the move-count word) if the new position is shallower: the table converges
-    // to the shallowest positions ever evaluated — the openings every restarted game walks through again — instead of whatever
-    // arrived first.  A filing claims its slot by swapping the key to key | CZ_XC_BUSY, writes the payload write-through and only
-    // then stores the real key, so a slot is never claimed twice before its payload is in memory.  k_select (a later launch: the
-    // kernel boundary publishes the payload) only reads, and verifies the stored position on every hit.  Emptied by the host
-    // (keys, values and counts) whenever the weights change.
-    // ONE base pointer (the kernels are short of scalar registers): with n = (xc_mask + 1) * 64 entries the block holds
-    //   keys u64 [n] | counters u64 [8] | value f32 [n] | move count u32 [n] | position u32 [n][12] | labels u16 [n][128] |
-    //   (src, dst) u16 [n][128] | priors f32 [n][128]        (czx_* below)
+    // cross-tree level, cz_search_set_xcache: ONE table per context behind ONE base pointer, its arrays through czx_*
     char *xc_base;                    // NULL: off
     uint32_t xc_mask;                 // buckets - 1 (a power of two); a bucket = 64 consecutive entries
     // compact evaluation batches (cz_search_select_compact): row of the step's leaf in planes / z / value, or -1
@@ -223,20 +201,6 @@ struct cz_ctx {
     void *ec_block;    // cz_search_set_eval_cache
 };
 
-// cross-tree cache: the arrays inside CzTrees::xc_base
-__host__ __device__ __forceinline__ size_t czx_n(const CzTrees &t) { return ((size_t)t.xc_mask + 1) * 64; }
-__host__ __device__ __forceinline__ unsigned long long *czx_key(const CzTrees &t) { return reinterpret_cast<unsigned long long *>(t.xc_base); }
-// statistics: PER TREE, [max_games][4] uint32 (hits, lookups, entries written, claims lost) behind the entries, updated by the
-// tree's own wave without atomics — four counters of the context bumped with same-address atomics by every probe of every tree
-// cost the select launch 95 us of its 167 (profiles/r04x_xcache_stats_atomics.txt); cz_search_xcache_stats sums them
-__host__ __device__ __forceinline__ uint32_t *czx_tree_stats(const CzTrees &t) { return reinterpret_cast<uint32_t *>(t.xc_base + czx_n(t) * 1088 + 64); }
-__host__ __device__ __forceinline__ float *czx_val(const CzTrees &t) { return reinterpret_cast<float *>(t.xc_base + czx_n(t) * 8 + 64); }
-__host__ __device__ __forceinline__ uint32_t *czx_cnt(const CzTrees &t) { return reinterpret_cast<uint32_t *>(t.xc_base + czx_n(t) * 12 + 64); }
-__host__ __device__ __forceinline__ uint32_t *czx_board(const CzTrees &t) { return reinterpret_cast<uint32_t *>(t.xc_base + czx_n(t) * 16 + 64); }
-__host__ __device__ __forceinline__ uint16_t *czx_moves(const CzTrees &t) { return reinterpret_cast<uint16_t *>(t.xc_base + czx_n(t) * 64 + 64); }
-__host__ __device__ __forceinline__ uint16_t *czx_sd(const CzTrees &t) { return reinterpret_cast<uint16_t *>(t.xc_base + czx_n(t) * 320 + 64); }
-__host__ __device__ __forceinline__ float *czx_P(const CzTrees &t) { return reinterpret_cast<float *>(t.xc_base + czx_n(t) * 576 + 64); }
-
 // ---- device helpers shared by cz_search.hip / cz_selfplay.hip / cz_match.hip ----------------------
 struct TreeView {
     float *P, *W, *Q;
@@ -261,12 +225,7 @@ __device__ __forceinline__ void init_root(TreeView v, int idx) {
     v.child_count[idx] = 0; v.move[idx] = 0xFFFF; v.sd[idx] = 0;
 }
 
-// evaluation cache: forget everything tree g knows (fresh root: reset / reload / re-seed / failed advance)
-__device__ __forceinline__ void ec_clear_tree(const CzTrees &t, int g, int tid, int nthreads) {
-    if (!t.ec_key) return;
-    unsigned long long *k = t.ec_key + (size_t)g * CZ_EC_ENTRIES;
-    for (int i = tid; i < CZ_EC_ENTRIES; i += nthreads) k[i] = 0ull;
-}
+#include "cz_evalcache.h"   // the evaluation cache: layout, czx_* accessors, ec_* / xc_* device helpers
 
 // ---- a game at a root (the bench loop of cz_search.hip, cz_selfplay.hip, cz_match.hip) -----------
 // MCTS_tree.reload (main.py:255-259): a fresh, unexpanded root for tree g on the position the root has, by one wave64.
@@ -440,6 +399,15 @@ int czk_selfplay_choose(cz_ctx *, const float *, const float *, const uint16_t *
 int czk_selfplay_adjudicate(cz_ctx *, int, const uint16_t *, int32_t *);
 int czk_selfplay_flush(cz_ctx *, const int32_t *, const long long *, uint8_t *, long long, const long long *);
 int czk_records_expand(cz_ctx *, const uint8_t *, int, const uint8_t *, double, float *, float *, float *);   // cz_records.hip
+
+// ---- a tree's records in pre-order, host side (cz_api.hip; cz_search_tree_dump, cz_search_debug_eval_cache_dump) ----
+struct CzPreorder {
+    int32_t n, root;                      // the tree's node count; its root node, -1 if that is no node of the tree
+    std::vector<int32_t> child_begin;     // [n] the expansion records as downloaded
+    std::vector<uint16_t> child_count;    // [n]
+    std::vector<int32_t> node, depth;     // [records] record k is node[k], depth[k] levels below the root's children
+};
+int cz_tree_preorder(cz_ctx *c, int g, CzPreorder &out);   // after a stream synchronise
 
 // ---- the rules at the root, host side (cz_rootrules.h; cz_match.hip, cz_selfplay.hip / cz_api.hip) ----
 // the arrays of G slots inside the carver's allocation: the chase rings (chase_part), or everything else

@@ -130,44 +130,6 @@ __device__ __forceinline__ void write_leaf(bool eval, const CzTrees &t, size_t r
     }
 }
 
-// Zobrist key of the position in LDS: cz_hash without its top bit, which marks "being written" in the cross-tree table
-// (CZ_XC_BUSY); 0 is reserved for "empty" in the evaluation cache (a position with key 0 is filed under 1)
-__device__ __forceinline__ unsigned long long wave_position_key(const uint8_t *b, int side, const uint64_t *__restrict__ zob, int lane) {
-    unsigned long long h = 0ull;
-    const int c0 = b[lane];
-    if (c0) h = zob[c0 * CZ_NSQ + lane];
-    if (lane + 64 < CZ_NSQ) { const int c1 = b[lane + 64]; if (c1) h ^= zob[c1 * CZ_NSQ + lane + 64]; }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) h ^= __shfl_xor(h, d, 64);
-    if (side) h ^= zob[15 * CZ_NSQ];
-    // the key is wave-uniform: keep it in scalar registers (the select kernel sits exactly at its 64-VGPR budget)
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)h), hi = __builtin_amdgcn_readfirstlane((uint32_t)(h >> 32));
-    h = ((unsigned long long)hi << 32) | lo;
-    h &= ~CZ_XC_BUSY;
-    return h ? h : 1ull;
-}
-// write-through store (agent scope, sc1): reaches memory, not only this XCD's L2 — followed by s_waitcnt vmcnt(0), the value is
-// in memory before anything stored after the wait (the cross-tree table's payload before its key)
-template <typename T> __device__ __forceinline__ void st_through(T *p, T x) {
-    __hip_atomic_store((__attribute__((address_space(1))) T *)p, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ int ec_bucket(unsigned long long key) { return (int)((key >> 17) & (CZ_EC_BUCKETS - 1)); }
-__device__ __forceinline__ uint32_t xc_bucket(unsigned long long key) { return (uint32_t)(key >> 24); }   // cross-tree table: other key bits
-// The position itself, packed: 90 squares x 4 bits (piece codes 0..14) in 12 dwords, side to move in the top nibble of the
-// last one.  Lane j < 12 packs squares 8j .. 8j+7 (LDS bytes 90..95 of the board are zero).  A cache entry carries this
-// image of its node's position and a hit is only taken when it equals the leaf's: the 64-bit key finds the candidate, the
-// position decides — a key collision cannot lend a wrong node.
-__device__ __forceinline__ uint32_t wave_pack_board(const uint8_t *b, int side, int lane) {
-    uint32_t pk = 0u;
-    if (lane < 12) {
-        const uint32_t w0 = ((const uint32_t *)b)[2 * lane], w1 = ((const uint32_t *)b)[2 * lane + 1];
-        pk = (w0 & 15u) | ((w0 >> 4) & 0xF0u) | ((w0 >> 8) & 0xF00u) | ((w0 >> 12) & 0xF000u);
-        pk |= ((w1 & 15u) | ((w1 >> 4) & 0xF0u) | ((w1 >> 8) & 0xF00u) | ((w1 >> 12) & 0xF000u)) << 16;
-        if (lane == 11) pk |= (uint32_t)side << 28;
-    }
-    return pk;
-}
-
 // COMPACT: the leaf planes of the trees that need a net evaluation are written to consecutive rows handed out by an
 // atomic counter (t.evcnt[parity]); t.slot_of[g] records the row (or -1), the other counter is zeroed for the next
 // step.  Terminal / drawn / parked trees then cost the net nothing (they are 9 % of the simulations on the bench
@@ -299,78 +261,19 @@ __device__ __forceinline__ void select_body(const CzTrees &t, const CzTables &ta
                 const bool may_cache = cache_left > 0 && depth <= CZ_PATH_MAX;
                 bool full = false;
                 if (CACHE && kind == 1) {
-                    // Evaluation cache.  The net is a pure function of (board, side to move) and every row of a batch is
-                    // computed independently of the others, so a position this tree has evaluated before would get the
-                    // same priors and value, bit for bit.  An expanded node with the same key lends its children's move
-                    // labels and priors and the value its evaluation backed up: the simulation completes here, without
-                    // a net row, and the tree is the one the net would have produced.
-                    key = wave_position_key(b, side, tab.zob, lane) & t.ec_key_mask;
-                    key = key ? key : 1ull;
-                    pk = wave_pack_board(b, side, lane);
+                    // Evaluation cache (cz_evalcache.h).  An expanded node of this tree with the leaf's position — or, behind it,
+                    // a cross-tree entry — lends its children's move labels and priors and the value its evaluation backed up:
+                    // the simulation completes here, without a net row, and the tree is the one the net would have produced.
+                    ec_leaf_key(t, b, side, tab.zob, lane, key, pk);
                     bool hit = false;
-                    int src = 0;
-                    unsigned long long xk = 0ull;   // XC: the cross-tree bucket's keys, requested together with the tree's own
-                    if (may_cache) {
-                        const size_t eb0 = (size_t)g * CZ_EC_ENTRIES + (size_t)ec_bucket(key) * 64;
-                        const unsigned long long ek = t.ec_key[eb0 + lane];
-                        if (XC) xk = czx_key(t)[(size_t)(xc_bucket(key) & t.xc_mask) * 64 + lane];   // one wait for both probes
-                        const int en = t.ec_node[eb0 + lane];
-                        const float ev = t.ec_val[eb0 + lane];
-                        // every entry of the bucket with the leaf's key is a candidate (after a key collision two positions
-                        // share a key): the stored position decides
-                        for (unsigned long long m = __ballot(ek == key); m; m &= m - 1ull) {
-                            const int hl = __ffsll((long long)m) - 1;
-                            // the candidate's position against the leaf's: 12 lanes, one dword each
-                            const uint32_t lb = lane < 12 ? t.ec_board[(eb0 + hl) * 12 + lane] : 0u;
-                            if (__ballot(lb != pk) == 0ull) {
-                                src = __builtin_amdgcn_readlane(en, hl);
-                                pend = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ev), hl));
-                                hit = true;
-                                break;
-                            }
-                            if (lane == 0) t.ec_collisions[g] += 1u;   // same key, another position: not this entry
-                        }
-                        if (lane == 0) { t.ec_hits[g] += hit ? 1u : 0u; t.ec_lookups[g] += 1u; }
-                    }
-                    // second level (XC kernels): the context's cross-tree table (cz_search_set_xcache) — a position ANOTHER tree
-                    // has had evaluated.  Its entries are self-contained (labels, (src, dst), priors, value) and read-only here.
-                    long long xe = -1;
-                    if (XC && !hit && may_cache) {
-                        const size_t xb0 = (size_t)(xc_bucket(key) & t.xc_mask) * 64;
-                        for (unsigned long long m = __ballot(xk == key); m; m &= m - 1ull) {
-                            const int hl = __ffsll((long long)m) - 1;
-                            const uint32_t lb = lane < 12 ? czx_board(t)[(xb0 + hl) * 12 + lane] : 0u;
-                            if (__ballot(lb != pk) == 0ull) { xe = (long long)(xb0 + hl); break; }
-                        }
-                        if (xe >= 0) { pend = czx_val(t)[xe]; hit = true; }
-                        if (lane == 0) { uint32_t *xs = czx_tree_stats(t) + (size_t)g * 8; xs[1] += 1u; if (xe >= 0) xs[0] += 1u; }
-                    }
+                    int lender = 0;         // the lender: an expanded node of this tree ...
+                    long long xe = -1;      // ... or (XC kernels) an entry of the context's cross-tree table
+                    unsigned long long xk = 0ull;   // XC: the cross-tree bucket's keys, which ec_probe requests with the tree's own
+                    if (may_cache) hit = ec_probe<XC>(t, g, key, pk, lane, lender, pend, xk);
+                    if (XC && !hit && may_cache) { xe = xc_probe(t, g, key, pk, xk, lane, pend); hit = xe >= 0; }
                     if (!hit) break;
-                    // the lender: an expanded node of this tree (its children's arrays) or a cross-tree entry's arrays
-                    const int scb = (XC && xe >= 0) ? 0 : v.child_begin[src];
-                    const int n = (XC && xe >= 0) ? (int)(czx_cnt(t)[xe] & 0xFFFFu) : (int)v.child_count[src];
-                    const int begin = t.n_nodes[g];
-                    if (begin + n <= t.cap) {   // leaf_node.expand with the lender's priors
-#pragma unroll
-                        for (int r = 0; r < 2; ++r) {
-                            const int i = lane + 64 * r;
-                            if (i < n) {
-                                const int c = begin + i;
-                                if (XC && xe >= 0) {
-                                    const size_t o = (size_t)xe * CZD_MAXMOVES + i;
-                                    v.P[c] = czx_P(t)[o]; v.move[c] = czx_moves(t)[o]; v.sd[c] = czx_sd(t)[o];
-                                } else {
-                                    v.P[c] = v.P[scb + i]; v.move[c] = v.move[scb + i]; v.sd[c] = v.sd[scb + i];
-                                }
-                                v.W[c] = 0.f; v.Q[c] = 0.f; v.N[c] = 0; v.parent[c] = leaf; v.child_begin[c] = -1;
-                                v.child_count[c] = 0;
-                            }
-                        }
-                        if (lane == 0) { v.child_begin[leaf] = begin; v.child_count[leaf] = (uint16_t)n; t.n_nodes[g] = begin + n; }
-                    } else {
-                        if (lane == 0) t.status[g] |= CZ_ST_POOL_EXHAUSTED;
-                        full = true;   // this simulation is still backed up; the tree then stops, as it does after k_expand_backup
-                    }
+                    // pool exhausted: this simulation is still backed up; the tree then stops, as it does after k_expand_backup
+                    full = !ec_expand_from<XC>(t, v, g, leaf, lender, xe, lane);
                 } else if (!(kind == 2 && may)) break;
                 // back_up_value along the path, exactly as k_expand_backup does it: lane d owns the node of level d
                 if (lane < depth) backup_level(v, path_s[lane], ((depth - 1 - lane) & 1) ? pend * -1.0f : pend);
@@ -404,11 +307,7 @@ __device__ __forceinline__ void select_body(const CzTrees &t, const CzTables &ta
     }
     write_leaf<T>(kind == 1 || kind == 3, t, (size_t)g, mv, nmoves, b, side, !COMPACT, pl, C, one, lane);
     if (CACHE && (kind == 1 || kind == 3)) {
-        if (kind == 3) {
-            key = wave_position_key(b, side, tab.zob, lane) & t.ec_key_mask;
-            key = key ? key : 1ull;
-            pk = wave_pack_board(b, side, lane);
-        }
+        if (kind == 3) ec_leaf_key(t, b, side, tab.zob, lane, key, pk);   // kind 1 has them from its lookup
         if (lane == 0) t.pend_key[g] = key;
         if (lane < 12) t.pend_board[(size_t)g * 12 + lane] = pk;   // k_expand_backup files it with the cache entry
     }
@@ -634,101 +533,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_num_sgpr(80), amdgpu_num_
         }
         val = to_f32<T>(value[FC ? row : g]) * -1.0f;  // return value[0] * -1, main.py:384
         if (t.ec_key && fits) {
-            // evaluation cache: this node now holds the priors of its position (its children's P), `val` is what its
-            // evaluation backs up.  First empty entry of the key's bucket; a full bucket replaces a pseudo-random entry.
+            // evaluation cache (cz_evalcache.h): remember the evaluation for this tree and, with the cross-tree level on, for the others
             const unsigned long long key = t.pend_key[g];
-            const size_t eb0 = (size_t)g * CZ_EC_ENTRIES + (size_t)ec_bucket(key) * 64;
-            const unsigned long long ek = t.ec_key[eb0 + lane];
-            // already remembered?  Only an entry with this key AND this position counts (the lookup may have been skipped by
-            // its per-launch budget); a same-key entry holding ANOTHER position — a key collision — does not keep this one out
-            bool have = false;
-            const uint32_t mine = lane < 12 ? t.pend_board[(size_t)g * 12 + lane] : 0u;
-            for (unsigned long long m = __ballot(ek == key); m && !have; m &= m - 1ull) {
-                const int hl = __ffsll((long long)m) - 1;
-                const uint32_t lb = lane < 12 ? t.ec_board[(eb0 + hl) * 12 + lane] : 0u;
-                have = __ballot(lb != mine) == 0ull;
-            }
-            if (!have) {
-                const unsigned long long em = __ballot(ek == 0ull);
-                int slot = em ? __ffsll((long long)em) - 1 : (int)((key >> 40) & 63);
-                if (lane == slot) { t.ec_key[eb0 + lane] = key; t.ec_node[eb0 + lane] = leaf; t.ec_val[eb0 + lane] = val; }
-                if (lane < 12) t.ec_board[(eb0 + slot) * 12 + lane] = t.pend_board[(size_t)g * 12 + lane];
-            }
-            // cross-tree level (cz_search_set_xcache): file the evaluation for the OTHER trees as well — in an empty slot of the key's
-            // bucket, or in place of the entry deepest in its game.  A slot is claimed in two phases: a compare-and-swap takes its key
-            // to key | CZ_XC_BUSY, the payload (ply included) is stored write-through and drained, and only then is the real key stored.
-            // So no two trees of a launch hold one slot at once, and a later claim of the slot (which has to find the real key) writes
-            // after this payload is in memory: the XCDs' L2s are not coherent with each other, and the plain stores of two claimants
-            // could reach memory in either order — a key and board of one position with the labels, priors or count of another.
-            // Two trees expanding the same position in this launch: one files it, the other finds the key, claimed or published (or
-            // loses the swap to it), and leaves.  Readers are the select kernels of later launches (the kernel boundary publishes the
-            // payload); they never match a claimed key, and none is left once this launch has ended.
-            if (t.xc_base) {
-                const size_t xb0 = (size_t)(xc_bucket(key) & t.xc_mask) * 64;
-                const unsigned long long xk = czx_key(t)[xb0 + lane];
-                const unsigned long long xm = __ballot(xk == 0ull);
-                if (__ballot((xk & ~CZ_XC_BUSY) == key) == 0ull) {
-                    // this position's game ply: re-roots of the tree + levels below the root (the priority of the entry: low = shared)
-                    const uint32_t myply = (uint32_t)min((int)t.root_ply[g] + (int)t.pend_depth[g], 0xFFFF);
-                    int slot = 0, won = 0, dup = 0;
-                    if (xm) {
-                        // the first empty slot at or behind a key-dependent position: trees filing different positions into one
-                        // bucket in the same launch do not all go for slot 0; a tree that loses the swap to ANOTHER position tries the
-                        // next empty slot, up to three times; losing it to the SAME position means it is filed
-                        const int rot = (int)((key >> 40) & 63);
-                        unsigned long long xr = rot ? (xm >> rot) | (xm << (64 - rot)) : xm;
-                        for (int attempt = 0; attempt < 3 && xr && !won && !dup; ++attempt) {
-                            slot = (__ffsll((long long)xr) - 1 + rot) & 63;
-                            xr &= xr - 1ull;
-                            unsigned long long seen = 0ull;
-                            if (lane == 0) seen = atomicCAS(&czx_key(t)[xb0 + slot], 0ull, key | CZ_XC_BUSY);
-                            seen = __shfl(seen, 0, 64);
-                            won = seen == 0ull ? 1 : 0;
-                            dup = (seen & ~CZ_XC_BUSY) == key ? 1 : 0;
-                        }
-                    } else {
-                        // full bucket: the entry deepest in its game makes room if this position is shallower.  A slot another tree of
-                        // this launch is writing (CZ_XC_BUSY set: its count word is not this key's) is no candidate.  One attempt: a lost swap
-                        // drops the filing.
-                        const uint32_t ep = (xk & CZ_XC_BUSY) ? 0u : czx_cnt(t)[xb0 + lane] >> 16;
-                        uint32_t best = (ep << 6) | (uint32_t)lane;
-#pragma unroll
-                        for (int o = 32; o >= 1; o >>= 1) best = max(best, (uint32_t)__shfl_xor((int)best, o, 64));
-                        if ((best >> 6) > myply) {
-                            slot = (int)(best & 63u);
-                            const unsigned long long old = __shfl(xk, slot, 64);
-                            unsigned long long seen = 0ull;
-                            if (lane == 0) seen = atomicCAS(&czx_key(t)[xb0 + slot], old, key | CZ_XC_BUSY);
-                            seen = __shfl(seen, 0, 64);
-                            won = seen == old ? 1 : 0;
-                            if (won && lane == 0) czx_tree_stats(t)[(size_t)g * 8 + 4] += 1u;
-                        }
-                    }
-                    if (won) {
-                        const size_t e = xb0 + slot;
-                        const int n2 = t.pend_nmoves[g];
-                        const int cb2 = begin;   // the children written above: lane l re-reads exactly the elements lane l wrote
-                        if (lane < 12) st_through(&czx_board(t)[e * 12 + lane], mine);
-#pragma unroll
-                        for (int r = 0; r < 2; ++r) {
-                            const int i = lane + 64 * r;
-                            if (i < n2) {
-                                st_through(&czx_P(t)[e * CZD_MAXMOVES + i], v.P[cb2 + i]);
-                                st_through(&czx_moves(t)[e * CZD_MAXMOVES + i], v.move[cb2 + i]);
-                                st_through(&czx_sd(t)[e * CZD_MAXMOVES + i], v.sd[cb2 + i]);
-                            }
-                        }
-                        if (lane == 0) { st_through(&czx_val(t)[e], val); st_through(&czx_cnt(t)[e], (uint32_t)n2 | (myply << 16)); }
-                        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the whole payload is in memory ...
-                        if (lane == 0) {                                    // ... before the slot shows its key
-                            __hip_atomic_store(&czx_key(t)[e], key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            czx_tree_stats(t)[(size_t)g * 8 + 2] += 1u;
-                        }
-                    } else if (!dup && lane == 0) {
-                        czx_tree_stats(t)[(size_t)g * 8 + 3] += 1u;     // filings that found no room (deeper than everything in a full bucket, or lost every swap)
-                    }
-                }
-            }
+            const uint32_t mine = ec_file(t, g, key, leaf, val, lane);
+            if (t.xc_base) xc_file(t, v, g, key, mine, begin, val, lane);
         }
         if (kind == 3) { if (lane == 0) t.pend_kind[g] = 0; return; }
     } else {

@@ -13,6 +13,17 @@ from . import _lib
 from ._lib import BF16, F16, F32, MAXMOVES, NLABELS, NSQ, _ptr, call, lib, out_pointers   # noqa: F401 (_ptr: tests and tools import it from here)
 
 
+# The evaluation cache's dump formats (include/cchess_hip.h; csrc/cz_evalcache.h states the same field list for the kernels).
+# Cross-tree table of n entries: field after field, (name, element type, elements per entry, bytes per entry of the fields
+# before it), with XC_COUNTER_BYTES between the keys and the rest — per entry 8 + 4 + 4 + 48 + 256 + 256 + 512 = 1088 bytes.
+XC_FIELDS, XC_ENTRY_BYTES, XC_COUNTER_BYTES = [], 0, 64
+for _name, _dt, _per in (("key", np.uint64, 1), ("value", np.float32, 1), ("count_ply", np.uint32, 1), ("board", np.uint32, 12),
+                         ("label", np.uint16, MAXMOVES), ("sd", np.uint16, MAXMOVES), ("P", np.float32, MAXMOVES)):
+    XC_FIELDS.append((_name, _dt, _per, XC_ENTRY_BYTES))
+    XC_ENTRY_BYTES += np.dtype(_dt).itemsize * _per
+EC_ENTRIES = 128 * 64   # per-tree level: 128 buckets x 64 entries per tree
+
+
 def plane_format(forward):
     """(plane dtype, channels) the select kernel writes a player's leaf planes in: a PolicyValueNet on the fused path (hip
     backend, or the strict ladder) reads 16 channels of its 16-bit type straight from the select kernel; any other net or a
@@ -154,24 +165,24 @@ class SearchEngine:
     def xcache_dump(self):
         """(tests) The cross-tree table as it stands (cz_search_debug_xcache_dump): dict of numpy arrays over its n entries —
         key u64 [n] (0 = empty), value f32 [n], count u16 [n], ply u16 [n], board u32 [n, 12] (the packed position),
-        label u16 [n, 128], sd u16 [n, 128] (src | dst << 8), P f32 [n, 128]."""
+        label u16 [n, 128], sd u16 [n, 128] (src | dst << 8), P f32 [n, 128].  The raw block is n * 1088 + 64 bytes, laid out by
+        XC_FIELDS; count and ply are the low and high half of its count word."""
         n = self.ctx.call("cz_search_debug_xcache_dump", None, 0)
-        raw = np.zeros(n * 1088 + 64, np.uint8)
+        raw = np.zeros(n * XC_ENTRY_BYTES + XC_COUNTER_BYTES, np.uint8)
         self.ctx.call("cz_search_debug_xcache_dump", raw.ctypes.data, raw.nbytes)
-
-        def part(off, dt, shape):
-            return raw[off:off + int(np.prod(shape)) * np.dtype(dt).itemsize].view(dt).reshape(shape).copy()
-        cnt = part(n * 12 + 64, np.uint32, (n,))
-        return dict(key=part(0, np.uint64, (n,)), value=part(n * 8 + 64, np.float32, (n,)),
-                    count=(cnt & 0xFFFF).astype(np.uint16), ply=(cnt >> 16).astype(np.uint16),
-                    board=part(n * 16 + 64, np.uint32, (n, 12)), label=part(n * 64 + 64, np.uint16, (n, MAXMOVES)),
-                    sd=part(n * 320 + 64, np.uint16, (n, MAXMOVES)), P=part(n * 576 + 64, np.float32, (n, MAXMOVES)))
+        out = {}
+        for name, dt, per, before in XC_FIELDS:
+            off = n * before + (XC_COUNTER_BYTES if before else 0)   # the counter block sits behind the keys
+            out[name] = raw[off:off + n * per * np.dtype(dt).itemsize].view(dt).reshape((n, per) if per > 1 else (n,)).copy()
+        cnt = out.pop("count_ply")
+        out.update(count=(cnt & 0xFFFF).astype(np.uint16), ply=(cnt >> 16).astype(np.uint16))
+        return out
 
     def eval_cache_dump(self, g):
         """(tests) Tree g's per-tree cache entries (cz_search_debug_eval_cache_dump): dict of numpy arrays over its 8192 entries —
         key u64 (0 = empty), node i32, value f32, board u32 [8192, 12], record i32 (the node's row in tree_dump(g), -1 = the root,
         -2 = not in the tree)."""
-        n = 128 * 64
+        n = EC_ENTRIES
         out = dict(key=np.zeros(n, np.uint64), node=np.zeros(n, np.int32), value=np.zeros(n, np.float32),
                    board=np.zeros((n, 12), np.uint32), record=np.zeros(n, np.int32))
         p = [out[k].ctypes.data for k in ("key", "node", "value", "board", "record")]

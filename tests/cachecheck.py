@@ -12,7 +12,7 @@ import numpy as np
 
 from oracle import oracle as O
 
-BUSY = 1 << 63                   # reserved key bit: a cross-tree entry being written, key | BUSY (cz_internal.h: CZ_XC_BUSY)
+BUSY = 1 << 63                   # reserved key bit: a cross-tree entry being written, key | BUSY (cz_evalcache.h: CZ_XC_BUSY)
 FULL_MASK = 0xFFFFFFFFFFFFFFFF
 EC_BUCKETS = 128
 
