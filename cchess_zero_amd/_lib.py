@@ -24,6 +24,8 @@ SP_CHASE_STATS = ("chases",)                               # cz_selfplay_chase_s
 # why a match game ended (include/cchess_hip.h: CZ_MATCH_*); 0 = not finished
 MATCH_KING, MATCH_RR60, MATCH_PLY_CAP, MATCH_ABORTED, MATCH_MATE, MATCH_REPETITION, MATCH_PERPETUAL = 1, 2, 3, 4, 5, 6, 7
 MATCH_CHASE = 9   # 8 is not assigned
+MATCH_RESIGN = 10
+SP_RESIGN_STATS = ("resigned", "playon_games", "playon_would_resign", "playon_false_positives")   # cz_selfplay_resign_stats
 # verdicts of cz_repetition (include/cchess_hip.h: CZ_REP_*)
 REP_NONE, REP_DRAW, REP_RED_LOSES, REP_BLACK_LOSES = 0, 1, 2, 3
 # why cz_repetition_chase gave its verdict (include/cchess_hip.h: CZ_CAUSE_*)
@@ -105,6 +107,9 @@ _SIGS = {
     "cz_selfplay_set_chase": (C.c_int, [C.c_void_p, C.c_int]),
     "cz_selfplay_chase_history": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "cz_selfplay_chase_stats": (C.c_int, [C.c_void_p, _vp]),
+    "cz_selfplay_set_resign": (C.c_int, [C.c_void_p, C.c_float, C.c_int, C.c_double, C.c_ulonglong]),
+    "cz_selfplay_resign_stats": (C.c_int, [C.c_void_p, _vp, _vp]),
+    "cz_match_set_resign": (C.c_int, [C.c_void_p, C.c_float, C.c_int]),
     "cz_match_create": (C.c_int, [C.c_void_p, C.c_void_p, _u8p, _u8p, _i32p, C.c_int, C.c_longlong, C.c_longlong, C.c_int,
                                   C.POINTER(C.c_void_p)]),
     "cz_match_destroy": (None, [C.c_void_p]),

@@ -27,22 +27,25 @@ import time
 import numpy as np
 import torch
 
-from ._lib import (MATCH_ABORTED, MATCH_CHASE, MATCH_KING, MATCH_MATE, MATCH_PERPETUAL, MATCH_PLY_CAP, MATCH_REPETITION, MATCH_RR60, NSQ, call,
+from ._lib import (MATCH_ABORTED, MATCH_CHASE, MATCH_KING, MATCH_MATE, MATCH_PERPETUAL, MATCH_PLY_CAP, MATCH_REPETITION, MATCH_RESIGN, MATCH_RR60, NSQ, call,
                    lib, out_pointers, tables)
 from .engine import SearchEngine, plane_format, pool_nodes
 from .notation import player_to_side, state_to_board
 from .rules import RULES, check_rule_options, root_rules_chase_history, root_rules_history, set_rule_options   # noqa: F401 (RULES: re-exported)
 
 REASONS = {0: "unfinished", MATCH_KING: "king", MATCH_RR60: "rr60", MATCH_PLY_CAP: "ply_cap", MATCH_ABORTED: "aborted", MATCH_MATE: "mate",
-           MATCH_REPETITION: "repetition", MATCH_PERPETUAL: "perpetual", MATCH_CHASE: "chase"}
+           MATCH_REPETITION: "repetition", MATCH_PERPETUAL: "perpetual", MATCH_CHASE: "chase", MATCH_RESIGN: "resign"}
 
 
-def is_scored(reason):
+def is_scored(reason, resign=False):
     """A finished game that counts: every ending but "aborted" (a mate, rules="xiangqi", is a loss for the mated side; with
     repetition != 0 a repetition is a draw and a perpetual check a loss for the checking side; with chase a perpetual chase is
-    a loss for the chasing side)."""
+    a loss for the chasing side).  resign: the match was played with resignation (Match(resign=...)) — then, and only then, a
+    game can end as "resign", a loss for the side that resigned, and counts; in a match without it no game carries that reason
+    and the code counts no more than an unassigned one."""
     reason = np.asarray(reason, np.int64)
-    return ((reason >= MATCH_KING) & (reason <= MATCH_PLY_CAP)) | ((reason >= MATCH_MATE) & (reason <= MATCH_PERPETUAL)) | (reason == MATCH_CHASE)
+    scored = ((reason >= MATCH_KING) & (reason <= MATCH_PLY_CAP)) | ((reason >= MATCH_MATE) & (reason <= MATCH_PERPETUAL)) | (reason == MATCH_CHASE)
+    return scored | (reason == MATCH_RESIGN) if resign else scored
 
 
 # ---- openings ------------------------------------------------------------------------------------------------------------
@@ -166,12 +169,12 @@ def elo(score):
     return -400.0 * math.log10(1.0 / score - 1.0)
 
 
-def pentanomial(result, reason):
+def pentanomial(result, reason, resign=False):
     """Counts of the opening pairs' scores for A: index k = points out of 2 times 2 (0, 0.5, 1, 1.5, 2 -> 0..4), over the
-    pairs (games 2p, 2p + 1) whose two games were both scored (an aborted game drops its pair)."""
+    pairs (games 2p, 2p + 1) whose two games were both scored (an aborted game drops its pair); resign as is_scored's."""
     result = np.asarray(result, np.int64)
     reason = np.asarray(reason, np.int64)
-    scored = is_scored(reason)
+    scored = is_scored(reason, resign)
     pair_ok = scored[0::2] & scored[1::2]
     x = (result[0::2] + 1) + (result[1::2] + 1)          # twice A's points of the pair: 0..4
     return np.bincount(x[pair_ok], minlength=5)[:5].astype(np.int64)
@@ -197,9 +200,10 @@ class MatchResult:
     elo and its 95 % interval from the pentanomial distribution of the opening pairs, simulations, seconds, sims_per_s;
     rules ("capture" / "xiangqi") and mates: the games that ended because the mover had no king-safe move; repetition (the
     fold, 0 = no such rule), repetitions: the games drawn by it, perpetuals: the games lost by perpetual check; chase (the
-    perpetual-chase rule was on), chases: the games lost by perpetual chase."""
+    perpetual-chase rule was on), chases: the games lost by perpetual chase; resign (the threshold the match resigned on, None = games were played
+    out), resigns: the games a mover resigned."""
 
-    def __init__(self, result, a_red, plies, reason, moves, simulations, seconds, players, rules="capture", repetition=0, chase=False):
+    def __init__(self, result, a_red, plies, reason, moves, simulations, seconds, players, rules="capture", repetition=0, chase=False, resign=None):
         self.result = np.asarray(result, np.int8)
         self.a_red = np.asarray(a_red, np.uint8)
         self.plies = np.asarray(plies, np.int32)
@@ -207,7 +211,8 @@ class MatchResult:
         lab = tables()["labels"] if moves is not None else None
         self.moves = [[lab[int(x)] for x in row if x != 0xFFFF] for row in moves] if moves is not None else None
         self.games = len(self.result)
-        scored = is_scored(self.reason)
+        self.resign = None if resign is None else float(resign)
+        scored = is_scored(self.reason, self.resign is not None)
         self.rules = rules
         self.mates = int((self.reason == MATCH_MATE).sum())
         self.repetition = int(repetition)
@@ -215,6 +220,7 @@ class MatchResult:
         self.perpetuals = int((self.reason == MATCH_PERPETUAL).sum())
         self.chase = bool(chase)
         self.chases = int((self.reason == MATCH_CHASE).sum())
+        self.resigns = int((self.reason == MATCH_RESIGN).sum())
         self.aborted = int((self.reason == MATCH_ABORTED).sum())
         self.unfinished = int((self.reason == 0).sum())
         self.scored = int(scored.sum())
@@ -227,7 +233,7 @@ class MatchResult:
         self.by_colour = {"red": wdl(self.a_red == 1), "black": wdl(self.a_red == 0)}
         self.score = (self.wins + 0.5 * self.draws) / self.scored if self.scored else None
         self.elo = elo(self.score)
-        self.pentanomial = pentanomial(self.result, self.reason)
+        self.pentanomial = pentanomial(self.result, self.reason, self.resign is not None)
         iv = pentanomial_interval(self.pentanomial)
         self.elo_95 = None if iv is None else (elo(iv[1]) if iv[1] > 0 else None, elo(iv[2]) if iv[2] < 1 else None)
         self.simulations = int(simulations)
@@ -240,7 +246,7 @@ class MatchResult:
         """The summary (no per-game arrays): what `python -m cchess_zero_amd.arena` prints.  elo None = infinite (every
         scored game won or lost) or no scored game; an interval end None = unbounded on that side."""
         return dict(rules=self.rules, mates=self.mates, repetition=self.repetition, repetitions=self.repetitions, perpetuals=self.perpetuals,
-                    chase=self.chase, chases=self.chases, games=self.games, scored=self.scored, aborted=self.aborted, unfinished=self.unfinished, W=self.wins,
+                    chase=self.chase, chases=self.chases, resign=self.resign, resigns=self.resigns, games=self.games, scored=self.scored, aborted=self.aborted, unfinished=self.unfinished, W=self.wins,
                     D=self.draws, L=self.losses, by_colour=self.by_colour, score=self.score, elo=self.elo,
                     elo_95=None if self.elo_95 is None else list(self.elo_95), pentanomial=self.pentanomial.tolist(),
                     mean_plies=float(self.plies.mean()) if self.games else 0.0,
@@ -316,11 +322,17 @@ class Match:
     every move of the cycle ("perpetual") (cz_match_set_repetition).
     chase (with a repetition fold only): False — a chase that repeats is a draw by repetition; True — when neither side checked
     perpetually, a side that alone threatened one and the same unprotected piece after every one of its moves of the cycle has
-    lost ("chase"; cz_match_set_chase, Rules.threats)."""
+    lost ("chase"; cz_match_set_chase, Rules.threats).
+    resign: None — every game is played out; a value — from ply resign_min_ply of a game on, a mover whose root value (the Q of its
+    most visited candidate child, on its own tree) is below it has lost ("resign"; cz_match_set_resign)."""
 
     def __init__(self, player_a, player_b, openings, slots, max_plies=512, sample_plies=0, seed=0, check_every=8,
-                 nodes_per_tree=None, rules="capture", repetition=0, chase=False):
+                 nodes_per_tree=None, rules="capture", repetition=0, chase=False, resign=None, resign_min_ply=0):
         check_rule_options("Match", rules, repetition, chase)
+        if int(resign_min_ply) < 0:
+            raise ValueError("Match: resign_min_ply >= 0")
+        self.resign = None if resign is None else float(resign)
+        self.resign_min_ply = int(resign_min_ply)
         self.rules = rules
         self.repetition = int(repetition)
         self.chase = bool(chase)
@@ -351,7 +363,7 @@ class Match:
             local = merge_ranks(local, n_pairs, rank, world)
         return MatchResult(local["result"], local["a_red"], local["plies"], local["reason"], local["moves"], local["simulations"],
                            local["seconds"], [_describe(p) for p in self.players], rules=self.rules, repetition=self.repetition,
-                           chase=self.chase)
+                           chase=self.chase, resign=self.resign)
 
     def _play_local(self, op, pair_base, pair_stride):
         self.start(op, pair_base, pair_stride)
@@ -399,6 +411,8 @@ class Match:
         self._h = C.c_void_p()
         call("cz_match_create", ea.ctx.h, eb.ctx.h, *self._op_dev, len(op), int(pair_base), int(pair_stride), self.max_plies, C.byref(self._h))
         set_rule_options("cz_match", self._h, self.rules, self.repetition, self.chase)
+        if self.resign is not None:
+            call("cz_match_set_resign", self._h, self.resign, self.resign_min_ply)
         self.masks = [out_pointers("cz_match_active", self._h, 1, player)[0] for player in (0, 1)]
         self.played = torch.empty(G, dtype=torch.int16, device=dev)
 
@@ -501,6 +515,9 @@ def main(argv=None):
                          "or a loss for the side that checked perpetually; 0 = no repetition rule")
     ap.add_argument("--chase", action="store_true",
                     help="with --repetition: a side that alone chased one unprotected piece with every move of the cycle loses")
+    ap.add_argument("--resign", type=float, default=None,
+                    help="a mover whose root value (Q of its most visited move) is below X resigns; default: games are played out")
+    ap.add_argument("--resign_min_ply", type=int, default=0, help="with --resign: plies of a game before anybody may resign")
     args = ap.parse_args(argv)
     try:
         check_rule_options("arena", args.rules, args.repetition, args.chase)
@@ -518,7 +535,8 @@ def main(argv=None):
         pairs = ((256 if args.games is None else args.games) + 1) // 2
         op = random_openings(pairs, args.opening_plies, args.seed)
     res = Match((a, args.playout), (b, args.playout_b or args.playout), op, slots=args.slots or 2 * pairs, max_plies=args.max_plies,
-                sample_plies=args.sample_plies, seed=args.seed, rules=args.rules, repetition=args.repetition, chase=args.chase).play()
+                sample_plies=args.sample_plies, seed=args.seed, rules=args.rules, repetition=args.repetition, chase=args.chase,
+                resign=args.resign, resign_min_ply=args.resign_min_ply).play()
     d = res.to_dict()
     d.update(a=args.a, b=args.b, blocks=args.blocks, opening_plies=args.opening_plies, slots=min(args.slots or 2 * pairs, 2 * pairs),
              seed=args.seed)

@@ -204,6 +204,7 @@ void cz_destroy(cz_ctx *c) {
     if (c->pool_block) (void)hipFree(c->pool_block);
     if (c->sp_block) (void)hipFree(c->sp_block);
     if (c->sp_chase_block) (void)hipFree(c->sp_chase_block);
+    if (c->sp_resign_block) (void)hipFree(c->sp_resign_block);
     if (c->ec_block) (void)hipFree(c->ec_block);
 #if defined(CZ_EXPERIMENT_MX2) || defined(CZ_EXPERIMENT_MX12)
     if (c->mx_xbuf) (void)hipFree(c->mx_xbuf);
@@ -490,7 +491,50 @@ int cz_selfplay_begin(cz_ctx *c, int max_plies, const uint8_t *boards, const uin
         c->sp.max_plies = max_plies;
     }
     c->sp_rules = 0; c->sp.rr.fold = 0; c->sp_chase = 0; c->sp_state = 1;
+    c->sp.rs = CzSpResign{};   // resignation off: no pointer, no kernel looks
+    c->sp.rs.threshold = NAN;
     return czk_selfplay_seed(c, boards, side, rr);
+}
+int cz_selfplay_set_resign(cz_ctx *c, float threshold, int min_ply, double playon_fraction, unsigned long long seed) {
+    CZ_REQUIRE(c && c->sp_block && c->sp_state != 0, "cz_selfplay_set_resign: call cz_selfplay_begin first");
+    CZ_REQUIRE(min_ply >= 0 && playon_fraction >= 0.0 && playon_fraction <= 1.0, "cz_selfplay_set_resign: min_ply >= 0 and 0 <= playon_fraction <= 1 required");
+    CzSpResign &rs = c->sp.rs;
+    if (rs.game_no) {   // a later call retunes: the per-game state, the counters and the seed stay
+        rs.threshold = threshold; rs.min_ply = min_ply; rs.playon_fraction = playon_fraction;
+        return CZ_OK;
+    }
+    if (threshold != threshold) return CZ_OK;   // off stays off
+    const size_t G = (size_t)c->max_games;
+    auto carve = [&](Carver &k, CzSpResign &r) {
+        r.game_no = k.take<uint32_t>(G);
+        r.playon = k.take<uint8_t>(G);
+        r.minq = k.take<float>(G * 2);
+        r.would = k.take<uint8_t>(G);
+        r.resigned = k.take<uint8_t>(G);
+        r.stats = k.take<long long>(4);
+        r.hist = k.take<long long>(64);
+    };
+    Carver m{nullptr};
+    CzSpResign sized{};
+    carve(m, sized);
+    if (const int rc = alloc_zeroed(&c->sp_resign_block, m.off, c->stream, "cz_selfplay_set_resign")) return rc;   // the counters start with the games
+    Carver k{(char *)c->sp_resign_block};
+    carve(k, sized);
+    sized.threshold = threshold; sized.min_ply = min_ply; sized.playon_fraction = playon_fraction; sized.seed = seed;
+    rs = sized;
+    return czk_selfplay_resign_init(c);
+}
+int cz_selfplay_resign_stats(cz_ctx *c, long long *stats_dev, long long *hist_dev) {
+    CZ_REQUIRE(c && c->sp_block && stats_dev, "cz_selfplay_resign_stats: call cz_selfplay_begin first / null argument");
+    const CzSpResign &rs = c->sp.rs;
+    if (rs.game_no) {
+        CZ_HIP(hipMemcpyAsync(stats_dev, rs.stats, sizeof(long long) * 4, hipMemcpyDeviceToDevice, c->stream));
+        if (hist_dev) CZ_HIP(hipMemcpyAsync(hist_dev, rs.hist, sizeof(long long) * 64, hipMemcpyDeviceToDevice, c->stream));
+    } else {
+        CZ_HIP(hipMemsetAsync(stats_dev, 0, sizeof(long long) * 4, c->stream));
+        if (hist_dev) CZ_HIP(hipMemsetAsync(hist_dev, 0, sizeof(long long) * 64, c->stream));
+    }
+    return CZ_OK;
 }
 // the setters' order (cz_root_rules_order), in self-play's names
 static int sp_order(const cz_ctx *c, int what, int value) {

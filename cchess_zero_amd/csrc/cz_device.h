@@ -452,3 +452,14 @@ __device__ __forceinline__ uint16_t czd_f32_to_bf16_bits(float f) {
     return (uint16_t)(u >> 16);
 }
 __device__ __forceinline__ float czd_bf16_bits_to_f32(uint16_t h) { return __uint_as_float(((unsigned int)h) << 16); }
+
+// splitmix64's finaliser, and the uniform in [0, 1) of a counter-based draw: the top 53 bits of a hash.  The match's sampled
+// plies (cz_match.hip: seed, global game, ply) and self-play's play-on draw (cz_selfplay.hip: seed, slot, game number) are
+// uniform53(splitmix64(seed ^ splitmix64(counter))) — pure functions of what they name, whatever slot, G or rank ran them.
+__device__ __forceinline__ unsigned long long splitmix64(unsigned long long x) {
+    x += 0x9E3779B97F4A7C15ull;
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+    return x ^ (x >> 31);
+}
+__device__ __forceinline__ double uniform53(unsigned long long h) { return (double)(h >> 11) * 0x1.0p-53; }

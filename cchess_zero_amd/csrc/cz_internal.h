@@ -74,6 +74,25 @@ struct CzPool {
     uint16_t *sd;   // src | dst << 8 of `move` (k_select applies the move without the label -> (src, dst) table round trip)
 };
 
+// cz_selfplay_set_resign: what resignation keeps per slot, and its counters — an allocation of its own (cz_ctx::sp_resign_block).
+// game_no == NULL: the setter has not run since cz_selfplay_begin, and no kernel does anything for it.
+struct CzSpResign {
+    float threshold;             // a mover whose root value (wave_root_value) is below it resigns; NaN: no ply is judged
+    int min_ply;                 // plies of a game before the first judged one
+    double playon_fraction;      // a game plays on iff uniform53(seed, slot, game_no) < playon_fraction
+    unsigned long long seed;
+    uint32_t *game_no;           // [max_games] games the slot has started before the one in progress
+    uint8_t *playon;             // [max_games] the game in progress plays on: it is judged, counted, and never resigned
+    float *minq;                 // [max_games][2] lowest judged root value of red / black in the game in progress; 2.0: none yet
+    uint8_t *would;              // [max_games] play-on game: 0, or 1 + the side that first crossed the threshold
+    uint8_t *resigned;           // [max_games] the last choose resigned the game (k_sp_adjudicate ends it)
+    long long *stats;            // [4] resigned, playon_games, playon_would_resign, playon_false_positives
+    long long *hist;             // [64] lowest root values of the sides that did not lose a play-on game, bins of 1/32 over [-1, 1)
+};
+__device__ __forceinline__ bool sp_plays_on(const CzSpResign &rs, int g, uint32_t game_no) {
+    return uniform53(splitmix64(rs.seed ^ splitmix64(((unsigned long long)g << 32) | (unsigned long long)game_no))) < rs.playon_fraction;
+}
+
 // cz_selfplay_*: per game slot, the (s, pi, z) records of the game in progress (cchess_main.selfplay keeps
 // states / mcts_probs / current_players lists, main.py:1496-1518) and the counters of finished games
 struct CzSelfplay {
@@ -91,6 +110,7 @@ struct CzSelfplay {
     CzRootRules rr;
     long long *xq_stats;         // [3] games ended by mate, by a repetition draw, by perpetual check (cz_selfplay_rules_stats)
     long long *chase_stat;       // [1] games ended by perpetual chase (cz_selfplay_chase_stats)
+    CzSpResign rs;               // cz_selfplay_set_resign
 };
 
 // Per-tree scalars: ONE 64-byte record per tree instead of sixteen arrays.  A wave owns a tree, so what it reads at entry
@@ -197,7 +217,8 @@ struct cz_ctx {
     int sp_rules;      // cz_selfplay_set_rules: 0 king capture, 1 xiangqi
     int sp_chase;      // cz_selfplay_set_chase: 0 off, 1 on (needs a fold, sp.rr.fold: cz_selfplay_set_repetition)
     void *sp_chase_block;
-    int sp_state;      // 0: no cz_selfplay_begin yet, 1: begun (the setters may be called), 2: a cz_selfplay_choose has run since
+    void *sp_resign_block;   // cz_selfplay_set_resign: allocated by its first call, sp.rs points into it while resignation is set
+    int sp_state;     // 0: no cz_selfplay_begin yet, 1: begun (the setters may be called), 2: a cz_selfplay_choose has run since
     void *ec_block;    // cz_search_set_eval_cache
 };
 
@@ -310,6 +331,18 @@ __device__ __forceinline__ int wave_most_visited(const int N[2], int n, int lane
     return bi;
 }
 
+// The value a mover resigns on (cz_selfplay_set_resign, cz_match_set_resign): Q of the most visited candidate — the child
+// wave_most_visited picks among the n candidates, N[r] / at[r] the visit count / the index among the root's children (at cb) of
+// candidate lane + 64 r.  Q as the pool holds it, in the sign PUCT maximises: larger is better for the mover, a child that
+// takes the king reads +1.  -> that child has a visit (a root value exists); q is wave-uniform
+__device__ __forceinline__ bool wave_root_value(const TreeView &v, int cb, const int N[2], const int at[2], int n, int lane, float &q) {
+    const int best = wave_most_visited(N, n, lane);
+    const int bn = __shfl(best < 64 ? N[0] : N[1], best & 63, 64);
+    const int bi = __shfl(best < 64 ? at[0] : at[1], best & 63, 64);
+    q = v.Q[cb + bi];
+    return bn > 0;
+}
+
 __device__ __forceinline__ double wave_sum(double x) {
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) x += __shfl_xor(x, d, 64);
@@ -395,6 +428,7 @@ int czk_search_reload_finished(cz_ctx *, const uint8_t *, const uint16_t *, cons
 int czk_search_select_k(cz_ctx *, int, int, const uint8_t *, void *, int, int, uint8_t *);
 int czk_search_expand_backup_k(cz_ctx *, int, const void *, const void *, int);
 int czk_selfplay_seed(cz_ctx *, const uint8_t *, const uint8_t *, const int32_t *);
+int czk_selfplay_resign_init(cz_ctx *);   // the first cz_selfplay_set_resign: c->sp.rs on its zeroed block
 int czk_selfplay_choose(cz_ctx *, const float *, const float *, const uint16_t *, double, float, int, uint16_t *);   // by c->sp_rules / sp.rr.fold / c->sp_chase
 int czk_selfplay_adjudicate(cz_ctx *, int, const uint16_t *, int32_t *);
 int czk_selfplay_flush(cz_ctx *, const int32_t *, const long long *, uint8_t *, long long, const long long *);

@@ -25,7 +25,10 @@ struct CzMatch {
     uint8_t *mover_a;             // [G] player A is to move in the slot's game
     uint8_t *act_a, *act_b;       // [G] mover masks: this player is to move and the game is live
     uint8_t *stalled;             // [G] the last choose found no root child
-    int8_t *result;               // [n_games] +1 / 0 / -1 from A's point of view
+    uint8_t *resigned;            // [G] the last choose found the mover's root value below resign_threshold
+    float resign_threshold;       // cz_match_set_resign; NaN: nobody resigns
+    int resign_min_ply;
+    int8_t *result;              // [n_games] +1 / 0 / -1 from A's point of view
     uint8_t *a_red;               // [n_games] 1: A played red
     int32_t *plies;               // [n_games]
     uint8_t *reason;              // [n_games] CZ_MATCH_*
@@ -47,17 +50,9 @@ struct cz_match {
 
 namespace {
 
-__device__ __forceinline__ unsigned long long splitmix64(unsigned long long x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-
 // the uniform of a sampled move (include/cchess_hip.h cz_match_choose): a pure function of (seed, global game, ply)
 __device__ __forceinline__ double match_uniform(unsigned long long seed, long long game, int ply) {
-    const unsigned long long h = splitmix64(seed ^ splitmix64(((unsigned long long)game << 16) | (unsigned long long)ply));
-    return (double)(h >> 11) * 0x1.0p-53;
+    return uniform53(splitmix64(seed ^ splitmix64(((unsigned long long)game << 16) | (unsigned long long)ply)));
 }
 
 __device__ __forceinline__ long long global_game(const CzMatch &m, int game) {
@@ -98,6 +93,8 @@ __global__ __launch_bounds__(64) void k_match_start(CzTrees ta, CzTrees tb, CzMa
 // order, and the choice runs on the compacted visit counts exactly as it runs on all children under king-capture rules.
 // From CZ_RULES_REPETITION: first the root position goes through the slot's history (wave_root_history), whose verdict ends the
 // game before a move is chosen: no move is logged, the ply stays (k_match_adjudicate).
+// At every level, with cz_match_set_resign: behind those exits and before the choice, a mover whose root value (wave_root_value,
+// cz_internal.h) is below the threshold resigns — the game ends the same way, as CZ_MATCH_RESIGN.
 template <int LEVEL>
 __device__ __forceinline__ void choose_on(const CzTrees &t, const CzMatch &m, int g, int game, int sample_plies, unsigned long long seed,
                                           uint16_t *__restrict__ played, int lane) {
@@ -135,6 +132,13 @@ __device__ __forceinline__ void choose_on(const CzTrees &t, const CzMatch &m, in
         for (int r = 0; r < 2; ++r) {
             const int i = lane + 64 * r;
             if (i < n) { N[r] = v.N[cb + i]; at[r] = i; }
+        }
+    }
+    if (m.resign_threshold == m.resign_threshold) {   // cz_match_set_resign: the mover resigns on its own tree's value, sampled plies too
+        float q;
+        if (ply >= m.resign_min_ply && wave_root_value(v, cb, N, at, n, lane, q) && q < m.resign_threshold) {
+            if (lane == 0) { played[g] = 0xFFFF; m.resigned[g] = 1; }   // no move is logged, the ply stays (k_match_adjudicate)
+            return;
         }
     }
     int pick;
@@ -198,6 +202,7 @@ __global__ __launch_bounds__(64) void k_match_adjudicate(CzTrees ta, CzTrees tb,
     if constexpr (CHASE) { by_chase = (verdict & CZ_REP_BY_CHASE) != 0; verdict &= ~CZ_REP_BY_CHASE; }
     if (verdict != CZ_REP_NONE) reason = verdict == CZ_REP_DRAW ? CZ_MATCH_REPETITION : (by_chase ? CZ_MATCH_CHASE : CZ_MATCH_PERPETUAL);
     else if (XQ && m.rr.mated[g]) reason = CZ_MATCH_MATE;
+    else if (m.resigned[g]) reason = CZ_MATCH_RESIGN;   // before aborted: its played is 0xFFFF too
     else if (aborted) reason = CZ_MATCH_ABORTED;
     else if (Kmiss || kmiss) reason = CZ_MATCH_KING;
     else if (restrict_round_draw(mv.root_rr[g])) reason = CZ_MATCH_RR60;
@@ -211,13 +216,14 @@ __global__ __launch_bounds__(64) void k_match_adjudicate(CzTrees ta, CzTrees tb,
     if (lane == 0) {
         const bool a_red = (game & 1) == 0;
         const bool a_wins = (king_capture_winner(Kmiss) == 0) == a_red;
-        int8_t result = (int8_t)(reason == CZ_MATCH_KING ? (a_wins ? 1 : -1) : (reason == CZ_MATCH_MATE ? (ma ? -1 : 1) : 0));
+        int8_t result = (int8_t)(reason == CZ_MATCH_KING ? (a_wins ? 1 : -1) : (reason == CZ_MATCH_MATE || reason == CZ_MATCH_RESIGN ? (ma ? -1 : 1) : 0));
         if constexpr (REP) {
             if (reason == CZ_MATCH_PERPETUAL || reason == CZ_MATCH_CHASE) result = (int8_t)(((verdict == CZ_REP_RED_LOSES) == a_red) ? -1 : 1);   // A has the losing colour
         }
         m.result[game] = result;
         if (XQ) m.rr.mated[g] = 0;
         if constexpr (REP) m.rr.rep[g] = CZ_REP_NONE;
+        m.resigned[g] = 0;
         m.a_red[game] = a_red ? 1 : 0;
         m.plies[game] = ply;
         m.reason[game] = (uint8_t)reason;
@@ -244,6 +250,7 @@ static void carve(Carver &k, CzMatch &m, size_t G, size_t n) {
     m.act_a = k.take<uint8_t>(G);
     m.act_b = k.take<uint8_t>(G);
     m.stalled = k.take<uint8_t>(G);
+    m.resigned = k.take<uint8_t>(G);
     m.result = k.take<int8_t>(n);
     m.a_red = k.take<uint8_t>(n);
     m.plies = k.take<int32_t>(n);
@@ -266,6 +273,7 @@ int cz_match_create(cz_ctx *a, cz_ctx *b, const uint8_t *boards, const uint8_t *
     mh->a = a; mh->b = b; mh->G = a->G; mh->n_games = 2 * n_openings;
     CzMatch &m = mh->m;
     m.G = mh->G; m.n_games = mh->n_games; m.max_plies = max_plies; m.pair_base = pair_base; m.pair_stride = pair_stride;
+    m.resign_threshold = NAN; m.resign_min_ply = 0;
     Carver sizing{nullptr};
     carve(sizing, m, (size_t)mh->G, (size_t)mh->n_games);
     const size_t bytes = sizing.off;
@@ -354,6 +362,13 @@ int cz_match_set_chase(cz_match *mh, int on) {
 int cz_match_chase_history(cz_match *mh, const uint64_t **chase) {
     CZ_REQUIRE(mh && mh->chase != 0, "cz_match_chase_history: cz_match_set_chase first");
     if (chase) *chase = mh->m.rr.ring_chase;
+    return CZ_OK;
+}
+
+int cz_match_set_resign(cz_match *mh, float threshold, int min_ply) {
+    CZ_REQUIRE(mh && min_ply >= 0, "cz_match_set_resign: null match / min_ply < 0");
+    mh->m.resign_threshold = threshold;   // NaN: off
+    mh->m.resign_min_ply = min_ply;
     return CZ_OK;
 }
 

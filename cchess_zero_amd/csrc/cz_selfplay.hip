@@ -16,6 +16,10 @@
 // rules act AT THE ROOT ONLY.  The move is chosen, and the record written, over the root children whose move is king-safe; a mover
 // without one is mated; with a fold, a fold-th occurrence of the root position ends the game.  The search below the root is
 // untouched: in the tree a mate is a king capture two plies down, which it already sees.
+//
+// cz_selfplay_set_resign — at every rule level a mover whose root value (wave_root_value, cz_internal.h) is below the threshold
+// resigns, except in the games drawn to play on, which are played out and counted instead: how often the side that crossed the
+// threshold did not lose, and a histogram of the lowest values of the sides that did not lose (CzSpResign, cz_internal.h).
 #include "cz_internal.h"
 
 #include <math.h>
@@ -44,6 +48,20 @@ __global__ __launch_bounds__(64) void k_sp_seed(CzTrees t, CzSelfplay sp, int G,
     sp.rr.ring_check[(size_t)g * 64 + lane] = 0;
 }
 
+// Resignation's state of slot g for game number game_no of the slot: the play-on draw, no value judged yet, nobody crossed
+__device__ __forceinline__ void sp_resign_new_game(const CzSpResign &rs, int g, uint32_t game_no) {
+    rs.game_no[g] = game_no;
+    rs.playon[g] = sp_plays_on(rs, g, game_no) ? 1 : 0;
+    rs.minq[2 * g] = 2.0f; rs.minq[2 * g + 1] = 2.0f;
+    rs.would[g] = 0; rs.resigned[g] = 0;
+}
+
+// the first cz_selfplay_set_resign after cz_selfplay_begin, on its zeroed block: every slot is in its game 0
+__global__ __launch_bounds__(64) void k_sp_resign_init(CzSpResign rs, int G) {
+    const int g = blockIdx.x * 64 + threadIdx.x;
+    if (g < G) sp_resign_new_game(rs, g, 0u);
+}
+
 // level >= CZ_RULES_KINGSAFE, before the choice: the root position of every slot, for czk_root_rules_prepare
 __global__ __launch_bounds__(64) void k_sp_roots_xq(CzTrees t, CzSelfplay sp, int G) {
     const int g = blockIdx.x, lane = threadIdx.x;
@@ -58,7 +76,8 @@ __global__ __launch_bounds__(64) void k_sp_roots_xq(CzTrees t, CzSelfplay sp, in
 // pick and the record run on the compacted children exactly as they run on all n under king-capture rules.  None: the mover is mated.
 // From CZ_RULES_REPETITION: first the root position goes through the slot's history (wave_root_history), whose verdict ends the
 // game.  On either ending played = 0xFFFF, no record is written and the ply stays; k_sp_adjudicate ends the game.  A forced
-// label is played as given.
+// label is played as given.  At every level, with cz_selfplay_set_resign: behind those exits and before the pick the mover's root
+// value is judged, and a resignation ends the ply the same way.
 template <int LEVEL>
 __global__ __launch_bounds__(64) void k_sp_choose(CzTrees t, CzSelfplay sp, int G, const float *__restrict__ gamma,
                                                   const float *__restrict__ u, const uint16_t *__restrict__ forced,
@@ -83,7 +102,7 @@ __global__ __launch_bounds__(64) void k_sp_choose(CzTrees t, CzSelfplay sp, int 
         return;
     }
     const int ply = sp.ply[g];
-    int N[2] = {0, 0};
+    int N[2] = {0, 0}, at[2] = {0, 0};   // the visits of candidate lane + 64 r and its index among the root's children
     uint16_t lab[2] = {0xFFFF, 0xFFFF};
     double pi[2], p[2];
     if constexpr (XQ) {
@@ -102,13 +121,31 @@ __global__ __launch_bounds__(64) void k_sp_choose(CzTrees t, CzSelfplay sp, int 
 #pragma unroll
         for (int r = 0; r < 2; ++r) {
             const int i = lane + 64 * r;
-            if (i < n) { N[r] = sN[i]; lab[r] = v.move[cb + sI[i]]; }
+            if (i < n) { N[r] = sN[i]; at[r] = sI[i]; lab[r] = v.move[cb + at[r]]; }
         }
     } else {
 #pragma unroll
         for (int r = 0; r < 2; ++r) {
             const int i = lane + 64 * r;
-            if (i < n) { N[r] = v.N[cb + i]; lab[r] = v.move[cb + i]; }
+            if (i < n) { N[r] = v.N[cb + i]; at[r] = i; lab[r] = v.move[cb + i]; }
+        }
+    }
+    // cz_selfplay_set_resign: the mover's root value is judged — unless a forced label is played — and a mover below the threshold
+    // resigns: played = 0xFFFF, no record, the ply stays, k_sp_adjudicate ends the game.  A play-on game only notes the first crossing.
+    if (sp.rs.game_no && sp.rs.threshold == sp.rs.threshold && ply >= sp.rs.min_ply && !(forced && forced[g] < CZ_NLABELS)) {
+        float q;
+        if (wave_root_value(v, cb, N, at, n, lane, q)) {
+            const int mover = t.root_side[g] ? 1 : 0;
+            const bool quits = q < sp.rs.threshold && sp.rs.playon[g] == 0;
+            if (lane == 0) {
+                float *mq = sp.rs.minq + 2 * g + mover;
+                if (q < *mq) *mq = q;
+                if (q < sp.rs.threshold) {
+                    if (quits) { played[g] = 0xFFFF; sp.rs.resigned[g] = 1; }
+                    else if (sp.rs.would[g] == 0) sp.rs.would[g] = (uint8_t)(mover + 1);
+                }
+            }
+            if (quits) return;
         }
     }
     wave_visit_policy(N, n, inv_temp, lane, pi);
@@ -162,6 +199,9 @@ __global__ __launch_bounds__(64) void k_sp_choose(CzTrees t, CzSelfplay sp, int 
 // verdict (a draw, or a loss for the side that checked perpetually), then a mated mover (the side to move loses); z as for a king
 // capture.  At CZ_RULES_CHASE the verdict may carry CZ_REP_BY_CHASE — a loss for the side that chased, z as for perpetual check,
 // counted in chase_stat and not among the perpetuals.
+// cz_selfplay_set_resign, at every level: a game the last choose resigned is lost by the side to move, z as for a king capture,
+// behind the verdict and the mate and before everything else; a play-on game that ends here — however it ends, unless it
+// stalled — goes into the play-on counters and the histogram; the slot's resignation state starts over with its next game.
 template <int LEVEL>
 __global__ __launch_bounds__(64) void k_sp_adjudicate(CzTrees t, CzSelfplay sp, int G, int reseed, const uint16_t *__restrict__ played,
                                                       int32_t *__restrict__ fin_n) {
@@ -173,8 +213,10 @@ __global__ __launch_bounds__(64) void k_sp_adjudicate(CzTrees t, CzSelfplay sp, 
     const bool by_chase = CHASE && (stored & CZ_REP_BY_CHASE) != 0;
     const int verdict = CHASE ? (stored & ~CZ_REP_BY_CHASE) : stored;
     const bool mated = XQ && verdict == CZ_REP_NONE && sp.rr.mated[g] != 0;
-    const bool by_rules = verdict != CZ_REP_NONE || mated;
-    // asynchronous plies: only the slots that just moved (or stalled, or ended by the rules) can have ended their game
+    // cz_selfplay_set_resign: the last choose resigned the game — behind the verdict and the mate, which it came after
+    const bool resigned = sp.rs.game_no && sp.rs.resigned[g] != 0 && verdict == CZ_REP_NONE && !mated;
+    const bool by_rules = verdict != CZ_REP_NONE || mated || resigned;
+    // asynchronous plies: only the slots that just moved (or stalled, or ended by the rules or by resignation) can have ended their game
     if (played && played[g] == 0xFFFF && !sp.stalled[g] && !by_rules) { if (lane == 0) fin_n[g] = 0; return; }
     bool Kmiss, kmiss;
     wave_kings_missing(t.root_board + (size_t)g * CZD_BOARD_LDS, lane, Kmiss, kmiss);
@@ -183,7 +225,7 @@ __global__ __launch_bounds__(64) void k_sp_adjudicate(CzTrees t, CzSelfplay sp, 
     const bool decided = by_rules ? verdict != CZ_REP_DRAW : (Kmiss || kmiss);
     const bool draw = !decided && (by_rules || restrict_round_draw(t.root_rr[g]) || ply >= sp.max_plies);
     if (!(decided || draw || stalled)) { if (lane == 0) fin_n[g] = 0; return; }
-    const int winner = mated ? 1 - (int)t.root_side[g] : (verdict == CZ_REP_RED_LOSES ? 1 : (verdict == CZ_REP_BLACK_LOSES ? 0 : king_capture_winner(Kmiss)));
+    const int winner = mated || resigned ? 1 - (int)t.root_side[g] : (verdict == CZ_REP_RED_LOSES ? 1 : (verdict == CZ_REP_BLACK_LOSES ? 0 : king_capture_winner(Kmiss)));
     const int n = stalled ? 0 : min(ply, sp.max_plies);
     for (int j = lane; j < n; j += 64) {
         uint8_t *rec = sp.hist + ((size_t)g * sp.max_plies + j) * CZ_REC_BYTES;
@@ -200,8 +242,26 @@ __global__ __launch_bounds__(64) void k_sp_adjudicate(CzTrees t, CzSelfplay sp, 
         atomicAdd((unsigned long long *)&sp.stats[CZ_SP_PLIES], (unsigned long long)n);
         if constexpr (XQ) {
             if (by_chase) atomicAdd((unsigned long long *)sp.chase_stat, 1ull);
-            else if (by_rules) atomicAdd((unsigned long long *)&sp.xq_stats[mated ? 0 : (verdict == CZ_REP_DRAW ? 1 : 2)], 1ull);
+            else if (by_rules && !resigned) atomicAdd((unsigned long long *)&sp.xq_stats[mated ? 0 : (verdict == CZ_REP_DRAW ? 1 : 2)], 1ull);
             sp.rr.mated[g] = 0; sp.rr.rep[g] = CZ_REP_NONE;
+        }
+        if (sp.rs.game_no) {
+            unsigned long long *rstat = (unsigned long long *)sp.rs.stats, *rhist = (unsigned long long *)sp.rs.hist;
+            if (resigned) atomicAdd(&rstat[0], 1ull);
+            if (sp.rs.playon[g] && !stalled) {   // what the game would have done had it not played on, against how it ended
+                const int loser = decided ? 1 - winner : -1, would = sp.rs.would[g];
+                atomicAdd(&rstat[1], 1ull);
+                if (would) {
+                    atomicAdd(&rstat[2], 1ull);
+                    if (loser != would - 1) atomicAdd(&rstat[3], 1ull);   // the side that would have resigned won or drew
+                }
+                for (int s = 0; s < 2; ++s) {
+                    const float q = sp.rs.minq[2 * g + s];
+                    if (loser != s && q < 2.0f) atomicAdd(&rhist[min(max((int)floorf((q + 1.0f) * 32.0f), 0), 63)], 1ull);
+                }
+            }
+            // the slot's next game (reseed), or a parked slot with nothing left over
+            sp_resign_new_game(sp.rs, g, sp.rs.game_no[g] + (reseed ? 1u : 0u));
         }
     }
     if (reseed) {   // the slot's next game: a fresh root on its start position
@@ -234,6 +294,12 @@ __global__ __launch_bounds__(64) void k_sp_flush(CzSelfplay sp, int G, const int
 
 int czk_selfplay_seed(cz_ctx *c, const uint8_t *boards, const uint8_t *side, const int32_t *rr) {
     hipLaunchKernelGGL(k_sp_seed, dim3(c->G), dim3(64), 0, c->stream, c->t, c->sp, c->G, boards, side, rr);
+    CZ_HIP(hipGetLastError());
+    return CZ_OK;
+}
+
+int czk_selfplay_resign_init(cz_ctx *c) {
+    hipLaunchKernelGGL(k_sp_resign_init, dim3((c->max_games + 63) / 64), dim3(64), 0, c->stream, c->sp.rs, c->max_games);
     CZ_HIP(hipGetLastError());
     return CZ_OK;
 }

@@ -11,6 +11,8 @@ Mirrors, for G games at once, cchess_main.get_action (main.py:1332-1358) and cch
 With rules="xiangqi" (cz_selfplay_set_rules / cz_selfplay_set_repetition, as arena.Match) the games are Xiangqi: pi and the
 played move are over the king-safe root children only, a mover without one is mated, and with repetition=N the N-th occurrence
 of a position ends the game — the rules act at the root, the search below it stays the reference's.
+With resign=X (cz_selfplay_set_resign; the reference plays every game out) a mover whose root value is below X resigns, and a
+share of the games plays on to measure how often that would have been wrong (suggest_resign_threshold).
 All of it runs on the device (cz_selfplay_choose / cz_search_advance / cz_selfplay_adjudicate / cz_selfplay_flush,
 csrc/cz_selfplay.hip): there is no per-ply host synchronisation and no per-game Python loop; finished games hand their
 records to a device ring and — in continuous mode — their slot starts the next game at once, so the device stays full
@@ -25,7 +27,7 @@ import numpy as np
 import torch
 
 from ._lib import (MAXMOVES, NLABELS, NSQ, REC_BYTES, REC_COUNT, REC_FLAGS, REC_LABELS, REC_PLY, REC_SIDE, REC_VISITS, REC_Z,
-                   SP_CHASE_STATS, SP_RULES_STATS, SP_STATS, out_pointers, tables)
+                   SP_CHASE_STATS, SP_RESIGN_STATS, SP_RULES_STATS, SP_STATS, out_pointers, tables)
 from .rules import RULES, check_rule_options, root_rules_chase_history, root_rules_history, set_rule_options
 
 REC_MAXMOVES = MAXMOVES
@@ -129,6 +131,22 @@ def to_dense(rec, temperature=1.0, exact=True):
     return canonical_planes(u["boards"], u["side"]), pi, u["z"].astype(np.float32)
 
 
+def suggest_resign_threshold(hist, target_fp, min_samples=100):
+    """The resignation threshold that the play-on games' histogram (SelfPlay.resign_histogram: the lowest root value of every
+    side that did not lose its play-on game, 64 bins of 1/32 over [-1, 1)) allows at a false-positive rate of target_fp: the
+    largest bin edge e = -1 + b / 32, b in 0..64, with sum(hist[:b]) / sum(hist) <= target_fp — a side resigns below the
+    threshold, and the edges are exact in float32, so the entries below e are the bins < b (the kernel rounds q + 1 to float32
+    before it bins: a value within one rounding step below an edge counts in the bin above it).  None below min_samples
+    entries (too few play-on games to say)."""
+    hist = np.asarray(hist, np.int64).reshape(64)
+    total = int(hist.sum())
+    if total < max(int(min_samples), 1):
+        return None
+    below = np.concatenate([[0], np.cumsum(hist)])            # below[b] = entries in the bins < b
+    ok = np.nonzero(below / total <= float(target_fp))[0]
+    return -1.0 + int(ok[-1]) / 32.0 if len(ok) else None
+
+
 class SelfPlay:
     """G concurrent self-play games on one GPU, device-resident.
 
@@ -141,11 +159,23 @@ class SelfPlay:
     chase (with a repetition fold only): True — when neither side checked so, a side that alone chased one and the same
     unprotected piece with every move of the cycle has lost (cz_selfplay_set_chase, as arena.Match(chase=True)); z as for
     perpetual check.
+    resign: None — every game is played out; a value — from ply resign_min_ply on, a mover whose root value (the Q of its most
+    visited candidate child) is below it resigns (cz_selfplay_set_resign), except in the games that play on: a share
+    resign_playon of the games, drawn from `seed` per slot and game, never resigns and is counted instead — stats() says how many
+    of them crossed the threshold and how many of those did not lose (the false positives), resign_histogram() what threshold
+    a false-positive rate allows (suggest_resign_threshold).
     """
 
     def __init__(self, engine, net, playouts, exploration=True, temperature=1.0, seed=0, max_plies=512, ring_records=None,
-                 continuous=True, eval_cache=False, xcache_log2=0, rules="capture", repetition=0, chase=False):
+                 continuous=True, eval_cache=False, xcache_log2=0, rules="capture", repetition=0, chase=False, resign=None,
+                 resign_min_ply=0, resign_playon=0.1):
         check_rule_options("SelfPlay", rules, repetition, chase)
+        if int(resign_min_ply) < 0 or not 0.0 <= float(resign_playon) <= 1.0:
+            raise ValueError("SelfPlay: resign_min_ply >= 0 and 0 <= resign_playon <= 1")
+        self.resign = None if resign is None else float(resign)
+        self.resign_min_ply = int(resign_min_ply)
+        self.resign_playon = float(resign_playon)
+        self.seed = int(seed) & ((1 << 64) - 1)
         self.rules = rules
         self.repetition = int(repetition)
         self.chase = bool(chase)
@@ -180,6 +210,8 @@ class SelfPlay:
         G = eng.G
         eng.ctx.call("cz_selfplay_begin", self.max_plies, None, None, None)
         set_rule_options("cz_selfplay", eng.ctx.h, self.rules, self.repetition, self.chase)
+        self._resign_on = self.resign is not None
+        self._apply_resign()
         self._active_ptr, = out_pointers("cz_selfplay_active", eng.ctx.h, 1)
         R = int(self.ring_records or max(65536, 64 * G))
         self.ring = torch.zeros((R, REC_BYTES), dtype=torch.uint8, device=self.dev)
@@ -192,10 +224,24 @@ class SelfPlay:
         self._stats = torch.zeros(len(SP_STATS), dtype=torch.int64, device=self.dev)
         self._rules_stats = torch.zeros(len(SP_RULES_STATS), dtype=torch.int64, device=self.dev)
         self._chase_stats = torch.zeros(len(SP_CHASE_STATS), dtype=torch.int64, device=self.dev)
+        self._resign_stats = torch.zeros(len(SP_RESIGN_STATS), dtype=torch.int64, device=self.dev)
+        self._resign_hist = torch.zeros(64, dtype=torch.int64, device=self.dev)
         self.plies = 0
         self.lock_steps = 0
         self._dropped_seen = 0
         self.overflow_intervals = 0
+
+    def _apply_resign(self):
+        if self._resign_on:
+            self.eng.ctx.call("cz_selfplay_set_resign", float("nan") if self.resign is None else self.resign, self.resign_min_ply,
+                              self.resign_playon, self.seed)
+
+    def set_resign_threshold(self, threshold):
+        """Retunes the resignation threshold of a started loop (None: no ply is judged until the next call): the games in
+        progress, their play-on draws and the counters stay.  On a loop started without resignation this switches it on."""
+        self.resign = None if threshold is None else float(threshold)
+        self._resign_on = self._resign_on or self.resign is not None
+        self._apply_resign()
 
     # -- one ply of every game ------------------------------------------------------------------------
     def step_ply(self, forward=None, forced=None, rand=None):
@@ -337,7 +383,9 @@ class SelfPlay:
         """Running totals since start(): games, red_wins, black_wins, draws, plies (records), stalled, dropped, sims; with
         rules="xiangqi" also mates, repetitions, perpetuals — the games among them that ended by mate (a win), by a repetition
         draw, by perpetual check (a win); with chase=True also chases — the games that ended by perpetual chase (a win; not
-        among the perpetuals)."""
+        among the perpetuals); with resignation on also resigned, playon_games, playon_would_resign, playon_false_positives —
+        the games a mover resigned (a win for the other side), the play-on games finished, those in which a side crossed the
+        threshold, and those of them that side won or drew."""
         self.eng.ctx.call("cz_selfplay_stats", self._stats)
         s = self._stats.cpu().numpy()
         d = {k: int(v) for k, v in zip(SP_STATS, s)}
@@ -347,7 +395,16 @@ class SelfPlay:
         if self.chase:
             self.eng.ctx.call("cz_selfplay_chase_stats", self._chase_stats)
             d.update((k, int(v)) for k, v in zip(SP_CHASE_STATS, self._chase_stats.cpu().numpy()))
+        if self._resign_on:
+            self.eng.ctx.call("cz_selfplay_resign_stats", self._resign_stats, None)
+            d.update((k, int(v)) for k, v in zip(SP_RESIGN_STATS, self._resign_stats.cpu().numpy()))
         d["sims"] += int(self.eng.status()[2].sum().item())   # + the simulations of the searches in progress
         d["plies_played"] = self.plies          # lock-step plies (step_ply)
         d["lock_steps"] = self.lock_steps       # select / net / expand steps of the asynchronous loop (run_async)
         return d
+
+    def resign_histogram(self):
+        """int64 [64] on the host: the lowest root value of every side that did not lose its play-on game, in bins of 1 / 32 over
+        [-1, 1) (cz_selfplay_resign_stats; all zero without resignation) — the input of suggest_resign_threshold."""
+        self.eng.ctx.call("cz_selfplay_resign_stats", self._resign_stats, self._resign_hist)
+        return self._resign_hist.cpu().numpy().copy()

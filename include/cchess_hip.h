@@ -484,6 +484,32 @@ int cz_selfplay_rules_stats(cz_ctx *, long long *stats_dev /* [3]: mates, repeti
 int cz_selfplay_set_chase(cz_ctx *, int on);
 int cz_selfplay_chase_history(cz_ctx *, const uint64_t **chase);
 int cz_selfplay_chase_stats(cz_ctx *, long long *stats_dev /* [1]: chases */);
+/* cz_selfplay_set_resign: resignation (AlphaGo Zero's), at every rule level.  threshold NaN = off (the default: everything above,
+ *   launch for launch and byte for byte).  THE VALUE A MOVER RESIGNS ON is the Q of its most visited candidate child — the first
+ *   maximum of N in generation order, as cz_match_choose's greedy pick; under rules 1 among the king-safe children the move is
+ *   chosen from — read from the tree as it is, in the sign the search maximises: larger is better for the mover, a child that takes
+ *   the king reads +1.  A ply is judged when that child has a visit, ply >= min_ply and no forced label is played; the mover
+ *   resigns when Q < threshold, a float32 compare with no arithmetic on Q (cz_search_root_stats' Q reproduces it exactly).
+ *   Order in cz_selfplay_choose: stalled, repetition, mate, then this, then the pick.  On a resignation played = 0xFFFF, no
+ *   record is written, the ply stays, and cz_selfplay_adjudicate — behind the verdict and the mate, before every other test, also
+ *   for a slot its `played` argument would skip — ends the game as a loss for the side to move: z as for a king capture,
+ *   fin_n = min(plies played, max_plies), counted in CZ_SP_GAMES, the winner's wins and CZ_SP_PLIES.
+ *   PLAY-ON GAMES measure what resignation costs: game number n of slot g (0 for the slot's first game, + 1 at every re-seed)
+ *   plays on iff (splitmix64(seed ^ splitmix64(g << 32 | n)) >> 11) * 2^-53 < playon_fraction (0 <= playon_fraction <= 1).  Such a
+ *   game never resigns; it notes the side that first crossed the threshold and is played out.  Every game keeps the lowest judged
+ *   value of each side.  When a play-on game ends (unless it stalled): playon_games + 1; if a side crossed, playon_would_resign
+ *   + 1, and if that side then won or drew, playon_false_positives + 1; and for each side that did not lose and was judged at all,
+ *   its lowest value q goes into the histogram at bin clamp((int)floorf((q + 1.0f) * 32.0f), 0, 63): 64 bins of 1/32 over [-1, 1)
+ *   — the values a threshold must stay below to spare those sides.
+ *   The first call after cz_selfplay_begin (which switches resignation off) allocates and zeroes the state and the counters, draws
+ *   every slot's game 0 and may come at any time; seed is taken then.  A later call only changes threshold, min_ply and
+ *   playon_fraction — the game numbers, the games' state and the counters stay, so a threshold can be retuned between batches; with
+ *   NaN no ply is judged until the next call.  playon_fraction applies from the slots' next games.
+ * cz_selfplay_resign_stats: device int64 [4] <- games resigned, play-on games finished, those in which a side crossed the
+ *   threshold, those of them that side did not lose; device int64 [64] <- the histogram (may be NULL).  Zeros while off. */
+int cz_selfplay_set_resign(cz_ctx *, float threshold, int min_ply, double playon_fraction, unsigned long long seed);
+int cz_selfplay_resign_stats(cz_ctx *, long long *stats_dev /* [4]: resigned, playon_games, playon_would_resign, playon_false_positives */,
+                             long long *hist_dev /* [64], may be NULL */);
 
 /* ---- device-resident evaluation matches between two players (one wave per game slot; no host round trip per ply) -------
  * replaces: cchess_main.policy_evaluate (main.py:1207-1222, commented out in the reference) — many games of player A
@@ -524,6 +550,7 @@ int cz_selfplay_chase_stats(cz_ctx *, long long *stats_dev /* [1]: chases */);
 #define CZ_MATCH_PERPETUAL 7    /* ... and one side alone checked with every move of the cycle: that side loses */
 #define CZ_MATCH_CHASE 9        /* cz_match_set_chase: ... neither side checked so, and one side alone chased one piece with every
                                    move of the cycle: that side loses (8 is not assigned) */
+#define CZ_MATCH_RESIGN 10      /* cz_match_set_resign: the mover's root value was below the threshold: it loses */
 typedef struct cz_match cz_match;
 int cz_match_create(cz_ctx *a, cz_ctx *b, const uint8_t *open_boards, const uint8_t *open_side, const int32_t *open_rr,
                     int n_openings, long long pair_base, long long pair_stride, int max_plies, cz_match **out);
@@ -557,7 +584,15 @@ int cz_match_set_rules(cz_match *, int rules);
  *   cz_repetition_chase's rule with the same window: a verdict whose cause is CZ_CAUSE_CHASE ends the game as CZ_MATCH_CHASE, a
  *   scored game like CZ_MATCH_PERPETUAL (result -1 when the chaser is A's colour in that game, else +1); every other verdict
  *   ends it as before.
- * cz_match_chase_history: the device pointer of the third ring, owned by the match; CZ_EINVAL while the rule is off. */
+ * cz_match_chase_history: the device pointer of the third ring, owned by the match; CZ_EINVAL while the rule is off.
+ * cz_match_set_resign: threshold NaN = nobody resigns (the default: everything above, launch for launch).  Otherwise both
+ *   players resign on their own tree's value, the one cz_selfplay_set_resign describes: from ply min_ply of a game on, in sampled
+ *   plies too, a mover whose most visited candidate child has a visit and Q < threshold resigns — after the repetition verdict
+ *   and the mate, before the choice: played = 0xFFFF, no move is logged, the ply is not advanced, and cz_match_adjudicate ends the
+ *   game as CZ_MATCH_RESIGN, a scored loss for the mover, behind CZ_MATCH_REPETITION / _PERPETUAL / _CHASE and CZ_MATCH_MATE and
+ *   before CZ_MATCH_ABORTED.  There is no play-on fraction: a match measures strength, not the threshold.  May change between
+ *   two plies. */
+int cz_match_set_resign(cz_match *, float threshold, int min_ply);
 int cz_match_set_repetition(cz_match *, int fold);
 int cz_match_history(cz_match *, const uint64_t **keys, const uint8_t **checks);
 int cz_match_set_chase(cz_match *, int on);

@@ -341,6 +341,9 @@ class cchess_main(object):
         self.last_evaluation = None
         self.rules, self.repetition = "capture", 0   # the batched self-play games and the evaluation matches (--rules, --repetition)
         self.chase = False                            # ... and whether they judge perpetual chase (--chase)
+        # resignation in the batched self-play games and the evaluation matches (--resign_threshold, --resign_min_ply,
+        # --resign_playon, --resign_auto): off unless a threshold or a false-positive target is given
+        self.resign_threshold, self.resign_min_ply, self.resign_playon, self.resign_auto = None, 0, 0.1, None
         # --mirror_augment: every sample a policy update draws is learnt from as it is or as its left-right mirror image, and the
         # mini-batch is built on the GPU from the packed records (cchess_zero_amd/records.py)
         self.mirror_augment = False
@@ -511,13 +514,15 @@ class cchess_main(object):
         net = self.policy_value_netowrk.net
         sp = getattr(self, "_sp", None)
         if (sp is None or sp.eng.G != G or sp.eng.ctx.cap < cap or sp.playouts != self.playout_counts or sp.net is not net
-                or sp.rules != self.rules or sp.repetition != self.repetition or sp.chase != self.chase):
+                or sp.rules != self.rules or sp.repetition != self.repetition or sp.chase != self.chase
+                or getattr(sp, "resign_options", None) != self._resign_options()):
             # planes are written by the select kernel straight in the fused net's input format (16 channels of its 16-bit type)
             plane_dtype, channels = plane_format(net)
             eng = SearchEngine(G, cap, torch.cuda.current_device(), plane_dtype=plane_dtype, channels=channels)
             # every rank seeds its games differently but reproducibly from the shared Python RNG state
             base_seed = random.randrange(1 << 30)
             rank = int(os.environ.get("RANK", "0"))
+            ro = self._resign_options()
             sp = SelfPlay(eng, net, self.playout_counts, self.exploration, self.temperature,
                           seed=base_seed + 7919 * rank, continuous=True,
                           # the evaluation cache pays from a few hundred playouts per move on (in-tree repeat rate 1 % at 100
@@ -530,7 +535,9 @@ class cchess_main(object):
                           # 4.16 M, 2**24 entries 4.38 M (+21.6 %); the write-once table is full either way
                           xcache_log2=min(24, max(18, (G * 2048 - 1).bit_length())) if self.playout_counts >= 400 else 0,
                           # a drain interval can end every game of every slot in the worst case: room for ~160 plies per slot
-                          ring_records=max(65536, 160 * G), rules=self.rules, repetition=self.repetition, chase=self.chase)
+                          ring_records=max(65536, 160 * G), rules=self.rules, repetition=self.repetition, chase=self.chase,
+                          **({} if ro is None else dict(resign=ro[0], resign_min_ply=ro[1], resign_playon=ro[2])))
+            sp.resign_options = ro       # as given: --resign_auto retunes sp.resign, the slots are rebuilt when the options change
             b0 = np.tile(state_to_board(START_STATE), (G, 1))
             sp.start(b0, np.zeros(G, np.uint8), np.zeros(G, np.int32))
             self._sp, self._batch_eng = sp, eng
@@ -553,11 +560,30 @@ class cchess_main(object):
             st = sp.stats()
             if st["games"] - before["games"] >= target or (max_plies is not None and plies >= max_plies):
                 break
-        self.last_selfplay_stats = {k: (st[k] - before[k] if k in ("games", "red_wins", "black_wins", "draws", "plies", "sims", "lock_steps", "mates", "repetitions", "perpetuals", "chases") else st[k])
+        self.last_selfplay_stats = {k: (st[k] - before[k] if k in ("games", "red_wins", "black_wins", "draws", "plies", "sims", "lock_steps", "mates", "repetitions", "perpetuals", "chases",
+                                                                           "resigned", "playon_games", "playon_would_resign", "playon_false_positives") else st[k])
                                     for k in st}
         self.last_selfplay_sims = self.last_selfplay_stats["sims"]
         rec = torch.cat(chunks, 0) if chunks else sp.ring[:0]
         return parallel.gather_records(rec)
+
+    def _resign_options(self):
+        """What the self-play slots are built with: None = games are played out.  With --resign_auto alone the first threshold is
+        -1, which no value is below: every ply is judged and the play-on games fill the histogram, nobody resigns yet."""
+        if self.resign_threshold is None and self.resign_auto is None:
+            return None
+        return (-1.0 if self.resign_threshold is None else float(self.resign_threshold), int(self.resign_min_ply), float(self.resign_playon))
+
+    def _retune_resign(self):
+        """--resign_auto FP, after a batch: the threshold the play-on games' histogram allows at that false-positive rate, never
+        above 0; unchanged while the histogram is too small to say."""
+        from cchess_zero_amd.selfplay import suggest_resign_threshold
+        sp = getattr(self, "_sp", None)
+        if sp is None or self.resign_auto is None:
+            return
+        t = suggest_resign_threshold(sp.resign_histogram(), self.resign_auto)
+        if t is not None:
+            sp.set_resign_threshold(min(t, 0.0))
 
     def policy_evaluate(self, n_games=10, opponent=None):
         """Reference: main.py:1207-1222 (commented out there) — a match of the live net against `opponent` on the GPU
@@ -580,8 +606,10 @@ class cchess_main(object):
             opp = getattr(opponent, "net", opponent)
         self._eval_round = getattr(self, "_eval_round", 0) + 1
         openings = random_openings(pairs, 4, seed=self.update_seed + self._eval_round)
+        ro = self._resign_options()      # the matches resign as self-play does now: on the threshold --resign_auto last set
         res = Match((live, self.playout_counts), (opp, self.playout_counts), openings, slots=max(2, min(2 * pairs, self.games)),
-                    seed=self.update_seed + self._eval_round, rules=self.rules, repetition=self.repetition, chase=self.chase).play()
+                    seed=self.update_seed + self._eval_round, rules=self.rules, repetition=self.repetition, chase=self.chase,
+                    resign=ro and getattr(getattr(self, "_sp", None), "resign", ro[0]), resign_min_ply=ro[1] if ro else 0).play()
         self.last_evaluation = res
         if opponent is None and res.score is not None and res.score >= 0.55:
             self._eval_snapshot = self._snapshot_net()
@@ -660,6 +688,10 @@ class cchess_main(object):
                           "eval_cache": bool(getattr(self._sp, "eval_cache", False)), "xcache_log2": int(getattr(self._sp, "xcache_log2", 0))}
                 if "chases" in st:
                     timing["chases"] = int(st["chases"])
+                if "resigned" in st:
+                    timing.update((k, int(st[k])) for k in ("resigned", "playon_games", "playon_would_resign", "playon_false_positives"))
+                    self._retune_resign()
+                    timing["resign_threshold"] = self._sp.resign     # what the next batch resigns on
                 if self.mirror_augment:
                     timing["mirrored_samples"] = int(self.mirrored_samples - mirrored_before)   # of this rank's slices of the batch's updates
                 msg = "batch_timing: " + json.dumps(timing)
@@ -736,6 +768,15 @@ if __name__ == '__main__':
                              'or a loss for the side that checked perpetually; 0 = no repetition rule')
     parser.add_argument('--chase', action='store_true',
                         help='with --repetition: a side that alone chased one unprotected piece with every move of the cycle loses')
+    parser.add_argument('--resign_threshold', default=None, type=float,
+                        help='batched self-play and evaluation matches: a mover whose root value (Q of its most visited move) is below X '
+                             'resigns; default: every game is played out')
+    parser.add_argument('--resign_min_ply', default=0, type=int, help='plies of a game before anybody may resign')
+    parser.add_argument('--resign_playon', default=0.1, type=float,
+                        help='share of the self-play games that never resign and measure the false-positive rate instead')
+    parser.add_argument('--resign_auto', default=None, type=float,
+                        help='after every batch set the threshold to what the play-on games allow at this false-positive rate '
+                             '(never above 0; without --resign_threshold nobody resigns until enough play-on games have ended)')
     parser.add_argument('--mirror_augment', action='store_true',
                         help='policy updates learn from every drawn sample as it is or as its left-right mirror image (one coin per '
                              'sample), and build the mini-batch on the GPU from the packed records')
@@ -748,6 +789,8 @@ if __name__ == '__main__':
         parser.error("--repetition is 0 or 2..8 and needs --rules xiangqi")
     if args.chase and not args.repetition:
         parser.error("--chase needs --repetition")
+    if args.resign_min_ply < 0 or not 0.0 <= args.resign_playon <= 1.0 or not (args.resign_auto is None or 0.0 <= args.resign_auto <= 1.0):
+        parser.error("--resign_min_ply >= 0, --resign_playon and --resign_auto in [0, 1]")
 
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:   # launched by torch.distributed.run: one rank per GPU
         import torch
@@ -773,6 +816,8 @@ if __name__ == '__main__':
                                  args.res_block_nums, args.human_color, games=args.games)
         train_main.eval_every, train_main.eval_games = args.eval_every, args.eval_games
         train_main.rules, train_main.repetition, train_main.chase = args.rules, args.repetition, args.chase
+        train_main.resign_threshold, train_main.resign_min_ply = args.resign_threshold, args.resign_min_ply
+        train_main.resign_playon, train_main.resign_auto = args.resign_playon, args.resign_auto
         train_main.mirror_augment = args.mirror_augment
         train_main.run(args.max_batches)
         if os.environ.get("CCHESS_WEIGHT_DIGEST_DIR"):   # tests: every rank leaves a digest of its replica (they must be equal)
