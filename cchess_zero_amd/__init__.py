@@ -6,6 +6,7 @@ Layout
   rules.py       batched rules ops (K1-K3) over device tensors
   engine.py      lock-step search engine over G trees
   net.py         residual policy/value network (PyTorch-ROCm; MFMA convs)
+  analysis.py    best move, score and principal variations of N positions (cz_search_lines); ucci.py: the UCCI engine on top of it
 The reference-named façade (GameBoard, MCTS_tree, cchess_main, policy_value_network) lives in
 main.py / policy_value_network.py at the repository root.
 """

@@ -1,0 +1,158 @@
+"""Analysis of N positions at once: best move, score and principal variations per position.
+
+    python -m cchess_zero_amd.analysis --fen "<fen>" [--fen "<fen>" ...] [--fen-file F] --model M.pt --blocks 7 --playout 400 --lines 3
+
+prints one JSON object per position.  Positions are searched in chunks of `games` trees through one SearchEngine; per chunk:
+reset, one Rules.movegen_kingsafe launch for the root masks, `playouts` simulations, one cz_search_lines launch.
+
+What the search is: the reference's king-capture search (a position's value is decided by taking the king, 60 plies without
+a capture are a draw), with the Xiangqi rules applied AT THE ROOT — the lines start at king-safe root moves only, and a mover
+without a king-safe move is reported as such and not searched.  That is what matches and self-play do under --rules xiangqi
+(cz_match_set_rules, cz_selfplay_set_rules); below the root the tree holds pseudo-legal moves.  rules="capture" drops the root
+mask.  Scores are Q of the line's first move as the tree holds it, from the mover's view (-1 .. 1).
+"""
+import argparse
+import json
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import MASK_WORDS, NLABELS, POS_NO_SAFE_MOVE
+from .engine import SearchEngine, plane_format, pool_nodes
+from .notation import fen_to_position
+from .rules import Rules
+
+RULES = ("capture", "xiangqi")
+
+
+def label_of(move):
+    """A move given as its label or its ICCS text -> the label (ValueError for text that is no move of the board)."""
+    if isinstance(move, str):
+        try:
+            return _lib.tables()["label2i"][move]
+        except KeyError:
+            raise ValueError("no such move: %r" % move)
+    return int(move)
+
+
+def ban_words(ban, G):
+    """ban[i] = the moves (labels or text) position i may not start a line with -> uint32 [G, 66], their bits set."""
+    words = np.zeros((G, MASK_WORDS), np.uint32)
+    for i, moves in enumerate(ban):
+        for m in moves or ():
+            l = label_of(m)
+            if not 0 <= l < NLABELS:
+                raise ValueError("no such move label: %r" % (m,))
+            words[i, l >> 5] |= np.uint32(1) << np.uint32(l & 31)
+    return words
+
+
+class Analyzer:
+    """analyse() for any number of positions, `games` at a time, on one SearchEngine of `games` trees sized for `playouts`."""
+
+    def __init__(self, net, playouts, games, width=1, rules="xiangqi", device=0):
+        if rules not in RULES:
+            raise ValueError("rules: %s" % " or ".join(RULES))
+        if int(games) < 1:
+            raise ValueError("an analysis needs at least one tree")
+        from .arena import _player   # a PolicyValueNet, the policy_value_network facade or a device forward -> what search() takes
+        self.forward, self.playouts = _player((net, playouts))
+        self.games, self.rules = int(games), rules
+        # the fused net path reads 16-bit planes straight from the select kernel at width 1; k simulations in flight use the
+        # reference's float32 planes and the net's full forward
+        pd, ch = plane_format(self.forward) if int(width) == 1 else (torch.float32, 14)
+        self.engine = SearchEngine(self.games, pool_nodes(self.playouts), device, plane_dtype=pd, channels=ch, width=int(width))
+        self.engine.compact = int(width) == 1   # parked positions cost the net nothing
+        self.rule_kernels = Rules(ctx=self.engine.ctx)
+        self.labels = _lib.tables()["labels"]
+
+    # -- one chunk, stage by stage (analyse() drives them; the UCCI engine steps them) ----------------------------------------
+    def root_masks(self, boards, side, ban=None):
+        """-> (allowed [G, 66] int32 device tensor or None, flags uint8 [G] host array) of G positions: under rules "xiangqi" the
+        king-safe sets (one cz_movegen_kingsafe launch) and the CZ_POS_* flags, under "capture" no mask and no flags; the bits
+        of ban[i] cleared."""
+        G = len(side)
+        allowed, flags = None, np.zeros(G, np.uint8)
+        if self.rules == "xiangqi":
+            _, _, allowed, pos_flags = self.rule_kernels.movegen_kingsafe(boards, side, want_moves=False)
+            flags = pos_flags.cpu().numpy()
+        if ban is not None and any(ban):
+            if allowed is None:
+                allowed = torch.full((G, MASK_WORDS), -1, dtype=torch.int32, device=self.engine.dev)
+            allowed = allowed & ~self.engine.ctx.tensor(ban_words(ban, G), torch.int32)
+        return allowed, flags
+
+    def read_lines(self, allowed, n_lines, max_len):
+        """One cz_search_lines launch -> per tree the list of its lines, dict(pv=[labels], visits=[...], q=[float32 ...])."""
+        ln = self.engine.lines_host(n_lines, max_len, allowed)
+        out = []
+        for g in range(self.engine.G):
+            rows = []
+            for j in range(n_lines):
+                n = int(ln["len"][g, j])
+                if n:
+                    rows.append(dict(pv=[int(x) for x in ln["moves"][g, j, :n]], visits=[int(x) for x in ln["visits"][g, j, :n]],
+                                     q=[np.float32(x) for x in ln["q"][g, j, :n]]))
+            out.append(rows)
+        return out
+
+    def analyse(self, positions, n_lines=1, max_len=16, ban=None):
+        """positions: FEN strings or (board uint8[90], side, restrict round) tuples, any number; ban: None or, per position, the
+        moves no line may start with.  -> per position dict(bestmove, score, lines=[dict(pv=[move text ...], visits, q)], sims,
+        flags): lines in rank order (more visits first), visits / q those of the line's first move, bestmove = lines[0].pv[0],
+        score = its q; flags = the position's CZ_POS_* bits.  A mover without a king-safe move reports bestmove None with
+        POS_NO_SAFE_MOVE in flags and is not searched; so does, without the flag, a position whose every candidate is banned."""
+        pos = [fen_to_position(p) if isinstance(p, str) else p for p in positions]
+        if ban is not None and len(ban) != len(pos):
+            raise ValueError("ban has one entry per position")
+        out = []
+        for at in range(0, len(pos), self.games):
+            chunk = pos[at:at + self.games]
+            boards = np.stack([np.asarray(p[0], np.uint8).reshape(90) for p in chunk])
+            side = np.array([1 if p[1] else 0 for p in chunk], np.uint8)
+            rr = np.array([int(p[2]) if len(p) > 2 else 0 for p in chunk], np.int32)
+            eng = self.engine
+            eng.reset(boards, side, rr)
+            allowed, flags = self.root_masks(boards, side, None if ban is None else ban[at:at + self.games])
+            live = (flags & POS_NO_SAFE_MOVE) == 0
+            if live.any():
+                eng.search(self.forward, self.playouts, active=None if live.all() else eng.ctx.tensor(live.astype(np.uint8), torch.uint8))
+            lines = self.read_lines(allowed, n_lines, max_len)
+            sims = eng.status()[2].cpu().numpy()
+            for g in range(len(chunk)):
+                rows = [dict(pv=[self.labels[m] for m in r["pv"]], visits=r["visits"][0], q=float(r["q"][0])) for r in lines[g]] if live[g] else []
+                out.append(dict(bestmove=rows[0]["pv"][0] if rows else None, score=rows[0]["q"] if rows else None, lines=rows,
+                                sims=int(sims[g]), flags=int(flags[g])))
+        return out
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(prog="python -m cchess_zero_amd.analysis",
+                                 description="Best move, score and principal variations of Xiangqi positions; one JSON object per position.")
+    ap.add_argument("--fen", action="append", default=[], help="a position as standard Xiangqi FEN (may be given more than once)")
+    ap.add_argument("--fen-file", default=None, help="a file with one FEN per line")
+    ap.add_argument("--model", default=None, help="checkpoint (own .pt, reference TF bundle, .npz); none = fresh weights")
+    ap.add_argument("--blocks", type=int, default=7, help="residual blocks of the net")
+    ap.add_argument("--playout", type=int, default=400, help="playouts per position")
+    ap.add_argument("--lines", type=int, default=1, help="principal variations per position")
+    args = ap.parse_args(argv)
+    fens = list(args.fen)
+    if args.fen_file:
+        fens += [l.strip() for l in open(args.fen_file) if l.strip()]
+    if not fens:
+        ap.error("no position: give --fen or --fen-file")
+    try:
+        pos = [fen_to_position(f) for f in fens]
+    except ValueError as e:
+        ap.error(str(e))
+    from .arena import load_player
+    net = load_player(args.model, args.blocks)
+    res = Analyzer(net, args.playout, min(len(pos), 8192)).analyse(pos, args.lines)
+    for f, r in zip(fens, res):
+        print(json.dumps(dict(fen=f, **r)), flush=True)
+    return res
+
+
+if __name__ == "__main__":
+    main()

@@ -295,6 +295,27 @@ class SearchEngine:
         return dict(label=st["label"].cpu().numpy().view(np.uint16), N=st["N"].cpu().numpy(), Q=st["Q"].cpu().numpy(),
                     P=st["P"].cpu().numpy(), W=st["W"].cpu().numpy(), count=st["count"].cpu().numpy().view(np.uint16))
 
+    def lines(self, n_lines=1, max_len=16, allowed=None):
+        """Principal variations (cz_search_lines): for every tree the lines that start at its n_lines most visited root
+        candidates — the root's children whose label is set in allowed [G, 66] int32 (a move set as Rules.movegen_kingsafe
+        returns it; None: all children) — and follow the most visited child below them, every tie to the earlier child.  Call it
+        between complete steps.  -> dict of device tensors: moves int16 (u16 bits, 0xFFFF padding) [G, n_lines, max_len],
+        visits int32 and q float32 of the same shape, len int16 [G, n_lines].  Line 0's first move is the greedy move."""
+        G, dev = self.G, self.dev
+        n_lines, max_len = int(n_lines), int(max_len)
+        allowed = self.ctx.tensor(allowed, torch.int32)
+        assert allowed is None or allowed.shape == (G, _lib.MASK_WORDS), "allowed is a [G, 66] mask"
+        shape = (G, max(n_lines, 0), max(max_len, 0))
+        out = dict(moves=torch.empty(shape, dtype=torch.int16, device=dev), visits=torch.empty(shape, dtype=torch.int32, device=dev),
+                   q=torch.empty(shape, dtype=torch.float32, device=dev), len=torch.empty(shape[:2], dtype=torch.int16, device=dev))
+        self.ctx.call("cz_search_lines", allowed, n_lines, max_len, out["moves"], out["visits"], out["q"], out["len"])
+        return out
+
+    def lines_host(self, n_lines=1, max_len=16, allowed=None):
+        ln = self.lines(n_lines, max_len, allowed)
+        return dict(moves=ln["moves"].cpu().numpy().view(np.uint16), visits=ln["visits"].cpu().numpy(), q=ln["q"].cpu().numpy(),
+                    len=ln["len"].cpu().numpy().view(np.uint16))
+
     def advance(self, played):
         if not torch.is_tensor(played):
             played = np.asarray(played, np.uint16)   # labels as u16 bits (0xFFFF: no move)

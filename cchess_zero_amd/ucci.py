@@ -1,0 +1,279 @@
+"""A UCCI engine (the protocol Xiangqi GUIs and match tools speak) on stdin / stdout.
+
+    python -m cchess_zero_amd.ucci --model M.pt --blocks 7 [--playout 400] [--search_threads 16]
+
+Commands: ucci, isready, setoption <name> <value> (Playouts, MultiPV), position {startpos | fen <fen>} [moves m1 m2 ...],
+banmoves m1 ..., go [nodes N | time T | depth D], stop, quit.  Moves are ICCS coordinates ("h2e2": files a-i, ranks 0-9 with
+red at rank 0), positions standard Xiangqi FEN (notation.fen_to_position).  After each go: one `info depth <len> [multipv k]
+score <round(1000 q)> nodes <sims> time <ms> pv m1 m2 ...` per line, then `bestmove m1 [ponder m2]`, or `nobestmove` when the
+mover has no king-safe move that is not banned.  Unknown commands are ignored.
+
+The search is the one analysis.py describes: the reference's king-capture search with the Xiangqi rules applied at the root.
+Out of scope: the engine does not judge repetition itself (GUIs send banmoves), it does not ponder (`ponder m2` is only the
+line's second move), and it does not reuse the tree between position commands — every go starts from a fresh root.
+
+UcciEngine(searcher, inp, out) is the protocol loop; `searcher` is what it needs from a search:
+    set_position(board uint8[90], side, restrict round)
+    kingsafe_mask() -> (uint32 [66] move set of the position, its CZ_POS_* flags)
+    search(playouts) -> simulations completed by the call (the tree of the position is kept between calls)
+    lines(allowed uint32 [66], n_lines, max_len) -> [dict(pv=[labels], visits=[...], q=[...])] in rank order
+    width (optional attribute): simulations in flight per lock-step
+AnalyzerSearcher provides it on one device tree; the tests fake it on the C oracle.
+"""
+import argparse
+import queue
+import sys
+import threading
+import time
+
+import numpy as np
+
+from . import _lib
+from .notation import START_FEN, fen_to_position
+
+CHUNK_STEPS = 32     # lock-steps between two looks at the clock / the input
+MAX_MULTIPV = 8
+PV_LEN = 16
+
+
+class UcciEngine:
+    def __init__(self, searcher, inp, out, playouts=400, clock=time.monotonic):
+        self.searcher, self.inp, self.out, self.clock = searcher, inp, out, clock
+        self.options = dict(playouts=int(playouts), multipv=1)
+        t = _lib.tables()
+        self.labels, self.label2i, self.srcdst = t["labels"], t["label2i"], t["srcdst"]
+        self.pos = fen_to_position(START_FEN)
+        self.ban = []
+        self.searcher.set_position(*self.pos)
+        self._lines = queue.Queue()
+        self._deferred = []
+
+    # -- output / input ------------------------------------------------------------------------------------------------------
+    def say(self, text):
+        self.out.write(text + "\n")
+        self.out.flush()
+
+    def _reader(self):
+        for line in self.inp:
+            self._lines.put(line)
+        self._lines.put(None)   # end of input: quit
+
+    def _next(self):
+        return self._deferred.pop(0) if self._deferred else self._lines.get()
+
+    def _stop_requested(self):
+        """Between two chunks of a search: `stop` ends it, `isready` is answered, everything else waits for the search's end."""
+        while True:
+            try:
+                line = self._lines.get_nowait()
+            except queue.Empty:
+                return False
+            word = line.split()[0] if line and line.split() else ""
+            if word == "stop":
+                return True
+            if word == "isready":
+                self.say("readyok")
+            else:
+                self._deferred.append(line)
+                if line is None:
+                    return False
+
+    def run(self):
+        threading.Thread(target=self._reader, daemon=True).start()
+        while True:
+            line = self._next()
+            if line is None or not self.handle(line):
+                break
+        self.say("bye")
+
+    # -- commands ------------------------------------------------------------------------------------------------------------
+    def handle(self, line):
+        """One command line -> False when it was quit."""
+        tok = line.split()
+        if not tok:
+            return True
+        cmd, args = tok[0], tok[1:]
+        if cmd == "quit":
+            return False
+        if cmd == "ucci":
+            self.say("id name cchess-zero-amd")
+            self.say("id author the cchess-zero-amd authors")
+            self.say("option Playouts type spin min 1 max 1000000 default %d" % self.options["playouts"])
+            self.say("option MultiPV type spin min 1 max %d default 1" % MAX_MULTIPV)
+            self.say("ucciok")
+        elif cmd == "isready":
+            self.say("readyok")
+        elif cmd == "setoption":
+            self.setoption(args)
+        elif cmd == "position":
+            self.position(args)
+        elif cmd == "banmoves":
+            self.banmoves(args)
+        elif cmd == "go":
+            self.go(args)
+        return True   # stop outside a search and unknown commands: ignored
+
+    def setoption(self, args):
+        if len(args) < 2:
+            return
+        name = args[0].lower()
+        try:
+            value = int(args[1])
+        except ValueError:
+            return self.say("info string setoption %s: %r is no number" % (args[0], args[1]))
+        if name == "playouts":
+            self.options["playouts"] = max(1, value)
+        elif name == "multipv":
+            self.options["multipv"] = min(max(1, value), MAX_MULTIPV)
+
+    def _legal(self, pos, text):
+        """Is `text` a king-safe move of pos?  (The searcher is left on pos.)"""
+        label = self.label2i.get(text)
+        if label is None:
+            return None
+        self.searcher.set_position(*pos)
+        mask, _ = self.searcher.kingsafe_mask()
+        return label if (int(mask[label >> 5]) >> (label & 31)) & 1 else None
+
+    def apply(self, pos, label):
+        """pos after the move: the restrict round counts the plies since the last capture."""
+        board, side, rr = pos
+        src, dst = int(self.srcdst[label]) & 0xFF, int(self.srcdst[label]) >> 8
+        nb = np.array(board, np.uint8, copy=True)
+        capture = nb[dst] != 0
+        nb[dst], nb[src] = nb[src], 0
+        return nb, 1 - side, 0 if capture else rr + 1
+
+    def position(self, args):
+        """position {startpos | fen <fen>} [moves ...]: on a malformed FEN or an illegal move one `info string` line, and the
+        previous position (and its banmoves) stays."""
+        moves = args[args.index("moves") + 1:] if "moves" in args else []
+        head = args[:args.index("moves")] if "moves" in args else args
+        try:
+            if head[:1] == ["startpos"]:
+                pos = fen_to_position(START_FEN)
+            elif head[:1] == ["fen"]:
+                pos = fen_to_position(" ".join(head[1:]))
+            else:
+                raise ValueError("position startpos | position fen <fen>")
+            for m in moves:
+                label = self._legal(pos, m)
+                if label is None:
+                    raise ValueError("illegal move %s in %s" % (m, " ".join(args)))
+                pos = self.apply(pos, label)
+        except ValueError as e:
+            self.searcher.set_position(*self.pos)
+            return self.say("info string %s" % e)
+        self.pos, self.ban = pos, []
+        self.searcher.set_position(*pos)
+
+    def banmoves(self, args):
+        for m in args:
+            if m in self.label2i:
+                self.ban.append(self.label2i[m])
+            else:
+                self.say("info string banmoves: no such move %s" % m)
+
+    def go(self, args):
+        mode, amount = "playouts", self.options["playouts"]
+        for k in ("nodes", "time", "depth"):
+            if k in args[:-1]:
+                try:
+                    mode, amount = k, max(1, int(args[args.index(k) + 1]))
+                except ValueError:
+                    pass
+        start = self.clock()
+        s = self.searcher
+        s.set_position(*self.pos)    # a fresh root for every go
+        mask, _ = s.kingsafe_mask()
+        allowed = np.array(mask, np.uint32)
+        for label in self.ban:
+            allowed[label >> 5] &= ~(np.uint32(1) << np.uint32(label & 31))
+        if not allowed.any():
+            return self.say("nobestmove")
+        chunk = CHUNK_STEPS * max(1, int(getattr(s, "width", 1)))
+        budget = amount if mode in ("playouts", "nodes") else self.options["playouts"] if mode == "depth" else None
+        sims = 0
+        while True:
+            n = chunk if budget is None else min(chunk, budget - sims)
+            if n <= 0:
+                break
+            done = s.search(n)
+            sims += done
+            if done <= 0 or self._stop_requested():
+                break
+            if mode == "time" and (self.clock() - start) * 1000.0 >= 0.9 * amount:
+                break
+            if mode == "depth":
+                top = s.lines(allowed, 1, min(max(amount, 1), 64))
+                if top and len(top[0]["pv"]) >= amount:
+                    break
+        lines = s.lines(allowed, self.options["multipv"], min(64, max(PV_LEN, amount if mode == "depth" else 0)))
+        if not lines:
+            return self.say("nobestmove")
+        ms = int(round((self.clock() - start) * 1000.0))
+        for k, ln in enumerate(lines):
+            multipv = " multipv %d" % (k + 1) if self.options["multipv"] > 1 else ""
+            self.say("info depth %d%s score %d nodes %d time %d pv %s" % (len(ln["pv"]), multipv, int(round(1000.0 * float(ln["q"][0]))), sims, ms,
+                                                                         " ".join(self.labels[m] for m in ln["pv"])))
+        pv = lines[0]["pv"]
+        self.say("bestmove %s%s" % (self.labels[pv[0]], " ponder %s" % self.labels[pv[1]] if len(pv) > 1 else ""))
+
+
+class AnalyzerSearcher:
+    """The searcher of UcciEngine on tree 0 of an Analyzer (games = 1, rules "xiangqi")."""
+
+    def __init__(self, analyzer):
+        assert analyzer.rules == "xiangqi", "a UCCI engine plays by the Xiangqi rules"
+        self.a = analyzer
+        self.width = analyzer.engine.width
+        self.pos, self._rooted = None, False
+
+    def set_position(self, board, side, rr):
+        self.pos = (np.asarray(board, np.uint8).reshape(1, 90), np.array([1 if side else 0], np.uint8), np.array([int(rr)], np.int32))
+        self._rooted = False   # the tree is reset by the first search of the position
+
+    def kingsafe_mask(self):
+        allowed, flags = self.a.root_masks(self.pos[0], self.pos[1])
+        return allowed.cpu().numpy().view(np.uint32)[0], int(flags[0])
+
+    def _sims(self):
+        return int(self.a.engine.status()[2].cpu().numpy()[0])
+
+    def _root(self):
+        if not self._rooted:
+            self.a.engine.reset(*self.pos)
+            self._rooted = True
+            return False
+        return True
+
+    def search(self, playouts):
+        expanded = self._root()
+        before = self._sims()
+        self.a.engine.search(self.a.forward, int(playouts), root_done=expanded)
+        return self._sims() - before
+
+    def lines(self, allowed, n_lines, max_len):
+        self._root()
+        mask = np.ascontiguousarray(allowed, np.uint32).reshape(1, -1)
+        return self.a.read_lines(mask, n_lines, max_len)[0]
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(prog="python -m cchess_zero_amd.ucci", description="UCCI engine on stdin / stdout.")
+    ap.add_argument("--model", default=None, help="checkpoint (own .pt, reference TF bundle, .npz); none = fresh weights")
+    ap.add_argument("--blocks", type=int, default=7, help="residual blocks of the net")
+    ap.add_argument("--playout", type=int, default=400, help="default of the Playouts option: playouts of a bare `go`")
+    ap.add_argument("--search_threads", type=int, default=16, help="simulations in flight per lock-step")
+    args = ap.parse_args(argv)
+    from .analysis import Analyzer
+    from .arena import load_player
+    net = load_player(args.model, args.blocks)
+    # the node pool is sized once: for the Playouts default or 4096 playouts, whichever is more (a longer search stops expanding
+    # when the pool is full and answers from the visits it has)
+    analyzer = Analyzer(net, max(args.playout, 4096), 1, width=max(1, min(args.search_threads, 64)))
+    UcciEngine(AnalyzerSearcher(analyzer), sys.stdin, sys.stdout, playouts=args.playout).run()
+
+
+if __name__ == "__main__":
+    main()

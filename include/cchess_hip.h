@@ -377,6 +377,21 @@ int cz_search_expand_backup_k(cz_ctx *, int k, const void *logits, const void *v
  *   arrays [G][128] (any may be NULL), count [G]. */
 int cz_search_root_stats(cz_ctx *, uint16_t *move_label, int32_t *N, float *Q, float *P, float *W,
                          uint16_t *count);
+/* Principal variations: for every tree, n_lines lines of at most max_len moves read from the tree as it stands (read-only; call
+ *   it between complete lock-steps, as cz_search_root_stats: with width > 1 a pending descent still carries its virtual loss).
+ *   root_allowed [G][CZ_MASK_WORDS] (a move set as cz_movegen_kingsafe writes it) or NULL; moves / visits / q [G][n_lines][max_len]
+ *   (any may be NULL), len [G][n_lines]; all device memory.  1 <= n_lines <= 128, 1 <= max_len <= 64, CZ_EINVAL otherwise.
+ *   Candidates of tree g: the root's children, in generation order, whose label has its bit set in root_allowed[g] (NULL: all of
+ *   them) - the list cz_match_choose / cz_selfplay_choose choose from under rules 1.  Line j starts at the candidate of rank j
+ *   under "more visits first, earlier in generation order first among equals": line 0's first move is the greedy move of
+ *   cz_search_pick_ready / cz_match_choose.  A candidate without a visit still gives a line of length 1; j >= the number of
+ *   candidates gives len 0, as does every line of an unexpanded root or a root without children.  From the node just appended,
+ *   while it is expanded and the line is shorter than max_len, the line takes the first maximum of N over its children and stops,
+ *   without appending it, when that child has no visit.  Entry i < len: moves = the child's label (board coordinates at every
+ *   depth), visits = its N, q = its Q as the pool holds it, bit for bit, in the sign the search maximises for the mover at that
+ *   node's parent.  Entries i >= len: 0xFFFF, 0, 0.0f - every element of every output array is written. */
+int cz_search_lines(cz_ctx *, const uint32_t *root_allowed, int n_lines, int max_len, uint16_t *moves, int32_t *visits, float *q,
+                    uint16_t *len);
 /* K7  replaces MCTS_tree.update_tree (main.py:272-276) + the board bookkeeping of selfplay
  *   (:1522-1528): re-root on the played child keeping its subtree (compacted in place: one node
  *   pool per tree); clears CZ_ST_POOL_EXHAUSTED.  played_label 0xFFFF leaves the tree untouched. */
