@@ -335,6 +335,21 @@ int cz_records_expand(cz_ctx *c, const uint8_t *records, int n, const uint8_t *m
     return czk_records_expand(c, records, n, mirror, temperature, planes, pi, z);
 }
 
+int cz_games_replay(cz_ctx *c, const uint8_t *start_boards, const uint8_t *start_side, const uint16_t *moves, int stride, const int32_t *len,
+                    const int8_t *result, int G, int rules, const int32_t *rec_offset, int total, uint8_t *records, int32_t *valid, uint8_t *status,
+                    uint8_t *end_flags, uint8_t *final_boards, uint8_t *final_side) {
+    CZ_REQUIRE(c && G >= 0, "cz_games_replay: null ctx / negative G");
+    CZ_REQUIRE(stride >= 0 && stride <= 65535 && total >= 0, "cz_games_replay: 0 <= stride <= 65535 and total >= 0 required");
+    CZ_REQUIRE(rules == 0 || rules == 1, "cz_games_replay: rules is 0 (capture) or 1 (king-safe)");
+    if (G == 0) return CZ_OK;
+    CZ_REQUIRE(moves && len && result && rec_offset && valid && status && end_flags,
+               "cz_games_replay: moves, len, result, rec_offset, valid, status, end_flags required");
+    CZ_REQUIRE((reinterpret_cast<uintptr_t>(records) & 15u) == 0, "cz_games_replay: records must be 16-byte aligned");
+    CZ_REQUIRE(!final_boards || final_side, "cz_games_replay: final_boards needs final_side");
+    return czk_games_replay(c, start_boards, start_side, moves, stride, len, result, G, rules, rec_offset, total, records, valid, status, end_flags,
+                            final_boards, final_side);
+}
+
 int cz_search_set_width(cz_ctx *c, int width) {
     CZ_REQUIRE(c, "null ctx");
     if (width < 1 || width > 64) { cz_set_error("cz_search_set_width: width %d outside 1..64", width); return CZ_EINVAL; }

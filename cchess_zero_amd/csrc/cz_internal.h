@@ -433,6 +433,8 @@ int czk_selfplay_choose(cz_ctx *, const float *, const float *, const uint16_t *
 int czk_selfplay_adjudicate(cz_ctx *, int, const uint16_t *, int32_t *);
 int czk_selfplay_flush(cz_ctx *, const int32_t *, const long long *, uint8_t *, long long, const long long *);
 int czk_records_expand(cz_ctx *, const uint8_t *, int, const uint8_t *, double, float *, float *, float *);   // cz_records.hip
+int czk_games_replay(cz_ctx *, const uint8_t *, const uint8_t *, const uint16_t *, int, const int32_t *, const int8_t *, int, int, const int32_t *, int, uint8_t *,
+                     int32_t *, uint8_t *, uint8_t *, uint8_t *, uint8_t *);   // cz_games.hip
 
 // ---- a tree's records in pre-order, host side (cz_api.hip; cz_search_tree_dump, cz_search_debug_eval_cache_dump) ----
 struct CzPreorder {

@@ -255,6 +255,48 @@ int cz_encode_planes(cz_ctx *, const uint8_t *boards, const uint8_t *side, int G
 int cz_records_expand(cz_ctx *, const uint8_t *records /* [n][CZ_REC_BYTES], device */, int n,
                       const uint8_t *mirror /* [n] 0/1, or NULL = none */, double temperature,
                       float *planes /* [n][9][10][14] */, float *pi /* [n][2086] */, float *z /* [n] */);
+/* Game replay: G RECORDED GAMES (move lists) -> CZ_REC_* records, one launch.  No reference function: the reference learns
+ *     from its own self-play only (cchess_main.selfplay, main.py:1493-1554) and never reads a game back.
+ *     Game g starts from start_boards[g] / start_side[g] (NULL: the opening position, main.py:585 / red to move) and is given
+ *     len[g] moves, moves[g * stride + i] the label of ply i.  At ply i the LEGAL LIST of the position is, for rules = 0, the
+ *     pseudo-legal list of cz_movegen, in the reference's order; for rules = 1, the king-safe list of cz_movegen_kingsafe, in
+ *     the same order.  If the move is in that list, record rec_offset[g] + i is written and the move is made exactly as
+ *     cz_apply_move makes it.  The record is one that cz_records_expand takes as it is: the board BEFORE the move, the side
+ *     to move, count and labels = the legal list, visits = 1 at the played child and 0 elsewhere (pi is one-hot at any
+ *     temperature), z = result[g] for a red-to-move record and -result[g] for a black one (the mover's view, as self-play
+ *     writes it), ply = i, flags = 0, unused label slots 0xFFFF and unused visits 0.
+ *     The replay of a game STOPS at the first ply whose move cannot be made.  valid[g]: the plies made.  status[g], the
+ *     tests in this order:
+ *       CZ_GAME_BAD_LEN    len[g] is outside 0 .. stride: nothing is read, valid[g] = 0, no record is written;
+ *       CZ_GAME_BAD_BOARD  the stand-alone generators refuse the position of that ply (count 0xFFFF);
+ *       CZ_GAME_AFTER_END  a move was given in a position with a king missing or, under rules = 1, without a king-safe move;
+ *       CZ_GAME_ILLEGAL    the label is not in the list (a label >= 2086, 0xFFFF included, never is);
+ *       CZ_GAME_OK         all len[g] plies were made.
+ *     The records of the plies given but not made, valid[g] .. len[g] - 1, are written as CZ_REC_BYTES zero bytes, so that a
+ *     caller can compact by a mask: every byte of records rec_offset[g] .. rec_offset[g] + len[g] - 1 is written exactly once
+ *     and nothing else of `records` is touched.  The caller keeps the games' ranges disjoint; a record index outside
+ *     [0, total) is not written: no access leaves the arrays whatever they hold.
+ *     end_flags[g]: the position after valid[g] plies — its CZ_POS_* bits as cz_movegen_kingsafe reports them (at both rule
+ *     levels; 0 for a board it refuses), CZ_GAME_RED_KING_GONE, CZ_GAME_BLACK_KING_GONE.  final_boards [G][90] / final_side
+ *     [G] (may be NULL): that position.  records may be NULL (legality, counts and the final positions alone).
+ *     One lane per game, the board in registers from ply to ply; a wave of 64 games runs as long as its longest game: sort
+ *     the games by length and let rec_offset put the records in the order wanted.
+ *     G == 0: CZ_OK, no launch.  CZ_EINVAL: a NULL moves, len, result, rec_offset, valid, status or end_flags; stride < 0 or
+ *     > 65535 (ply is 16 bits); total < 0; rules outside 0 .. 1; records not 16-byte aligned; final_boards without
+ *     final_side.  Everything else at any address its element type allows. */
+#define CZ_GAME_OK 0
+#define CZ_GAME_ILLEGAL 1
+#define CZ_GAME_AFTER_END 2
+#define CZ_GAME_BAD_BOARD 3
+#define CZ_GAME_BAD_LEN 4
+#define CZ_GAME_RED_KING_GONE 16    /* end_flags: no 'K' on the board */
+#define CZ_GAME_BLACK_KING_GONE 32  /* end_flags: no 'k' on the board */
+int cz_games_replay(cz_ctx *, const uint8_t *start_boards /* [G][90] or NULL: the opening position */,
+                    const uint8_t *start_side /* [G] or NULL: red */, const uint16_t *moves /* [G][stride] labels */, int stride,
+                    const int32_t *len /* [G], 0..stride */, const int8_t *result /* [G]: +1 red won, -1 black won, 0 draw */, int G,
+                    int rules /* 0 capture, 1 king-safe */, const int32_t *rec_offset /* [G] */, int total,
+                    uint8_t *records /* [total][CZ_REC_BYTES] or NULL */, int32_t *valid /* [G] */, uint8_t *status /* [G] */,
+                    uint8_t *end_flags /* [G] */, uint8_t *final_boards /* [G][90] or NULL */, uint8_t *final_side /* [G] or NULL */);
 
 /* ---- lock-step search over G trees, one wavefront per tree ---------------------------------
  * replaces: MCTS_tree.__init__/reload (main.py:235-259): fresh, unexpanded roots. */

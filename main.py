@@ -645,6 +645,44 @@ class cchess_main(object):
         self.log_file.flush()
         return info
 
+    def pretrain(self, path, steps, rules=None, learning_rate=None):
+        """--pretrain: supervised steps on the recorded games of `path` (ICCS lines or PGN-style blocks, cchess_zero_amd/games.py)
+        before the first self-play batch.  The games are replayed into packed records on the GPU in one launch (cz_games_replay)
+        under `rules` (default: the self-play games' rules), games that are not legal under them are dropped; a twentieth of
+        the games is held out and reported on.  Honours --batch_size and --mirror_augment, saves a checkpoint, prints one
+        `pretrain: {json}` line, and the records seed the data buffer.  No reference function: the reference learns from its own
+        games only."""
+        import torch
+        import torch.distributed as dist
+        from cchess_zero_amd import games as G
+        from cchess_zero_amd.records import RecordExpander
+        rules = rules or self.rules
+        t0 = time.time()
+        parsed = G.parse_games(open(path).read())
+        rp = G.GameReplayer(device=torch.cuda.current_device())
+        res = rp.replay(parsed, rules=rules, on_illegal="drop")
+        if getattr(self, "_expander", None) is None:
+            self._expander = RecordExpander(ctx=rp.ctx)
+        info = G.pretrain(self.policy_value_netowrk, res.records, res.game_of_record, steps, self.batch_size,
+                          self.learning_rate if learning_rate is None else learning_rate, self.update_seed, mirror=self.mirror_augment,
+                          expand=self._expander.expand if self.mirror_augment else None, log=lambda *_: None)
+        self.global_step = self.policy_value_netowrk.global_step
+        if not (dist.is_available() and dist.is_initialized()) or dist.get_rank() == 0:
+            self.policy_value_netowrk.save(self.global_step)
+        rec = res.records.cpu().numpy()
+        if self.data_buffer.maxlen < len(rec):
+            self.data_buffer = deque(self.data_buffer, maxlen=len(rec))
+        self.data_buffer.extend(rec[i] for i in np.random.RandomState(self.update_seed).permutation(len(rec)))   # same on every rank
+        out = {"file": os.path.basename(path), "rules": rules, "skipped_blocks": len(parsed.skipped), "seconds": round(time.time() - t0, 3)}
+        out.update(res.counts)
+        out.update((k, info[k]) for k in ("steps", "train_records", "holdout_records", "holdout_games", "mirrored", "top1", "logloss", "value_sign"))
+        out["losses"] = [round(x, 6) for x in info["losses"]]
+        msg = "pretrain: " + json.dumps(out)
+        print(msg, flush=True)
+        self.log_file.write(msg + '\n')
+        self.log_file.flush()
+        return out
+
     def run(self, max_batches=None):
         """The training loop (main.py:1206-1248).  One iteration = a self-play batch of `games` slots per GPU (thousands
         of samples where the reference's single game gives ~100), so the reference's cadence is rescaled: the buffer
@@ -780,6 +818,13 @@ if __name__ == '__main__':
     parser.add_argument('--mirror_augment', action='store_true',
                         help='policy updates learn from every drawn sample as it is or as its left-right mirror image (one coin per '
                              'sample), and build the mini-batch on the GPU from the packed records')
+    parser.add_argument('--pretrain', default=None, type=str,
+                        help='recorded games (one per line of ICCS moves, or PGN-style blocks with ICCS movetext): supervised steps on '
+                             'them before the first self-play batch; their records also seed the data buffer')
+    parser.add_argument('--pretrain_steps', default=1000, type=int, help='training steps of --pretrain (of --batch_size samples)')
+    parser.add_argument('--pretrain_rules', default=None, choices=['capture', 'xiangqi'], type=str,
+                        help='the rules the recorded games must be legal under (default: the value of --rules)')
+    parser.add_argument('--pretrain_lr', default=None, type=float, help='learning rate of --pretrain (default: the training loop\'s)')
     parser.add_argument('--net_precision', default=None, choices=['strict', 'mx6', 'fp16x2', 'fp16', 'bf16', 'bf16x2', 'fp32'], type=str,
                         help='net engine (policy_value_network.PRECISIONS): strict (default) = measured within 5e-4 absolute of the '
                              'fp32 graph on 64 positions with the LIVE weights after every weight change, falling over mx6 -> fp16x2 -> '
@@ -819,6 +864,8 @@ if __name__ == '__main__':
         train_main.resign_threshold, train_main.resign_min_ply = args.resign_threshold, args.resign_min_ply
         train_main.resign_playon, train_main.resign_auto = args.resign_playon, args.resign_auto
         train_main.mirror_augment = args.mirror_augment
+        if args.pretrain:
+            train_main.pretrain(args.pretrain, args.pretrain_steps, args.pretrain_rules, args.pretrain_lr)
         train_main.run(args.max_batches)
         if os.environ.get("CCHESS_WEIGHT_DIGEST_DIR"):   # tests: every rank leaves a digest of its replica (they must be equal)
             import hashlib

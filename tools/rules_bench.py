@@ -9,7 +9,10 @@ usage: python tools/rules_bench.py [N positions, default 1048576]
        python tools/rules_bench.py --threats [N]      the threat kernel of the chase rule (cz_threats) beside the king-safe
            generator's flags-only and list forms on the same N positions, in the same run; one JSON line at the end
        python tools/rules_bench.py --successors [N]   cz_successors on the first N positions of the start position's depth-4
-           frontier (3 290 240 positions) with their king-safe lists: time and achieved store bandwidth; one JSON line at the end"""
+           frontier (3 290 240 positions) with their king-safe lists: time and achieved store bandwidth; one JSON line at the end
+       python tools/rules_bench.py --replay [G]       cz_games_replay on G (default 8192) games of games.random_games under each rule
+           level against the same answer from the ply-by-ply path that made them (one move-list launch and one cz_apply_move launch
+           per ply, games.ply_by_ply_replay), both timed in the same run, alternating; one JSON line at the end"""
 import os
 import sys
 import time
@@ -25,8 +28,9 @@ from cchess_zero_amd.rules import Rules  # noqa: E402
 KINGSAFE = "--kingsafe" in sys.argv
 THREATS = "--threats" in sys.argv
 SUCCESSORS = "--successors" in sys.argv
-_args = [a for a in sys.argv[1:] if a not in ("--kingsafe", "--threats", "--successors")]
-N = int(_args[0]) if _args else 1 << 20
+REPLAY = "--replay" in sys.argv
+_args = [a for a in sys.argv[1:] if a not in ("--kingsafe", "--threats", "--successors", "--replay")]
+N = int(_args[0]) if _args else (8192 if REPLAY else 1 << 20)
 ctx = Context(1, 2, 0)
 rules = Rules(ctx)
 
@@ -188,6 +192,69 @@ def successors_leg():
     print(json.dumps(out), flush=True)
 
 
+def replay_leg(max_ply=160):
+    """Per rule level: N games of random_games (U[0, max_ply] plies, less where a game ends before).  The fused replay is the bare
+    C call into buffers allocated once, the games sorted by length as GameReplayer sorts them (and once more in the order they
+    came: what the sort is worth); the yardstick is ply_by_ply_replay on the same device arrays.  Device events, 3 warm-up
+    launches, then 25 rounds of fused / unsorted / ply by ply one after the other; medians.  The final boards of all three are
+    asserted equal to the ones random_games reached before anything is timed."""
+    import json
+    from cchess_zero_amd import games as G
+    from cchess_zero_amd._lib import check, lib
+    from cchess_zero_amd.engine import _ptr
+    out = {"games": N, "max_ply": max_ply}
+    for level, r in (("capture", 0), ("xiangqi", 1)):
+        rg = G.random_games(level, N, 23, max_ply, engine_rules=rules)
+        lens, plies = rg["lens"].astype(np.int64), int(rg["lens"].sum())
+        offset = np.concatenate([[0], np.cumsum(lens)[:-1]])
+        rec = torch.empty((plies, 608), dtype=torch.uint8, device="cuda")
+        valid, status = torch.empty(N, dtype=torch.int32, device="cuda"), torch.empty(N, dtype=torch.uint8, device="cuda")
+        flags, fside = torch.empty(N, dtype=torch.uint8, device="cuda"), torch.empty(N, dtype=torch.uint8, device="cuda")
+        fboards = torch.empty((N, 90), dtype=torch.uint8, device="cuda")
+        zero = torch.zeros(N, dtype=torch.int8, device="cuda")
+        forms = {}
+        for name, order in (("fused_sorted", np.argsort(lens, kind="stable")), ("fused_input_order", np.arange(N))):
+            mv = ctx.tensor(rg["moves"][order], torch.int16)
+            ln, off = ctx.tensor(lens[order], torch.int32), ctx.tensor(offset[order], torch.int32)
+            forms[name] = (lambda mv=mv, ln=ln, off=off: check(lib().cz_games_replay(ctx.h, None, None, _ptr(mv), max_ply, _ptr(ln), _ptr(zero), N, r, _ptr(off),
+                                                                                     plies, _ptr(rec), _ptr(valid), _ptr(status), _ptr(flags), _ptr(fboards),
+                                                                                     _ptr(fside))), order)
+        d_mv, d_ln = ctx.tensor(rg["moves"], torch.int16), ctx.tensor(rg["lens"], torch.int32)
+        ctx.bind_stream()
+        for name, (fn, order) in forms.items():
+            fn()
+            torch.cuda.synchronize()
+            assert (status == 0).all() and np.array_equal(fboards.cpu().numpy(), rg["final_boards"][order]) and np.array_equal(valid.cpu().numpy(), lens[order]), name
+        v, fb, _ = G.ply_by_ply_replay(level, d_mv, d_ln, engine_rules=rules)
+        assert np.array_equal(fb.cpu().numpy(), rg["final_boards"]) and np.array_equal(v.cpu().numpy(), lens), "ply by ply"
+        timed_forms = {k: f for k, (f, _) in forms.items()}
+        timed_forms["ply_by_ply"] = lambda: G.ply_by_ply_replay(level, d_mv, d_ln, engine_rules=rules)
+        ts = {k: [] for k in timed_forms}
+        for it in range(3 + 25):
+            for name, fn in timed_forms.items():
+                ctx.bind_stream()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                fn()
+                e1.record()
+                e1.synchronize()
+                if it >= 3:
+                    ts[name].append(e0.elapsed_time(e1))
+        o = {"plies": plies, "mean_len": round(plies / N, 2), "max_len": int(lens.max())}
+        for name, t in ts.items():
+            t.sort()
+            o[name] = dict(ms=round(t[12], 4), min_ms=round(t[0], 4), max_ms=round(t[-1], 4), plies_per_s=round(plies / t[12] * 1e3))
+            print("%-8s %-18s: median %.3f ms (min %.3f, max %.3f) for %d games, %d plies = %.2f M plies/s"
+                  % (level, name, t[12], t[0], t[-1], N, plies, plies / t[12] / 1e3))
+        o["fused_vs_ply_by_ply"] = round(o["ply_by_ply"]["ms"] / o["fused_sorted"]["ms"], 2)
+        o["sorted_vs_input_order"] = round(o["fused_input_order"]["ms"] / o["fused_sorted"]["ms"], 3)
+        out[level] = o
+    print(json.dumps(out), flush=True)
+
+
+if REPLAY:
+    replay_leg()
+    sys.exit(0)
 if SUCCESSORS:
     successors_leg()
     sys.exit(0)
