@@ -291,31 +291,76 @@ __device__ __forceinline__ void root_children(const CzTrees &t, int g, const Tre
 }
 // the mover has no child to play: the node pool was exhausted at the root, or the rules kernels overflowed (the reference
 // has no node limit, so it has no such case); the driver's adjudication ends the game
-__device__ __forceinline__ bool root_cannot_move(int status, int n) {
-    return n == 0 || (status & (CZ_ST_NO_MOVES | CZ_ST_MOVE_OVERFLOW)) != 0;
+__device__ __forceinline__ bool root_cannot_move(const CzTrees &t, int g, int n) {
+    return n == 0 || (t.status[g] & (CZ_ST_NO_MOVES | CZ_ST_MOVE_OVERFLOW)) != 0;
 }
 
-// rules = 1 (cz_match_set_rules, cz_selfplay_set_rules): the root children whose move is in the king-safe set `safe`
-// ([CZ_MASK_WORDS], cz_movegen_kingsafe of the root position), compacted in generation order by one wave64 — sN[j] / sI[j]
-// (LDS, 128 ints each) = the visit count / the child index of the j-th of them, visible to every lane on return -> their number
-__device__ __forceinline__ int wave_kingsafe_children(const TreeView &v, int cb, int n, const uint32_t *__restrict__ safe, int lane,
-                                                      int *sN, int *sI) {
+// How the game at a root ended: `how` is 0 while it goes on, else the CZ_MATCH_* code (include/cchess_hip.h) of the ending, for
+// every driver; `loser` the side code of the side that lost, -1 for a draw, an aborted game and a game that goes on.
+struct CzGameEnd { int how, loser; };
+// THE PRECEDENCE OF THE ENDINGS, at rule level LEVEL, on slot g after its choose and advance, by one wave64: the verdict of the
+// repetition rule the choose left in rr.rep[g] (with CZ_REP_BY_CHASE: a chase) > a mated mover (rr.mated[g]) > a resignation >
+// an aborted game > check_end (main.py:1380-1392: a king is gone, then 60 plies without a capture) > the driver's ply cap.
+// The first three were found by the choose on the root it then left untouched, so the side to move (root_side) is the mover that
+// loses a mate or a resignation; `resigned` and `aborted` are the caller's own.  rr is not read below CZ_RULES_KINGSAFE.
+template <int LEVEL>
+__device__ __forceinline__ CzGameEnd wave_game_end(const CzRootRules &rr, int g, bool resigned, bool aborted, const uint8_t *root_board, int root_rr,
+                                                   int root_side, int ply, int max_plies, int lane) {
+    int verdict = CZ_REP_NONE;
+    bool by_chase = false;
+    if constexpr (LEVEL >= CZ_RULES_REPETITION) verdict = rr.rep[g];
+    if constexpr (LEVEL >= CZ_RULES_CHASE) { by_chase = (verdict & CZ_REP_BY_CHASE) != 0; verdict &= ~CZ_REP_BY_CHASE; }
+    bool Kmiss, kmiss;
+    wave_kings_missing(root_board, lane, Kmiss, kmiss);
+    if (verdict == CZ_REP_DRAW) return {CZ_MATCH_REPETITION, -1};
+    if (verdict != CZ_REP_NONE) return {by_chase ? CZ_MATCH_CHASE : CZ_MATCH_PERPETUAL, verdict == CZ_REP_RED_LOSES ? 0 : 1};
+    if (LEVEL >= CZ_RULES_KINGSAFE && rr.mated[g]) return {CZ_MATCH_MATE, root_side};
+    if (resigned) return {CZ_MATCH_RESIGN, root_side};
+    if (aborted) return {CZ_MATCH_ABORTED, -1};
+    if (Kmiss || kmiss) return {CZ_MATCH_KING, 1 - king_capture_winner(Kmiss)};
+    if (restrict_round_draw(root_rr)) return {CZ_MATCH_RR60, -1};
+    if (ply >= max_plies) return {CZ_MATCH_PLY_CAP, -1};
+    return {0, -1};
+}
+
+// ---- move choice at a root (k_pick_ready, k_lines, and k_sp_choose / k_match_choose behind wave_choose_prologue) ----
+// The candidates of a choice at a root, in generation order, by one wave64: the root's n <= CZD_MAXMOVES children at cb, or —
+// mask != NULL ([CZ_MASK_WORDS]: the king-safe set of cz_movegen_kingsafe under rules = 1, root_allowed of cz_search_lines) —
+// those of them whose label has its bit set, compacted.  N[r] / at[r] = the visit count / the index among the root's children
+// of candidate lane + 64 r (0 past the last) -> their number.  sN / sI (LDS, CZD_MAXMOVES ints each): the same lists visible to
+// every lane on return; the compaction goes through them, so a mask needs them, and all children without them (k_pick_ready,
+// the king-capture choosers) cost no LDS and no barrier.
+__device__ __forceinline__ int wave_root_candidates(const TreeView &v, int cb, int n, const uint32_t *__restrict__ mask, int lane, int N[2],
+                                                    int at[2], int *sN, int *sI) {
     bool ok[2];
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
         const int i = lane + 64 * r;
-        const uint32_t mv = i < n ? v.move[cb + i] : 0xFFFFu;
-        ok[r] = mv < CZ_NLABELS && ((safe[mv >> 5] >> (mv & 31)) & 1u) != 0u;
+        N[r] = 0; at[r] = 0;
+        ok[r] = i < n;
+        if (mask) {
+            const uint32_t mv = ok[r] ? v.move[cb + i] : 0xFFFFu;
+            ok[r] = mv < CZ_NLABELS && ((mask[mv >> 5] >> (mv & 31)) & 1u) != 0u;
+        }
+        if (ok[r]) { N[r] = v.N[cb + i]; at[r] = i; }
     }
+    if (!sN) return n;
+    // candidate j is the j-th child that is ok (without a mask: child j)
     const unsigned long long b0 = __ballot(ok[0]), b1 = __ballot(ok[1]), below = (1ull << lane) - 1ull;
-    const int n0 = __popcll(b0), ns = n0 + __popcll(b1);
-    if (ok[0]) { const int at = __popcll(b0 & below); sN[at] = v.N[cb + lane]; sI[at] = lane; }
-    if (ok[1]) { const int at = n0 + __popcll(b1 & below); sN[at] = v.N[cb + lane + 64]; sI[at] = lane + 64; }
+    const int to[2] = {(int)__popcll(b0 & below), (int)(__popcll(b0) + __popcll(b1 & below))};
+    n = __popcll(b0) + __popcll(b1);
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+        if (ok[r]) { sN[to[r]] = N[r]; sI[to[r]] = at[r]; }
     __syncthreads();
-    return ns;
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        const int i = lane + 64 * r;
+        N[r] = i < n ? sN[i] : 0; at[r] = i < n ? sI[i] : 0;
+    }
+    return n;
 }
 
-// ---- move choice at a root (k_pick_ready, k_sp_choose, k_match_choose) ---------------------------
 // get_action in its T -> 0 limit (main.py:1332-1341): the first maximum of N over a root's n <= 128 children, in generation
 // order (Python max() over root.child.items()) — N[r] is the visit count of child lane + 64 r; the index is wave-uniform
 __device__ __forceinline__ int wave_most_visited(const int N[2], int n, int lane) {

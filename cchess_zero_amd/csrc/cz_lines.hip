@@ -4,7 +4,7 @@
 //
 // Tie rules, the ones the choosers have (cz_internal.h):
 //   candidates   the root's children in generation order, with root_allowed only those whose label has its bit set — the list
-//                wave_kingsafe_children compacts for k_match_choose / k_sp_choose
+//                of wave_root_candidates, as k_match_choose / k_sp_choose get it under rules = 1
 //   ranking      more visits first, earlier in generation order first among equals: rank 0 is wave_most_visited's pick, the
 //                move cz_search_pick_ready / cz_match_choose play greedily
 //   below        the first maximum of N over the children (wave_most_visited); a best child without a visit ends the line
@@ -30,23 +30,13 @@ __global__ __launch_bounds__(64) void k_lines(CzTrees t, int G, const uint32_t *
     int cb, n;
     root_children(t, g, v, cb, n);
     if (n > CZD_MAXMOVES) n = CZD_MAXMOVES;
-    // the candidates' visit counts and child indices, in generation order
-    int nc;
-    if (root_allowed) {
-        nc = wave_kingsafe_children(v, cb, n, root_allowed + (size_t)g * CZ_MASK_WORDS, lane, sN, sI);
-    } else {
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-            const int i = lane + 64 * r;
-            if (i < n) { sN[i] = v.N[cb + i]; sI[i] = i; }
-        }
-        __syncthreads();
-        nc = n;
-    }
+    // the candidates' visit counts and child indices, in generation order: each lane's two, and all of them in sN / sI
+    int N[2], at[2];
+    const int nc = wave_root_candidates(v, cb, n, root_allowed ? root_allowed + (size_t)g * CZ_MASK_WORDS : nullptr, lane, N, at, sN, sI);
     // each lane ranks its two candidates by scanning all of them; the one of rank j starts this line
     int rank[2] = {0, 0};
     const int c0 = lane, c1 = lane + 64;
-    const int n0 = c0 < nc ? sN[c0] : 0, n1 = c1 < nc ? sN[c1] : 0;
+    const int n0 = N[0], n1 = N[1];
     for (int k = 0; k < nc; ++k) {
         const int nk = sN[k];
         rank[0] += (nk > n0 || (nk == n0 && k < c0)) ? 1 : 0;

@@ -86,53 +86,33 @@ __global__ __launch_bounds__(64) void k_match_start(CzTrees ta, CzTrees tb, CzMa
     take_game(ta, tb, m, g, g, lane);
 }
 
-// get_action of the mover (main.py:1332-1341) on its own tree t, at rule level LEVEL (CzRulesLevel, cz_rootrules.h): greedy, or
+// get_action of the mover (main.py:1332-1341) on its own tree, at rule level LEVEL (CzRulesLevel, cz_rootrules.h): greedy, or
 // sampled for the game's first sample_plies plies (select_move -> get_action(state, temperature = 1), main.py:1123,1433-1435: no
-// Dirichlet noise).
-// From CZ_RULES_KINGSAFE: among the root children whose move is in the slot's king-safe set — they are compacted, in generation
-// order, and the choice runs on the compacted visit counts exactly as it runs on all children under king-capture rules.
-// From CZ_RULES_REPETITION: first the root position goes through the slot's history (wave_root_history), whose verdict ends the
-// game before a move is chosen: no move is logged, the ply stays (k_match_adjudicate).
+// Dirichlet noise), among the candidates wave_choose_prologue (cz_rootrules.h) leaves.  On each of its endings no move is logged
+// and the ply stays (k_match_adjudicate).
 // At every level, with cz_match_set_resign: behind those exits and before the choice, a mover whose root value (wave_root_value,
 // cz_internal.h) is below the threshold resigns — the game ends the same way, as CZ_MATCH_RESIGN.
 template <int LEVEL>
-__device__ __forceinline__ void choose_on(const CzTrees &t, const CzMatch &m, int g, int game, int sample_plies, unsigned long long seed,
-                                          uint16_t *__restrict__ played, int lane) {
+__global__ __launch_bounds__(64) void k_match_choose(CzTrees ta, CzTrees tb, CzMatch m, int sample_plies, unsigned long long seed,
+                                                     uint16_t *__restrict__ played) {
+    const int g = blockIdx.x, lane = threadIdx.x;
+    if (g >= m.G) return;
+    const int game = m.game[g];
+    if (game < 0) { if (lane == 0) played[g] = 0xFFFF; return; }   // a parked slot: before any ring is touched
+    const CzTrees &t = m.mover_a[g] ? ta : tb;
     if (lane == 0) atomicAdd(m.sims, (unsigned long long)t.sims[g]);
+    if (LEVEL >= CZ_RULES_KINGSAFE && lane == 0) m.rr.mated[g] = 0;   // rr.rep is cleared when a game ends (k_match_adjudicate)
     const TreeView v = view_of(t, g);
-    int cb, n;
-    root_children(t, g, v, cb, n);
-    if (LEVEL >= CZ_RULES_KINGSAFE && lane == 0) m.rr.mated[g] = 0;
-    if (root_cannot_move(t.status[g], n)) {   // the game is aborted by the adjudication
-        if (lane == 0) { played[g] = 0xFFFF; m.stalled[g] = 1; }
-        return;
-    }
     const int ply = m.ply[g];
-    if constexpr (LEVEL >= CZ_RULES_REPETITION) {
-        if (wave_root_history<LEVEL >= CZ_RULES_CHASE>(m.rr, g, ply, t.root_rr[g], lane) != CZ_REP_NONE) {
-            if (lane == 0) played[g] = 0xFFFF;
-            return;
+    int cb, n, N[2], at[2];
+    const CzRootFound found = wave_choose_prologue<LEVEL>(m.rr, t, v, g, ply, lane, cb, n, N, at);
+    if (found != CZ_ROOT_CANDIDATES) {
+        if (lane == 0) {
+            played[g] = 0xFFFF;
+            if (found == CZ_ROOT_CANNOT_MOVE) m.stalled[g] = 1;   // the game is aborted by the adjudication
+            if (found == CZ_ROOT_MATED) m.rr.mated[g] = 1;        // the mover loses
         }
-    }
-    int N[2] = {0, 0}, at[2] = {0, 0};   // the visits of candidate lane + 64 r and its index among the root's children
-    if constexpr (LEVEL >= CZ_RULES_KINGSAFE) {
-        __shared__ int sN[128], sI[128];
-        n = wave_kingsafe_children(v, cb, n, m.rr.safe + (size_t)g * CZ_MASK_WORDS, lane, sN, sI);
-        if (n == 0) {   // children, none of them king-safe: checkmate or stalemate, the mover loses (k_match_adjudicate)
-            if (lane == 0) { played[g] = 0xFFFF; m.rr.mated[g] = 1; }
-            return;
-        }
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-            const int i = lane + 64 * r;
-            if (i < n) { N[r] = sN[i]; at[r] = sI[i]; }
-        }
-    } else {
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-            const int i = lane + 64 * r;
-            if (i < n) { N[r] = v.N[cb + i]; at[r] = i; }
-        }
+        return;
     }
     if (m.resign_threshold == m.resign_threshold) {   // cz_match_set_resign: the mover resigns on its own tree's value, sampled plies too
         float q;
@@ -158,17 +138,6 @@ __device__ __forceinline__ void choose_on(const CzTrees &t, const CzMatch &m, in
     }
 }
 
-template <int LEVEL>
-__global__ __launch_bounds__(64) void k_match_choose(CzTrees ta, CzTrees tb, CzMatch m, int sample_plies, unsigned long long seed,
-                                                     uint16_t *__restrict__ played) {
-    const int g = blockIdx.x, lane = threadIdx.x;
-    if (g >= m.G) return;
-    const int game = m.game[g];
-    if (game < 0) { if (lane == 0) played[g] = 0xFFFF; return; }   // a parked slot: before any ring is touched
-    if (m.mover_a[g]) choose_on<LEVEL>(ta, m, g, game, sample_plies, seed, played, lane);
-    else choose_on<LEVEL>(tb, m, g, game, sample_plies, seed, played, lane);
-}
-
 // level >= CZ_RULES_KINGSAFE, before the choice: the mover's root position of every slot, for czk_root_rules_prepare
 __global__ __launch_bounds__(64) void k_match_roots_xq(CzTrees ta, CzTrees tb, CzMatch m) {
     const int g = blockIdx.x, lane = threadIdx.x;
@@ -178,14 +147,13 @@ __global__ __launch_bounds__(64) void k_match_roots_xq(CzTrees ta, CzTrees tb, C
 
 // After cz_search_advance(played) on both contexts: the follower's failed advance (its root was never expanded, so it has no
 // child for the move) is its normal case — it starts a fresh root on the new position; then check_end (main.py:1380-1392)
-// plus the match's own endings (ply cap, aborted game), the result, and the slot's next game.
-// From CZ_RULES_KINGSAFE: the slot's mover had no king-safe move — CZ_MATCH_MATE, before every other ending but these:
-// from CZ_RULES_REPETITION: the slot's choose found a fold-th occurrence — CZ_MATCH_REPETITION (a draw) or CZ_MATCH_PERPETUAL
-// (the side that checked with every move of the cycle loses), before mate and everything else;
-// at CZ_RULES_CHASE the verdict may carry CZ_REP_BY_CHASE — CZ_MATCH_CHASE, lost by the side that chased, scored like a perpetual check
+// plus the match's own endings (ply cap, aborted game), the result, and the slot's next game.  Whether and how the game ended
+// is wave_game_end's answer (cz_internal.h: the one precedence of the endings, in the match's own CZ_MATCH_* codes), the result
+// follows from the side it names as the loser; `aborted` here is a stalled choose, no label played, or a label that is no child
+// of the mover's root.
 template <int LEVEL>
 __global__ __launch_bounds__(64) void k_match_adjudicate(CzTrees ta, CzTrees tb, CzMatch m, const uint16_t *__restrict__ played) {
-    constexpr bool XQ = LEVEL >= CZ_RULES_KINGSAFE, REP = LEVEL >= CZ_RULES_REPETITION, CHASE = LEVEL >= CZ_RULES_CHASE;
+    constexpr bool XQ = LEVEL >= CZ_RULES_KINGSAFE, REP = LEVEL >= CZ_RULES_REPETITION;
     const int g = blockIdx.x, lane = threadIdx.x;
     if (g >= m.G) return;
     const int game = m.game[g];
@@ -193,40 +161,25 @@ __global__ __launch_bounds__(64) void k_match_adjudicate(CzTrees ta, CzTrees tb,
     const bool ma = m.mover_a[g] != 0;
     const CzTrees &mv = ma ? ta : tb, &fo = ma ? tb : ta;   // the mover's tree, the follower's
     const bool aborted = m.stalled[g] != 0 || played[g] >= CZ_NLABELS || (mv.status[g] & CZ_ST_BAD_ADVANCE) != 0;
-    bool Kmiss, kmiss;
-    wave_kings_missing(mv.root_board + (size_t)g * CZD_BOARD_LDS, lane, Kmiss, kmiss);
     const int ply = m.ply[g];
-    int reason = 0, verdict = CZ_REP_NONE;
-    bool by_chase = false;
-    if constexpr (REP) verdict = m.rr.rep[g];
-    if constexpr (CHASE) { by_chase = (verdict & CZ_REP_BY_CHASE) != 0; verdict &= ~CZ_REP_BY_CHASE; }
-    if (verdict != CZ_REP_NONE) reason = verdict == CZ_REP_DRAW ? CZ_MATCH_REPETITION : (by_chase ? CZ_MATCH_CHASE : CZ_MATCH_PERPETUAL);
-    else if (XQ && m.rr.mated[g]) reason = CZ_MATCH_MATE;
-    else if (m.resigned[g]) reason = CZ_MATCH_RESIGN;   // before aborted: its played is 0xFFFF too
-    else if (aborted) reason = CZ_MATCH_ABORTED;
-    else if (Kmiss || kmiss) reason = CZ_MATCH_KING;
-    else if (restrict_round_draw(mv.root_rr[g])) reason = CZ_MATCH_RR60;
-    else if (ply >= m.max_plies) reason = CZ_MATCH_PLY_CAP;
+    const CzGameEnd end = wave_game_end<LEVEL>(m.rr, g, m.resigned[g] != 0, aborted, mv.root_board + (size_t)g * CZD_BOARD_LDS, mv.root_rr[g],
+                                               mv.root_side[g], ply, m.max_plies, lane);
     if (lane == 0) fo.status[g] &= ~CZ_ST_BAD_ADVANCE;
-    if (!reason) {
+    if (!end.how) {
         if (lane == 0) { m.mover_a[g] = ma ? 0 : 1; m.act_a[g] = ma ? 0 : 1; m.act_b[g] = ma ? 1 : 0; }
         return;
     }
     int next = 0;
     if (lane == 0) {
         const bool a_red = (game & 1) == 0;
-        const bool a_wins = (king_capture_winner(Kmiss) == 0) == a_red;
-        int8_t result = (int8_t)(reason == CZ_MATCH_KING ? (a_wins ? 1 : -1) : (reason == CZ_MATCH_MATE || reason == CZ_MATCH_RESIGN ? (ma ? -1 : 1) : 0));
-        if constexpr (REP) {
-            if (reason == CZ_MATCH_PERPETUAL || reason == CZ_MATCH_CHASE) result = (int8_t)(((verdict == CZ_REP_RED_LOSES) == a_red) ? -1 : 1);   // A has the losing colour
-        }
+        const int8_t result = (int8_t)(end.loser < 0 ? 0 : ((end.loser == 0) == a_red ? -1 : 1));   // -1: A has the losing colour
         m.result[game] = result;
         if (XQ) m.rr.mated[g] = 0;
         if constexpr (REP) m.rr.rep[g] = CZ_REP_NONE;
         m.resigned[g] = 0;
         m.a_red[game] = a_red ? 1 : 0;
         m.plies[game] = ply;
-        m.reason[game] = (uint8_t)reason;
+        m.reason[game] = (uint8_t)end.how;
         atomicAdd(&m.queue[1], 1);
         next = atomicAdd(&m.queue[0], 1);
     }

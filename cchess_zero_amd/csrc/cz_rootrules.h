@@ -1,7 +1,8 @@
 // cz_rootrules.h — the Xiangqi rules that act at the root of a game slot, shared by the match (cz_match.hip) and self-play
 // (cz_selfplay.hip): the king-safe set of the root position, the slot's rings of position keys, check flags and chase records,
-// and the repetition / perpetual-check / perpetual-chase verdict on them.  The search below the root is untouched.
-// The host side (carve_root_rules, czk_root_rules_prepare, cz_root_rules_order) is in cz_internal.h.
+// and the repetition / perpetual-check / perpetual-chase verdict on them; and wave_choose_prologue, the steps both choose kernels
+// take at a root before they choose.  The search below the root is untouched.  How a game then ends is wave_game_end's
+// (cz_internal.h), for these two and the bench driver.  The host side (carve_root_rules, czk_root_rules_prepare, cz_root_rules_order) is in cz_internal.h.
 #pragma once
 #include <type_traits>
 
@@ -83,4 +84,34 @@ __device__ __forceinline__ int wave_root_history(const CzRootRules &rr, int g, i
     }
     if (verdict != CZ_REP_NONE && lane == 0) rr.rep[g] = (uint8_t)verdict;
     return verdict;
+}
+
+// What a choose kernel finds at the root of slot g before it chooses, in this order
+enum CzRootFound {
+    CZ_ROOT_CANDIDATES = 0,   // cb, n, N, at hold the candidates (wave_root_candidates): the consumer chooses among them
+    CZ_ROOT_CANNOT_MOVE,      // no child to play (root_cannot_move): the consumer's adjudication aborts the game
+    CZ_ROOT_VERDICT,          // from CZ_RULES_REPETITION: the root position ends the game (wave_root_history, left in rr.rep[g])
+    CZ_ROOT_MATED,            // from CZ_RULES_KINGSAFE: children, none of them king-safe: checkmate or stalemate
+};
+// The steps every chooser of a game takes at rule level LEVEL on slot g of tree set t (CzTrees; v = view_of(t, g)), at the
+// slot's ply, by one wave64.  From CZ_RULES_KINGSAFE the candidates are the root children whose move is in the slot's king-safe
+// set, compacted in generation order, and everything the consumer does with N / at runs on them exactly as it runs on all
+// children under king-capture rules.  The consumer's reactions are its own: played[g] = 0xFFFF, its stalled flag and
+// rr.mated[g], the moments at which it clears rr.mated / rr.rep, resignation, the record or the move log.
+template <int LEVEL, typename Trees, typename View>
+__device__ __forceinline__ CzRootFound wave_choose_prologue(const CzRootRules &rr, const Trees &t, const View &v, int g, int ply, int lane,
+                                                            int &cb, int &n, int N[2], int at[2]) {
+    root_children(t, g, v, cb, n);
+    if (root_cannot_move(t, g, n)) return CZ_ROOT_CANNOT_MOVE;
+    if constexpr (LEVEL >= CZ_RULES_REPETITION) {
+        if (wave_root_history<LEVEL >= CZ_RULES_CHASE>(rr, g, ply, t.root_rr[g], lane) != CZ_REP_NONE) return CZ_ROOT_VERDICT;
+    }
+    if constexpr (LEVEL >= CZ_RULES_KINGSAFE) {
+        __shared__ int sN[128], sI[128];
+        n = wave_root_candidates(v, cb, n, rr.safe + (size_t)g * CZ_MASK_WORDS, lane, N, at, sN, sI);
+        return n == 0 ? CZ_ROOT_MATED : CZ_ROOT_CANDIDATES;
+    } else {
+        n = wave_root_candidates(v, cb, n, nullptr, lane, N, at, nullptr, nullptr);
+        return CZ_ROOT_CANDIDATES;
+    }
 }

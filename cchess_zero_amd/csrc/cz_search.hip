@@ -40,11 +40,9 @@ __global__ __launch_bounds__(64) void k_pick_ready(CzTrees t, int G, int32_t *__
         const TreeView v = view_of(t, g);
         int cb, n;
         root_children(t, g, v, cb, n);
-        // first maximum of N in generation order (Python max() over root.child.items())
-        int N[2] = {0, 0};
-#pragma unroll
-        for (int r = 0; r < 2; ++r)
-            if (lane + 64 * r < n) N[r] = v.N[cb + lane + 64 * r];
+        // first maximum of N in generation order (Python max() over root.child.items()): all children are candidates, no LDS
+        int N[2], at[2];
+        n = wave_root_candidates(v, cb, n, nullptr, lane, N, at, nullptr, nullptr);
         const int bi = wave_most_visited(N, n, lane);
         if (n > 0) label = v.move[cb + bi];
         if (lane == 0) {
@@ -61,11 +59,11 @@ __global__ __launch_bounds__(64) void k_reload_finished(CzTrees t, int G, const 
                                                         unsigned long long *__restrict__ reloaded) {
     const int g = blockIdx.x, lane = threadIdx.x;
     if (g >= G || !ready[g]) return;
-    bool Kmiss, kmiss;
-    wave_kings_missing(t.root_board + (size_t)g * CZD_BOARD_LDS, lane, Kmiss, kmiss);
     // check_end (main.py:1380-1392): a king is gone or 60 plies without a capture; a root without a move to play is over too
-    const bool over = Kmiss || kmiss || restrict_round_draw(t.root_rr[g]) || played[g] == 0xFFFF;
-    if (!over) return;
+    // (aborted).  King-capture rules, nobody resigns, no ply cap.
+    const CzGameEnd end = wave_game_end<CZ_RULES_CAPTURE>(CzRootRules{}, g, false, played[g] == 0xFFFF, t.root_board + (size_t)g * CZD_BOARD_LDS,
+                                                          t.root_rr[g], t.root_side[g], 0, 0x7fffffff, lane);
+    if (!end.how) return;
     fresh_root(t, g, lane, boards, CZ_NSQ, side, rr, g);
     if (lane == 0 && reloaded) atomicAdd(reloaded, 1ull);
 }

@@ -70,12 +70,11 @@ __global__ __launch_bounds__(64) void k_sp_roots_xq(CzTrees t, CzSelfplay sp, in
 }
 
 // get_action (main.py:1337-1351) + the record append of selfplay (:1504-1518) for every active game, at rule level LEVEL
-// (CzRulesLevel, cz_rootrules.h).
-// From CZ_RULES_KINGSAFE (cz_selfplay_set_rules(1)): over the root children whose move is in the slot's king-safe set — they are
-// compacted, in generation order, and pi, the noise (gamma[g][j] of compacted child j: a Dirichlet over len(probs) entries), the
-// pick and the record run on the compacted children exactly as they run on all n under king-capture rules.  None: the mover is mated.
-// From CZ_RULES_REPETITION: first the root position goes through the slot's history (wave_root_history), whose verdict ends the
-// game.  On either ending played = 0xFFFF, no record is written and the ply stays; k_sp_adjudicate ends the game.  A forced
+// (CzRulesLevel, cz_rootrules.h), over the candidates wave_choose_prologue (cz_rootrules.h) leaves.
+// From CZ_RULES_KINGSAFE (cz_selfplay_set_rules(1)) those are the king-safe root children, compacted: pi, the noise (gamma[g][j] of
+// compacted child j: a Dirichlet over len(probs) entries), the pick and the record run on them exactly as they run on all n under
+// king-capture rules.  None: the mover is mated.  From CZ_RULES_REPETITION the root position's verdict may end the game first.
+// On either ending played = 0xFFFF, no record is written and the ply stays; k_sp_adjudicate ends the game.  A forced
 // label is played as given.  At every level, with cz_selfplay_set_resign: behind those exits and before the pick the mover's root
 // value is judged, and a resignation ends the ply the same way.
 template <int LEVEL>
@@ -93,43 +92,24 @@ __global__ __launch_bounds__(64) void k_sp_choose(CzTrees t, CzSelfplay sp, int 
         return;
     }
     if (lane == 0) atomicAdd((unsigned long long *)&sp.stats[CZ_SP_SIMS], (unsigned long long)t.sims[g]);
-    const TreeView v = view_of(t, g);
-    int cb, n;
-    root_children(t, g, v, cb, n);
     if (XQ && lane == 0) { sp.rr.mated[g] = 0; sp.rr.rep[g] = CZ_REP_NONE; }
-    if (root_cannot_move(t.status[g], n)) {   // the adjudication drops the game and re-seeds the slot
-        if (lane == 0) { played[g] = 0xFFFF; sp.stalled[g] = 1; }
+    const TreeView v = view_of(t, g);
+    const int ply = sp.ply[g];
+    int cb, n, N[2], at[2];   // the visits of candidate lane + 64 r and its index among the root's children
+    const CzRootFound found = wave_choose_prologue<LEVEL>(sp.rr, t, v, g, ply, lane, cb, n, N, at);
+    if (found != CZ_ROOT_CANDIDATES) {
+        if (lane == 0) {
+            played[g] = 0xFFFF;
+            if (found == CZ_ROOT_CANNOT_MOVE) sp.stalled[g] = 1;   // the adjudication drops the game and re-seeds the slot
+            if (found == CZ_ROOT_MATED) sp.rr.mated[g] = 1;        // the mover loses
+        }
         return;
     }
-    const int ply = sp.ply[g];
-    int N[2] = {0, 0}, at[2] = {0, 0};   // the visits of candidate lane + 64 r and its index among the root's children
     uint16_t lab[2] = {0xFFFF, 0xFFFF};
     double pi[2], p[2];
-    if constexpr (XQ) {
-        if constexpr (LEVEL >= CZ_RULES_REPETITION) {
-            if (wave_root_history<LEVEL >= CZ_RULES_CHASE>(sp.rr, g, ply, t.root_rr[g], lane) != CZ_REP_NONE) {
-                if (lane == 0) played[g] = 0xFFFF;
-                return;
-            }
-        }
-        __shared__ int sN[128], sI[128];
-        n = wave_kingsafe_children(v, cb, n, sp.rr.safe + (size_t)g * CZ_MASK_WORDS, lane, sN, sI);
-        if (n == 0) {   // children, none of them king-safe: checkmate or stalemate, the mover loses
-            if (lane == 0) { played[g] = 0xFFFF; sp.rr.mated[g] = 1; }
-            return;
-        }
 #pragma unroll
-        for (int r = 0; r < 2; ++r) {
-            const int i = lane + 64 * r;
-            if (i < n) { N[r] = sN[i]; at[r] = sI[i]; lab[r] = v.move[cb + at[r]]; }
-        }
-    } else {
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-            const int i = lane + 64 * r;
-            if (i < n) { N[r] = v.N[cb + i]; at[r] = i; lab[r] = v.move[cb + i]; }
-        }
-    }
+    for (int r = 0; r < 2; ++r)
+        if (lane + 64 * r < n) lab[r] = v.move[cb + at[r]];
     // cz_selfplay_set_resign: the mover's root value is judged — unless a forced label is played — and a mover below the threshold
     // resigns: played = 0xFFFF, no record, the ply stays, k_sp_adjudicate ends the game.  A play-on game only notes the first crossing.
     if (sp.rs.game_no && sp.rs.threshold == sp.rs.threshold && ply >= sp.rs.min_ply && !(forced && forced[g] < CZ_NLABELS)) {
@@ -195,37 +175,35 @@ __global__ __launch_bounds__(64) void k_sp_choose(CzTrees t, CzSelfplay sp, int 
 // The game-end tests of selfplay (main.py:1532-1545) on the position after the move, z for every recorded ply, and —
 // reseed != 0 — MCTS_tree.reload / GameBoard.reload for the next game of the slot (:1549-1551, :1494).
 // fin_n[g] = number of records the finished game hands to the ring (0: not finished, or dropped).
-// From CZ_RULES_KINGSAFE: before those tests, the endings the last choose found on the root it left untouched — a repetition
-// verdict (a draw, or a loss for the side that checked perpetually), then a mated mover (the side to move loses); z as for a king
-// capture.  At CZ_RULES_CHASE the verdict may carry CZ_REP_BY_CHASE — a loss for the side that chased, z as for perpetual check,
-// counted in chase_stat and not among the perpetuals.
-// cz_selfplay_set_resign, at every level: a game the last choose resigned is lost by the side to move, z as for a king capture,
-// behind the verdict and the mate and before everything else; a play-on game that ends here — however it ends, unless it
-// stalled — goes into the play-on counters and the histogram; the slot's resignation state starts over with its next game.
+// Whether and how the game ended is wave_game_end's answer (cz_internal.h: the one precedence of the endings); `aborted` here is a
+// stalled choose or a played label that is no root child, and such a game is dropped with no record.  From CZ_RULES_KINGSAFE the
+// endings the last choose found on the root it left untouched come first — a repetition verdict (a draw, or a loss for the side
+// that checked perpetually), then a mated mover (the side to move loses); z as for a king capture.  At CZ_RULES_CHASE the verdict
+// may be a chase — a loss for the side that chased, z as for perpetual check, counted in chase_stat and not among the perpetuals.
+// cz_selfplay_set_resign, at every level: a game the last choose resigned is lost by the side to move, z as for a king capture;
+// a play-on game that ends here — however it ends, unless it stalled — goes into the play-on counters and the histogram; the
+// slot's resignation state starts over with its next game.
 template <int LEVEL>
 __global__ __launch_bounds__(64) void k_sp_adjudicate(CzTrees t, CzSelfplay sp, int G, int reseed, const uint16_t *__restrict__ played,
                                                       int32_t *__restrict__ fin_n) {
-    constexpr bool XQ = LEVEL >= CZ_RULES_KINGSAFE, CHASE = LEVEL >= CZ_RULES_CHASE;
+    constexpr bool XQ = LEVEL >= CZ_RULES_KINGSAFE;
     const int g = blockIdx.x, lane = threadIdx.x;
     if (g >= G) return;
     if (!sp.active[g]) { if (lane == 0) fin_n[g] = 0; return; }
-    const int stored = XQ ? (int)sp.rr.rep[g] : CZ_REP_NONE;
-    const bool by_chase = CHASE && (stored & CZ_REP_BY_CHASE) != 0;
-    const int verdict = CHASE ? (stored & ~CZ_REP_BY_CHASE) : stored;
-    const bool mated = XQ && verdict == CZ_REP_NONE && sp.rr.mated[g] != 0;
-    // cz_selfplay_set_resign: the last choose resigned the game — behind the verdict and the mate, which it came after
-    const bool resigned = sp.rs.game_no && sp.rs.resigned[g] != 0 && verdict == CZ_REP_NONE && !mated;
-    const bool by_rules = verdict != CZ_REP_NONE || mated || resigned;
+    // cz_selfplay_set_resign: the last choose resigned the game
+    const bool resigned = sp.rs.game_no && sp.rs.resigned[g] != 0;
     // asynchronous plies: only the slots that just moved (or stalled, or ended by the rules or by resignation) can have ended their game
-    if (played && played[g] == 0xFFFF && !sp.stalled[g] && !by_rules) { if (lane == 0) fin_n[g] = 0; return; }
-    bool Kmiss, kmiss;
-    wave_kings_missing(t.root_board + (size_t)g * CZD_BOARD_LDS, lane, Kmiss, kmiss);
+    if (played && played[g] == 0xFFFF && !sp.stalled[g] && !resigned && !(XQ && (sp.rr.rep[g] != CZ_REP_NONE || sp.rr.mated[g] != 0))) {
+        if (lane == 0) fin_n[g] = 0;
+        return;
+    }
     const int ply = sp.ply[g];
-    const bool stalled = !by_rules && (sp.stalled[g] != 0 || (t.status[g] & CZ_ST_BAD_ADVANCE) != 0);
-    const bool decided = by_rules ? verdict != CZ_REP_DRAW : (Kmiss || kmiss);
-    const bool draw = !decided && (by_rules || restrict_round_draw(t.root_rr[g]) || ply >= sp.max_plies);
-    if (!(decided || draw || stalled)) { if (lane == 0) fin_n[g] = 0; return; }
-    const int winner = mated || resigned ? 1 - (int)t.root_side[g] : (verdict == CZ_REP_RED_LOSES ? 1 : (verdict == CZ_REP_BLACK_LOSES ? 0 : king_capture_winner(Kmiss)));
+    const bool aborted = sp.stalled[g] != 0 || (t.status[g] & CZ_ST_BAD_ADVANCE) != 0;
+    const CzGameEnd end = wave_game_end<LEVEL>(sp.rr, g, resigned, aborted, t.root_board + (size_t)g * CZD_BOARD_LDS, t.root_rr[g], t.root_side[g], ply,
+                                               sp.max_plies, lane);
+    if (!end.how) { if (lane == 0) fin_n[g] = 0; return; }
+    const bool stalled = end.how == CZ_MATCH_ABORTED, decided = end.loser >= 0;   // neither: a draw
+    const int winner = 1 - end.loser;
     const int n = stalled ? 0 : min(ply, sp.max_plies);
     for (int j = lane; j < n; j += 64) {
         uint8_t *rec = sp.hist + ((size_t)g * sp.max_plies + j) * CZ_REC_BYTES;
@@ -241,15 +219,16 @@ __global__ __launch_bounds__(64) void k_sp_adjudicate(CzTrees t, CzSelfplay sp, 
         else atomicAdd((unsigned long long *)&sp.stats[CZ_SP_DRAWS], 1ull);
         atomicAdd((unsigned long long *)&sp.stats[CZ_SP_PLIES], (unsigned long long)n);
         if constexpr (XQ) {
-            if (by_chase) atomicAdd((unsigned long long *)sp.chase_stat, 1ull);
-            else if (by_rules && !resigned) atomicAdd((unsigned long long *)&sp.xq_stats[mated ? 0 : (verdict == CZ_REP_DRAW ? 1 : 2)], 1ull);
+            if (end.how == CZ_MATCH_CHASE) atomicAdd((unsigned long long *)sp.chase_stat, 1ull);
+            else if (end.how == CZ_MATCH_MATE) atomicAdd((unsigned long long *)&sp.xq_stats[0], 1ull);
+            else if (end.how == CZ_MATCH_REPETITION || end.how == CZ_MATCH_PERPETUAL) atomicAdd((unsigned long long *)&sp.xq_stats[end.how == CZ_MATCH_REPETITION ? 1 : 2], 1ull);
             sp.rr.mated[g] = 0; sp.rr.rep[g] = CZ_REP_NONE;
         }
         if (sp.rs.game_no) {
             unsigned long long *rstat = (unsigned long long *)sp.rs.stats, *rhist = (unsigned long long *)sp.rs.hist;
-            if (resigned) atomicAdd(&rstat[0], 1ull);
+            if (end.how == CZ_MATCH_RESIGN) atomicAdd(&rstat[0], 1ull);
             if (sp.rs.playon[g] && !stalled) {   // what the game would have done had it not played on, against how it ended
-                const int loser = decided ? 1 - winner : -1, would = sp.rs.would[g];
+                const int loser = end.loser, would = sp.rs.would[g];
                 atomicAdd(&rstat[1], 1ull);
                 if (would) {
                     atomicAdd(&rstat[2], 1ull);

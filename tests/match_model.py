@@ -4,7 +4,8 @@
   choose         k_match_choose: the first maximum of N (greedy), or softmax(log N) by inverse CDF for the first sample_plies
   choose_safe    choose over the king-safe root children (rules="xiangqi")
   ending         a verdict of the repetition or chase rule as (reason, result for A)
-  adjudicate     k_match_adjudicate's game end: king missing, rr >= 60, ply cap, aborted (no child to play)
+  adjudicate     k_match_adjudicate's game end (wave_game_end, csrc/cz_internal.h): aborted (no child to play), king missing,
+                 rr >= 60, ply cap
   queue          which game a slot starts with, which opening a game plays, who is red
   play_game      one game replayed with one oracle.Search per player and the same follow rule: the mover searches and
                  re-roots on its child, the other player's tree keeps its subtree for the move or starts a fresh root; at
@@ -114,10 +115,12 @@ def _search(S, fwd, playouts):
         S.expand_backup(logits, value)
 
 
-def play_game(players, board, side, rr, game, max_plies, sample_plies=0, seed=0, rules="capture", fold=0, chase=False, cap=1 << 20, trace=None):
+def play_game(players, board, side, rr, game, max_plies, sample_plies=0, seed=0, rules="capture", fold=0, chase=False, cap=1 << 20, trace=None,
+              preset=None):
     """Global game `game` from (board, side, rr): players = [(fwd_a, playouts_a), (fwd_b, playouts_b)] with numpy forwards, at
     the rule level of (rules, fold, chase).  -> dict(moves, plies, reason, result, a_red), and records (the chase records of the
-    roots) at the chase level.  trace (a list): receives (ply, first) of the game's verdict, (ply, first, cause) at the chase level."""
+    roots) at the chase level.  trace (a list): receives (ply, first) of the game's verdict, (ply, first, cause) at the chase level.
+    preset: hand-set ring keys (rootrules_model.History)."""
     from oracle import oracle as O
     level = RR.level(rules, fold, chase)
     a_red = game % 2 == 0
@@ -125,7 +128,7 @@ def play_game(players, board, side, rr, game, max_plies, sample_plies=0, seed=0,
     for S in trees:
         S.reset(np.asarray(board, np.uint8)[None], np.array([side], np.uint8), np.array([rr], np.int32))
     moves, ply, side = [], 0, int(side)
-    history = RR.History(level, fold)
+    history = RR.History(level, fold, preset=preset)
     try:
         while True:
             mover = 0 if (side == 0) == a_red else 1

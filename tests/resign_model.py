@@ -155,11 +155,12 @@ class _Slot:
 
 
 def play_selfplay(fwd, playouts, boards, side, rr, stream, rules="capture", fold=0, chase=False, continuous=False, max_plies=512,
-                  temperature=1.0, eps=0.25, forced=None, resign=None, retune=None, cap=1 << 20):
+                  temperature=1.0, eps=0.25, forced=None, resign=None, retune=None, cap=1 << 20, preset=None):
     """G slots in lock-step (SelfPlay(..., continuous=continuous, rules=rules, repetition=fold, chase=chase, resign=...,
     resign_min_ply=..., resign_playon=..., seed=...).step_ply(rand=stream[t], forced=forced[t]) for every t).
     resign: None (off) or dict(threshold, min_ply, playon, seed); retune: {t: threshold} applied before step t
-    (SelfPlay.set_resign_threshold).  stream / forced as selfplay_rules_model.play_games.
+    (SelfPlay.set_resign_threshold).  stream / forced as selfplay_rules_model.play_games.  preset: per slot, hand-set ring keys
+    of the slot's first game (rootrules_model.History), or None.
     -> dict(records in ring order, outcomes [(t, slot, Outcome)] (.how "resign" for a resigned game, .playon, .would, .game_no),
     stats (games .. stalled, and mates / repetitions / perpetuals / chases), resign_stats (the four counters), hist int64 [64],
     active [G] bool, min_margin over the unforced picks, game_no [G] at the end)."""
@@ -174,7 +175,7 @@ def play_selfplay(fwd, playouts, boards, side, rr, stream, rules="capture", fold
         start = (np.asarray(boards[g], np.uint8)[None], np.array([side[g]], np.uint8), np.array([0 if rr is None else rr[g]], np.int32))
         S.reset(*start)
         recs, movers, ply = [], [], 0
-        history = RR.History(level, fold)
+        history = RR.History(level, fold, preset=None if preset is None else preset[g])
         rs = None if resign is None else dict(resign)
         slot = None if rs is None else _Slot(g, rs)
         try:

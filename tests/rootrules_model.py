@@ -17,11 +17,15 @@ def level(rules, fold, chase):
 
 class History:
     """wave_root_history: the keys and check flags of a game's root positions — with their chase records at the chase level, or
-    when records is set — and the verdict of the rule on each new one."""
+    when records is set — and the verdict of the rule on each new one.  preset {i: key}: a hand-set ring — the key of position i
+    is overwritten once the verdict on position i is in, as a test overwrites ring_key[i & 63] between two chooses; the rule
+    reads the ring, not the game, so this is the one way to a verdict on a position that is mate (its first occurrence ends
+    a game)."""
 
-    def __init__(self, level, fold, records=False):
+    def __init__(self, level, fold, records=False, preset=None):
         self.level, self.fold, self.keep = level, fold, records or level >= CHASE
         self.keys, self.checks, self.records = [], [], []
+        self.preset = dict(preset or {})
 
     def root(self, board, side, rr, ply):
         """Append the root (board, side to move) of ply `ply` -> (code, first, cause) with window min(rr, ply, 63); the cause is
@@ -32,11 +36,14 @@ class History:
         if self.keep:
             self.records.append(CM.record(board, side))
         window = min(int(rr), ply, 63)
+        out = RM.NONE, -1, CM.CAUSE_NONE
         if self.level >= CHASE:
-            return CM.verdict(self.keys, self.checks, self.records, side, window, self.fold)
-        if self.level >= REPETITION:
-            return RM.verdict(self.keys, self.checks, side, window, self.fold) + (CM.CAUSE_NONE,)
-        return RM.NONE, -1, CM.CAUSE_NONE
+            out = CM.verdict(self.keys, self.checks, self.records, side, window, self.fold)
+        elif self.level >= REPETITION:
+            out = RM.verdict(self.keys, self.checks, side, window, self.fold) + (CM.CAUSE_NONE,)
+        if ply in self.preset:
+            self.keys[ply] = int(self.preset[ply])
+        return out
 
 
 def safe_children(board, side, labels):

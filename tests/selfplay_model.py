@@ -2,8 +2,8 @@
 
   choose_ref      k_sp_choose's pick: cchess_main.get_action (main.py:1339-1348) with np.random.choice's inverse CDF driven
                   by an explicit uniform, plus the kernel's two documented departures (all-zero visits, gamma summing to 0)
-  adjudicate_ref  k_sp_adjudicate's game-end test: cchess_main.selfplay (main.py:1525-1545) plus the documented extensions
-                  of include/cchess_hip.h (max_plies draw, stalled games)
+  adjudicate_ref  k_sp_adjudicate's game-end test (wave_game_end, csrc/cz_internal.h): cchess_main.selfplay
+                  (main.py:1525-1545) plus the documented extensions of include/cchess_hip.h (max_plies draw, stalled games)
   stats_ref       the cz_selfplay_stats counters of a list of finished games
   flush_ref       k_sp_flush: finished games' records into the ring, modulo ring_records, dropped whole past read_cursor
   golden_stream   a golden game's own numpy stream: per ply the Dirichlet vector and the uniform np.random.choice draws

@@ -4,7 +4,8 @@ with the king-safe filter and the repetition or chase verdict of tests/rootrules
 
   choose_xq_ref      selfplay_model.choose_ref over rootrules_model.safe_children: pi, noise and pick over the king-safe
                      root children alone, gamma[j] belonging to compacted child j
-  adjudicate_xq_ref  the ending order — repetition verdict, mate, then selfplay_model.adjudicate_ref — and the z values
+  adjudicate_xq_ref  the ending order (wave_game_end, csrc/cz_internal.h) — repetition verdict, mate, then
+                     selfplay_model.adjudicate_ref — and the z values
   replay_line        a forced line on the oracle's boards: the history of keys and check flags and the first verdict
   play_games         whole games of G slots in lock-step (continuous=False) on oracle.Search trees from a given random stream:
                      packed records in ring order, the outcomes, the counters; z of a chase loss is a perpetual check's
