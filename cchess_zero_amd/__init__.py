@@ -1,7 +1,8 @@
 """cchess_zero_amd — MI355X-native hot path of cchess-zero (MCTS rollout + move legality + batched net eval).
 
 Layout
-  csrc/          hand-written HIP kernels + the C-ABI (include/cchess_hip.h) -> libcchess_hip.so
+  csrc/          hand-written HIP kernels, each file with the C-ABI entry points (include/cchess_hip.h) that launch them
+                 -> libcchess_hip.so; a new entry point: the header, _lib.py's _SIGS, the kernel's file
   _lib.py        ctypes binding of the C-ABI (fails loudly if the library is missing)
   rules.py       batched rules ops (K1-K3) over device tensors
   engine.py      lock-step search engine over G trees

@@ -43,8 +43,11 @@ __global__ __launch_bounds__(64) void k_threats(const CzmTables *__restrict__ gt
 
 }  // namespace
 
-int czk_threats(cz_ctx *c, const uint8_t *boards, const uint8_t *side, int G, uint64_t *chase) {
+int cz_threats(cz_ctx *c, const uint8_t *boards, const uint8_t *side, int G, uint64_t *chase) {
+    CZ_REQUIRE(c && G >= 0, "cz_threats: null ctx / negative G");
     if (G == 0) return CZ_OK;
+    CZ_REQUIRE(boards && side && chase, "cz_threats: boards, side, chase required");
+    CZ_REQUIRE((reinterpret_cast<uintptr_t>(chase) & 7u) == 0, "cz_threats: chase must be 8-byte aligned");
     // 11.1 KB of LDS per wave: twelve persistent waves per CU
     hipLaunchKernelGGL(k_threats, dim3(czf_persistent_grid((G + 63) / 64, 12)), dim3(64), 0, c->stream, c->mask_tab, boards, side, G, chase);
     CZ_HIP(hipGetLastError());

@@ -49,7 +49,7 @@ int cz_search_set_eval_cache(cz_ctx *c, int on) {
         if (!c->t.ec_key_mask) c->t.ec_key_mask = ~0ull;
         // an empty cache: entries of an earlier use would point into trees that no longer exist
         CZ_HIP(hipMemsetAsync(c->t.ec_key, 0, per * sizeof(*c->t.ec_key), c->stream));
-        czk_search_clear_cache_stats(c);
+        cz_search_clear_cache_stats(c);
         if (c->t.xc_base) CZ_HIP(hipMemsetAsync(c->xc_block, 0, czx_clear_bytes(czx_n(c->t)), c->stream));   // and the cross-tree level
     } else {
 #define CZ_EC_POINT(name, type, n) c->t.ec_##name = nullptr;

@@ -152,11 +152,17 @@ __global__ __launch_bounds__(64) void k_games_replay(const CzmTables *__restrict
 
 }  // namespace
 
-int czk_games_replay(cz_ctx *c, const uint8_t *start_boards, const uint8_t *start_side, const uint16_t *moves, int stride, const int32_t *len,
-                     const int8_t *result, int G, int rules, const int32_t *rec_offset, int total, uint8_t *records, int32_t *valid,
-                     uint8_t *status, uint8_t *end_flags, uint8_t *final_boards, uint8_t *final_side) {
+int cz_games_replay(cz_ctx *c, const uint8_t *start_boards, const uint8_t *start_side, const uint16_t *moves, int stride, const int32_t *len,
+                    const int8_t *result, int G, int rules, const int32_t *rec_offset, int total, uint8_t *records, int32_t *valid,
+                    uint8_t *status, uint8_t *end_flags, uint8_t *final_boards, uint8_t *final_side) {
+    CZ_REQUIRE(c && G >= 0, "cz_games_replay: null ctx / negative G");
+    CZ_REQUIRE(stride >= 0 && stride <= 65535 && total >= 0, "cz_games_replay: 0 <= stride <= 65535 and total >= 0 required");
+    CZ_REQUIRE(rules == 0 || rules == 1, "cz_games_replay: rules is 0 (capture) or 1 (king-safe)");
     if (G == 0) return CZ_OK;
-    if (records && (reinterpret_cast<uintptr_t>(records) & 15u)) { cz_set_error("cz_games_replay: records must be 16-byte aligned"); return CZ_EINVAL; }
+    CZ_REQUIRE(moves && len && result && rec_offset && valid && status && end_flags,
+               "cz_games_replay: moves, len, result, rec_offset, valid, status, end_flags required");
+    CZ_REQUIRE((reinterpret_cast<uintptr_t>(records) & 15u) == 0, "cz_games_replay: records must be 16-byte aligned");
+    CZ_REQUIRE(!final_boards || final_side, "cz_games_replay: final_boards needs final_side");
     const dim3 grid(czf_persistent_grid((G + 63) / 64, 3));   // 49.0 KB of LDS per wave: three waves per CU
 #define CZG_LAUNCH(R) hipLaunchKernelGGL((k_games_replay<R>), grid, dim3(64), 0, c->stream, c->mask_tab, c->tab.srcdst, start_boards, start_side, moves, stride, \
                                          len, result, G, rec_offset, total, records, valid, status, end_flags, final_boards, final_side)

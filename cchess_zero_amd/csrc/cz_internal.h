@@ -37,14 +37,22 @@ struct Carver {
         return p;
     }
 };
-// *block (allocated here unless it already is) of `bytes` zeros, in stream order; who: the API call the error text names
-inline int alloc_zeroed(void **block, size_t bytes, hipStream_t stream, const char *who) {
-    if (!*block && hipMalloc(block, bytes) != hipSuccess) {
+// One device allocation laid out by lay(Carver &), which takes its arrays: lay runs once on a NULL Carver for the size (the
+// pointers it stores are NULL then) and once on the block.  *block is allocated here unless it already is; zero: all of it is
+// cleared, in stream order; who: the API call the error text names.  After an error lay's pointers are not to be used, and
+// *block, if it is set, stays the caller's to free.
+template <typename Lay>
+inline int carve_alloc(void **block, hipStream_t stream, bool zero, const char *who, Lay lay) {
+    Carver sizing{nullptr};
+    lay(sizing);
+    if (!*block && hipMalloc(block, sizing.off) != hipSuccess) {
         *block = nullptr;
-        cz_set_error("%s: hipMalloc(%zu B) failed", who, bytes);
+        cz_set_error("%s: hipMalloc(%zu B) failed", who, sizing.off);
         return CZ_ENOMEM;
     }
-    CZ_HIP(hipMemsetAsync(*block, 0, bytes, stream));
+    if (zero) CZ_HIP(hipMemsetAsync(*block, 0, sizing.off, stream));
+    Carver k{(char *)*block};
+    lay(k);
     return CZ_OK;
 }
 
@@ -448,40 +456,8 @@ __device__ __forceinline__ int wave_pick_inverse_cdf(const double p[2], double u
     return pick;
 }
 
-// kernels' launch wrappers (cz_rules.hip / cz_search.hip)
-int czk_movegen(cz_ctx *, const uint8_t *, const uint8_t *, int, uint16_t *, uint16_t *, uint32_t *, int flags);
-int czk_movegen_kingsafe(cz_ctx *, const uint8_t *, const uint8_t *, int, uint16_t *, uint16_t *, uint32_t *, uint8_t *, int flags);   // cz_kingsafe.hip
-int czk_repetition(cz_ctx *, const uint64_t *, const uint8_t *, int, const int32_t *, const int32_t *, const uint8_t *, int, int, uint8_t *, int32_t *);   // cz_repetition.hip
-int czk_threats(cz_ctx *, const uint8_t *, const uint8_t *, int, uint64_t *);   // cz_chase.hip
-int czk_repetition_chase(cz_ctx *, const uint64_t *, const uint8_t *, const uint64_t *, int, const int32_t *, const int32_t *, const uint8_t *, int, int, uint8_t *, int32_t *,
-                         uint8_t *);   // cz_repetition.hip
-int czk_apply_move(cz_ctx *, uint8_t *, uint8_t *, const uint16_t *, int, uint64_t *, uint8_t *, int8_t *);
-int czk_hash(cz_ctx *, const uint8_t *, const uint8_t *, int, uint64_t *);
-int czk_successors(cz_ctx *, const uint8_t *, const uint8_t *, int, const uint16_t *, const int32_t *, int, uint8_t *, uint8_t *, uint8_t *, int32_t *,
-                   uint16_t *);   // cz_successors.hip
-int czk_encode_planes(cz_ctx *, const uint8_t *, const uint8_t *, int, void *, int, int, int);
-int czk_search_reset(cz_ctx *, const uint8_t *, const uint8_t *, const int32_t *, int, const uint8_t *which);
-int czk_search_status(cz_ctx *, int32_t *, int32_t *, int32_t *, int32_t *);
-int czk_search_clear_cache_stats(cz_ctx *);
-int czk_search_select(cz_ctx *, int, const uint8_t *, void *, int, int, uint8_t *, bool compact = false);
-int czk_search_expand_backup(cz_ctx *, const void *, const void *, int);
-int czk_search_expand_backup_fc(cz_ctx *, const float *, const float *, const float *, const float *, bool compact);
-int czk_search_root_stats(cz_ctx *, uint16_t *, int32_t *, float *, float *, float *, uint16_t *);
-int czk_search_advance(cz_ctx *, const uint16_t *);
-int czk_search_pick_ready(cz_ctx *, int32_t *, int, uint16_t *, uint8_t *, unsigned long long *);
-int czk_search_reload_finished(cz_ctx *, const uint8_t *, const uint16_t *, const uint8_t *, const uint8_t *, const int32_t *, unsigned long long *);
-int czk_search_select_k(cz_ctx *, int, int, const uint8_t *, void *, int, int, uint8_t *);
-int czk_search_expand_backup_k(cz_ctx *, int, const void *, const void *, int);
-int czk_selfplay_seed(cz_ctx *, const uint8_t *, const uint8_t *, const int32_t *);
-int czk_selfplay_resign_init(cz_ctx *);   // the first cz_selfplay_set_resign: c->sp.rs on its zeroed block
-int czk_selfplay_choose(cz_ctx *, const float *, const float *, const uint16_t *, double, float, int, uint16_t *);   // by c->sp_rules / sp.rr.fold / c->sp_chase
-int czk_selfplay_adjudicate(cz_ctx *, int, const uint16_t *, int32_t *);
-int czk_selfplay_flush(cz_ctx *, const int32_t *, const long long *, uint8_t *, long long, const long long *);
-int czk_records_expand(cz_ctx *, const uint8_t *, int, const uint8_t *, double, float *, float *, float *);   // cz_records.hip
-int czk_games_replay(cz_ctx *, const uint8_t *, const uint8_t *, const uint16_t *, int, const int32_t *, const int8_t *, int, int, const int32_t *, int, uint8_t *,
-                     int32_t *, uint8_t *, uint8_t *, uint8_t *, uint8_t *);   // cz_games.hip
-
-// ---- a tree's records in pre-order, host side (cz_api.hip; cz_search_tree_dump, cz_search_debug_eval_cache_dump) ----
+// ---- host functions of cz_search.hip that a second file calls -------------------------------------
+// a tree's records in pre-order (cz_search_tree_dump; the second caller is cz_search_debug_eval_cache_dump, cz_evalcache.hip)
 struct CzPreorder {
     int32_t n, root;                      // the tree's node count; its root node, -1 if that is no node of the tree
     std::vector<int32_t> child_begin;     // [n] the expansion records as downloaded
@@ -489,8 +465,10 @@ struct CzPreorder {
     std::vector<int32_t> node, depth;     // [records] record k is node[k], depth[k] levels below the root's children
 };
 int cz_tree_preorder(cz_ctx *c, int g, CzPreorder &out);   // after a stream synchronise
+// every tree's evaluation-cache counters (CzTreeRec::ec_*) back to 0, in stream order: cz_search_set_eval_cache (cz_evalcache.hip)
+int cz_search_clear_cache_stats(cz_ctx *c);
 
-// ---- the rules at the root, host side (cz_rootrules.h; cz_match.hip, cz_selfplay.hip / cz_api.hip) ----
+// ---- the rules at the root, host side (cz_rootrules.h; cz_match.hip, cz_selfplay.hip) ----
 // the arrays of G slots inside the carver's allocation: the chase rings (chase_part), or everything else
 inline void carve_root_rules(Carver &k, CzRootRules &rr, size_t G, bool chase_part) {
     if (chase_part) {
@@ -510,11 +488,12 @@ inline void carve_root_rules(Carver &k, CzRootRules &rr, size_t G, bool chase_pa
 }
 
 // Between a consumer's root gather (wave_gather_root) and its choose kernel, level >= CZ_RULES_KINGSAFE: the king-safe sets of
-// the G root positions; from CZ_RULES_REPETITION their check flags and keys; at CZ_RULES_CHASE their chase records
+// the G root positions; from CZ_RULES_REPETITION their check flags and keys; at CZ_RULES_CHASE their chase records.  Through
+// the public entry points: their checks hold for a carved rr (every array set at the level that reads it, 256-byte aligned).
 inline int czk_root_rules_prepare(cz_ctx *c, const CzRootRules &rr, int G, int level) {
-    int rc = czk_movegen_kingsafe(c, rr.board, rr.side, G, nullptr, nullptr, rr.safe, level >= CZ_RULES_REPETITION ? rr.flags : nullptr, 0);
-    if (rc == CZ_OK && level >= CZ_RULES_REPETITION) rc = czk_hash(c, rr.board, rr.side, G, rr.root_key);
-    if (rc == CZ_OK && level >= CZ_RULES_CHASE) rc = czk_threats(c, rr.board, rr.side, G, rr.root_chase);
+    int rc = cz_movegen_kingsafe(c, rr.board, rr.side, G, nullptr, nullptr, rr.safe, level >= CZ_RULES_REPETITION ? rr.flags : nullptr, 0);
+    if (rc == CZ_OK && level >= CZ_RULES_REPETITION) rc = cz_hash(c, rr.board, rr.side, G, rr.root_key);
+    if (rc == CZ_OK && level >= CZ_RULES_CHASE) rc = cz_threats(c, rr.board, rr.side, G, rr.root_chase);
     return rc;
 }
 

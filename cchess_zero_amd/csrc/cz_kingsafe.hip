@@ -68,9 +68,13 @@ __global__ __launch_bounds__(64) void k_movegen_kingsafe(const CzmTables *__rest
 
 }  // namespace
 
-int czk_movegen_kingsafe(cz_ctx *c, const uint8_t *boards, const uint8_t *side, int G, uint16_t *moves, uint16_t *count, uint32_t *mask,
-                         uint8_t *pos_flags, int flags) {
+int cz_movegen_kingsafe(cz_ctx *c, const uint8_t *boards, const uint8_t *side, int G, uint16_t *moves, uint16_t *count, uint32_t *mask,
+                        uint8_t *pos_flags, int flags) {
+    CZ_REQUIRE(c && G >= 0, "cz_movegen_kingsafe: null ctx / negative G");
+    CZ_REQUIRE((flags & ~CZ_MOVES_NO_PAD) == 0, "cz_movegen_kingsafe: unknown flag");
     if (G == 0) return CZ_OK;
+    CZ_REQUIRE(boards && side, "cz_movegen_kingsafe: boards, side required");
+    CZ_REQUIRE(moves || count || mask || pos_flags, "cz_movegen_kingsafe: no output requested");
     if (moves && (reinterpret_cast<uintptr_t>(moves) & 15u)) { cz_set_error("cz_movegen_kingsafe: moves must be 16-byte aligned"); return CZ_EINVAL; }
     const int pad = (flags & CZ_MOVES_NO_PAD) ? 0 : 1;
     const dim3 grid(czf_persistent_grid((G + 63) / 64, (moves || mask) ? 6 : 10));   // 26.6 / 15.5 KB of LDS per wave: six / ten waves per CU

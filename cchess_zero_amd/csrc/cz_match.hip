@@ -227,29 +227,19 @@ int cz_match_create(cz_ctx *a, cz_ctx *b, const uint8_t *boards, const uint8_t *
     CzMatch &m = mh->m;
     m.G = mh->G; m.n_games = mh->n_games; m.max_plies = max_plies; m.pair_base = pair_base; m.pair_stride = pair_stride;
     m.resign_threshold = NAN; m.resign_min_ply = 0;
-    Carver sizing{nullptr};
-    carve(sizing, m, (size_t)mh->G, (size_t)mh->n_games);
-    const size_t bytes = sizing.off;
-    if (hipMalloc(&mh->block, bytes) != hipSuccess) {
-        mh->block = nullptr;
-        delete mh;
-        cz_set_error("cz_match_create: hipMalloc(%zu B) failed", bytes);
-        return CZ_ENOMEM;
-    }
-    Carver k{(char *)mh->block};
-    carve(k, m, (size_t)mh->G, (size_t)mh->n_games);
     const size_t np = (size_t)n_openings;
-    int rc = CZ_OK;
+    int rc = carve_alloc(&mh->block, a->stream, true, "cz_match_create", [&](Carver &k) { carve(k, m, (size_t)mh->G, (size_t)mh->n_games); });
     auto fail = [&](hipError_t e, const char *what) {
         cz_set_error("cz_match_create: %s failed: %s", what, hipGetErrorString(e));
         rc = CZ_EHIP;
     };
     hipError_t e;
-    if ((e = hipMemsetAsync(mh->block, 0, bytes, a->stream)) != hipSuccess) fail(e, "hipMemsetAsync");
-    else if ((e = hipMemsetAsync(m.moves, 0xFF, (size_t)mh->n_games * max_plies * 2, a->stream)) != hipSuccess) fail(e, "hipMemsetAsync");
-    else if ((e = hipMemcpyAsync((void *)m.open_board, boards, np * CZ_NSQ, hipMemcpyDeviceToDevice, a->stream)) != hipSuccess) fail(e, "hipMemcpyAsync");
-    else if ((e = hipMemcpyAsync((void *)m.open_side, side, np, hipMemcpyDeviceToDevice, a->stream)) != hipSuccess) fail(e, "hipMemcpyAsync");
-    else if (rr && (e = hipMemcpyAsync((void *)m.open_rr, rr, np * 4, hipMemcpyDeviceToDevice, a->stream)) != hipSuccess) fail(e, "hipMemcpyAsync");
+    if (rc == CZ_OK) {
+        if ((e = hipMemsetAsync(m.moves, 0xFF, (size_t)mh->n_games * max_plies * 2, a->stream)) != hipSuccess) fail(e, "hipMemsetAsync");
+        else if ((e = hipMemcpyAsync((void *)m.open_board, boards, np * CZ_NSQ, hipMemcpyDeviceToDevice, a->stream)) != hipSuccess) fail(e, "hipMemcpyAsync");
+        else if ((e = hipMemcpyAsync((void *)m.open_side, side, np, hipMemcpyDeviceToDevice, a->stream)) != hipSuccess) fail(e, "hipMemcpyAsync");
+        else if (rr && (e = hipMemcpyAsync((void *)m.open_rr, rr, np * 4, hipMemcpyDeviceToDevice, a->stream)) != hipSuccess) fail(e, "hipMemcpyAsync");
+    }
     if (rc == CZ_OK) {
         hipLaunchKernelGGL(k_match_start, dim3(mh->G), dim3(64), 0, a->stream, a->t, b->t, m);
         if ((e = hipGetLastError()) != hipSuccess) fail(e, "k_match_start");
@@ -273,12 +263,7 @@ static int match_order(const cz_match *mh, int what, int value) {
 
 // one part of m.rr (carve_root_rules) in a zeroed allocation of its own
 static int alloc_root_rules(cz_match *mh, void **block, bool chase_part, const char *who) {
-    Carver sizing{nullptr};
-    carve_root_rules(sizing, mh->m.rr, (size_t)mh->G, chase_part);
-    if (const int rc = alloc_zeroed(block, sizing.off, mh->a->stream, who)) return rc;
-    Carver k{(char *)*block};
-    carve_root_rules(k, mh->m.rr, (size_t)mh->G, chase_part);
-    return CZ_OK;
+    return carve_alloc(block, mh->a->stream, true, who, [&](Carver &k) { carve_root_rules(k, mh->m.rr, (size_t)mh->G, chase_part); });
 }
 
 int cz_match_set_rules(cz_match *mh, int rules) {

@@ -76,8 +76,15 @@ __global__ __launch_bounds__(64 * CZR_WAVES) void k_records_expand(const uint8_t
 
 }  // namespace
 
-int czk_records_expand(cz_ctx *c, const uint8_t *records, int n, const uint8_t *mirror, double temperature, float *planes, float *pi, float *z) {
+int cz_records_expand(cz_ctx *c, const uint8_t *records, int n, const uint8_t *mirror, double temperature, float *planes, float *pi, float *z) {
+    CZ_REQUIRE(c && n >= 0, "cz_records_expand: null ctx / negative n");
+    CZ_REQUIRE(temperature > 0.0, "cz_records_expand: temperature > 0 required");   // false for a NaN too
+    CZ_REQUIRE(planes && pi && z, "cz_records_expand: planes, pi, z required");
     if (n == 0) return CZ_OK;
+    CZ_REQUIRE(records, "cz_records_expand: records required");
+    CZ_REQUIRE((reinterpret_cast<uintptr_t>(records) & 3u) == 0 && (reinterpret_cast<uintptr_t>(pi) & 7u) == 0 &&
+                   (reinterpret_cast<uintptr_t>(planes) & 3u) == 0 && (reinterpret_cast<uintptr_t>(z) & 3u) == 0,
+               "cz_records_expand: records 4-byte, pi 8-byte, planes and z 4-byte aligned");
     static_assert(CZ_NLABELS % 2 == 0 && CZ_REC_BYTES % 4 == 0, "pi rows leave as 8-byte pieces; records keep their 2-byte fields aligned");
     // 33.8 KB of LDS per workgroup of four waves: 4 persistent workgroups per CU
     const int ngroups = (int)(((long long)n + CZR_WAVES - 1) / CZR_WAVES);

@@ -41,18 +41,26 @@ __global__ __launch_bounds__(64) void k_repetition(const uint64_t *__restrict__ 
 
 }  // namespace
 
-int czk_repetition(cz_ctx *c, const uint64_t *keys, const uint8_t *in_check, int stride, const int32_t *len, const int32_t *window,
-                   const uint8_t *side, int G, int fold, uint8_t *verdict, int32_t *first) {
+int cz_repetition(cz_ctx *c, const uint64_t *keys, const uint8_t *in_check, int stride, const int32_t *len, const int32_t *window,
+                  const uint8_t *side, int G, int fold, uint8_t *verdict, int32_t *first) {
+    CZ_REQUIRE(c && G >= 0, "cz_repetition: null ctx / negative G");
+    CZ_REQUIRE(fold >= 2 && fold <= 8, "cz_repetition: 2 <= fold <= 8");
+    CZ_REQUIRE(stride >= 1, "cz_repetition: stride >= 1");
     if (G == 0) return CZ_OK;
+    CZ_REQUIRE(keys && in_check && len && side && verdict, "cz_repetition: keys, in_check, len, side, verdict required");
     hipLaunchKernelGGL(k_repetition<false>, dim3(G < 65536 ? G : 65536), dim3(64), 0, c->stream, keys, in_check, (const uint64_t *)nullptr, stride,
                        len, window, side, G, fold, verdict, first, (uint8_t *)nullptr);
     CZ_HIP(hipGetLastError());
     return CZ_OK;
 }
 
-int czk_repetition_chase(cz_ctx *c, const uint64_t *keys, const uint8_t *in_check, const uint64_t *chase, int stride, const int32_t *len,
-                         const int32_t *window, const uint8_t *side, int G, int fold, uint8_t *verdict, int32_t *first, uint8_t *cause) {
+int cz_repetition_chase(cz_ctx *c, const uint64_t *keys, const uint8_t *in_check, const uint64_t *chase, int stride, const int32_t *len,
+                        const int32_t *window, const uint8_t *side, int G, int fold, uint8_t *verdict, int32_t *first, uint8_t *cause) {
+    CZ_REQUIRE(c && G >= 0, "cz_repetition_chase: null ctx / negative G");
+    CZ_REQUIRE(fold >= 2 && fold <= 8, "cz_repetition_chase: 2 <= fold <= 8");
+    CZ_REQUIRE(stride >= 1, "cz_repetition_chase: stride >= 1");
     if (G == 0) return CZ_OK;
+    CZ_REQUIRE(keys && in_check && chase && len && side && verdict, "cz_repetition_chase: keys, in_check, chase, len, side, verdict required");
     hipLaunchKernelGGL(k_repetition<true>, dim3(G < 65536 ? G : 65536), dim3(64), 0, c->stream, keys, in_check, chase, stride, len, window, side,
                        G, fold, verdict, first, cause);
     CZ_HIP(hipGetLastError());

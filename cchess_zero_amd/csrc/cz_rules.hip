@@ -292,8 +292,8 @@ inline int grid_for(int G) { return G < 65536 ? G : 65536; }
 
 }  // namespace
 
-int czk_movegen(cz_ctx *c, const uint8_t *boards, const uint8_t *side, int G, uint16_t *moves, uint16_t *count, uint32_t *mask, int flags) {
-    if (G == 0) return CZ_OK;
+// cz_movegen and cz_movegen_ex behind their own checks, G > 0 (the alignment text names cz_movegen for both)
+static int movegen(cz_ctx *c, const uint8_t *boards, const uint8_t *side, int G, uint16_t *moves, uint16_t *count, uint32_t *mask, int flags) {
     const bool pad = !(flags & CZ_MOVES_NO_PAD);
     if (moves && (reinterpret_cast<uintptr_t>(moves) & 15u)) { cz_set_error("cz_movegen: moves must be 16-byte aligned"); return CZ_EINVAL; }
     const int ngroups = (G + 63) / 64;
@@ -310,23 +310,46 @@ int czk_movegen(cz_ctx *c, const uint8_t *boards, const uint8_t *side, int G, ui
     return CZ_OK;
 }
 
-int czk_apply_move(cz_ctx *c, uint8_t *boards, uint8_t *side, const uint16_t *label, int G, uint64_t *hash, uint8_t *captured, int8_t *terminal) {
+int cz_movegen(cz_ctx *c, const uint8_t *boards, const uint8_t *side, int G, uint16_t *moves, uint16_t *count, uint32_t *mask) {
+    CZ_REQUIRE(c && G >= 0, "cz_movegen: null ctx / negative G");
     if (G == 0) return CZ_OK;
+    CZ_REQUIRE(boards && side && count, "cz_movegen: boards, side, count required");
+    return movegen(c, boards, side, G, moves, count, mask, 0);
+}
+
+int cz_movegen_ex(cz_ctx *c, const uint8_t *boards, const uint8_t *side, int G, uint16_t *moves, uint16_t *count, uint32_t *mask, int flags) {
+    CZ_REQUIRE(c && G >= 0, "cz_movegen_ex: null ctx / negative G");
+    CZ_REQUIRE((flags & ~CZ_MOVES_NO_PAD) == 0, "cz_movegen_ex: unknown flag");
+    if (G == 0) return CZ_OK;
+    CZ_REQUIRE(boards && side && count, "cz_movegen_ex: boards, side, count required");
+    return movegen(c, boards, side, G, moves, count, mask, flags);
+}
+
+int cz_apply_move(cz_ctx *c, uint8_t *boards, uint8_t *side, const uint16_t *label, int G, uint64_t *hash, uint8_t *captured, int8_t *terminal) {
+    CZ_REQUIRE(c && G >= 0, "cz_apply_move: null ctx / negative G");
+    if (G == 0) return CZ_OK;
+    CZ_REQUIRE(boards && side && label, "cz_apply_move: boards, side, move_label required");
     hipLaunchKernelGGL(k_apply_move, dim3((G + 255) / 256), dim3(256), 0, c->stream, c->tab, boards, side, label, G, hash, captured, terminal);
     CZ_HIP(hipGetLastError());
     return CZ_OK;
 }
 
-int czk_hash(cz_ctx *c, const uint8_t *boards, const uint8_t *side, int G, uint64_t *hash) {
+int cz_hash(cz_ctx *c, const uint8_t *boards, const uint8_t *side, int G, uint64_t *hash) {
+    CZ_REQUIRE(c && G >= 0, "cz_hash: null ctx / negative G");
     if (G == 0) return CZ_OK;
+    CZ_REQUIRE(boards && side && hash, "cz_hash: null argument");
     const int ngroups = (G + 63) / 64, wgs = (ngroups + CZR_HASH_WAVES - 1) / CZR_HASH_WAVES;   // 34.6 KB of LDS per workgroup of four waves: 4 persistent workgroups per CU
     hipLaunchKernelGGL(k_hash, dim3(czf_persistent_grid(wgs, 4)), dim3(64 * CZR_HASH_WAVES), 0, c->stream, c->tab, boards, side, G, hash);
     CZ_HIP(hipGetLastError());
     return CZ_OK;
 }
 
-int czk_encode_planes(cz_ctx *c, const uint8_t *boards, const uint8_t *side, int G, void *planes, int dtype, int C, int quirk) {
+int cz_encode_planes(cz_ctx *c, const uint8_t *boards, const uint8_t *side, int G, void *planes, int dtype, int C, int quirk) {
+    CZ_REQUIRE(c && G >= 0, "cz_encode_planes: null ctx / negative G");
     if (G == 0) return CZ_OK;
+    CZ_REQUIRE(boards && side && planes, "cz_encode_planes: null argument");
+    CZ_REQUIRE(dtype == CZ_F32 || dtype == CZ_BF16 || dtype == CZ_F16, "cz_encode_planes: dtype must be CZ_F32, CZ_BF16 or CZ_F16");
+    CZ_REQUIRE(C >= 14 && C <= 64, "cz_encode_planes: 14 <= channels <= 64");
     if (dtype == CZ_F32)
         hipLaunchKernelGGL(k_encode_planes<float>, dim3(grid_for(G)), dim3(64), 0, c->stream, boards, side, G, (float *)planes, C, quirk, 1.0f);
     else

@@ -13,6 +13,8 @@
 #include "cz_internal.h"
 
 #include <math.h>
+#include <string.h>
+#include <vector>
 
 namespace {
 
@@ -998,22 +1000,66 @@ __global__ void k_clear_cache_stats(CzTrees t, int G) {
 
 }  // namespace
 
-int czk_search_status(cz_ctx *c, int32_t *status, int32_t *nodes, int32_t *sims, int32_t *depth) {
-    hipLaunchKernelGGL(k_status, dim3((c->G + 255) / 256), dim3(256), 0, c->stream, c->t, c->G, status, nodes, sims, depth);
-    CZ_HIP(hipGetLastError());
+// ---- the entry points (include/cchess_hip.h): argument checks and launch in one function --------------------------
+
+int cz_search_set_width(cz_ctx *c, int width) {
+    CZ_REQUIRE(c, "null ctx");
+    if (width < 1 || width > 64) { cz_set_error("cz_search_set_width: width %d outside 1..64", width); return CZ_EINVAL; }
+    if (width <= c->width) return CZ_OK;
+    if (c->t.ec_key) { cz_set_error("cz_search_set_width: the evaluation cache needs width 1 (cz_search_set_eval_cache(ctx, 0) first)"); return CZ_EINVAL; }
+    CZ_HIP(hipStreamSynchronize(c->stream));
+    // the pending arrays at the new width, in a zeroed block of their own: c->t and the old block change only once it stands
+    const size_t n = (size_t)c->max_games * (size_t)width;
+    CzTrees t = c->t;
+    void *blk = nullptr;
+    const int rc = carve_alloc(&blk, c->stream, true, "cz_search_set_width", [&](Carver &k) {
+        t.pk_kind = k.take<int32_t>(n); t.pk_leaf = k.take<int32_t>(n); t.pk_value = k.take<float>(n);
+        t.pk_side = k.take<uint8_t>(n); t.pk_nmoves = k.take<uint16_t>(n); t.pend_moves = k.take<uint16_t>(n * CZD_MAXMOVES);
+    });
+    if (rc != CZ_OK) { (void)hipFree(blk); return rc; }
+    c->t = t;
+    if (c->pend_block) (void)hipFree(c->pend_block);
+    c->pend_block = blk;
+    c->width = width;
     return CZ_OK;
 }
 
-int czk_search_clear_cache_stats(cz_ctx *c) {
-    hipLaunchKernelGGL(k_clear_cache_stats, dim3((c->max_games + 255) / 256), dim3(256), 0, c->stream, c->t, c->max_games);
-    CZ_HIP(hipGetLastError());
+int cz_search_set_sim_target(cz_ctx *c, int target) {
+    CZ_REQUIRE(c && target >= 0, "cz_search_set_sim_target: null ctx / negative target");
+    c->sim_target = target;
     return CZ_OK;
 }
 
-int czk_search_reset(cz_ctx *c, const uint8_t *boards, const uint8_t *side, const int32_t *rr, int G, const uint8_t *which) {
+int cz_search_debug_advance_in_global_memory(cz_ctx *c, int on) {
+    CZ_REQUIRE(c, "cz_search_debug_advance_in_global_memory: null context");
+    c->adv_force_global = on != 0;
+    return CZ_OK;
+}
+
+int cz_search_set_terminal_extra(cz_ctx *c, int n) {
+    CZ_REQUIRE(c && n >= 0 && n <= 64, "cz_search_set_terminal_extra: 0 <= n <= 64 required");
+    c->terminal_extra = n;
+    return CZ_OK;
+}
+
+// k_reset on the first G trees, or on those of them `which` marks
+static int reset_trees(cz_ctx *c, const uint8_t *boards, const uint8_t *side, const int32_t *rr, int G, const uint8_t *which) {
     hipLaunchKernelGGL(k_reset, dim3(G), dim3(64), 0, c->stream, c->t, boards, side, rr, G, which);
     CZ_HIP(hipGetLastError());
     return CZ_OK;
+}
+
+int cz_search_reset(cz_ctx *c, const uint8_t *boards, const uint8_t *side, const int32_t *rr, int G) {
+    CZ_REQUIRE(c && boards && side, "cz_search_reset: null argument");
+    if (G <= 0 || G > c->max_games) { cz_set_error("cz_search_reset: G=%d outside 1..%d", G, c->max_games); return CZ_EINVAL; }
+    c->G = G;
+    return reset_trees(c, boards, side, rr, G, nullptr);
+}
+
+int cz_search_reload(cz_ctx *c, const uint8_t *which, const uint8_t *boards, const uint8_t *side, const int32_t *rr) {
+    CZ_REQUIRE(c && c->G > 0, "cz_search_reload: call cz_search_reset first");
+    CZ_REQUIRE(which && boards && side, "cz_search_reload: null argument");
+    return reset_trees(c, boards, side, rr, c->G, which);
 }
 
 // The element type of planes and logits: CZ_F32 as float, the 16-bit formats as their bits.  f(one) is called with 1.0 in
@@ -1023,7 +1069,19 @@ template <typename F> static void with_dtype(int dtype, F f) {
     else f((uint16_t)(dtype == CZ_F16 ? 0x3C00 : 0x3F80));
 }
 
-int czk_search_select(cz_ctx *c, int mode, const uint8_t *active, void *planes, int dtype, int C, uint8_t *needs_eval, bool compact) {
+// what the three selects ask of the arguments they share, in the words of the one called (who)
+static int check_select(const char *who, int mode, int dtype, int channels) {
+    const char *bad = nullptr;
+    if (mode != 0 && mode != 1) bad = "mode must be 0 or 1";
+    else if (dtype != CZ_F32 && dtype != CZ_BF16 && dtype != CZ_F16) bad = "dtype must be CZ_F32, CZ_BF16 or CZ_F16";
+    else if (channels < 14 || channels > 64) bad = "14 <= channels <= 64";
+    if (!bad) return CZ_OK;
+    cz_set_error("%s: %s", who, bad);
+    return CZ_EINVAL;
+}
+
+// the width-1 select kernel for the context's cache levels; compact: the leaves' rows are handed out by the step's counter
+static int launch_select(cz_ctx *c, int mode, const uint8_t *active, void *planes, int dtype, int C, uint8_t *needs_eval, bool compact) {
     const bool cache = c->t.ec_key != nullptr, xc = cache && c->t.xc_base != nullptr;
     with_dtype(dtype, [&](auto one) {
         using T = decltype(one);
@@ -1037,7 +1095,37 @@ int czk_search_select(cz_ctx *c, int mode, const uint8_t *active, void *planes, 
     return CZ_OK;
 }
 
-int czk_search_expand_backup(cz_ctx *c, const void *logits, const void *value, int dtype) {
+int cz_search_select(cz_ctx *c, int mode, const uint8_t *active, void *planes, int dtype, int channels, uint8_t *needs_eval) {
+    CZ_REQUIRE(c && c->G > 0, "cz_search_select: call cz_search_reset first");
+    if (const int rc = check_select("cz_search_select", mode, dtype, channels)) return rc;
+    return launch_select(c, mode, active, planes, dtype, channels, needs_eval, false);
+}
+
+int cz_search_select_compact(cz_ctx *c, int mode, const uint8_t *active, void *planes, int dtype, int channels,
+                             const int32_t **slot_of, const int32_t **n_rows) {
+    CZ_REQUIRE(c && c->G > 0 && planes, "cz_search_select_compact: call cz_search_reset first / null planes");
+    if (const int rc = check_select("cz_search_select_compact", mode, dtype, channels)) return rc;
+    c->step_parity ^= 1;
+    if (slot_of) *slot_of = c->t.slot_of;
+    if (n_rows) *n_rows = c->t.evcnt + c->step_parity;
+    return launch_select(c, mode, active, planes, dtype, channels, nullptr, true);
+}
+
+int cz_search_select_k(cz_ctx *c, int mode, int k, const uint8_t *active, void *planes, int dtype, int channels, uint8_t *needs_eval) {
+    CZ_REQUIRE(c && c->G > 0, "cz_search_select_k: call cz_search_reset first");
+    if (const int rc = check_select("cz_search_select_k", mode, dtype, channels)) return rc;
+    if (k < 1 || k > c->width) { cz_set_error("cz_search_select_k: k=%d outside 1..width=%d (cz_search_set_width)", k, c->width); return CZ_EINVAL; }
+    with_dtype(dtype, [&](auto one) {
+        using T = decltype(one);
+        hipLaunchKernelGGL(k_select_k<T>, dim3(c->G), dim3(64), 0, c->stream, c->t, c->tab, c->G, mode, k, c->sim_target, active, (T *)planes, channels, one, needs_eval);
+    });
+    CZ_HIP(hipGetLastError());
+    return CZ_OK;
+}
+
+int cz_search_expand_backup(cz_ctx *c, const void *logits, const void *value, int dtype) {
+    CZ_REQUIRE(c && c->G > 0 && logits && value, "cz_search_expand_backup: null argument / no search");
+    CZ_REQUIRE(dtype == CZ_F32 || dtype == CZ_BF16, "cz_search_expand_backup: dtype must be CZ_F32 or CZ_BF16");
     with_dtype(dtype, [&](auto one) {
         using T = decltype(one);
         hipLaunchKernelGGL((k_expand_backup<T, false>), dim3(c->G), dim3(64), 0, c->stream, c->t, c->tab, c->G, (const T *)logits,
@@ -1047,33 +1135,35 @@ int czk_search_expand_backup(cz_ctx *c, const void *logits, const void *value, i
     return CZ_OK;
 }
 
-int czk_search_expand_backup_fc(cz_ctx *c, const float *z, const float *value, const float *fcw, const float *fcb, bool compact) {
-    hipLaunchKernelGGL((k_expand_backup<float, true>), dim3(c->G), dim3(64), 0, c->stream, c->t, c->tab, c->G, z, value, fcw, fcb,
+int cz_search_expand_backup_fc(cz_ctx *c, const float *z, const float *value, const float *pfc_w, const float *pfc_b, int compact) {
+    CZ_REQUIRE(c && c->G > 0 && z && value && pfc_w && pfc_b, "cz_search_expand_backup_fc: null argument / no search");
+    hipLaunchKernelGGL((k_expand_backup<float, true>), dim3(c->G), dim3(64), 0, c->stream, c->t, c->tab, c->G, z, value, pfc_w, pfc_b,
                        compact ? c->step_parity : -1);
     CZ_HIP(hipGetLastError());
     return CZ_OK;
 }
 
-int czk_search_root_stats(cz_ctx *c, uint16_t *label, int32_t *N, float *Q, float *P, float *W, uint16_t *count) {
+int cz_search_expand_backup_k(cz_ctx *c, int k, const void *logits, const void *value, int dtype) {
+    CZ_REQUIRE(c && c->G > 0 && logits && value, "cz_search_expand_backup_k: null argument / no search");
+    CZ_REQUIRE(dtype == CZ_F32 || dtype == CZ_BF16, "cz_search_expand_backup_k: dtype must be CZ_F32 or CZ_BF16");
+    if (k < 1 || k > c->width) { cz_set_error("cz_search_expand_backup_k: k=%d outside 1..width=%d", k, c->width); return CZ_EINVAL; }
+    with_dtype(dtype, [&](auto one) {
+        using T = decltype(one);
+        hipLaunchKernelGGL(k_expand_backup_k<T>, dim3(c->G), dim3(64), 0, c->stream, c->t, c->tab, c->G, k, (const T *)logits, (const T *)value);
+    });
+    CZ_HIP(hipGetLastError());
+    return CZ_OK;
+}
+
+int cz_search_root_stats(cz_ctx *c, uint16_t *label, int32_t *N, float *Q, float *P, float *W, uint16_t *count) {
+    CZ_REQUIRE(c && c->G > 0, "cz_search_root_stats: no search");
     hipLaunchKernelGGL(k_root_stats, dim3(c->G), dim3(64), 0, c->stream, c->t, c->G, label, N, Q, P, W, count);
     CZ_HIP(hipGetLastError());
     return CZ_OK;
 }
 
-int czk_search_pick_ready(cz_ctx *c, int32_t *thr, int next_thr, uint16_t *played, uint8_t *ready, unsigned long long *banked) {
-    hipLaunchKernelGGL(k_pick_ready, dim3(c->G), dim3(64), 0, c->stream, c->t, c->G, thr, next_thr, played, ready, banked);
-    CZ_HIP(hipGetLastError());
-    return CZ_OK;
-}
-
-int czk_search_reload_finished(cz_ctx *c, const uint8_t *ready, const uint16_t *played, const uint8_t *boards, const uint8_t *side,
-                               const int32_t *rr, unsigned long long *reloaded) {
-    hipLaunchKernelGGL(k_reload_finished, dim3(c->G), dim3(64), 0, c->stream, c->t, c->G, ready, played, boards, side, rr, reloaded);
-    CZ_HIP(hipGetLastError());
-    return CZ_OK;
-}
-
-int czk_search_advance(cz_ctx *c, const uint16_t *played) {
+int cz_search_advance(cz_ctx *c, const uint16_t *played) {
+    CZ_REQUIRE(c && c->G > 0 && played, "cz_search_advance: null argument / no search");
     // bitmap + ranks of one tree in LDS: 12 bytes per 64 nodes (38 KB for the bench's 205 056-node pools)
     const size_t lds = (size_t)c->t.words * 12;
     const size_t lds_max = 150 * 1024;   // 160 KB per CU minus the kernel's static LDS; the attribute is per function, so always the maximum
@@ -1091,6 +1181,28 @@ int czk_search_advance(cz_ctx *c, const uint16_t *played) {
     return CZ_OK;
 }
 
+int cz_search_pick_ready(cz_ctx *c, int32_t *sim_threshold, int next_threshold, uint16_t *played, uint8_t *ready, unsigned long long *banked_sims) {
+    CZ_REQUIRE(c && c->G > 0 && sim_threshold && played, "cz_search_pick_ready: null argument / no search");
+    hipLaunchKernelGGL(k_pick_ready, dim3(c->G), dim3(64), 0, c->stream, c->t, c->G, sim_threshold, next_threshold, played, ready, banked_sims);
+    CZ_HIP(hipGetLastError());
+    return CZ_OK;
+}
+
+int cz_search_reload_finished(cz_ctx *c, const uint8_t *ready, const uint16_t *played, const uint8_t *boards, const uint8_t *side,
+                              const int32_t *rr, unsigned long long *reloaded) {
+    CZ_REQUIRE(c && c->G > 0 && ready && played && boards && side, "cz_search_reload_finished: null argument / no search");
+    hipLaunchKernelGGL(k_reload_finished, dim3(c->G), dim3(64), 0, c->stream, c->t, c->G, ready, played, boards, side, rr, reloaded);
+    CZ_HIP(hipGetLastError());
+    return CZ_OK;
+}
+
+int cz_search_status(cz_ctx *c, int32_t *status, int32_t *nodes, int32_t *sims, int32_t *depth) {
+    CZ_REQUIRE(c && c->G > 0, "cz_search_status: no search");
+    hipLaunchKernelGGL(k_status, dim3((c->G + 255) / 256), dim3(256), 0, c->stream, c->t, c->G, status, nodes, sims, depth);
+    CZ_HIP(hipGetLastError());
+    return CZ_OK;
+}
+
 int cz_search_root_state(cz_ctx *c, uint8_t *boards, uint8_t *side, int32_t *rr) {
     if (!c) { cz_set_error("null ctx"); return CZ_EINVAL; }
     if (c->G == 0) return CZ_OK;
@@ -1099,20 +1211,75 @@ int cz_search_root_state(cz_ctx *c, uint8_t *boards, uint8_t *side, int32_t *rr)
     return CZ_OK;
 }
 
-int czk_search_select_k(cz_ctx *c, int mode, int K, const uint8_t *active, void *planes, int dtype, int C, uint8_t *needs_eval) {
-    with_dtype(dtype, [&](auto one) {
-        using T = decltype(one);
-        hipLaunchKernelGGL(k_select_k<T>, dim3(c->G), dim3(64), 0, c->stream, c->t, c->tab, c->G, mode, K, c->sim_target, active, (T *)planes, C, one, needs_eval);
-    });
+int cz_search_clear_cache_stats(cz_ctx *c) {
+    hipLaunchKernelGGL(k_clear_cache_stats, dim3((c->max_games + 255) / 256), dim3(256), 0, c->stream, c->t, c->max_games);
     CZ_HIP(hipGetLastError());
     return CZ_OK;
 }
 
-int czk_search_expand_backup_k(cz_ctx *c, int K, const void *logits, const void *value, int dtype) {
-    with_dtype(dtype, [&](auto one) {
-        using T = decltype(one);
-        hipLaunchKernelGGL(k_expand_backup_k<T>, dim3(c->G), dim3(64), 0, c->stream, c->t, c->tab, c->G, K, (const T *)logits, (const T *)value);
-    });
-    CZ_HIP(hipGetLastError());
+int cz_search_eval_totals(cz_ctx *c, unsigned long long *rows, unsigned long long *steps) {
+    CZ_REQUIRE(c, "null ctx");
+    unsigned long long h[2] = {0, 0};
+    CZ_HIP(hipStreamSynchronize(c->stream));
+    CZ_HIP(hipMemcpy(h, c->t.evtotal, sizeof(h), hipMemcpyDeviceToHost));
+    if (rows) *rows = h[0];
+    if (steps) *steps = h[1];
     return CZ_OK;
+}
+
+// Tree g's expansion records in pre-order (children in generation order, the root itself not numbered): the numbering of
+// cz_search_tree_dump's records, which cz_search_debug_eval_cache_dump reports its entries' nodes in.  A record that points
+// outside the tree's nodes ends the walk: what was numbered so far stands.
+int cz_tree_preorder(cz_ctx *c, int g, CzPreorder &o) {
+    int32_t root = 0;
+    CZ_HIP(hipMemcpy(&root, &c->t.root_node[g], 4, hipMemcpyDeviceToHost));
+    CZ_HIP(hipMemcpy(&o.n, &c->t.n_nodes[g], 4, hipMemcpyDeviceToHost));
+    const int n = o.n;
+    const size_t base = (size_t)g * (size_t)c->cap;
+    std::vector<int32_t> &cb = o.child_begin;
+    std::vector<uint16_t> &cc = o.child_count;
+    cb.resize(n); cc.resize(n);
+    CZ_HIP(hipMemcpy(cb.data(), c->t.pool.child_begin + base, 4 * (size_t)n, hipMemcpyDeviceToHost));
+    CZ_HIP(hipMemcpy(cc.data(), c->t.pool.child_count + base, 2 * (size_t)n, hipMemcpyDeviceToHost));
+    o.root = root >= 0 && root < n ? root : -1;
+    o.node.clear(); o.depth.clear();
+    struct Frame { int node, next, depth; };
+    std::vector<Frame> st;
+    if (o.root >= 0 && cb[root] >= 0) st.push_back({root, 0, 0});
+    while (!st.empty()) {
+        Frame &f = st.back();
+        if (f.next >= cc[f.node]) { st.pop_back(); continue; }
+        const int ch = cb[f.node] + f.next++, depth = f.depth;
+        if (ch < 0 || ch >= n) break;
+        o.node.push_back(ch); o.depth.push_back(depth);
+        if (cb[ch] >= 0) st.push_back({ch, 0, depth + 1});
+    }
+    return CZ_OK;
+}
+
+int cz_search_tree_dump(cz_ctx *c, int g, int32_t *out, int max_records) {
+    CZ_REQUIRE(c && c->G > 0 && g >= 0 && g < c->G, "cz_search_tree_dump: bad tree index");
+    CZ_HIP(hipStreamSynchronize(c->stream));
+    CzPreorder po;
+    if (const int rc = cz_tree_preorder(c, g, po)) return rc;
+    const int n = po.n, nrec = (int)po.node.size();
+    if (!out) return nrec;
+    const CzPool &p = c->t.pool;
+    const size_t base = (size_t)g * (size_t)c->cap;
+    std::vector<float> P(n), W(n), Q(n);
+    std::vector<int32_t> N(n);
+    std::vector<uint16_t> mv(n);
+    CZ_HIP(hipMemcpy(P.data(), p.P + base, 4 * (size_t)n, hipMemcpyDeviceToHost));
+    CZ_HIP(hipMemcpy(W.data(), p.W + base, 4 * (size_t)n, hipMemcpyDeviceToHost));
+    CZ_HIP(hipMemcpy(Q.data(), p.Q + base, 4 * (size_t)n, hipMemcpyDeviceToHost));
+    CZ_HIP(hipMemcpy(N.data(), p.N + base, 4 * (size_t)n, hipMemcpyDeviceToHost));
+    CZ_HIP(hipMemcpy(mv.data(), p.move + base, 2 * (size_t)n, hipMemcpyDeviceToHost));
+    auto bits = [](float f) { int32_t i; memcpy(&i, &f, 4); return i; };
+    for (int k = 0; k < nrec && k < max_records; ++k) {
+        const int ch = po.node[k];
+        int32_t *r = out + (size_t)k * 7;
+        r[0] = po.depth[k]; r[1] = mv[ch]; r[2] = N[ch]; r[3] = bits(W[ch]); r[4] = bits(Q[ch]); r[5] = bits(P[ch]);
+        r[6] = po.child_begin[ch] < 0 ? -1 : po.child_count[ch];
+    }
+    return nrec;
 }

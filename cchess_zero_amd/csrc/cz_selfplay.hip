@@ -271,20 +271,128 @@ __global__ __launch_bounds__(64) void k_sp_flush(CzSelfplay sp, int G, const int
 
 }  // namespace
 
-int czk_selfplay_seed(cz_ctx *c, const uint8_t *boards, const uint8_t *side, const int32_t *rr) {
+// ---- the entry points, in cz_match.hip's order: create, setters, getters, choose, adjudicate ------------------------
+// The state lives in cz_ctx (sp, sp_rules, sp_chase, sp_state and the three blocks): cz_destroy frees the blocks.
+
+int cz_selfplay_begin(cz_ctx *c, int max_plies, const uint8_t *boards, const uint8_t *side, const int32_t *rr) {
+    CZ_REQUIRE(c && c->G > 0, "cz_selfplay_begin: call cz_search_reset first");
+    CZ_REQUIRE(max_plies >= 1 && max_plies <= 65535, "cz_selfplay_begin: 1 <= max_plies <= 65535");
+    CZ_REQUIRE(boards == nullptr || side != nullptr, "cz_selfplay_begin: start_side required with start_boards");
+    if (!c->sp_block || c->sp.max_plies != max_plies) {
+        CZ_HIP(hipStreamSynchronize(c->stream));
+        if (c->sp_block) { (void)hipFree(c->sp_block); c->sp_block = nullptr; }
+        const size_t G = (size_t)c->max_games;
+        CzSelfplay &sp = c->sp;
+        const int rc = carve_alloc(&c->sp_block, c->stream, false, "cz_selfplay_begin", [&](Carver &k) {
+            sp.hist = k.take<uint8_t>(G * (size_t)max_plies * CZ_REC_BYTES);
+            sp.ply = k.take<int32_t>(G);
+            sp.stalled = k.take<uint8_t>(G);
+            sp.active = k.take<uint8_t>(G);
+            sp.start_board = k.take<uint8_t>(G * CZD_BOARD_LDS);
+            sp.start_side = k.take<uint8_t>(G);
+            sp.start_rr = k.take<int32_t>(G);
+            sp.stats = k.take<long long>(CZ_SP_NSTATS);
+            sp.xq_stats = k.take<long long>(3);
+            carve_root_rules(k, sp.rr, G, false);
+        });
+        if (rc != CZ_OK) return rc;
+        sp.max_plies = max_plies;
+    }
+    c->sp_rules = 0; c->sp.rr.fold = 0; c->sp_chase = 0; c->sp_state = 1;
+    c->sp.rs = CzSpResign{};   // resignation off: no pointer, no kernel looks
+    c->sp.rs.threshold = NAN;
     hipLaunchKernelGGL(k_sp_seed, dim3(c->G), dim3(64), 0, c->stream, c->t, c->sp, c->G, boards, side, rr);
     CZ_HIP(hipGetLastError());
     return CZ_OK;
 }
 
-int czk_selfplay_resign_init(cz_ctx *c) {
+// the setters' order (cz_root_rules_order), in self-play's names
+static int sp_order(const cz_ctx *c, int what, int value) {
+    return cz_root_rules_order("cz_selfplay", "ctx", "the history starts at the games' first positions", what, value, c->sp_rules, c->sp.rr.fold,
+                               c->sp_chase, c->sp_state != 1);
+}
+
+int cz_selfplay_set_rules(cz_ctx *c, int rules) {
+    CZ_REQUIRE(c && c->sp_block && c->sp_state != 0, "cz_selfplay_set_rules: call cz_selfplay_begin first");
+    if (const int rc = sp_order(c, CZ_SET_RULES, rules)) return rc;
+    c->sp_rules = rules;
+    return CZ_OK;
+}
+
+int cz_selfplay_set_repetition(cz_ctx *c, int fold) {
+    CZ_REQUIRE(c && c->sp_block && c->sp_state != 0, "cz_selfplay_set_repetition: call cz_selfplay_begin first");
+    if (const int rc = sp_order(c, CZ_SET_REPETITION, fold)) return rc;
+    c->sp.rr.fold = fold;
+    return CZ_OK;
+}
+
+int cz_selfplay_history(cz_ctx *c, const uint64_t **keys, const uint8_t **checks) {
+    CZ_REQUIRE(c && c->sp_block && c->sp.rr.fold != 0, "cz_selfplay_history: cz_selfplay_set_repetition first");
+    if (keys) *keys = c->sp.rr.ring_key;
+    if (checks) *checks = c->sp.rr.ring_check;
+    return CZ_OK;
+}
+
+int cz_selfplay_set_chase(cz_ctx *c, int on) {
+    CZ_REQUIRE(c && c->sp_block && c->sp_state != 0, "cz_selfplay_set_chase: call cz_selfplay_begin first");
+    if (const int rc = sp_order(c, CZ_SET_CHASE, on)) return rc;
+    if (on) {   // zeroed at every switching on: the counter starts with the games, as cz_selfplay_begin's
+        const int rc = carve_alloc(&c->sp_chase_block, c->stream, true, "cz_selfplay_set_chase", [&](Carver &k) {
+            carve_root_rules(k, c->sp.rr, (size_t)c->max_games, true);
+            c->sp.chase_stat = k.take<long long>(1);
+        });
+        if (rc != CZ_OK) return rc;
+    }
+    c->sp_chase = on;
+    return CZ_OK;
+}
+
+int cz_selfplay_chase_history(cz_ctx *c, const uint64_t **chase) {
+    CZ_REQUIRE(c && c->sp_block && c->sp_chase != 0, "cz_selfplay_chase_history: cz_selfplay_set_chase first");
+    if (chase) *chase = c->sp.rr.ring_chase;
+    return CZ_OK;
+}
+
+int cz_selfplay_set_resign(cz_ctx *c, float threshold, int min_ply, double playon_fraction, unsigned long long seed) {
+    CZ_REQUIRE(c && c->sp_block && c->sp_state != 0, "cz_selfplay_set_resign: call cz_selfplay_begin first");
+    CZ_REQUIRE(min_ply >= 0 && playon_fraction >= 0.0 && playon_fraction <= 1.0, "cz_selfplay_set_resign: min_ply >= 0 and 0 <= playon_fraction <= 1 required");
+    CzSpResign &rs = c->sp.rs;
+    if (rs.game_no) {   // a later call retunes: the per-game state, the counters and the seed stay
+        rs.threshold = threshold; rs.min_ply = min_ply; rs.playon_fraction = playon_fraction;
+        return CZ_OK;
+    }
+    if (threshold != threshold) return CZ_OK;   // off stays off
+    const size_t G = (size_t)c->max_games;
+    CzSpResign r{};   // c->sp.rs stays "off" until the block stands
+    r.threshold = threshold; r.min_ply = min_ply; r.playon_fraction = playon_fraction; r.seed = seed;
+    const int rc = carve_alloc(&c->sp_resign_block, c->stream, true, "cz_selfplay_set_resign", [&](Carver &k) {   // the counters start with the games
+        r.game_no = k.take<uint32_t>(G);
+        r.playon = k.take<uint8_t>(G);
+        r.minq = k.take<float>(G * 2);
+        r.would = k.take<uint8_t>(G);
+        r.resigned = k.take<uint8_t>(G);
+        r.stats = k.take<long long>(4);
+        r.hist = k.take<long long>(64);
+    });
+    if (rc != CZ_OK) return rc;
+    rs = r;
     hipLaunchKernelGGL(k_sp_resign_init, dim3((c->max_games + 63) / 64), dim3(64), 0, c->stream, c->sp.rs, c->max_games);
     CZ_HIP(hipGetLastError());
     return CZ_OK;
 }
 
-int czk_selfplay_choose(cz_ctx *c, const float *gamma, const float *u, const uint16_t *forced, double temperature, float eps,
-                        int min_sims, uint16_t *played) {
+int cz_selfplay_active(cz_ctx *c, const uint8_t **active) {
+    CZ_REQUIRE(c && c->sp_block && active, "cz_selfplay_active: call cz_selfplay_begin first");
+    *active = c->sp.active;
+    return CZ_OK;
+}
+
+int cz_selfplay_choose(cz_ctx *c, const float *gamma, const float *u, const uint16_t *forced, double temperature, float eps, int min_sims, uint16_t *played) {
+    CZ_REQUIRE(c && c->sp_block && c->G > 0, "cz_selfplay_choose: call cz_selfplay_begin first");
+    CZ_REQUIRE(u && played, "cz_selfplay_choose: u and played required");
+    CZ_REQUIRE(temperature > 0.0 && eps >= 0.f && eps <= 1.f, "cz_selfplay_choose: temperature > 0 and 0 <= noise_eps <= 1 required");
+    CZ_REQUIRE(min_sims >= 0, "cz_selfplay_choose: min_sims >= 0 required");
+    c->sp_state = 2;
     const int level = cz_rules_level(c->sp_rules, c->sp.rr.fold, c->sp_chase);
     if (level >= CZ_RULES_KINGSAFE) {   // what the rules need of every slot's root position, then the choice
         hipLaunchKernelGGL(k_sp_roots_xq, dim3(c->G), dim3(64), 0, c->stream, c->t, c->sp, c->G);
@@ -299,7 +407,8 @@ int czk_selfplay_choose(cz_ctx *c, const float *gamma, const float *u, const uin
     return CZ_OK;
 }
 
-int czk_selfplay_adjudicate(cz_ctx *c, int reseed, const uint16_t *played, int32_t *fin_n) {
+int cz_selfplay_adjudicate(cz_ctx *c, int reseed, const uint16_t *played, int32_t *fin_n) {
+    CZ_REQUIRE(c && c->sp_block && c->G > 0 && fin_n, "cz_selfplay_adjudicate: call cz_selfplay_begin first / null fin_n");
     cz_by_rules_level(cz_rules_level(c->sp_rules, c->sp.rr.fold, c->sp_chase), [&](auto L) {
         hipLaunchKernelGGL(k_sp_adjudicate<decltype(L)::value>, dim3(c->G), dim3(64), 0, c->stream, c->t, c->sp, c->G, reseed, played, fin_n);
     });
@@ -307,9 +416,42 @@ int czk_selfplay_adjudicate(cz_ctx *c, int reseed, const uint16_t *played, int32
     return CZ_OK;
 }
 
-int czk_selfplay_flush(cz_ctx *c, const int32_t *fin_n, const long long *offset, uint8_t *ring, long long ring_records,
-                       const long long *read_cursor) {
+int cz_selfplay_flush(cz_ctx *c, const int32_t *fin_n, const long long *offset, uint8_t *ring, long long ring_records, const long long *read_cursor) {
+    CZ_REQUIRE(c && c->sp_block && c->G > 0, "cz_selfplay_flush: call cz_selfplay_begin first");
+    CZ_REQUIRE(fin_n && offset && ring && ring_records > 0, "cz_selfplay_flush: null argument / empty ring");
     hipLaunchKernelGGL(k_sp_flush, dim3(c->G), dim3(64), 0, c->stream, c->sp, c->G, fin_n, offset, ring, ring_records, read_cursor);
     CZ_HIP(hipGetLastError());
+    return CZ_OK;
+}
+
+int cz_selfplay_stats(cz_ctx *c, long long *stats_dev) {
+    CZ_REQUIRE(c && c->sp_block && stats_dev, "cz_selfplay_stats: call cz_selfplay_begin first / null argument");
+    CZ_HIP(hipMemcpyAsync(stats_dev, c->sp.stats, sizeof(long long) * CZ_SP_NSTATS, hipMemcpyDeviceToDevice, c->stream));
+    return CZ_OK;
+}
+
+int cz_selfplay_rules_stats(cz_ctx *c, long long *stats_dev) {
+    CZ_REQUIRE(c && c->sp_block && stats_dev, "cz_selfplay_rules_stats: call cz_selfplay_begin first / null argument");
+    CZ_HIP(hipMemcpyAsync(stats_dev, c->sp.xq_stats, sizeof(long long) * 3, hipMemcpyDeviceToDevice, c->stream));
+    return CZ_OK;
+}
+
+int cz_selfplay_chase_stats(cz_ctx *c, long long *stats_dev) {
+    CZ_REQUIRE(c && c->sp_block && stats_dev, "cz_selfplay_chase_stats: call cz_selfplay_begin first / null argument");
+    if (c->sp_chase) CZ_HIP(hipMemcpyAsync(stats_dev, c->sp.chase_stat, sizeof(long long), hipMemcpyDeviceToDevice, c->stream));
+    else CZ_HIP(hipMemsetAsync(stats_dev, 0, sizeof(long long), c->stream));
+    return CZ_OK;
+}
+
+int cz_selfplay_resign_stats(cz_ctx *c, long long *stats_dev, long long *hist_dev) {
+    CZ_REQUIRE(c && c->sp_block && stats_dev, "cz_selfplay_resign_stats: call cz_selfplay_begin first / null argument");
+    const CzSpResign &rs = c->sp.rs;
+    if (rs.game_no) {
+        CZ_HIP(hipMemcpyAsync(stats_dev, rs.stats, sizeof(long long) * 4, hipMemcpyDeviceToDevice, c->stream));
+        if (hist_dev) CZ_HIP(hipMemcpyAsync(hist_dev, rs.hist, sizeof(long long) * 64, hipMemcpyDeviceToDevice, c->stream));
+    } else {
+        CZ_HIP(hipMemsetAsync(stats_dev, 0, sizeof(long long) * 4, c->stream));
+        if (hist_dev) CZ_HIP(hipMemsetAsync(hist_dev, 0, sizeof(long long) * 64, c->stream));
+    }
     return CZ_OK;
 }

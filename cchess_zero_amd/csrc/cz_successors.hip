@@ -148,9 +148,11 @@ __global__ __launch_bounds__(64) void k_successors(const uint16_t *__restrict__ 
 
 }  // namespace
 
-int czk_successors(cz_ctx *c, const uint8_t *boards, const uint8_t *side, int G, const uint16_t *moves, const int32_t *offsets, int total,
-                   uint8_t *out_boards, uint8_t *out_side, uint8_t *out_captured, int32_t *out_parent, uint16_t *out_label) {
+int cz_successors(cz_ctx *c, const uint8_t *boards, const uint8_t *side, int G, const uint16_t *moves, const int32_t *offsets, int total,
+                  uint8_t *out_boards, uint8_t *out_side, uint8_t *out_captured, int32_t *out_parent, uint16_t *out_label) {
+    CZ_REQUIRE(c && G >= 0 && total >= 0, "cz_successors: null ctx / negative G or total");
     if (G == 0 || total == 0) return CZ_OK;
+    CZ_REQUIRE(boards && side && moves && offsets && out_boards, "cz_successors: boards, side, moves, offsets, out_boards required");
     if (reinterpret_cast<uintptr_t>(out_boards) & 15u) { cz_set_error("cz_successors: out_boards must be 16-byte aligned"); return CZ_EINVAL; }
     const dim3 grid(czf_persistent_grid((G + 63) / 64, 10));   // 15.5 KB of LDS per wave: ten waves per CU
     hipLaunchKernelGGL(k_successors, grid, dim3(64), 0, c->stream, c->tab.srcdst, boards, side, G, moves, offsets, total, out_boards, out_side,
