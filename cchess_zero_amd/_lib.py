@@ -34,8 +34,8 @@ CAUSE_NONE, CAUSE_CHECK, CAUSE_CHASE = 0, 1, 2
 POS_IN_CHECK, POS_CAN_TAKE_KING, POS_NO_SAFE_MOVE = 1, 2, 4
 
 # cz_games_replay (include/cchess_hip.h: CZ_GAME_*): why a game's replay stopped, and the end_flags bits beside POS_*
-GAME_OK, GAME_ILLEGAL, GAME_AFTER_END, GAME_BAD_BOARD, GAME_BAD_LEN = 0, 1, 2, 3, 4
-GAME_STATUS = ("ok", "illegal", "after_end", "bad_board", "bad_len")
+GAME_OK, GAME_ILLEGAL, GAME_AFTER_END, GAME_BAD_BOARD, GAME_BAD_LEN, GAME_AMBIGUOUS = 0, 1, 2, 3, 4, 5   # 5: cz_games_read only
+GAME_STATUS = ("ok", "illegal", "after_end", "bad_board", "bad_len", "ambiguous")
 GAME_RED_KING_GONE, GAME_BLACK_KING_GONE = 16, 32
 
 _u8p, _u16p, _i32p, _f32p, _vp = C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p
@@ -67,6 +67,7 @@ _SIGS = {
     "cz_encode_planes": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_int, _vp, C.c_int, C.c_int, C.c_int]),
     "cz_records_expand": (C.c_int, [C.c_void_p, _u8p, C.c_int, _u8p, C.c_double, _f32p, _f32p, _f32p]),
     "cz_games_replay": (C.c_int, [C.c_void_p, _u8p, _u8p, _u16p, C.c_int, _i32p, _vp, C.c_int, C.c_int, _i32p, C.c_int, _u8p, _i32p, _u8p, _u8p, _u8p, _u8p]),
+    "cz_games_read": (C.c_int, [C.c_void_p, _u8p, _u8p, _vp, C.c_int, _i32p, _vp, C.c_int, C.c_int, _i32p, C.c_int, _u8p, _i32p, _u8p, _u8p, _u8p, _u8p, _u16p]),
     "cz_search_reset": (C.c_int, [C.c_void_p, _u8p, _u8p, _i32p, C.c_int]),
     "cz_search_set_eval_cache": (C.c_int, [C.c_void_p, C.c_int]),
     "cz_search_eval_cache_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]),

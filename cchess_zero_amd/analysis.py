@@ -97,12 +97,15 @@ class Analyzer:
             out.append(rows)
         return out
 
-    def analyse(self, positions, n_lines=1, max_len=16, ban=None):
+    def analyse(self, positions, n_lines=1, max_len=16, ban=None, notation="iccs"):
         """positions: FEN strings or (board uint8[90], side, restrict round) tuples, any number; ban: None or, per position, the
         moves no line may start with.  -> per position dict(bestmove, score, lines=[dict(pv=[move text ...], visits, q)], sims,
         flags): lines in rank order (more visits first), visits / q those of the line's first move, bestmove = lines[0].pv[0],
         score = its q; flags = the position's CZ_POS_* bits.  A mover without a king-safe move reports bestmove None with
-        POS_NO_SAFE_MOVE in flags and is not searched; so does, without the flag, a position whose every candidate is banned."""
+        POS_NO_SAFE_MOVE in flags and is not searched; so does, without the flag, a position whose every candidate is banned.
+        notation: "iccs" (the default: what UCCI tools read), "wxf" or "chinese" — every move of a line written in the position it
+        is played in (notation.line_text)."""
+        from .notation import line_text
         pos = [fen_to_position(p) if isinstance(p, str) else p for p in positions]
         if ban is not None and len(ban) != len(pos):
             raise ValueError("ban has one entry per position")
@@ -121,7 +124,8 @@ class Analyzer:
             lines = self.read_lines(allowed, n_lines, max_len)
             sims = eng.status()[2].cpu().numpy()
             for g in range(len(chunk)):
-                rows = [dict(pv=[self.labels[m] for m in r["pv"]], visits=r["visits"][0], q=float(r["q"][0])) for r in lines[g]] if live[g] else []
+                rows = [dict(pv=line_text(boards[g], side[g], r["pv"], notation), visits=r["visits"][0], q=float(r["q"][0]))
+                        for r in lines[g]] if live[g] else []
                 out.append(dict(bestmove=rows[0]["pv"][0] if rows else None, score=rows[0]["q"] if rows else None, lines=rows,
                                 sims=int(sims[g]), flags=int(flags[g])))
         return out
@@ -136,6 +140,7 @@ def main(argv=None):
     ap.add_argument("--blocks", type=int, default=7, help="residual blocks of the net")
     ap.add_argument("--playout", type=int, default=400, help="playouts per position")
     ap.add_argument("--lines", type=int, default=1, help="principal variations per position")
+    ap.add_argument("--notation", choices=("iccs", "wxf", "chinese"), default="iccs", help="how the moves of the output are written (default: ICCS)")
     args = ap.parse_args(argv)
     fens = list(args.fen)
     if args.fen_file:
@@ -148,9 +153,9 @@ def main(argv=None):
         ap.error(str(e))
     from .arena import load_player
     net = load_player(args.model, args.blocks)
-    res = Analyzer(net, args.playout, min(len(pos), 8192)).analyse(pos, args.lines)
+    res = Analyzer(net, args.playout, min(len(pos), 8192)).analyse(pos, args.lines, notation=args.notation)
     for f, r in zip(fens, res):
-        print(json.dumps(dict(fen=f, **r)), flush=True)
+        print(json.dumps(dict(fen=f, **r), ensure_ascii=args.notation != "chinese"), flush=True)
     return res
 
 

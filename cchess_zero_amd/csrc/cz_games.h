@@ -16,6 +16,7 @@
 #define CZG_AFTER_END 2   // a move in a position with a king missing, or (level 1) without a king-safe move
 #define CZG_BAD_BOARD 3   // czm_list / czk_position refuse the position (-1)
 #define CZG_BAD_LEN 4     // the game's length is outside 0 .. stride
+#define CZG_AMBIGUOUS 5   // a notation token names two or more moves of the list (cz_notation.h; cz_games_read only)
 // end_flags beside the CZK_* bits (CZ_GAME_*_KING_GONE)
 #define CZG_RED_KING_GONE 16u
 #define CZG_BLACK_KING_GONE 32u
@@ -66,8 +67,13 @@ struct CzgStep { int n, idx, status; };
 //   srcdst[label] = from | to << 8 (cz_tables: label -> squares), read for a move that is made only.
 // The order of the tests is the order of CZ_GAME_* in include/cchess_hip.h: a refused board before a missing king before a
 // move that is not in the list.
-template <int RULES, typename Scr, typename Put, typename Mid>
-CZM_FN CzgStep czg_step(uint32_t (&w)[23], int side, uint32_t label, bool go, const CzmTables &T, const uint16_t *srcdst, Scr scr, Put put, Mid mid) {
+//   czg_step_pick is the same ply with one more hook, for a move that is NAMED against the position instead of given as a label
+//   (cz_notation.h): pick(n, label, idx) runs once, when the list of n moves has been put and before the tests; it may replace
+//   label and idx (the place in the list, or < 0: none) and answers the status of a move it did not find (CZG_ILLEGAL, or its
+//   own).  czg_step is czg_step_pick with a pick that leaves both alone.
+template <int RULES, typename Scr, typename Put, typename Mid, typename Pick>
+CZM_FN CzgStep czg_step_pick(uint32_t (&w)[23], int side, uint32_t label, bool go, const CzmTables &T, const uint16_t *srcdst, Scr scr, Put put, Mid mid,
+                             Pick pick) {
     uint32_t wa[23];
 #pragma unroll
     for (int k = 0; k < 23; ++k) wa[k] = go ? w[k] : 0u;
@@ -90,9 +96,10 @@ CZM_FN CzgStep czg_step(uint32_t (&w)[23], int side, uint32_t label, bool go, co
             [&](int k, int l) { put(k, l); r.idx = (uint32_t)l == label ? k : r.idx; },
             [](int, uint32_t) {}, mid, &pf);
     }
+    const int miss = pick(r.n, label, r.idx);
     const CzmSets S = czm_sets(wa, side);
     const bool ended = czg_kings_gone(S, side) != 0u || (RULES == 1 && r.n == 0);
-    r.status = !go ? CZG_ILLEGAL : r.n < 0 ? CZG_BAD_BOARD : ended ? CZG_AFTER_END : r.idx < 0 ? CZG_ILLEGAL : CZG_OK;
+    r.status = !go ? CZG_ILLEGAL : r.n < 0 ? CZG_BAD_BOARD : ended ? CZG_AFTER_END : r.idx < 0 ? miss : CZG_OK;
     if (CZM_ANY(r.status == CZG_OK)) {
         const uint32_t sq = r.status == CZG_OK ? srcdst[label] : 0u;   // a listed label is < 2086
         uint32_t wn[23];
@@ -103,6 +110,10 @@ CZM_FN CzgStep czg_step(uint32_t (&w)[23], int side, uint32_t label, bool go, co
         for (int k = 0; k < 23; ++k) w[k] = r.status == CZG_OK ? wn[k] : w[k];
     }
     return r;
+}
+template <int RULES, typename Scr, typename Put, typename Mid>
+CZM_FN CzgStep czg_step(uint32_t (&w)[23], int side, uint32_t label, bool go, const CzmTables &T, const uint16_t *srcdst, Scr scr, Put put, Mid mid) {
+    return czg_step_pick<RULES>(w, side, label, go, T, srcdst, scr, put, mid, [](int, uint32_t &, int &) { return CZG_ILLEGAL; });
 }
 
 // end_flags of the position a replay reached: cz_movegen_kingsafe's CZ_POS_* bits of it (0 for a board it refuses), at both

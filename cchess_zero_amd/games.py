@@ -3,8 +3,12 @@ cchess_main.selfplay, main.py:1493-1554).
 
   parse_games / write_games   games as MOVE LISTS in two text formats: one game per line of ICCS moves with an optional result
                               token ("h2e2 h9g7 ... 1-0"), and PGN-style blocks ([FEN "..."], [Result "..."], ICCS movetext
-                              "1. H2-E2 H9-G7").  Anything that is not ICCS is reported and skipped, never guessed.
-  GameReplayer.replay         cz_games_replay (csrc/cz_games.hip): all games in ONE launch, one lane per game -> the packed
+                              "1. H2-E2 H9-G7").  Anything that is not ICCS is reported and skipped, never guessed — unless
+                              notations= names "wxf" and / or "chinese": such a game ("C2=5 H8+7", "炮二平五 馬8進7") is read to
+                              TOKENS (notation.wxf_token / chinese_token) with no board, and the replay decodes them.
+  GameReplayer.replay         cz_games_replay (csrc/cz_games.hip), or with a game of tokens cz_games_read (csrc/cz_notation.hip:
+                              every token found among its position's legal moves inside the replay): all games in ONE launch,
+                              one lane per game -> the packed
                               CZ_REC_* records selfplay.to_dense / records.RecordExpander take as they are (pi one-hot at the
                               played move, z the game's result from the mover's side), and for every game how far it is legal
                               under the rules asked for: "capture" (the reference's pseudo-legal moves) or "xiangqi" (king-safe).
@@ -12,9 +16,9 @@ cchess_main.selfplay, main.py:1493-1554).
                               the yardstick the fused replay is measured against (ply_by_ply_replay)
   pretrain                    supervised steps on such records with a holdout BY GAME, seeded and rank-consistent like
                               train.policy_update
-  python -m cchess_zero_amd.games --in F [--rules xiangqi] [--out records.npy] [--write-pgn G.pgn]
+  python -m cchess_zero_amd.games --in F [--rules xiangqi] [--notation any] [--out records.npy] [--write-pgn G.pgn [--write-notation wxf]]
 
-Not read: WXF, Chinese and binary (XQF, CBR) notations; no repetition verdicts on imported games.
+Not read: binary formats (XQF, CBR); no repetition verdicts on imported games.
 """
 import argparse
 import collections
@@ -28,12 +32,15 @@ import numpy as np
 
 from ._lib import (GAME_BLACK_KING_GONE, GAME_OK, GAME_RED_KING_GONE, GAME_STATUS, MAXMOVES, NSQ, POS_NO_SAFE_MOVE, REC_BYTES, REC_SIDE, REC_Z,
                    tables)
-from .notation import START_FEN, fen_to_position, position_to_fen
+from .notation import NOTATIONS, START_FEN, chinese_token, fen_to_position, move_text, position_to_fen, wxf_token
 
 # board: the 90 piece codes as bytes (comparable: parse_games(write_games(x)) == x); side 0 red / 1 black; rr: the restrict round
 # of the start (a FEN's halfmove clock); labels: a tuple of move labels; result +1 red won / -1 black won / 0 draw / None
-# unknown; tags: the other PGN tags as (name, value) pairs, in order
-Game = collections.namedtuple("Game", "board side rr labels result tags")
+# unknown; tags: the other PGN tags as (name, value) pairs, in order; tokens: None, or — a game read from WXF / Chinese notation —
+# a tuple of uint32 tokens (include/cchess_hip.h: cz_games_read), labels is then ()
+Game = collections.namedtuple("Game", "board side rr labels result tags tokens", defaults=(None,))
+_FORMAT_NAMES = {"ICCS": "iccs", "WXF": "wxf", "CHINESE": "chinese"}
+_READERS = {"wxf": wxf_token, "chinese": chinese_token}
 RESULT_TOKENS = {"1-0": 1, "0-1": -1, "1/2-1/2": 0, "*": None}
 _TOKEN_OF = {1: "1-0", -1: "0-1", 0: "1/2-1/2", None: "*"}
 _MOVE = re.compile(r"^([a-i][0-9])-?([a-i][0-9])$")
@@ -51,26 +58,73 @@ class GameList(list):
     skipped = ()
 
 
-def _moves(tokens, where):
-    """movetext tokens -> (labels, result token or None); ValueError names the token that is not an ICCS move"""
-    l2i = tables()["label2i"]
-    labels, result = [], None
+def _iccs(t):
+    m = _MOVE.match(t.lower())
+    return m and tables()["label2i"].get(m.group(1) + m.group(2))
+
+
+def _moves(tokens, where, notations=("iccs",), fmt=None):
+    """movetext tokens -> (labels, tokens or None, result token or None).  The game's notation is fmt (its [Format] tag), or what
+    its first move reads as among `notations`; every move is then read in that one notation, and ValueError names the text that
+    is not a move in it."""
+    return _moves_in(tokens, where, tuple(notations), fmt)
+
+
+def _movetext(tokens):
+    """the result tokens and the moves, without move numbers"""
     for t in tokens:
         if t in RESULT_TOKENS:
-            result = t
+            yield t
             continue
         t = re.sub(r"^\d+\.+", "", t)   # "1." and "1..." glued to a move or alone
         if not t or set(t) == {"."}:
             continue
-        m = _MOVE.match(t.lower())
-        if not m or m.group(1) + m.group(2) not in l2i:
-            raise ValueError("%s: %r is not an ICCS move" % (where, t))
-        labels.append(l2i[m.group(1) + m.group(2)])
-    return tuple(labels), result
+        yield t
 
 
-def parse_games(text):
-    """Text -> GameList of Game.  With a line that starts with '[' the text is PGN-style blocks, else one game per line."""
+def _reads(t, notation):
+    if notation == "iccs":
+        return _iccs(t) is not None
+    try:
+        _READERS[notation](t)
+        return True
+    except ValueError:
+        return False
+
+
+def _moves_in(tokens, where, notations, fmt):
+    out, result, notation = [], None, fmt or ("iccs" if notations == ("iccs",) else None)
+    for t in _movetext(tokens):
+        if t in RESULT_TOKENS:
+            result = t
+            continue
+        if notation is None:
+            notation = next((n for n in NOTATIONS if n in notations and _reads(t, n)), None)
+            if notation is None:
+                raise ValueError("%s: %r is not a move in %s notation" % (where, t, " / ".join(n for n in NOTATIONS if n in notations)))
+        if notation == "iccs":
+            v = _iccs(t)
+            if v is None:
+                raise ValueError("%s: %r is not an ICCS move" % (where, t))
+        else:
+            try:
+                v = _READERS[notation](t)
+            except ValueError as e:
+                raise ValueError("%s: %s" % (where, e))
+        out.append(v)
+    if notation in (None, "iccs"):
+        return tuple(out), None, result
+    return (), tuple(out), result
+
+
+def parse_games(text, notations=("iccs",)):
+    """Text -> GameList of Game.  With a line that starts with '[' the text is PGN-style blocks, else one game per line.
+    notations: the move notations read, out of "iccs", "wxf", "chinese".  With more than ICCS named, a block's [Format] tag
+    decides a game's notation, without a tag its first move does; a game in one notation never mixes another (it is skipped,
+    the text named).  A WXF / Chinese game comes back with tokens instead of labels."""
+    notations = tuple(notations)
+    if not notations or any(n not in NOTATIONS for n in notations):
+        raise ValueError("parse_games: notations are out of %r" % (NOTATIONS,))
     out, skipped = GameList(), []
     lines = text.splitlines()
     if not any(l.lstrip().startswith("[") for l in lines):
@@ -79,12 +133,12 @@ def parse_games(text):
             if not line:
                 continue
             try:
-                labels, res = _moves(line.split(), "line %d" % no)
+                labels, toks, res = _moves(line.split(), "line %d" % no, notations)
             except ValueError as e:
                 skipped.append((no, str(e)))
                 continue
             b, s, rr = _start()
-            out.append(Game(b, s, rr, labels, RESULT_TOKENS[res] if res else None, ()))
+            out.append(Game(b, s, rr, labels, RESULT_TOKENS[res] if res else None, (), toks))
         out.skipped = tuple(skipped)
         return out
     # PGN-style: a block is its tag lines and the movetext behind them, up to the next tag line
@@ -112,12 +166,14 @@ def parse_games(text):
             if blk["bad"]:
                 raise ValueError(blk["bad"])
             tags = dict(blk["tags"])
-            if tags.get("Format", "ICCS").strip().upper() != "ICCS":
-                raise ValueError("%s: Format %r is not ICCS" % (where, tags["Format"]))
+            fmt = _FORMAT_NAMES.get(tags["Format"].strip().upper(), "") if "Format" in tags else None
+            if fmt is not None and fmt not in notations:
+                raise ValueError("%s: Format %r is not %s" % (where, tags["Format"], " / ".join(k for k, v in _FORMAT_NAMES.items() if v in notations)
+                                                              if notations != ("iccs",) else "ICCS"))
             text = re.sub(r"\{[^}]*\}", " ", " ".join(blk["text"]))
             if "{" in text or "}" in text:
                 raise ValueError("%s: unbalanced comment" % where)
-            labels, res = _moves(text.split(), where)
+            labels, toks, res = _moves(text.split(), where, notations, fmt)
             if "FEN" in tags:
                 b, s, rr = fen_to_position(tags["FEN"])
                 b = bytes(b)
@@ -127,21 +183,67 @@ def parse_games(text):
                 if tags["Result"] not in RESULT_TOKENS:
                     raise ValueError("%s: Result %r" % (where, tags["Result"]))
                 res = tags["Result"]
-            out.append(Game(b, s, rr, labels, RESULT_TOKENS[res] if res else None, tuple(t for t in blk["tags"] if t[0] not in _DERIVED_TAGS)))
+            out.append(Game(b, s, rr, labels, RESULT_TOKENS[res] if res else None, tuple(t for t in blk["tags"] if t[0] not in _DERIVED_TAGS), toks))
         except ValueError as e:
             skipped.append((blk["line"], str(e)))
     out.skipped = tuple(skipped)
     return out
 
 
-def write_games(games, pgn=True):
+def _plies(g):
+    return g.labels if g.tokens is None else g.tokens
+
+
+def _texts_from_replay(games, replay, notation):
+    """per game the move texts in `notation` out of a replay's records (the board before every kept ply and the move played
+    there), or None for a game whose plies are not all among the records, or with a ply the notation has no text for; and
+    the games' decoded labels, or None likewise"""
+    from ._lib import REC_LABELS, REC_VISITS
+    rec = replay.records.cpu().numpy() if hasattr(replay.records, "cpu") else np.asarray(replay.records)
+    lo = np.searchsorted(replay.game_of_record, np.arange(len(games)), "left")
+    hi = np.searchsorted(replay.game_of_record, np.arange(len(games)), "right")
+    texts, labels = [], []
+    for g, game in enumerate(games):
+        r = rec[lo[g]:hi[g]]
+        if len(r) != len(_plies(game)):
+            texts.append(None); labels.append(None)
+            continue
+        lab = np.ascontiguousarray(r[:, REC_LABELS:REC_LABELS + 2 * MAXMOVES]).view(np.uint16)
+        vis = np.ascontiguousarray(r[:, REC_VISITS:REC_VISITS + 2 * MAXMOVES]).view(np.uint16)
+        played = lab[np.arange(len(r)), vis.argmax(axis=1)] if len(r) else np.zeros(0, np.uint16)
+        labels.append(tuple(int(x) for x in played))
+        t = [move_text(r[i, :NSQ], int(r[i, REC_SIDE]), int(played[i]), notation) for i in range(len(r))]
+        texts.append(None if any(x is None for x in t) else t)
+    return texts, labels
+
+
+def write_games(games, pgn=True, notation="iccs", replay=None):
     """The inverse of parse_games: parse_games(write_games(x)) == x.  pgn=False (one game per line) has no place for a start
-    position or tags: ValueError for a game that has either."""
+    position or tags: ValueError for a game that has either.
+    notation "wxf" / "chinese" (PGN form only) writes the moves in that notation under a [Format] tag.  That needs every ply's
+    position: replay is GameReplayer.replay's answer for these very games, and a game is written from its records — the board
+    before each ply and the move played there (notation.move_text).  A game with a ply that has no such text, or whose plies are
+    not all among the records (it did not replay completely, or was dropped), is written whole as it came: ICCS from its labels,
+    WXF from its tokens.  With a replay, a game of tokens that replayed completely can also be written as ICCS."""
+    from .notation import token_text
     names = tables()["labels"]
+    if notation not in NOTATIONS or (notation != "iccs" and (not pgn or replay is None)):
+        raise ValueError("write_games: notation is one of %r; wxf and chinese need pgn=True and the games' replay" % (NOTATIONS,))
+    games = list(games)
+    texts, decoded = _texts_from_replay(games, replay, notation) if replay is not None else ([None] * len(games), [None] * len(games))
     out = []
-    for g in games:
-        mv = [names[l] for l in g.labels]
+    for gi, g in enumerate(games):
+        fmt = "ICCS"
+        if notation != "iccs" and texts[gi] is not None:
+            mv, fmt = texts[gi], {"wxf": "WXF", "chinese": "Chinese"}[notation]
+        elif g.tokens is None or decoded[gi] is not None:
+            mv = [names[l] for l in (g.labels if g.tokens is None else decoded[gi])]
+            mv = [m[:2].upper() + "-" + m[2:].upper() for m in mv] if pgn else mv
+        else:
+            mv, fmt = [token_text(t) for t in g.tokens], "WXF"
         if not pgn:
+            if fmt != "ICCS":
+                raise ValueError("write_games(pgn=False): a game of tokens needs the PGN form")
             if (g.board, g.side, g.rr) != _start() or g.tags:
                 raise ValueError("write_games(pgn=False): a game with a start position or tags needs the PGN form")
             out.append(" ".join(mv + ([_TOKEN_OF[g.result]] if g.result is not None else [])))
@@ -150,7 +252,7 @@ def write_games(games, pgn=True):
             out.append('[%s "%s"]' % (k, v))
         if (g.board, g.side, g.rr) != _start():
             out.append('[FEN "%s"]' % position_to_fen(np.frombuffer(g.board, np.uint8), g.side, g.rr))
-        out.append('[Format "ICCS"]')
+        out.append('[Format "%s"]' % fmt)
         out.append('[Result "%s"]' % _TOKEN_OF[g.result])
         out.append("")
         text = []
@@ -158,7 +260,7 @@ def write_games(games, pgn=True):
             text.append("1. ...")
         for i, m in enumerate(mv):
             k = i + (1 if g.side else 0)
-            text.append(("%d. " % (k // 2 + 1) if k % 2 == 0 else "") + m[:2].upper() + "-" + m[2:].upper())
+            text.append(("%d. " % (k // 2 + 1) if k % 2 == 0 else "") + m)
         text.append(_TOKEN_OF[g.result])
         for i in range(0, len(text), 10):
             out.append(" ".join(text[i:i + 10]))
@@ -175,7 +277,7 @@ def games_from_labels(moves, lens, results=None, boards=None, sides=None):
             for g in range(len(lens))]
 
 
-ReplayResult = collections.namedtuple("ReplayResult", "records game_of_record valid status end_flags final_boards final_side results kept counts")
+ReplayResult = collections.namedtuple("ReplayResult", "records game_of_record valid status end_flags final_boards final_side results kept counts labels")
 
 
 def infer_result(end_flags, final_side):
@@ -191,7 +293,7 @@ def infer_result(end_flags, final_side):
 
 
 class GameReplayer:
-    """cz_games_replay on a context of its own, or on a given one."""
+    """cz_games_replay / cz_games_read on a context of its own, or on a given one."""
 
     def __init__(self, ctx=None, device=0):
         from .engine import Context
@@ -215,34 +317,38 @@ class GameReplayer:
         inferred_results, unknown_result, red_king_gone, black_king_gone, no_safe_move.
         on_illegal: "drop" keeps the games that replay completely, "truncate" also the legal part of the others.  A game whose
         result is unknown is dropped.  z is written by the kernel from the result given; for a game whose result is inferred
-        the z bytes of its records are patched on the device afterwards (one masked write — no second replay)."""
+        the z bytes of its records are patched on the device afterwards (one masked write — no second replay).
+        No game with tokens: cz_games_replay, as ever.  Otherwise cz_games_read for ALL of them in one launch, a game of labels
+        passing its labels as small tokens; counts["ambiguous"] are the games a token stopped by naming two moves.  labels (the
+        last field): uint16 [G, stride], the label every made ply was (decoded to), 0xFFFF elsewhere."""
         import torch
         from .rules import RULES
         if rules not in RULES or on_illegal not in ("drop", "truncate"):
             raise ValueError("GameReplayer.replay: rules is 'capture' or 'xiangqi', on_illegal 'drop' or 'truncate'")
         games = list(games)
         G = len(games)
-        lens = np.array([len(g.labels) for g in games], np.int64)
+        lens = np.array([len(_plies(g)) for g in games], np.int64)
+        tokens = any(g.tokens is not None for g in games)
         if G == 0 or lens.max() > 65535 or lens.sum() >= 2 ** 31:
             if G:
                 raise ValueError("GameReplayer.replay: a game longer than 65535 plies, or 2^31 plies in one call")
             return ReplayResult(torch.zeros((0, REC_BYTES), dtype=torch.uint8, device=self.dev), np.zeros(0, np.int32), np.zeros(0, np.int32),
                                 np.zeros(0, np.uint8), np.zeros(0, np.uint8), np.zeros((0, NSQ), np.uint8), np.zeros(0, np.uint8), [], np.zeros(0, bool),
                                 dict({k: 0 for k in GAME_STATUS}, games=0, plies=0, kept_games=0, kept_plies=0, inferred_results=0, unknown_result=0,
-                                     red_king_gone=0, black_king_gone=0, no_safe_move=0))
+                                     red_king_gone=0, black_king_gone=0, no_safe_move=0), np.zeros((0, 1), np.uint16))
         stride, total = max(int(lens.max()), 1), int(lens.sum())
         order = np.argsort(lens, kind="stable") if (G >= self.SORT_FROM_GAMES if sort is None else sort) else np.arange(G)
         offset = np.concatenate([[0], np.cumsum(lens)[:-1]])
-        moves = np.full((G, stride), 0xFFFF, np.uint16)
+        moves = np.full((G, stride), 0xFFFF, np.uint32 if tokens else np.uint16)
         for j, g in enumerate(order):
-            moves[j, :lens[g]] = games[g].labels
+            moves[j, :lens[g]] = _plies(games[g])
         start = _start()
         custom = any((g.board, g.side) != start[:2] for g in games)
         boards = np.stack([np.frombuffer(games[g].board, np.uint8) for g in order]) if custom else None
         side = np.array([games[g].side for g in order], np.uint8) if custom else None
         given = np.array([0 if games[g].result is None else games[g].result for g in order], np.int8)
         t = self.ctx.tensor
-        d_moves, d_len, d_res, d_off = t(moves, torch.int16), t(lens[order], torch.int32), t(given, torch.int8), t(offset[order], torch.int32)
+        d_moves, d_len, d_res, d_off = t(moves, torch.int32 if tokens else torch.int16), t(lens[order], torch.int32), t(given, torch.int8), t(offset[order], torch.int32)
         d_boards, d_side = t(boards, torch.uint8), t(side, torch.uint8)
         rec = torch.empty((total, REC_BYTES), dtype=torch.uint8, device=self.dev)
         valid = torch.empty(G, dtype=torch.int32, device=self.dev)
@@ -250,11 +356,17 @@ class GameReplayer:
         flags = torch.empty(G, dtype=torch.uint8, device=self.dev)
         fboards = torch.empty((G, NSQ), dtype=torch.uint8, device=self.dev)
         fside = torch.empty(G, dtype=torch.uint8, device=self.dev)
-        self.ctx.call("cz_games_replay", d_boards, d_side, d_moves, stride, d_len, d_res, G, RULES[rules], d_off, total, rec, valid, status, flags,
-                      fboards, fside)
+        if tokens:
+            d_labels = torch.empty((G, stride), dtype=torch.int16, device=self.dev)
+            self.ctx.call("cz_games_read", d_boards, d_side, d_moves, stride, d_len, d_res, G, RULES[rules], d_off, total, rec, valid, status, flags,
+                          fboards, fside, d_labels)
+        else:
+            self.ctx.call("cz_games_replay", d_boards, d_side, d_moves, stride, d_len, d_res, G, RULES[rules], d_off, total, rec, valid, status, flags,
+                          fboards, fside)
         inv = np.empty(G, np.int64)
         inv[order] = np.arange(G)
         valid, status, flags = valid.cpu().numpy()[inv], status.cpu().numpy()[inv], flags.cpu().numpy()[inv]
+        labels = d_labels.cpu().numpy().view(np.uint16)[inv] if tokens else np.where(np.arange(stride)[None, :] < valid[:, None], moves[inv], 0xFFFF).astype(np.uint16)
         fboards, fside = fboards.cpu().numpy()[inv], fside.cpu().numpy()[inv]
         results, inferred = [], np.zeros(G, bool)
         for g in range(G):
@@ -278,7 +390,7 @@ class GameReplayer:
         counts.update(games=G, plies=total, kept_games=int(kept.sum()), kept_plies=int(keep.sum()), inferred_results=int((inferred & kept).sum()),
                       unknown_result=int((~known).sum()), red_king_gone=int((flags & GAME_RED_KING_GONE != 0).sum()),
                       black_king_gone=int((flags & GAME_BLACK_KING_GONE != 0).sum()), no_safe_move=int((flags & POS_NO_SAFE_MOVE != 0).sum()))
-        return ReplayResult(records, game_of[keep].astype(np.int32), valid, status, flags, fboards, fside, results, kept, counts)
+        return ReplayResult(records, game_of[keep].astype(np.int32), valid, status, flags, fboards, fside, results, kept, counts, labels)
 
 
 def _playout(rules_obj, level, boards, side, max_ply, pick):
@@ -434,18 +546,23 @@ def pretrain(net, records, game_of_record, steps, batch_size, learning_rate, see
 
 
 def main(argv=None):
-    ap = argparse.ArgumentParser(prog="python -m cchess_zero_amd.games", description="Recorded games (ICCS lines or PGN-style blocks) -> packed training records")
+    ap = argparse.ArgumentParser(prog="python -m cchess_zero_amd.games", description="Recorded games (lines of moves or PGN-style blocks; ICCS, with --notation any also WXF and Chinese) -> packed training records")
     ap.add_argument("--in", dest="src", required=True, help="the games: one per line of ICCS moves, or PGN-style blocks with ICCS movetext")
     ap.add_argument("--rules", choices=("capture", "xiangqi"), default="capture")
     ap.add_argument("--on_illegal", choices=("drop", "truncate"), default="drop")
     ap.add_argument("--out", help="write the kept records here (numpy uint8 [n, 608]; <out>.games.npy: their games)")
     ap.add_argument("--write-pgn", dest="write_pgn", help="write the games read back as PGN-style blocks")
+    ap.add_argument("--notation", choices=("iccs", "any"), default="iccs", help="the move notations read: ICCS only, or any of ICCS, WXF and Chinese")
+    ap.add_argument("--write-notation", dest="write_notation", choices=NOTATIONS, default="iccs", help="the notation --write-pgn writes (from the replay)")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
-    games = parse_games(open(a.src).read())
-    if a.write_pgn:
+    games = parse_games(open(a.src, encoding="utf-8").read(), notations=NOTATIONS if a.notation == "any" else ("iccs",))
+    plain = a.write_notation == "iccs" and not any(g.tokens is not None for g in games)
+    if a.write_pgn and plain:
         open(a.write_pgn, "w").write(write_games(games, pgn=True))
     r = GameReplayer(device=a.device).replay(games, rules=a.rules, on_illegal=a.on_illegal)
+    if a.write_pgn and not plain:   # the positions come from the replay
+        open(a.write_pgn, "w", encoding="utf-8").write(write_games(games, pgn=True, notation=a.write_notation, replay=r))
     if a.out:
         np.save(a.out, r.records.cpu().numpy())
         np.save(a.out + ".games.npy", r.game_of_record)

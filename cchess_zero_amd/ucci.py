@@ -2,11 +2,12 @@
 
     python -m cchess_zero_amd.ucci --model M.pt --blocks 7 [--playout 400] [--search_threads 16]
 
-Commands: ucci, isready, setoption <name> <value> (Playouts, MultiPV), position {startpos | fen <fen>} [moves m1 m2 ...],
+Commands: ucci, isready, setoption <name> <value> (Playouts, MultiPV, Notation), position {startpos | fen <fen>} [moves m1 m2 ...],
 banmoves m1 ..., go [nodes N | time T | depth D], stop, quit.  Moves are ICCS coordinates ("h2e2": files a-i, ranks 0-9 with
 red at rank 0), positions standard Xiangqi FEN (notation.fen_to_position).  After each go: one `info depth <len> [multipv k]
 score <round(1000 q)> nodes <sims> time <ms> pv m1 m2 ...` per line, then `bestmove m1 [ponder m2]`, or `nobestmove` when the
-mover has no king-safe move that is not banned.  Unknown commands are ignored.
+mover has no king-safe move that is not banned.  Unknown commands are ignored.  `setoption Notation wxf` (or chinese; default
+iccs, which is what GUIs read) writes the pv of the info lines in that notation; bestmove and ponder stay ICCS.
 
 The search is the one analysis.py describes: the reference's king-capture search with the Xiangqi rules applied at the root.
 Out of scope: the engine does not judge repetition itself (GUIs send banmoves), it does not ponder (`ponder m2` is only the
@@ -29,7 +30,7 @@ import time
 import numpy as np
 
 from . import _lib
-from .notation import START_FEN, fen_to_position
+from .notation import NOTATIONS, START_FEN, fen_to_position, line_text
 
 CHUNK_STEPS = 32     # lock-steps between two looks at the clock / the input
 MAX_MULTIPV = 8
@@ -40,6 +41,7 @@ class UcciEngine:
     def __init__(self, searcher, inp, out, playouts=400, clock=time.monotonic):
         self.searcher, self.inp, self.out, self.clock = searcher, inp, out, clock
         self.options = dict(playouts=int(playouts), multipv=1)
+        self.pv_notation = "iccs"   # setoption Notation: how the info lines write their pv
         t = _lib.tables()
         self.labels, self.label2i, self.srcdst = t["labels"], t["label2i"], t["srcdst"]
         self.pos = fen_to_position(START_FEN)
@@ -117,6 +119,11 @@ class UcciEngine:
         if len(args) < 2:
             return
         name = args[0].lower()
+        if name == "notation":
+            if args[1].lower() not in NOTATIONS:
+                return self.say("info string setoption Notation: %r is not one of %s" % (args[1], " ".join(NOTATIONS)))
+            self.pv_notation = args[1].lower()
+            return
         try:
             value = int(args[1])
         except ValueError:
@@ -215,7 +222,7 @@ class UcciEngine:
         for k, ln in enumerate(lines):
             multipv = " multipv %d" % (k + 1) if self.options["multipv"] > 1 else ""
             self.say("info depth %d%s score %d nodes %d time %d pv %s" % (len(ln["pv"]), multipv, int(round(1000.0 * float(ln["q"][0]))), sims, ms,
-                                                                         " ".join(self.labels[m] for m in ln["pv"])))
+                                                                         " ".join(line_text(self.pos[0], self.pos[1], ln["pv"], self.pv_notation))))
         pv = lines[0]["pv"]
         self.say("bestmove %s%s" % (self.labels[pv[0]], " ponder %s" % self.labels[pv[1]] if len(pv) > 1 else ""))
 

@@ -297,6 +297,32 @@ int cz_games_replay(cz_ctx *, const uint8_t *start_boards /* [G][90] or NULL: th
                     int rules /* 0 capture, 1 king-safe */, const int32_t *rec_offset /* [G] */, int total,
                     uint8_t *records /* [total][CZ_REC_BYTES] or NULL */, int32_t *valid /* [G] */, uint8_t *status /* [G] */,
                     uint8_t *end_flags /* [G] */, uint8_t *final_boards /* [G][90] or NULL */, uint8_t *final_side /* [G] or NULL */);
+/* Game replay from TOKENS: cz_games_replay for games written in WXF / Chinese notation.  Such a move ("C2=5", 炮二平五) has
+ *     no coordinates; it is read against the position it is played in, inside the replay.  Everything not said here is as in
+ *     cz_games_replay: records, the order of the tests, zero records for plies given but not made, end_flags, G == 0.
+ *     tokens[g * stride + i] is one uint32.  Below 65536 it is a move label and is used as cz_games_replay uses it (label and
+ *     notation games go through one launch).  Otherwise it is four bytes, least significant first, b0 b1 b2 b3:
+ *       b0  a kind out of K A E H R C P, or a file digit 1-9: the mover's pawn on that file (b1 is then an ordinal);
+ *       b1  the source: a file digit 1-9, or an ordinal on the file: + frontmost, - rearmost, a-e the 1st .. 5th from the front;
+ *       b2  + forward, - backward, = sideways;      b3  a digit 1-9.
+ *     With x = 0..8 the files a..i and y = 0 red's back rank, the file number of x is 9 - x for red and x + 1 for black, and
+ *     forward is +y for red, -y for black.  A move from -> to of the ply's legal list MATCHES the token when
+ *       the mover's piece on `from` is of the token's kind (b0 a digit: a pawn, and the file of `from` is that digit);
+ *       source, a digit: `from` is on that file, however many of the kind stand there; an ordinal: at least two of the
+ *         mover's pieces of that kind stand on `from`'s file and `from` is the one the ordinal names;
+ *       move: R C P K with + / -: same file, that direction, |dy| == b3; any kind with =: dy == 0 and the file of `to` is b3;
+ *         H E A with + / -: dy in that direction and the file of `to` is b3; H E A never match =.
+ *     Exactly one match: that move is made.  None: CZ_GAME_ILLEGAL.  Two or more: CZ_GAME_AMBIGUOUS, tested where ILLEGAL
+ *     is; the game stops there as for any other status.  Any 32-bit value is safe: bytes outside the alphabet (and b0 a digit
+ *     with b1 a digit) match nothing, and no token value indexes anything.
+ *     labels_out [G][stride] (may be NULL): the label each made ply decoded to, 0xFFFF everywhere else; every element is
+ *     written exactly once.
+ *     CZ_EINVAL as cz_games_replay's (tokens for moves), and tokens not 4-byte or labels_out not 2-byte aligned. */
+#define CZ_GAME_AMBIGUOUS 5
+int cz_games_read(cz_ctx *, const uint8_t *start_boards, const uint8_t *start_side, const uint32_t *tokens /* [G][stride] */, int stride,
+                  const int32_t *len, const int8_t *result, int G, int rules, const int32_t *rec_offset, int total, uint8_t *records,
+                  int32_t *valid, uint8_t *status, uint8_t *end_flags, uint8_t *final_boards, uint8_t *final_side,
+                  uint16_t *labels_out /* [G][stride] or NULL */);
 
 /* ---- lock-step search over G trees, one wavefront per tree ---------------------------------
  * replaces: MCTS_tree.__init__/reload (main.py:235-259): fresh, unexpanded roots. */

@@ -645,20 +645,21 @@ class cchess_main(object):
         self.log_file.flush()
         return info
 
-    def pretrain(self, path, steps, rules=None, learning_rate=None):
+    def pretrain(self, path, steps, rules=None, learning_rate=None, notation="iccs"):
         """--pretrain: supervised steps on the recorded games of `path` (ICCS lines or PGN-style blocks, cchess_zero_amd/games.py)
         before the first self-play batch.  The games are replayed into packed records on the GPU in one launch (cz_games_replay)
         under `rules` (default: the self-play games' rules), games that are not legal under them are dropped; a twentieth of
         the games is held out and reported on.  Honours --batch_size and --mirror_augment, saves a checkpoint, prints one
         `pretrain: {json}` line, and the records seed the data buffer.  No reference function: the reference learns from its own
-        games only."""
+        games only.  notation "any" (--pretrain_notation) also reads games in WXF and Chinese notation; their moves are decoded
+        inside the same replay launch (cz_games_read)."""
         import torch
         import torch.distributed as dist
         from cchess_zero_amd import games as G
         from cchess_zero_amd.records import RecordExpander
         rules = rules or self.rules
         t0 = time.time()
-        parsed = G.parse_games(open(path).read())
+        parsed = G.parse_games(open(path, encoding="utf-8").read(), notations=G.NOTATIONS if notation == "any" else ("iccs",))
         rp = G.GameReplayer(device=torch.cuda.current_device())
         res = rp.replay(parsed, rules=rules, on_illegal="drop")
         if getattr(self, "_expander", None) is None:
@@ -824,6 +825,8 @@ if __name__ == '__main__':
     parser.add_argument('--pretrain_steps', default=1000, type=int, help='training steps of --pretrain (of --batch_size samples)')
     parser.add_argument('--pretrain_rules', default=None, choices=['capture', 'xiangqi'], type=str,
                         help='the rules the recorded games must be legal under (default: the value of --rules)')
+    parser.add_argument('--pretrain_notation', default='iccs', choices=['iccs', 'any'], type=str,
+                        help='move notations --pretrain reads: ICCS only (default), or any of ICCS, WXF ("C2=5") and Chinese')
     parser.add_argument('--pretrain_lr', default=None, type=float, help='learning rate of --pretrain (default: the training loop\'s)')
     parser.add_argument('--net_precision', default=None, choices=['strict', 'mx6', 'fp16x2', 'fp16', 'bf16', 'bf16x2', 'fp32'], type=str,
                         help='net engine (policy_value_network.PRECISIONS): strict (default) = measured within 5e-4 absolute of the '
@@ -865,7 +868,7 @@ if __name__ == '__main__':
         train_main.resign_playon, train_main.resign_auto = args.resign_playon, args.resign_auto
         train_main.mirror_augment = args.mirror_augment
         if args.pretrain:
-            train_main.pretrain(args.pretrain, args.pretrain_steps, args.pretrain_rules, args.pretrain_lr)
+            train_main.pretrain(args.pretrain, args.pretrain_steps, args.pretrain_rules, args.pretrain_lr, args.pretrain_notation)
         train_main.run(args.max_batches)
         if os.environ.get("CCHESS_WEIGHT_DIGEST_DIR"):   # tests: every rank leaves a digest of its replica (they must be equal)
             import hashlib

@@ -12,7 +12,9 @@ usage: python tools/rules_bench.py [N positions, default 1048576]
            frontier (3 290 240 positions) with their king-safe lists: time and achieved store bandwidth; one JSON line at the end
        python tools/rules_bench.py --replay [G]       cz_games_replay on G (default 8192) games of games.random_games under each rule
            level against the same answer from the ply-by-ply path that made them (one move-list launch and one cz_apply_move launch
-           per ply, games.ply_by_ply_replay), both timed in the same run, alternating; one JSON line at the end"""
+           per ply, games.ply_by_ply_replay), both timed in the same run, alternating; one JSON line at the end.  Then the
+           notation leg (--replay-notation [G]: that leg alone): the same games as labels through cz_games_replay and as WXF
+           tokens through cz_games_read, alternating, and a host decode in Python on a 256-game sample, scaled; one JSON line"""
 import os
 import sys
 import time
@@ -29,8 +31,9 @@ KINGSAFE = "--kingsafe" in sys.argv
 THREATS = "--threats" in sys.argv
 SUCCESSORS = "--successors" in sys.argv
 REPLAY = "--replay" in sys.argv
-_args = [a for a in sys.argv[1:] if a not in ("--kingsafe", "--threats", "--successors", "--replay")]
-N = int(_args[0]) if _args else (8192 if REPLAY else 1 << 20)
+REPLAY_NOTATION = "--replay-notation" in sys.argv
+_args = [a for a in sys.argv[1:] if a not in ("--kingsafe", "--threats", "--successors", "--replay", "--replay-notation")]
+N = int(_args[0]) if _args else (8192 if REPLAY or REPLAY_NOTATION else 1 << 20)
 ctx = Context(1, 2, 0)
 rules = Rules(ctx)
 
@@ -252,8 +255,132 @@ def replay_leg(max_ply=160):
     print(json.dumps(out), flush=True)
 
 
-if REPLAY:
-    replay_leg()
+def wxf_tokens(boards, side, labels, srcdst):
+    """The writer's rule (cchess_zero_amd/notation.py: move_token) for n plies at once: boards uint8 [n, 90] before the move, side
+    [n], labels [n] -> uint32 [n].  Standard material only (no side has three of a kind that is not the pawn)."""
+    n = len(labels)
+    ar, side = np.arange(n), side.astype(np.int64)
+    sq = srcdst[labels].astype(np.int64)
+    frm, to = sq & 0xFF, sq >> 8
+    fy, fx, ty, tx = frm // 9, frm % 9, to // 9, to % 9
+    grid = boards.reshape(n, 10, 9)
+    pc = boards[ar, frm]
+    kind = pc.astype(np.int64) - 7 * side                       # K A R E H P C = 1 .. 7
+    same = grid[ar, :, fx] == pc[:, None]                      # [n, 10]: the kind on the source's file
+    cnt = same.sum(axis=1)
+    ys = np.arange(10)[None, :]
+    ahead = (same & np.where(side[:, None] == 1, ys < fy[:, None], ys > fy[:, None])).sum(axis=1)
+    fileno = lambda x: np.where(side == 1, x + 1, 9 - x)
+    dy = np.where(side == 1, fy - ty, ty - fy)
+    digit = (cnt == 1) | (kind == 2) | (kind == 4)
+    b1 = np.where(digit, ord("0") + fileno(fx), np.where(ahead == 0, ord("+"), np.where(ahead == cnt - 1, ord("-"), ord("a") + ahead)))
+    doubled = ((grid == pc[:, None, None]).sum(axis=1) >= 2).sum(axis=1) > 1
+    b0 = np.where((kind == 6) & ~digit & doubled, ord("0") + fileno(fx), np.array([0] + [ord(c) for c in "KAREHPC"])[kind])
+    leaper = (kind == 2) | (kind == 4) | (kind == 5)
+    b2 = np.where(dy == 0, ord("="), np.where(dy > 0, ord("+"), ord("-")))
+    b3 = ord("0") + np.where((dy == 0) | leaper, fileno(tx), np.abs(dy))
+    return (b0 | b1 << 8 | b2 << 16 | b3 << 24).astype(np.uint32)
+
+
+def notation_leg(max_ply=160, sample=256):
+    """Per rule level: the N games of replay_leg, sorted by length, as labels through cz_games_replay (the path before
+    cz_games_read) and as WXF tokens through cz_games_read with labels_out: device events, 3 warm-up launches, then 25 rounds of
+    one after the other; medians.  The tokens are written from the label replay's records (wxf_tokens, checked against
+    notation.move_token on a sample); before anything is timed the token replay's final boards and decoded labels are asserted
+    equal to the games'.  The host leg steps `sample` of the games through the C oracle's lists in Python and names every token
+    with tests/notation_model.py's matcher, timed on the host clock and scaled to N games by plies."""
+    import json
+    from cchess_zero_amd import games as G
+    from cchess_zero_amd import notation
+    from cchess_zero_amd._lib import check, lib, tables
+    from cchess_zero_amd.engine import _ptr
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import games_model as GM
+    import notation_model as NM
+    from oracle import oracle as O
+    srcdst = tables()["srcdst"]
+    out = {"games": N, "max_ply": max_ply}
+    for level, r in (("capture", 0), ("xiangqi", 1)):
+        rg = G.random_games(level, N, 23, max_ply, engine_rules=rules)
+        order = np.argsort(rg["lens"], kind="stable")
+        moves, lens = rg["moves"][order], rg["lens"][order].astype(np.int64)
+        plies = int(lens.sum())
+        offset = np.concatenate([[0], np.cumsum(lens)[:-1]])
+        rec = torch.empty((plies, 608), dtype=torch.uint8, device="cuda")
+        valid, status = torch.empty(N, dtype=torch.int32, device="cuda"), torch.empty(N, dtype=torch.uint8, device="cuda")
+        flags, fside = torch.empty(N, dtype=torch.uint8, device="cuda"), torch.empty(N, dtype=torch.uint8, device="cuda")
+        fboards = torch.empty((N, 90), dtype=torch.uint8, device="cuda")
+        labels_out = torch.empty((N, max_ply), dtype=torch.int16, device="cuda")
+        zero = torch.zeros(N, dtype=torch.int8, device="cuda")
+        mv, ln, off = ctx.tensor(moves, torch.int16), ctx.tensor(lens, torch.int32), ctx.tensor(offset, torch.int32)
+        as_labels = lambda: check(lib().cz_games_replay(ctx.h, None, None, _ptr(mv), max_ply, _ptr(ln), _ptr(zero), N, r, _ptr(off), plies, _ptr(rec),
+                                                        _ptr(valid), _ptr(status), _ptr(flags), _ptr(fboards), _ptr(fside)))
+        ctx.bind_stream()
+        as_labels()
+        torch.cuda.synchronize()
+        assert (status == 0).all() and np.array_equal(fboards.cpu().numpy(), rg["final_boards"][order]), "labels"
+        played = moves[np.arange(max_ply)[None, :] < lens[:, None]].astype(np.int64)      # row-major: the records' order
+        tok = np.empty(plies, np.uint32)
+        for lo in range(0, plies, 1 << 20):
+            head = rec[lo:lo + (1 << 20), :91].cpu().numpy()
+            tok[lo:lo + (1 << 20)] = wxf_tokens(np.ascontiguousarray(head[:, :90]), head[:, 90], played[lo:lo + (1 << 20)], srcdst)
+        for i in np.random.default_rng(1).integers(0, plies, 2000):
+            h = rec[int(i), :91].cpu().numpy()
+            assert int(tok[i]) == notation.move_token(h[:90], int(h[90]), int(played[i])), (i, notation.token_text(tok[i]))
+        tokens = np.full((N, max_ply), 0xFFFF, np.uint32)
+        tokens[np.arange(max_ply)[None, :] < lens[:, None]] = tok
+        d_tok = ctx.tensor(tokens, torch.int32)
+        as_tokens = lambda: check(lib().cz_games_read(ctx.h, None, None, _ptr(d_tok), max_ply, _ptr(ln), _ptr(zero), N, r, _ptr(off), plies, _ptr(rec),
+                                                      _ptr(valid), _ptr(status), _ptr(flags), _ptr(fboards), _ptr(fside), _ptr(labels_out)))
+        want_rec = rec[:min(plies, 1 << 16)].clone()
+        rec.fill_(0xA5)
+        as_tokens()
+        torch.cuda.synchronize()
+        assert (status == 0).all() and np.array_equal(fboards.cpu().numpy(), rg["final_boards"][order]) and np.array_equal(valid.cpu().numpy(), lens), "tokens"
+        assert np.array_equal(labels_out.cpu().numpy().view(np.uint16), moves) and torch.equal(rec[:len(want_rec)], want_rec), "tokens decode to the labels"
+        timed_forms = {"labels_cz_games_replay": as_labels, "wxf_cz_games_read": as_tokens}
+        ts = {k: [] for k in timed_forms}
+        for it in range(3 + 25):
+            for name, fn in timed_forms.items():
+                ctx.bind_stream()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                fn()
+                e1.record()
+                e1.synchronize()
+                if it >= 3:
+                    ts[name].append(e0.elapsed_time(e1))
+        o = {"plies": plies, "text_tokens": int((tok >= 65536).sum()), "ordinal_tokens": int(np.isin((tok >> 8) & 0xFF, [ord(c) for c in "+-abcde"]).sum())}
+        for name, t in ts.items():
+            t.sort()
+            o[name] = dict(ms=round(t[12], 4), min_ms=round(t[0], 4), max_ms=round(t[-1], 4), plies_per_s=round(plies / t[12] * 1e3))
+            print("%-8s %-24s: median %.3f ms (min %.3f, max %.3f) for %d games, %d plies = %.2f M plies/s"
+                  % (level, name, t[12], t[0], t[-1], N, plies, plies / t[12] / 1e3))
+        # the host decode: a Python board stepped through every ply of `sample` games spread over the lengths
+        pick = np.linspace(0, N - 1, min(sample, N)).astype(np.int64)
+        t0, done = time.perf_counter(), 0
+        for g in pick:
+            b, s = GM.start_board(), 0
+            for i in range(int(lens[g])):
+                named = NM.Position(b, s, GM.legal_list(b, s, r)).matching(int(tokens[g, i]))
+                assert named == [int(moves[g, i])]
+                b, s = O.apply_move(b, named[0])[0], s ^ 1
+                done += 1
+        host_s = time.perf_counter() - t0
+        o["host_python_decode"] = dict(sample_games=len(pick), sample_plies=done, sample_s=round(host_s, 3), us_per_ply=round(host_s / max(done, 1) * 1e6, 1),
+                                       scaled_s=round(host_s / max(done, 1) * plies, 2))
+        o["read_vs_replay"] = round(o["wxf_cz_games_read"]["ms"] / o["labels_cz_games_replay"]["ms"], 3)
+        o["host_decode_vs_read"] = round(o["host_python_decode"]["scaled_s"] * 1e3 / o["wxf_cz_games_read"]["ms"], 1)
+        print("%-8s host decode in Python: %.1f us/ply on %d games -> %.1f s for all %d plies; cz_games_read / cz_games_replay = %.3f"
+              % (level, o["host_python_decode"]["us_per_ply"], len(pick), o["host_python_decode"]["scaled_s"], plies, o["read_vs_replay"]))
+        out[level] = o
+    print(json.dumps(out), flush=True)
+
+
+if REPLAY or REPLAY_NOTATION:
+    if REPLAY:
+        replay_leg()
+    notation_leg()
     sys.exit(0)
 if SUCCESSORS:
     successors_leg()
