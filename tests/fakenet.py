@@ -42,7 +42,9 @@ def make_forward(mode="pos", salt=0, log=None):
     raw-logit priors that can be negative); 'deep': every fourth label halves the logit — the labels are ranked by
     their hash and logit = (1 - (rank % 4) / 8) * 2^-(rank / 4) (exponent clamped at -120: no denormals), value
     scaled by 1/64 — so one legal move holds nearly all of a node's prior mass and a search digs one line far below
-    depth 32 (the long-path backups of the device search)."""
+    depth 32 (the long-path backups of the device search); 'posabs': the logits of 'pos' with the value |v| (exact: a sign
+    bit) — every leaf is good for its mover, so every visited child of the root gets a negative Q and the root, whose score is
+    Q alone (quirk Q2), walks through its whole list, the children of index 64-127 included."""
     salt = np.uint64(salt)
     if mode == "deep":
         def forward_deep(positions):
@@ -75,6 +77,8 @@ def make_forward(mode="pos", salt=0, log=None):
             v = ((_mix(h + np.uint64(12345)) >> np.uint64(48)).astype(np.float32) / np.float32(32768.0)) - np.float32(1.0)
         if mode == "signed":
             logits = logits - np.float32(0.5)
+        elif mode == "posabs":
+            v = np.abs(v)
         return logits.astype(np.float32), v.astype(np.float32).reshape(-1, 1)
 
     return forward

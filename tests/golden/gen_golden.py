@@ -18,6 +18,8 @@ Fixtures
                patterns), whole-tree digests, the ordered list of evaluated positions.
   mcts_deep.json  the same at the metric's depth — playout 1600, one black-to-move root, one near the 60-ply rule, one
                across update_tree — and with the 'deep' fake forward whose searches select paths of 40-60 levels.
+  mcts_wide.json  the same from open boards with 65-101 moves per position: roots and inner nodes whose selected children have
+               indices 64..127 (fake forwards 'signed' and 'posabs'), and the reference's move lists of those roots.
   policy_update.npz  cchess_main.policy_update (main.py:1157-1204) through a stand-in self with a scripted net: train steps
                taken, learning rates passed, lr_multiplier after, the logged KL / explained variances.
   selfplay.npz cchess_main.selfplay (main.py:1493) games with search_threads=1, the fake forward and
@@ -239,10 +241,10 @@ def dump_tree(node):
     return rec
 
 
-def run_spec(m, sp, deep=False):
+def run_spec(m, sp, deep=False, extra=None):
     """One golden search case: MCTS_tree.main per ply with the fake forward, most visited move played (update_tree).
     deep=True (mcts_deep.json): additionally the deepest level of the tree per ply, and the evaluated positions as a
-    digest instead of a list (1600-playout cases evaluate ~1600 positions per ply)."""
+    digest instead of a list (1600-playout cases evaluate ~1600 positions per ply).  extra(root) -> further per-ply fields."""
     log = []
     fwd = fakenet.make_forward(sp["mode"], sp["salt"], log)
     state, player, rr = sp["fen"], sp["player"], sp["rr"]
@@ -262,6 +264,8 @@ def run_spec(m, sp, deep=False):
                    root_N=int(t.root.N), evals=len(log))
         if deep:
             ply["max_level"] = max(d for (d, a, n, w, q, p, k) in tree if n > 0)   # deepest VISITED node, root children = level 0
+        if extra is not None:
+            ply.update(extra(t.root))
         plies.append(ply)
         nxt = m.GameBoard.sim_do_action(best, state)
         rr = rr + 1 if m.is_kill_move(state, nxt) == 0 else 0
@@ -340,6 +344,68 @@ def gen_mcts_deep(m, out):
     ]
     cases = [run_spec(m, sp, deep=True) for sp in specs]
     json.dump(dict(numpy=np.__version__, cases=cases), open(os.path.join(out, "mcts_deep.json"), "w"), separators=(",", ":"))
+
+
+def gen_mcts_wide(m, out):
+    """mcts_wide.json: searches from open boards (tests/conftest.py::open_boards) whose roots and inner nodes have 72-101
+    children — the ordered list's slots 64..127, which no playout from the start position reaches.  Both movers, four roots
+    with more than 96 moves; fakenet 'signed' (selects high-index children inside wide non-root nodes) and 'posabs' (value |v|:
+    the root, whose score is Q alone, walks through its whole list), 150 playouts — more than any root has children — and a
+    second ply on the kept subtree.  Same record shape as mcts_deep.json (digests instead of lists)."""
+    from conftest import open_boards
+    ob, os_ = open_boards(192, 41)
+    player = lambda i: "b" if os_[i] else "w"
+    moves = [m.GameBoard.get_legal_moves(board_to_fen(ob[i]), player(i)) for i in range(192)]
+    counts = [len(x) for x in moves]
+
+    def quiet_root(i):      # no move of the root takes a king: every child is searched
+        return all("K" in nxt and "k" in nxt for nxt in (m.GameBoard.sim_do_action(a, board_to_fen(ob[i])) for a in moves[i]))
+
+    def selected(root):
+        """Of the visited (N > 0) nodes: the highest index among the root's children, and among any other node's."""
+        def walk(n, is_root):
+            top_r, top_i = -1, -1
+            for j, c in enumerate(n.child.values()):
+                if c.N > 0:
+                    if is_root:
+                        top_r = max(top_r, j)
+                    else:
+                        top_i = max(top_i, j)
+                    r, i = walk(c, False)
+                    top_i = max(top_i, r, i)
+            return top_r, top_i
+        r, i = walk(root, True)
+        return dict(root_top_index=r, inner_top_index=i)
+    specs = []
+    for side in (0, 1):
+        mine = [i for i in range(192) if os_[i] == side and quiet_root(i)]
+        top = sorted([i for i in mine if counts[i] > 96], key=lambda i: (-counts[i], i))[:2]
+        mid = [i for i in mine if 64 < counts[i] <= 96][:2]
+        for j, i in enumerate(top + mid):
+            mode = ("posabs", "signed")[j % 2]
+            specs.append(dict(name="wide%d_%s_%s%d" % (counts[i], player(i), mode, i), fen=board_to_fen(ob[i]), player=player(i),
+                              rr=(0, 3, 57, 11)[j], playouts=[150, 60] if j < 2 else [150], mode=mode, salt=700 + i))
+    assert len(specs) == 8 and sum(int(sp["name"][4:].split("_")[0]) > 96 for sp in specs) >= 2
+    cases = [run_spec(m, sp, deep=True, extra=selected) for sp in specs]
+    for c, sp in zip(cases, specs):
+        c["moves"] = [m.label2i[a] for a in m.GameBoard.get_legal_moves(sp["fen"], sp["player"])]
+        print(c["name"], [(p["root_top_index"], p["inner_top_index"]) for p in c["plies"]])
+    json.dump(dict(numpy=np.__version__, cases=cases), open(os.path.join(out, "mcts_wide.json"), "w"), separators=(",", ":"))
+
+
+def board_to_fen(b):
+    b = np.asarray(b).reshape(10, 9)
+    rows = []
+    for y in range(10):
+        row, run = "", 0
+        for x in range(9):
+            if b[y, x] == 0:
+                run += 1
+            else:
+                row += (str(run) if run else "") + PIECES[b[y, x]]
+                run = 0
+        rows.append(row + (str(run) if run else ""))
+    return "/".join(rows)
 
 
 SELFPLAY_CASES = [
@@ -523,12 +589,15 @@ def main():
         return gen_policy_update(m, out)
     if "--deep-only" in sys.argv:
         return gen_mcts_deep(m, out)
+    if "--wide-only" in sys.argv:
+        return gen_mcts_wide(m, out)
     if "--selfplay-only" not in sys.argv:
         gen_tables(m, out)
         positions, king_roots = gen_rules(m, out)
         gen_mcts(m, out, positions, king_roots)
     gen_selfplay(m, out)
     gen_mcts_deep(m, out)
+    gen_mcts_wide(m, out)
     gen_policy_update(m, out)
 
 
