@@ -97,18 +97,26 @@ class Analyzer:
             out.append(rows)
         return out
 
-    def analyse(self, positions, n_lines=1, max_len=16, ban=None, notation="iccs"):
+    def analyse(self, positions, n_lines=1, max_len=16, ban=None, notation="iccs", mate_plies=0):
         """positions: FEN strings or (board uint8[90], side, restrict round) tuples, any number; ban: None or, per position, the
         moves no line may start with.  -> per position dict(bestmove, score, lines=[dict(pv=[move text ...], visits, q)], sims,
         flags): lines in rank order (more visits first), visits / q those of the line's first move, bestmove = lines[0].pv[0],
         score = its q; flags = the position's CZ_POS_* bits.  A mover without a king-safe move reports bestmove None with
         POS_NO_SAFE_MOVE in flags and is not searched; so does, without the flag, a position whose every candidate is banned.
         notation: "iccs" (the default: what UCCI tools read), "wxf" or "chinese" — every move of a line written in the position it
-        is played in (notation.line_text)."""
+        is played in (notation.line_text).
+        mate_plies = N > 0 (odd, 1 .. 15): before the search, Rules.mate looks for a continuous-check mate within N plies
+        ("checks" mode), and every position's dict gains mate = dict(plies=d, pv=[move text ...]) or mate = None; the search
+        and everything it reports are unchanged."""
         from .notation import line_text
         pos = [fen_to_position(p) if isinstance(p, str) else p for p in positions]
         if ban is not None and len(ban) != len(pos):
             raise ValueError("ban has one entry per position")
+        mates = None
+        if mate_plies:
+            from .mate import solve
+            mates = [dict(plies=m["plies"], pv=m["pv"]) if m["status"] == "mate" else None
+                     for m in solve(self.rule_kernels, pos, int(mate_plies), notation=notation)]
         out = []
         for at in range(0, len(pos), self.games):
             chunk = pos[at:at + self.games]
@@ -128,6 +136,9 @@ class Analyzer:
                         for r in lines[g]] if live[g] else []
                 out.append(dict(bestmove=rows[0]["pv"][0] if rows else None, score=rows[0]["q"] if rows else None, lines=rows,
                                 sims=int(sims[g]), flags=int(flags[g])))
+        if mates is not None:
+            for r, m in zip(out, mates):
+                r["mate"] = m
         return out
 
 

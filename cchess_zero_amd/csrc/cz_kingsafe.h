@@ -136,15 +136,24 @@ CZM_FN int czk_dest(int s, int q, int i) {
     return i < 8 ? 9 * y + (i < x ? i : i + 1) : 9 * (j < y ? j : j + 1) + x;
 }
 
+// Is sq on the rank or the file of the king on (ky, kx) or within two files and ranks of it?  A superset of the squares
+// czk_attacked reads for that king.
+CZM_FN bool czk_near(int sq, int ky, int kx) {
+    const int y = sq / 9, x = sq - y * 9, dy = y - ky, dx = x - kx;
+    return (dy == 0) | (dx == 0) | ((dy >= -2) & (dy <= 2) & (dx >= -2) & (dx <= 2));
+}
+// the set with its piece on q moved to dst
+CZM_FN CzmSet czk_moved(const CzmSet &s, int q, int dst) {
+    const CzmSet w = czm_without(s, q);
+    return CzmSet{w.lo | (dst < 64 ? 1ull << (dst & 63) : 0ull), w.hi | (dst >= 64 ? 1u << (dst & 31) : 0u)};
+}
+
 // The filter: clears the bits of the moves that are not king-safe in every slot; returns the number of moves left.
 // kq: the mover's king (-1: none, nothing is cleared); in_check = attacked(board, side).
 template <typename Scr>
 CZM_FN int czk_filter(const CzmSets &S, const CzkPieces &enemy, int side, const CzmTables &T, int kq, bool in_check, Scr scr) {
     const int ky = (kq >= 0 ? kq : 0) / 9, kx = (kq >= 0 ? kq : 0) - 9 * ky;
-    auto sensitive = [&](int sq) {   // on k's rank or file or within two files and ranks of it: a superset of the squares czk_attacked reads
-        const int y = sq / 9, x = sq - y * 9, dy = y - ky, dx = x - kx;
-        return (dy == 0) | (dx == 0) | ((dy >= -2) & (dy <= 2) & (dx >= -2) & (dx <= 2));
-    };
+    auto sensitive = [&](int sq) { return czk_near(sq, ky, kx); };
     int total = 0;
 #pragma unroll 1
     for (int s = 0; s < CZK_SLOTS; ++s) {
@@ -168,12 +177,59 @@ CZM_FN int czk_filter(const CzmSets &S, const CzkPieces &enemy, int side, const 
                 if (CZM_ANY(test)) {
                     if (test) {
                         const int k = king ? dst : kq;
-                        const CzmSet left_occ = czm_without(S.occ, q);
-                        const CzmSet occ2 = {left_occ.lo | (dst < 64 ? 1ull << (dst & 63) : 0ull), left_occ.hi | (dst >= 64 ? 1u << (dst & 31) : 0u)};
-                        bad = czk_attacked(occ2, czk_without(enemy, dst), 1 - side, k, T.knon[k]);
+                        bad = czk_attacked(czk_moved(S.occ, q, dst), czk_without(enemy, dst), 1 - side, k, T.knon[k]);
                     }
                 }
                 f &= ~((uint32_t)bad << i);
+            }
+            scr(s) = (f << 8) | (uint32_t)q;
+        }
+        total += __builtin_popcount(f);
+    }
+    return total;
+}
+
+// The checks: a second pass over the FILTERED slots that clears every move after which the other king is not attacked, so
+// that the slots hold the king-safe moves that give check; returns their number.  eq: the other king (-1: none, no move gives
+// check); can_take = attacked(board, 1 - side).  The test is the filter's, seen from the other king: czk_attacked for eq on
+// the occupancy and the MOVER's pieces after the move.  A move that takes that king gives no check (a side without a king is
+// not attacked) — the flying general of slot 16 is always one —, and a move whose source and destination lie off eq's rank,
+// file and 5 x 5 neighbourhood changes nothing czk_attacked reads: it keeps the position's own answer, can_take.
+template <typename Scr>
+CZM_FN int czk_checks(const CzmSets &S, const CzkPieces &mine, int side, const CzmTables &T, int eq, bool can_take, Scr scr) {
+    const int e = eq >= 0 ? eq : 0, ey = e / 9, ex = e - 9 * ey;
+    const uint32_t knon = T.knon[e];
+    int total = 0;
+#pragma unroll 1
+    for (int s = 0; s < CZK_SLOTS; ++s) {
+        const uint32_t v = scr(s);
+        const int q = czk_slot_sq(v);
+        uint32_t f = czk_slot_field(v);
+        const bool from = czk_near(q, ey, ex);
+        uint32_t left = f;
+        if (CZM_ANY(left != 0u)) {
+            while (CZM_ANY(left != 0u)) {   // every lane walks the set bits of its field, as in czk_filter
+                const bool b = left != 0u;
+                const int i = b ? czm_ctz32(left) : 0;
+                left &= left - 1u;
+                const int dst = b ? czk_dest(s, q, i) : 0;
+                const bool live = b && eq >= 0 && dst != eq;
+                const bool test = live && (from | czk_near(dst, ey, ex));
+                bool chk = live & !test & can_take;
+                if (CZM_ANY(test)) {
+                    if (test) {
+                        CzkPieces m = mine;   // the slot's kind is wave-uniform: one of the seven sets moves
+                        if (s < 2) m.R = czk_moved(mine.R, q, dst);
+                        else if (s < 4) m.C = czk_moved(mine.C, q, dst);
+                        else if (s < 6) m.N = czk_moved(mine.N, q, dst);
+                        else if (s == 6 || s == 16) m.K = czk_moved(mine.K, q, dst);
+                        else if (s < 12) m.P = czk_moved(mine.P, q, dst);
+                        else if (s < 14) m.A = czk_moved(mine.A, q, dst);
+                        else m.B = czk_moved(mine.B, q, dst);
+                        chk = czk_attacked(czk_moved(S.occ, q, dst), m, side, e, knon);
+                    }
+                }
+                f &= ~((uint32_t)(b & !chk) << i);
             }
             scr(s) = (f << 8) | (uint32_t)q;
         }
@@ -270,7 +326,9 @@ CZM_FN void czk_emit_list(const CzmSets &S, const CzmTables &T, int total, Scr s
 // called only with LIST / SET; mid() is called once, after the last emit and before the first put (a caller may build the set's
 // rows and the list's rows in the same memory, as k_movegen_kingsafe does).  *pos_flags: the CZK_* bits.  Returns the number of king-safe moves, or -1 for a board the
 // stand-alone generators refuse (czm_not_a_set, an advisor / bishop move without a label): its flags are 0.
-template <bool LIST, bool SET, typename Scr, typename Put, typename Emit, typename Mid>
+// CHECKS: the list, the set and the number returned are those of the king-safe moves that give check (czk_checks); the flags
+// stay the position's own — CZK_NO_SAFE_MOVE speaks of all king-safe moves.
+template <bool LIST, bool SET, bool CHECKS = false, typename Scr, typename Put, typename Emit, typename Mid>
 CZM_FN int czk_position(const uint32_t (&w)[23], int side, const CzmTables &T, Scr scr, Put put, Emit emit, Mid mid, uint32_t *pos_flags) {
     const CzmSets S = czm_sets(w, side);
     bool err = czm_not_a_set(S);
@@ -288,9 +346,10 @@ CZM_FN int czk_position(const uint32_t (&w)[23], int side, const CzmTables &T, S
         }
     }
     const int total = czk_filter(S, enemy, side, T, kq, in_check, scr);
+    const int listed = CHECKS ? czk_checks(S, mine, side, T, eq, can_take, scr) : total;
     if (SET) czk_emit_set(T, scr, emit);
     mid();
-    if (LIST) czk_emit_list(S, T, total, scr, put);
+    if (LIST) czk_emit_list(S, T, listed, scr, put);
     *pos_flags = err ? 0u : ((in_check ? CZK_IN_CHECK : 0u) | (can_take ? CZK_CAN_TAKE_KING : 0u) | (total == 0 ? CZK_NO_SAFE_MOVE : 0u));
-    return err ? -1 : total;
+    return err ? -1 : listed;
 }

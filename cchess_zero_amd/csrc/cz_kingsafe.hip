@@ -3,17 +3,19 @@
 // boards in LDS (the next group's prefetched), every lane takes its 90 bytes out as 23 dwords, and the results leave LDS as
 // rows — first the 64 mask rows (each lane ORs its own position's fields into its own row), then, in the same memory, the 64
 // list rows.  The 34 scratch words per position of czk_position (the piece slots) have their own 8.5 KB beside the rows.
+// cz_movegen_checks is the same wave with the second pass of czk_checks: the king-safe moves that give check.
 #include "cz_internal.h"
 #include "cz_kingsafe.h"
 #include "cz_posframe.h"
 
 namespace {
 
-template <bool LIST, bool SET>
-__global__ __launch_bounds__(64) void k_movegen_kingsafe(const CzmTables *__restrict__ gtab, const uint8_t *__restrict__ boards,
-                                                         const uint8_t *__restrict__ side, int G, uint16_t *__restrict__ moves,
-                                                         uint16_t *__restrict__ count, uint32_t *__restrict__ mask,
-                                                         uint8_t *__restrict__ pos_flags, int pad) {
+// The body of both kernels below.  CHECKS: czk_position keeps only the king-safe moves that give check (cz_movegen_checks).
+template <bool LIST, bool SET, bool CHECKS>
+__device__ __forceinline__ void movegen_kingsafe_wave(const CzmTables *__restrict__ gtab, const uint8_t *__restrict__ boards,
+                                                      const uint8_t *__restrict__ side, int G, uint16_t *__restrict__ moves,
+                                                      uint16_t *__restrict__ count, uint32_t *__restrict__ mask,
+                                                      uint8_t *__restrict__ pos_flags, int pad) {
     // the boards (1 440 words + the word lane 63's funnel shift reads behind them), then 64 mask rows, then 64 list rows (4 160
     // words); the flags-only form stages the boards alone: 15.5 instead of 26.6 KB of LDS per wave
     __shared__ __attribute__((aligned(16))) uint32_t rows[(LIST || SET) ? 64 * CZ_MASK_WORDS : CZF_BOARD_WORDS + 4];
@@ -40,7 +42,7 @@ __global__ __launch_bounds__(64) void k_movegen_kingsafe(const CzmTables *__rest
         uint32_t pf = 0u;
         uint32_t *const mrow = rows + lane * CZ_MASK_WORDS;
         uint16_t *const lrow = reinterpret_cast<uint16_t *>(rows + lane * CZF_LROW);
-        const int n = czk_position<LIST, SET>(w, sd, T,
+        const int n = czk_position<LIST, SET, CHECKS>(w, sd, T,
             [&](int i) -> uint32_t & { return slots[i * 64 + lane]; },
             [lrow](int k, int label) { lrow[k & 127] = (uint16_t)label; },                                             // k < 128: the slots hold at most 121 moves
             [mrow](int bit, uint32_t f) { czm_or_field([mrow](int wi, uint32_t x) { mrow[wi] |= x; }, bit, f); },     // the lane's own row: wi + 1 <= 65
@@ -66,7 +68,39 @@ __global__ __launch_bounds__(64) void k_movegen_kingsafe(const CzmTables *__rest
     }
 }
 
+template <bool LIST, bool SET>
+__global__ __launch_bounds__(64) void k_movegen_kingsafe(const CzmTables *__restrict__ gtab, const uint8_t *__restrict__ boards,
+                                                         const uint8_t *__restrict__ side, int G, uint16_t *__restrict__ moves,
+                                                         uint16_t *__restrict__ count, uint32_t *__restrict__ mask,
+                                                         uint8_t *__restrict__ pos_flags, int pad) {
+    movegen_kingsafe_wave<LIST, SET, false>(gtab, boards, side, G, moves, count, mask, pos_flags, pad);
+}
+
+// cz_movegen_checks: the same wave with czk_checks behind the filter; no set, so the rows hold the boards and then the list
+template <bool LIST>
+__global__ __launch_bounds__(64) void k_movegen_checks(const CzmTables *__restrict__ gtab, const uint8_t *__restrict__ boards,
+                                                       const uint8_t *__restrict__ side, int G, uint16_t *__restrict__ moves,
+                                                       uint16_t *__restrict__ count, uint8_t *__restrict__ pos_flags, int pad) {
+    movegen_kingsafe_wave<LIST, false, true>(gtab, boards, side, G, moves, count, nullptr, pos_flags, pad);
+}
+
 }  // namespace
+
+int cz_movegen_checks(cz_ctx *c, const uint8_t *boards, const uint8_t *side, int G, uint16_t *moves, uint16_t *count, uint8_t *pos_flags,
+                      int flags) {
+    CZ_REQUIRE(c && G >= 0, "cz_movegen_checks: null ctx / negative G");
+    CZ_REQUIRE((flags & ~CZ_MOVES_NO_PAD) == 0, "cz_movegen_checks: unknown flag");
+    if (G == 0) return CZ_OK;
+    CZ_REQUIRE(boards && side, "cz_movegen_checks: boards, side required");
+    CZ_REQUIRE(moves || count || pos_flags, "cz_movegen_checks: no output requested");
+    if (moves && (reinterpret_cast<uintptr_t>(moves) & 15u)) { cz_set_error("cz_movegen_checks: moves must be 16-byte aligned"); return CZ_EINVAL; }
+    const int pad = (flags & CZ_MOVES_NO_PAD) ? 0 : 1;
+    const dim3 grid(czf_persistent_grid((G + 63) / 64, moves ? 6 : 10));   // the LDS of k_movegen_kingsafe's list / flags-only forms
+    if (moves) hipLaunchKernelGGL((k_movegen_checks<true>), grid, dim3(64), 0, c->stream, c->mask_tab, boards, side, G, moves, count, pos_flags, pad);
+    else hipLaunchKernelGGL((k_movegen_checks<false>), grid, dim3(64), 0, c->stream, c->mask_tab, boards, side, G, moves, count, pos_flags, pad);
+    CZ_HIP(hipGetLastError());
+    return CZ_OK;
+}
 
 int cz_movegen_kingsafe(cz_ctx *c, const uint8_t *boards, const uint8_t *side, int G, uint16_t *moves, uint16_t *count, uint32_t *mask,
                         uint8_t *pos_flags, int flags) {

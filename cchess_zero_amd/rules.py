@@ -2,8 +2,8 @@
 import numpy as np
 import torch
 
-from ._lib import (BF16, F16, F32, MASK_WORDS, MAXMOVES, NLABELS, NSQ, POS_IN_CHECK, POS_NO_SAFE_MOVE, CchessHipError, call, out_pointers,
-                   tables)
+from ._lib import (BF16, F16, F32, MASK_WORDS, MATE_NONE, MAXMOVES, NLABELS, NSQ, POS_CAN_TAKE_KING, POS_IN_CHECK, POS_NO_SAFE_MOVE,
+                   CchessHipError, call, out_pointers, tables)
 from .engine import Context
 
 
@@ -120,6 +120,20 @@ class Rules:
         self.ctx.call("cz_movegen_kingsafe", boards, side, G, moves, count, mask, pos_flags, 0 if pad else 1)
         return moves, count, mask, pos_flags
 
+    def checks(self, boards, side, want_moves=True, pad=True):
+        """The king-safe moves of G positions that GIVE CHECK (cz_movegen_checks: movegen_kingsafe's list, in its order, without
+        the moves after which the other side is not attacked) -> (moves [G,128] i16(u16 bits) or None, count [G] i16, pos_flags
+        [G] u8).  pos_flags are the position's own, as movegen_kingsafe returns them: POS_NO_SAFE_MOVE speaks of all king-safe
+        moves.  pad=False: CZ_MOVES_NO_PAD.  A board movegen refuses answers count -1 (0xFFFF) and flags 0."""
+        boards = self._dev(boards, torch.uint8).reshape(-1, NSQ)
+        side = self._dev(side, torch.uint8)
+        G = boards.shape[0]
+        moves = torch.empty((G, MAXMOVES), dtype=torch.int16, device=self.dev) if want_moves else None
+        count = torch.empty(G, dtype=torch.int16, device=self.dev)
+        pos_flags = torch.empty(G, dtype=torch.uint8, device=self.dev)
+        self.ctx.call("cz_movegen_checks", boards, side, G, moves, count, pos_flags, 0 if pad else 1)
+        return moves, count, pos_flags
+
     def in_check(self, boards, side):
         """-> pos_flags [G] u8 alone (bit 0: the side to move is in check, bit 1: it can take the king, bit 2: it has no
         king-safe move): the launch that builds neither list nor set."""
@@ -196,21 +210,26 @@ class Rules:
         self.ctx.call("cz_apply_move", boards, side, labels, G, hash_, cap, term)
         return cap, term
 
-    def successors(self, boards, side, moves, count):
-        """Every successor of G positions (cz_successors): moves [G,128] i16 and count [G] i16 as movegen / movegen_kingsafe
-        return them (padded or not; count -1, a refused board, has no children) -> (boards [T,90] u8, side [T] u8, captured
-        [T] u8, parent [T] i32, label [T] i16), T the sum of the counts: child offsets[g] + j is parent g after moves[g][j], in
-        list order.  Reading T back is the call's only synchronisation."""
-        boards = self._dev(boards, torch.uint8).reshape(-1, NSQ)
-        side = self._dev(side, torch.uint8)
-        G = boards.shape[0]
-        moves = self._dev(moves, torch.int16).reshape(G, MAXMOVES)
+    def _child_offsets(self, count, G):
+        """-> (offsets int32 [G + 1]: the exclusive prefix sum of the counts, a refused board's -1 as 0; their total)"""
         offsets = torch.zeros(G + 1, dtype=torch.int64, device=self.dev)
         torch.cumsum(self._dev(count, torch.int16).reshape(G).clamp(min=0), 0, out=offsets[1:])
         T = int(offsets[-1].item())
         if T >= 2 ** 31:
             raise ValueError("Rules.successors: %d children do not fit one call (offsets are int32): pass fewer parents" % T)
-        offsets = offsets.to(torch.int32)
+        return offsets.to(torch.int32), T
+
+    def successors(self, boards, side, moves, count, offsets=None):
+        """Every successor of G positions (cz_successors): moves [G,128] i16 and count [G] i16 as movegen / movegen_kingsafe
+        return them (padded or not; count -1, a refused board, has no children) -> (boards [T,90] u8, side [T] u8, captured
+        [T] u8, parent [T] i32, label [T] i16), T the sum of the counts: child offsets[g] + j is parent g after moves[g][j], in
+        list order.  Reading T back is the call's only synchronisation.  offsets: the int32 [G + 1] prefix sum of the counts, for a
+        caller that has it already (mate)."""
+        boards = self._dev(boards, torch.uint8).reshape(-1, NSQ)
+        side = self._dev(side, torch.uint8)
+        G = boards.shape[0]
+        moves = self._dev(moves, torch.int16).reshape(G, MAXMOVES)
+        offsets, T = self._child_offsets(count, G) if offsets is None else (offsets, int(offsets[-1].item()))
         out = torch.empty((T, NSQ), dtype=torch.uint8, device=self.dev)
         cside = torch.empty(T, dtype=torch.uint8, device=self.dev)
         cap = torch.empty(T, dtype=torch.uint8, device=self.dev)
@@ -285,6 +304,99 @@ class Rules:
         elif N:
             walk(boards, side, root, 0)
         return {k: v.cpu().numpy() for k, v in tally.items()}
+
+    def mate_backup(self, offsets, child_dist, child_label, child_pv=None, mode=0):
+        """The AND/OR step of the mate search over child ranges (cz_mate_backup): offsets int32 [G + 1] as successors lays the
+        children out, child_dist i16 [T] (plies until the defender is mated, MATE_NONE = not proven), child_label i16 [T],
+        child_pv i16 [T, W] or None (W = 0) -> (dist i16 [G], pv i16(u16 bits) [G, W + 1]).  mode 0, the attacker to move: 1 + the
+        minimum over the proven children, MATE_NONE without one; mode 1, the defender: 0 without children, MATE_NONE when a
+        child is not proven, else 1 + the maximum.  pv: the label of the FIRST child that attains the value, then its line;
+        all -1 (0xFFFF) when dist is 0 or MATE_NONE."""
+        offsets = self._dev(offsets, torch.int32).reshape(-1)
+        G = offsets.shape[0] - 1
+        child_dist = self._dev(child_dist, torch.int16).reshape(-1)
+        T = child_dist.shape[0]
+        child_label = self._dev(child_label, torch.int16).reshape(T)
+        W = 0 if child_pv is None else int(child_pv.shape[-1])
+        child_pv = self._dev(child_pv, torch.int16).reshape(T, W) if W else None
+        dist = torch.empty(G, dtype=torch.int16, device=self.dev)
+        pv = torch.empty((G, W + 1), dtype=torch.int16, device=self.dev)
+        self.ctx.call("cz_mate_backup", offsets, G, T, child_dist if T else None, child_label if T else None, child_pv if T else None, W, int(mode), dist, pv)
+        return dist, pv
+
+    MATE_MAX_PLIES = 15
+
+    def mate(self, boards, side, plies, attacker="checks", chunk=None, node_limit=None):
+        """Forced mate within `plies` (odd, 1 .. 15) for the side to move of N root positions -> a dict of numpy arrays:
+        `status` u8 (0 no mate within plies, 1 mate, 2 bad root — movegen refuses it, a king is missing or the mover can already
+        take the king —, 3 node_limit reached before the root was decided), `dist` i16 (plies until the defender is mated,
+        MATE_NONE without a proven mate), `pv` u16 [N, plies] (the line, 0xFFFF behind it) and `nodes` i64 (positions made
+        for the root).
+        attacker="checks": the attacker plays king-safe moves that give check only (checks()) — the continuous-check mate of
+        Xiangqi puzzles; "all": every king-safe move.  The defender always has every king-safe move; a defender without one is
+        mated (dist 0, stalemate loses too), one at the horizon is not proven.  The attacker takes the FIRST move in list order
+        with the shortest mate, the defender the FIRST with the longest.  Repetition and perpetual-check rules are NOT applied
+        inside the proof: a forced mate within `plies` is a mate.
+        ONE PASS at `plies`, no iterative deepening: a distance within the horizon is the exact shortest mate whatever the
+        horizon (by induction over the plies left: a node's value is its true distance when that fits, MATE_NONE otherwise),
+        so deepening over 1, 3, 5, ... would answer the same, line included.
+        The tree is walked depth first in slices of at most `chunk` parents like perft (default PERFT_CHUNK); every slice hands
+        (dist, pv) of its nodes back through mate_backup, so the tree is never held whole.  At the attacker's last ply the
+        children are only asked for their flags: no lists, no grandchildren.  node_limit: once that many positions have been
+        made over the call, no further slice is expanded and every root with an unexpanded node below it answers status 3
+        (None: no limit); a root decided before that keeps its answer."""
+        boards = self._dev(boards, torch.uint8).reshape(-1, NSQ)
+        side = self._dev(side, torch.uint8).reshape(-1)
+        N, plies, chunk = boards.shape[0], int(plies), int(chunk or self.PERFT_CHUNK)
+        if plies < 1 or plies > self.MATE_MAX_PLIES or plies % 2 == 0 or chunk < 1:
+            raise ValueError("Rules.mate: plies is odd, 1 .. %d, and chunk >= 1" % self.MATE_MAX_PLIES)
+        if attacker not in ("checks", "all"):
+            raise ValueError("Rules.mate: attacker is 'checks' or 'all', not %r" % (attacker,))
+        nodes = torch.zeros(N, dtype=torch.int64, device=self.dev)
+        cut = torch.zeros(N, dtype=torch.bool, device=self.dev)
+        made = [0]
+
+        def walk(b, s, root, p, attack):   # the nodes of one level, p plies left -> (dist i16 [n], pv i16 [n, p])
+            n = b.shape[0]
+            dist = torch.full((n,), MATE_NONE, dtype=torch.int16, device=self.dev)
+            pv = torch.full((n, p), -1, dtype=torch.int16, device=self.dev)
+            for lo in range(0, n, chunk):
+                bb, ss, rr = b[lo:lo + chunk], s[lo:lo + chunk], root[lo:lo + chunk]
+                if node_limit is not None and made[0] >= node_limit:
+                    cut[rr] = True
+                    continue
+                if attack and attacker == "checks":
+                    mv, cnt, _ = self.checks(bb, ss, pad=False)
+                else:
+                    mv, cnt, _, _ = self.movegen_kingsafe(bb, ss, want_mask=False, pad=False)
+                offsets, T = self._child_offsets(cnt, bb.shape[0])
+                cb, cs, _, par, label = self.successors(bb, ss, mv, cnt, offsets)
+                del mv
+                cr = rr[par.to(torch.int64)]
+                del par
+                made[0] += T
+                nodes.index_add_(0, cr, torch.ones_like(cr))
+                if p == 1:     # the attacker's last ply: a child is mated or it is not proven
+                    mated = self.in_check(cb, cs) & POS_NO_SAFE_MOVE != 0
+                    cd, cpv = torch.where(mated, 0, MATE_NONE).to(torch.int16), None
+                else:
+                    cd, cpv = walk(cb, cs, cr, p - 1, not attack)
+                del cb, cs
+                dist[lo:lo + chunk], pv[lo:lo + chunk] = self.mate_backup(offsets, cd, label, cpv, 0 if attack else 1)
+            return dist, pv
+
+        _, cnt, _, pf = self.movegen_kingsafe(boards, side, want_mask=False, want_moves=False)
+        bad = (cnt < 0) | (pf & POS_CAN_TAKE_KING != 0) | ~(boards == 1).any(1) | ~(boards == 8).any(1)
+        good = (~bad).nonzero().flatten()
+        dist = torch.full((N,), MATE_NONE, dtype=torch.int16, device=self.dev)
+        pv = torch.full((N, plies), -1, dtype=torch.int16, device=self.dev)
+        if good.numel():
+            dist[good], pv[good] = walk(boards[good], side[good], good, plies, True)
+        status = torch.where(bad, 2, torch.where(cut, 3, torch.where(dist != MATE_NONE, 1, 0))).to(torch.uint8)
+        proven = status == 1
+        dist = torch.where(proven, dist, torch.full_like(dist, MATE_NONE))
+        pv = torch.where(proven.unsqueeze(1), pv, torch.full_like(pv, -1))
+        return dict(status=status.cpu().numpy(), dist=dist.cpu().numpy(), pv=pv.cpu().numpy().view(np.uint16), nodes=nodes.cpu().numpy())
 
     def divide(self, board, side, depth):
         """Perft of ONE position split by its first move -> {ICCS label: the move sequences of length `depth` that start with

@@ -2,12 +2,17 @@
 
     python -m cchess_zero_amd.ucci --model M.pt --blocks 7 [--playout 400] [--search_threads 16]
 
-Commands: ucci, isready, setoption <name> <value> (Playouts, MultiPV, Notation), position {startpos | fen <fen>} [moves m1 m2 ...],
+Commands: ucci, isready, setoption <name> <value> (Playouts, MultiPV, Notation, MateSearch), position {startpos | fen <fen>} [moves m1 m2 ...],
 banmoves m1 ..., go [nodes N | time T | depth D], stop, quit.  Moves are ICCS coordinates ("h2e2": files a-i, ranks 0-9 with
 red at rank 0), positions standard Xiangqi FEN (notation.fen_to_position).  After each go: one `info depth <len> [multipv k]
 score <round(1000 q)> nodes <sims> time <ms> pv m1 m2 ...` per line, then `bestmove m1 [ponder m2]`, or `nobestmove` when the
 mover has no king-safe move that is not banned.  Unknown commands are ignored.  `setoption Notation wxf` (or chinese; default
 iccs, which is what GUIs read) writes the pv of the info lines in that notation; bestmove and ponder stay ICCS.
+
+`setoption MateSearch N` (N odd, 1 .. 15; default 0 = off, and nothing changes): every go first asks the searcher for a
+continuous-check mate within N plies (Rules.mate, "checks" mode).  If there is one and its first move is not banned, the engine
+prints `info depth <d> score <30000 - d> nodes <nodes> time <ms> pv ...` (d = the plies to the mate) and `bestmove` without
+searching; otherwise it searches as without the option.  (The `ucci` banner lists Playouts and MultiPV as before.)
 
 The search is the one analysis.py describes: the reference's king-capture search with the Xiangqi rules applied at the root.
 Out of scope: the engine does not judge repetition itself (GUIs send banmoves), it does not ponder (`ponder m2` is only the
@@ -19,6 +24,7 @@ UcciEngine(searcher, inp, out) is the protocol loop; `searcher` is what it needs
     search(playouts) -> simulations completed by the call (the tree of the position is kept between calls)
     lines(allowed uint32 [66], n_lines, max_len) -> [dict(pv=[labels], visits=[...], q=[...])] in rank order
     width (optional attribute): simulations in flight per lock-step
+    mate(plies) -> (dist, [labels], nodes) or None: a continuous-check mate of the position (only called with MateSearch > 0)
 AnalyzerSearcher provides it on one device tree; the tests fake it on the C oracle.
 """
 import argparse
@@ -34,6 +40,8 @@ from .notation import NOTATIONS, START_FEN, fen_to_position, line_text
 
 CHUNK_STEPS = 32     # lock-steps between two looks at the clock / the input
 MAX_MULTIPV = 8
+MAX_MATE_PLIES = 15
+MATE_SCORE = 30000   # a mate in d plies scores MATE_SCORE - d
 PV_LEN = 16
 
 
@@ -41,6 +49,7 @@ class UcciEngine:
     def __init__(self, searcher, inp, out, playouts=400, clock=time.monotonic):
         self.searcher, self.inp, self.out, self.clock = searcher, inp, out, clock
         self.options = dict(playouts=int(playouts), multipv=1)
+        self.mate_plies = 0         # setoption MateSearch: the horizon of the mate solver in front of every go, 0 = off
         self.pv_notation = "iccs"   # setoption Notation: how the info lines write their pv
         t = _lib.tables()
         self.labels, self.label2i, self.srcdst = t["labels"], t["label2i"], t["srcdst"]
@@ -132,6 +141,10 @@ class UcciEngine:
             self.options["playouts"] = max(1, value)
         elif name == "multipv":
             self.options["multipv"] = min(max(1, value), MAX_MULTIPV)
+        elif name == "matesearch":
+            if value != 0 and (value < 1 or value > MAX_MATE_PLIES or value % 2 == 0):
+                return self.say("info string setoption MateSearch: %d is not 0 (off) or an odd number of plies up to %d" % (value, MAX_MATE_PLIES))
+            self.mate_plies = value
 
     def _legal(self, pos, text):
         """Is `text` a king-safe move of pos?  (The searcher is left on pos.)"""
@@ -198,6 +211,14 @@ class UcciEngine:
             allowed[label >> 5] &= ~(np.uint32(1) << np.uint32(label & 31))
         if not allowed.any():
             return self.say("nobestmove")
+        if self.mate_plies:
+            found = s.mate(self.mate_plies)
+            if found is not None and found[1] and found[1][0] not in self.ban:
+                dist, pv, nodes = found
+                ms = int(round((self.clock() - start) * 1000.0))
+                self.say("info depth %d score %d nodes %d time %d pv %s" % (dist, MATE_SCORE - dist, nodes, ms,
+                                                                           " ".join(line_text(self.pos[0], self.pos[1], pv, self.pv_notation))))
+                return self.say("bestmove %s%s" % (self.labels[pv[0]], " ponder %s" % self.labels[pv[1]] if len(pv) > 1 else ""))
         chunk = CHUNK_STEPS * max(1, int(getattr(s, "width", 1)))
         budget = amount if mode in ("playouts", "nodes") else self.options["playouts"] if mode == "depth" else None
         sims = 0
@@ -243,6 +264,12 @@ class AnalyzerSearcher:
     def kingsafe_mask(self):
         allowed, flags = self.a.root_masks(self.pos[0], self.pos[1])
         return allowed.cpu().numpy().view(np.uint32)[0], int(flags[0])
+
+    def mate(self, plies):
+        r = self.a.rule_kernels.mate(self.pos[0], self.pos[1], plies)
+        if int(r["status"][0]) != 1:
+            return None
+        return int(r["dist"][0]), [int(l) for l in r["pv"][0] if int(l) != 0xFFFF], int(r["nodes"][0])
 
     def _sims(self):
         return int(self.a.engine.status()[2].cpu().numpy()[0])

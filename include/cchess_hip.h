@@ -153,6 +153,15 @@ int cz_movegen_ex(cz_ctx *, const uint8_t *boards, const uint8_t *side, int G, u
 #define CZ_POS_NO_SAFE_MOVE 4    /* no king-safe move: checkmate or stalemate, both lost in Xiangqi */
 int cz_movegen_kingsafe(cz_ctx *, const uint8_t *boards, const uint8_t *side, int G, uint16_t *moves, uint16_t *count,
                         uint32_t *mask, uint8_t *pos_flags, int flags);
+/* K1c CHECKING MOVES: the king-safe moves of cz_movegen_kingsafe that GIVE CHECK — after the move the other side is attacked
+ *     (the definition above) — in the same order, the other moves taken out.  What a continuous-check mate search expands an
+ *     attacker's position by, without making the ~40 children and asking each whether it is in check.
+ *     moves [G][128], count [G]: that list (0xFFFF padding; CZ_MOVES_NO_PAD as in cz_movegen_ex) and its length; pos_flags [G]:
+ *     the POSITION's CZ_POS_* exactly as cz_movegen_kingsafe writes them — CZ_POS_NO_SAFE_MOVE speaks of all king-safe moves,
+ *     not of the checks.  A move that takes the other king gives no check (a side without a king is not attacked).  Any of
+ *     the three may be NULL, not all; `moves` 16-byte aligned; a refused board answers count 0xFFFF and flags 0. */
+int cz_movegen_checks(cz_ctx *, const uint8_t *boards, const uint8_t *side, int G, uint16_t *moves, uint16_t *count,
+                      uint8_t *pos_flags, int flags);
 /* K1r REPETITION AND PERPETUAL CHECK on G game records that the caller keeps.  No reference function: the reference's games
  *     have no repetition rule.  A game's history is the sequence of its positions: position i is the position after i plies
  *     (position 0 is the opening), with key[i] = its cz_hash (board and side to move; equal keys are taken as equal positions)
@@ -234,6 +243,23 @@ int cz_hash(cz_ctx *, const uint8_t *boards, const uint8_t *side, int G, uint64_
 int cz_successors(cz_ctx *, const uint8_t *boards, const uint8_t *side, int G, const uint16_t *moves /* [G][128] */,
                   const int32_t *offsets /* [G + 1] */, int total, uint8_t *out_boards /* [total][90] */, uint8_t *out_side,
                   uint8_t *out_captured, int32_t *out_parent, uint16_t *out_label);
+/* K2m MATE BACKUP: the AND/OR step of a forced-mate search over the child ranges cz_successors lays out.  dist is the number
+ *     of plies until the defender is mated, CZ_MATE_NONE = not proven.  Parent g has the children offsets[g] .. offsets[g + 1]
+ *     - 1 (0 .. 128 of them), child c the distance child_dist[c], the move child_label[c] that leads to it and, for W > 0, its
+ *     own line child_pv[c][0 .. W) (0xFFFF behind its end).
+ *       mode 0, the attacker to move (OR):  out_dist[g] = 1 + the minimum over the proven children; CZ_MATE_NONE when none is
+ *               proven or there is no child;
+ *       mode 1, the defender to move (AND): 0 without children (no king-safe move: mated, and stalemate loses too);
+ *               CZ_MATE_NONE when any child is not proven; else 1 + the maximum.
+ *     The best child is the FIRST in list order that attains the minimum / maximum.  out_pv[g][0 .. W]: its label, then its
+ *     child_pv row; all 0xFFFF when out_dist[g] is 0 or CZ_MATE_NONE.  A child_dist outside 0 .. CZ_MATE_NONE - 1 counts as not
+ *     proven.  Offsets outside [0, total] are clamped as in cz_successors: no access leaves the arrays whatever they hold.
+ *     0 <= W <= CZ_MATE_MAX_LINE; total == 0 is served (every parent is childless), G == 0 is CZ_OK without a launch. */
+#define CZ_MATE_NONE 0x7FFF
+#define CZ_MATE_MAX_LINE 255
+int cz_mate_backup(cz_ctx *, const int32_t *offsets /* [G + 1] */, int G, int total, const int16_t *child_dist /* [total] */,
+                   const uint16_t *child_label /* [total] */, const uint16_t *child_pv /* [total][W], NULL when W == 0 */, int W,
+                   int mode, int16_t *out_dist /* [G] */, uint16_t *out_pv /* [G][W + 1] */);
 /* K3  replaces MCTS_tree.generate_inputs = try_flip + state_to_positions, main.py:531-574.
  *     planes [G][9][10][channels] of dtype CZ_F32 / CZ_BF16.  quirk_q1 = 1 reproduces the
  *     reference bit for bit; 0 gives the transposed encoding its shapes suggest. */

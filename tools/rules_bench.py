@@ -14,7 +14,12 @@ usage: python tools/rules_bench.py [N positions, default 1048576]
            level against the same answer from the ply-by-ply path that made them (one move-list launch and one cz_apply_move launch
            per ply, games.ply_by_ply_replay), both timed in the same run, alternating; one JSON line at the end.  Then the
            notation leg (--replay-notation [G]: that leg alone): the same games as labels through cz_games_replay and as WXF
-           tokens through cz_games_read, alternating, and a host decode in Python on a 256-game sample, scaled; one JSON line"""
+           tokens through cz_games_read, alternating, and a host decode in Python on a 256-game sample, scaled; one JSON line
+       python tools/rules_bench.py --checks [N]       the checking-move generator (cz_movegen_checks) on N positions of
+           rules.random_positions against the composition it replaces (cz_movegen_kingsafe list -> cz_successors -> the flags-only
+           form on every child -> boolean compaction in torch), both in the same run; one JSON line at the end
+       python tools/rules_bench.py --mate [N]         Rules.mate ("checks" mode) at plies 5 and 9 on N (default 65 536) positions
+           of rules.random_positions: roots/s and nodes/s; one JSON line at the end"""
 import os
 import sys
 import time
@@ -32,8 +37,10 @@ THREATS = "--threats" in sys.argv
 SUCCESSORS = "--successors" in sys.argv
 REPLAY = "--replay" in sys.argv
 REPLAY_NOTATION = "--replay-notation" in sys.argv
-_args = [a for a in sys.argv[1:] if a not in ("--kingsafe", "--threats", "--successors", "--replay", "--replay-notation")]
-N = int(_args[0]) if _args else (8192 if REPLAY or REPLAY_NOTATION else 1 << 20)
+CHECKS = "--checks" in sys.argv
+MATE = "--mate" in sys.argv
+_args = [a for a in sys.argv[1:] if a not in ("--kingsafe", "--threats", "--successors", "--replay", "--replay-notation", "--checks", "--mate")]
+N = int(_args[0]) if _args else (8192 if REPLAY or REPLAY_NOTATION else 1 << 16 if MATE else 1 << 20)
 ctx = Context(1, 2, 0)
 rules = Rules(ctx)
 
@@ -148,6 +155,92 @@ def threats_leg():
         print("%-24s: median %.3f ms (min %.3f, max %.3f) = %.3f G positions/s" % (name, ts[12], ts[0], ts[-1], N / ts[12] / 1e6))
     rec = rules.threats(boards, side)
     out["positions_with_a_threat"] = int(((rec[:, 0] | rec[:, 1]) != 0).sum().item())
+    print(json.dumps(out), flush=True)
+
+
+def checks_leg():
+    """cz_movegen_checks (list, CZ_MOVES_NO_PAD; and the count / flags form) on all N positions: median of 25 launches (device
+    events, 3 warm-up launches).  The composition it replaces is a chain of launches that holds ~40 child boards per position,
+    so it runs on the first 131 072 positions, host clock around a synchronise, median of 5 — and so does cz_movegen_checks
+    once more, timed the same way on the same positions, which is the pair the ratio is taken from.  Before anything is
+    timed the two answers (list and count) are asserted equal."""
+    import json
+    from cchess_zero_amd._lib import POS_IN_CHECK
+    from cchess_zero_amd.rules import random_positions
+    boards, side, _ = random_positions(rules, N, seed=17)
+    M = min(N, 131072)
+    b, s = boards[:M].contiguous(), side[:M].contiguous()
+
+    def composed():
+        mv, cnt, _, _ = rules.movegen_kingsafe(b, s, want_mask=False, pad=False)
+        cb, cs, _, par, label = rules.successors(b, s, mv, cnt)
+        keep = rules.in_check(cb, cs) & POS_IN_CHECK != 0
+        par, label = par[keep].to(torch.int64), label[keep]
+        count = torch.zeros(M, dtype=torch.int64, device=b.device).index_add_(0, par, torch.ones_like(par))
+        first = torch.cumsum(count, 0) - count
+        rows = torch.full((M, 128), -1, dtype=torch.int16, device=b.device)
+        rows[par, torch.arange(par.numel(), device=b.device) - first[par]] = label
+        return rows, count, cb.shape[0]
+
+    rows, count, children = composed()
+    mv, cnt, _ = rules.checks(b, s)
+    assert torch.equal(cnt.to(torch.int64), count) and torch.equal(mv, rows), "the composed answer and cz_movegen_checks disagree"
+    out = {"positions": N, "checks_per_position": round(float(count.sum().item()) / M, 3), "positions_with_a_check": round(float((count > 0).sum().item()) / M, 4)}
+    forms = {"checks_list": lambda: rules.checks(boards, side, pad=False), "checks_count_only": lambda: rules.checks(boards, side, want_moves=False),
+             "kingsafe_list": lambda: rules.movegen_kingsafe(boards, side, want_mask=False, pad=False)}
+    for name, fn in forms.items():
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize()
+        ts = []
+        for _ in range(25):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            ts.append(e0.elapsed_time(e1))
+        ts.sort()
+        out[name] = dict(ms=round(ts[12], 4), min_ms=round(ts[0], 4), max_ms=round(ts[-1], 4), positions_per_s=round(N / ts[12] * 1e3))
+        print("%-18s: median %.3f ms (min %.3f, max %.3f) = %.3f G positions/s" % (name, ts[12], ts[0], ts[-1], N / ts[12] / 1e6))
+    for name, fn in (("composed", composed), ("checks_list_same_positions", lambda: rules.checks(b, s, pad=False))):
+        fn()
+        ts = []
+        for _ in range(5):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        ts.sort()
+        out[name] = dict(positions=M, ms=round(ts[2], 3), min_ms=round(ts[0], 3), max_ms=round(ts[-1], 3), positions_per_s=round(M / ts[2] * 1e3))
+        print("%-28s: median %.3f ms (min %.3f, max %.3f) for %d positions = %.4f G positions/s" % (name, ts[2], ts[0], ts[-1], M, M / ts[2] / 1e6))
+    out["composed"]["child_positions"] = children
+    out["checks_vs_composed"] = round(out["composed"]["ms"] / out["checks_list_same_positions"]["ms"], 2)
+    print(json.dumps(out), flush=True)
+
+
+def mate_leg():
+    """Rules.mate in "checks" mode on N positions of random_positions at plies 5 and 9: host clock around the call (it ends by
+    copying its answers to the host), one warm-up call at plies 1, then the median of 3 calls per horizon."""
+    import json
+    from cchess_zero_amd.rules import random_positions
+    boards, side, _ = random_positions(rules, N, seed=17)
+    rules.mate(boards, side, 1)
+    out = {"positions": N}
+    for plies in (5, 9):
+        ts = []
+        for _ in range(3):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            res = rules.mate(boards, side, plies)
+            ts.append(time.perf_counter() - t0)
+        ts.sort()
+        nodes = int(res["nodes"].sum())
+        out["plies_%d" % plies] = dict(s=round(ts[1], 4), min_s=round(ts[0], 4), max_s=round(ts[-1], 4), mates=int((res["status"] == 1).sum()),
+                                       bad_roots=int((res["status"] == 2).sum()), nodes=nodes, roots_per_s=round(N / ts[1]), nodes_per_s=round(nodes / ts[1]))
+        print("mate plies %d: median %.3f s (min %.3f, max %.3f) for %d roots, %d mates, %d nodes = %.1f k roots/s, %.2f M nodes/s"
+              % (plies, ts[1], ts[0], ts[-1], N, out["plies_%d" % plies]["mates"], nodes, N / ts[1] / 1e3, nodes / ts[1] / 1e6))
     print(json.dumps(out), flush=True)
 
 
@@ -381,6 +474,12 @@ if REPLAY or REPLAY_NOTATION:
     if REPLAY:
         replay_leg()
     notation_leg()
+    sys.exit(0)
+if CHECKS or MATE:
+    if CHECKS:
+        checks_leg()
+    if MATE:
+        mate_leg()
     sys.exit(0)
 if SUCCESSORS:
     successors_leg()
