@@ -33,6 +33,7 @@ CAUSE_NONE, CAUSE_CHECK, CAUSE_CHASE = 0, 1, 2
 # position flags of cz_movegen_kingsafe (include/cchess_hip.h: CZ_POS_*)
 POS_IN_CHECK, POS_CAN_TAKE_KING, POS_NO_SAFE_MOVE = 1, 2, 4
 MATE_NONE = 0x7FFF   # cz_mate_backup (include/cchess_hip.h: CZ_MATE_NONE): no mate proven
+TB_ILLEGAL, TB_UNKNOWN, TB_MISS, TB_MAX_SLOTS = -32768, 32767, 32766, 10   # tablebase values (include/cchess_hip.h: CZ_TB_*)
 
 # cz_games_replay (include/cchess_hip.h: CZ_GAME_*): why a game's replay stopped, and the end_flags bits beside POS_*
 GAME_OK, GAME_ILLEGAL, GAME_AFTER_END, GAME_BAD_BOARD, GAME_BAD_LEN, GAME_AMBIGUOUS = 0, 1, 2, 3, 4, 5   # 5: cz_games_read only
@@ -61,6 +62,10 @@ _SIGS = {
     "cz_movegen_kingsafe": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_int, _u16p, _u16p, _vp, _u8p, C.c_int]),
     "cz_movegen_checks": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_int, _u16p, _u16p, _u8p, C.c_int]),
     "cz_mate_backup": (C.c_int, [C.c_void_p, _i32p, C.c_int, C.c_int, _vp, _u16p, _u16p, C.c_int, C.c_int, _vp, _u16p]),
+    "cz_tb_entries": (C.c_int, [C.c_char_p, C.POINTER(C.c_longlong), C.POINTER(C.c_int)]),
+    "cz_tb_pass": (C.c_int, [C.c_void_p, C.c_char_p, _vp, C.POINTER(C.c_void_p), C.c_int, _vp]),
+    "cz_tb_probe": (C.c_int, [C.c_void_p, C.c_char_p, _vp, _u8p, _u8p, C.c_int, _vp, _i32p]),
+    "cz_tb_boards": (C.c_int, [C.c_void_p, C.c_char_p, _i32p, C.c_int, _u8p, _u8p]),
     "cz_repetition": (C.c_int, [C.c_void_p, _vp, _u8p, C.c_int, _i32p, _i32p, _u8p, C.c_int, C.c_int, _u8p, _i32p]),
     "cz_threats": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_int, _vp]),
     "cz_repetition_chase": (C.c_int, [C.c_void_p, _vp, _u8p, _vp, C.c_int, _i32p, _i32p, _u8p, C.c_int, C.c_int, _u8p, _i32p, _u8p]),

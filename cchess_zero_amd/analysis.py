@@ -97,7 +97,7 @@ class Analyzer:
             out.append(rows)
         return out
 
-    def analyse(self, positions, n_lines=1, max_len=16, ban=None, notation="iccs", mate_plies=0):
+    def analyse(self, positions, n_lines=1, max_len=16, ban=None, notation="iccs", mate_plies=0, tablebase=None):
         """positions: FEN strings or (board uint8[90], side, restrict round) tuples, any number; ban: None or, per position, the
         moves no line may start with.  -> per position dict(bestmove, score, lines=[dict(pv=[move text ...], visits, q)], sims,
         flags): lines in rank order (more visits first), visits / q those of the line's first move, bestmove = lines[0].pv[0],
@@ -107,7 +107,10 @@ class Analyzer:
         is played in (notation.line_text).
         mate_plies = N > 0 (odd, 1 .. 15): before the search, Rules.mate looks for a continuous-check mate within N plies
         ("checks" mode), and every position's dict gains mate = dict(plies=d, pv=[move text ...]) or mate = None; the search
-        and everything it reports are unchanged."""
+        and everything it reports are unchanged.
+        tablebase = a cchess_zero_amd.tablebase.Tablebase (default None: nothing changes): every position's dict gains tablebase =
+        dict(wdl, plies, pv=[move text ...]) — the exact value from the mover's view and the table's principal line — or
+        tablebase = None for a position no loaded table covers; the search and everything it reports are unchanged."""
         from .notation import line_text
         pos = [fen_to_position(p) if isinstance(p, str) else p for p in positions]
         if ban is not None and len(ban) != len(pos):
@@ -139,6 +142,10 @@ class Analyzer:
         if mates is not None:
             for r, m in zip(out, mates):
                 r["mate"] = m
+        if tablebase is not None:
+            for r, p in zip(out, pos):
+                d = tablebase.describe(p[0], 1 if p[1] else 0, notation)
+                r["tablebase"] = None if d is None else dict(wdl=d["wdl"], plies=d["plies"], pv=d["pv"])
         return out
 
 
@@ -152,6 +159,8 @@ def main(argv=None):
     ap.add_argument("--playout", type=int, default=400, help="playouts per position")
     ap.add_argument("--lines", type=int, default=1, help="principal variations per position")
     ap.add_argument("--notation", choices=("iccs", "wxf", "chinese"), default="iccs", help="how the moves of the output are written (default: ICCS)")
+    ap.add_argument("--tablebase", metavar="DIR", default=None, help="a directory of endgame tables (python -m cchess_zero_amd.tablebase --build): "
+                    "every position also reports its exact value and line from them")
     args = ap.parse_args(argv)
     fens = list(args.fen)
     if args.fen_file:
@@ -164,7 +173,13 @@ def main(argv=None):
         ap.error(str(e))
     from .arena import load_player
     net = load_player(args.model, args.blocks)
-    res = Analyzer(net, args.playout, min(len(pos), 8192)).analyse(pos, args.lines, notation=args.notation)
+    an = Analyzer(net, args.playout, min(len(pos), 8192))
+    tb = None
+    if args.tablebase:
+        from .tablebase import Tablebase
+        tb = Tablebase(an.rule_kernels)
+        tb.load(args.tablebase)
+    res = an.analyse(pos, args.lines, notation=args.notation, tablebase=tb)
     for f, r in zip(fens, res):
         print(json.dumps(dict(fen=f, **r), ensure_ascii=args.notation != "chinese"), flush=True)
     return res

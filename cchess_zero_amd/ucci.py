@@ -2,7 +2,7 @@
 
     python -m cchess_zero_amd.ucci --model M.pt --blocks 7 [--playout 400] [--search_threads 16]
 
-Commands: ucci, isready, setoption <name> <value> (Playouts, MultiPV, Notation, MateSearch), position {startpos | fen <fen>} [moves m1 m2 ...],
+Commands: ucci, isready, setoption <name> <value> (Playouts, MultiPV, Notation, MateSearch, Tablebase), position {startpos | fen <fen>} [moves m1 m2 ...],
 banmoves m1 ..., go [nodes N | time T | depth D], stop, quit.  Moves are ICCS coordinates ("h2e2": files a-i, ranks 0-9 with
 red at rank 0), positions standard Xiangqi FEN (notation.fen_to_position).  After each go: one `info depth <len> [multipv k]
 score <round(1000 q)> nodes <sims> time <ms> pv m1 m2 ...` per line, then `bestmove m1 [ponder m2]`, or `nobestmove` when the
@@ -13,6 +13,12 @@ iccs, which is what GUIs read) writes the pv of the info lines in that notation;
 continuous-check mate within N plies (Rules.mate, "checks" mode).  If there is one and its first move is not banned, the engine
 prints `info depth <d> score <30000 - d> nodes <nodes> time <ms> pv ...` (d = the plies to the mate) and `bestmove` without
 searching; otherwise it searches as without the option.  (The `ucci` banner lists Playouts and MultiPV as before.)
+
+`setoption Tablebase <dir>` (default: unset, and nothing changes; `setoption Tablebase none` unsets it): every go first asks the
+searcher for the position's value in the endgame tables of that directory (python -m cchess_zero_amd.tablebase --build).  A
+covered position is answered at once, as MateSearch answers a mate: `info depth <len> score <s> nodes 0 time <ms> pv ...`, then
+`bestmove` — s is 30000 - plies for a win, -30000 + plies for a loss and 0 for a draw, the pv the table's principal line.  When
+banmoves bans the table's best move, or no table covers the position, the engine goes on as without the option.
 
 The search is the one analysis.py describes: the reference's king-capture search with the Xiangqi rules applied at the root.
 Out of scope: the engine does not judge repetition itself (GUIs send banmoves), it does not ponder (`ponder m2` is only the
@@ -25,6 +31,9 @@ UcciEngine(searcher, inp, out) is the protocol loop; `searcher` is what it needs
     lines(allowed uint32 [66], n_lines, max_len) -> [dict(pv=[labels], visits=[...], q=[...])] in rank order
     width (optional attribute): simulations in flight per lock-step
     mate(plies) -> (dist, [labels], nodes) or None: a continuous-check mate of the position (only called with MateSearch > 0)
+    tablebase(directory) -> (value, [labels]) or None: the position's value in the endgame tables of the directory (int16 as
+        include/cchess_hip.h defines it, from the mover's view) and the table's line; None when no table covers the position
+        (only called after setoption Tablebase)
 AnalyzerSearcher provides it on one device tree; the tests fake it on the C oracle.
 """
 import argparse
@@ -51,6 +60,7 @@ class UcciEngine:
         self.options = dict(playouts=int(playouts), multipv=1)
         self.mate_plies = 0         # setoption MateSearch: the horizon of the mate solver in front of every go, 0 = off
         self.pv_notation = "iccs"   # setoption Notation: how the info lines write their pv
+        self.tablebase_dir = None   # setoption Tablebase: the directory of the endgame tables asked in front of every go, None = off
         t = _lib.tables()
         self.labels, self.label2i, self.srcdst = t["labels"], t["label2i"], t["srcdst"]
         self.pos = fen_to_position(START_FEN)
@@ -133,6 +143,10 @@ class UcciEngine:
                 return self.say("info string setoption Notation: %r is not one of %s" % (args[1], " ".join(NOTATIONS)))
             self.pv_notation = args[1].lower()
             return
+        if name == "tablebase":
+            value = " ".join(args[1:])
+            self.tablebase_dir = None if value.lower() == "none" else value
+            return
         try:
             value = int(args[1])
         except ValueError:
@@ -211,6 +225,15 @@ class UcciEngine:
             allowed[label >> 5] &= ~(np.uint32(1) << np.uint32(label & 31))
         if not allowed.any():
             return self.say("nobestmove")
+        if self.tablebase_dir:
+            found = s.tablebase(self.tablebase_dir)
+            if found is not None and found[1] and found[1][0] not in self.ban:
+                value, pv = found
+                plies = abs(int(value)) - 1
+                score = 0 if value == 0 else MATE_SCORE - plies if value > 0 else plies - MATE_SCORE
+                ms = int(round((self.clock() - start) * 1000.0))
+                self.say("info depth %d score %d nodes 0 time %d pv %s" % (len(pv), score, ms, " ".join(line_text(self.pos[0], self.pos[1], pv, self.pv_notation))))
+                return self.say("bestmove %s%s" % (self.labels[pv[0]], " ponder %s" % self.labels[pv[1]] if len(pv) > 1 else ""))
         if self.mate_plies:
             found = s.mate(self.mate_plies)
             if found is not None and found[1] and found[1][0] not in self.ban:
@@ -256,6 +279,7 @@ class AnalyzerSearcher:
         self.a = analyzer
         self.width = analyzer.engine.width
         self.pos, self._rooted = None, False
+        self._tb = {}   # directory -> its loaded Tablebase
 
     def set_position(self, board, side, rr):
         self.pos = (np.asarray(board, np.uint8).reshape(1, 90), np.array([1 if side else 0], np.uint8), np.array([int(rr)], np.int32))
@@ -270,6 +294,18 @@ class AnalyzerSearcher:
         if int(r["status"][0]) != 1:
             return None
         return int(r["dist"][0]), [int(l) for l in r["pv"][0] if int(l) != 0xFFFF], int(r["nodes"][0])
+
+    def tablebase(self, directory):
+        if directory not in self._tb:
+            from .tablebase import Tablebase
+            self._tb[directory] = Tablebase(self.a.rule_kernels)
+            self._tb[directory].load(directory)
+        tb = self._tb[directory]
+        value, covered = tb.probe(self.pos[0], self.pos[1])
+        if not bool(covered[0]):
+            return None
+        v = int(value[0])
+        return v, tb.line(self.pos[0][0], int(self.pos[1][0]), abs(v) - 1 if v else PV_LEN)
 
     def _sims(self):
         return int(self.a.engine.status()[2].cpu().numpy()[0])

@@ -260,6 +260,65 @@ int cz_successors(cz_ctx *, const uint8_t *boards, const uint8_t *side, int G, c
 int cz_mate_backup(cz_ctx *, const int32_t *offsets /* [G + 1] */, int G, int total, const int16_t *child_dist /* [total] */,
                    const uint16_t *child_label /* [total] */, const uint16_t *child_pv /* [total][W], NULL when W == 0 */, int W,
                    int mode, int16_t *out_dist /* [G] */, uint16_t *out_pv /* [G][W + 1] */);
+/* K2t TABLEBASES: the exact value of every position of a material class, by retrograde analysis.  No reference function.
+ *   SIGNATURE  a C string such as "KR-KAA": red pieces, '-', black pieces.  Letters from KRNCPAB, in that order within a side,
+ *     so K is first; each side has exactly one K, at most two each of R N C A B and at most five P.  Each letter is a SLOT,
+ *     numbered left to right: in KR-KAA the slots are K, R, k, a, a.
+ *   DOMAINS  the squares a slot may stand on, in ascending square order (sq = 9 y + x, red at home on ranks 0-2): K the 9 palace
+ *     squares; A 3, 5, 13, 21, 23; B 2, 6, 18, 22, 26, 38, 42; P 55 squares — files a, c, e, g, i of ranks 3 and 4 and every
+ *     square of ranks 5-9; R, N, C all 90.  A black piece's domain is the red one with y -> 9 - y, sorted ascending again.
+ *   INDEX  index = 2 * mixed_radix(d0, d1, ...) + side: slot 0 is the most significant digit, d_i the place of slot i's square in
+ *     its domain, side 0 for red to move; entries = 2 * the product of the domain sizes.  A signature with more than 2^31 - 1
+ *     entries (or more than 10 slots, which has more) is refused.  Two equal pieces give two indices for one position; both
+ *     hold the same value — the redundancy is accepted — and cz_tb_probe reads the one that puts the k-th of equal pieces in
+ *     ascending square order on their k-th slot.  Mirror symmetry is not exploited.
+ *   VALUE  int16, from the side to move's view, plies(v) = |v| - 1:
+ *       0                 a draw: neither side can force mate;
+ *       v > 0             the mover mates in v - 1 plies (an odd count, v is even);
+ *       v < 0             the mover is mated in -v - 1 plies (an even count); -1: no king-safe move now — stalemate loses, as
+ *                         in CZ_POS_NO_SAFE_MOVE;
+ *       CZ_TB_ILLEGAL     the index has no position: two slots share a square, cz_movegen_kingsafe refuses the board, or the
+ *                         mover can take the king (CZ_POS_CAN_TAKE_KING);
+ *       CZ_TB_UNKNOWN     during a build only;
+ *       CZ_TB_MISS        cz_tb_probe's answer for a board whose pieces are not the signature's.
+ *     A win's ply count is the distance of the forced-mate search over all king-safe moves (cz_mate_backup's dist).
+ *     Repetition, perpetual check and chase, and any move limit are NOT part of the table: a forced mate is a mate.
+ *   THE BUILD  cz_tb_pass is one pass over every index of one table, in ONE launch, in place.
+ *     pass 0: every index becomes CZ_TB_ILLEGAL, -1 (no king-safe move) or CZ_TB_UNKNOWN.
+ *     pass d >= 1: every CZ_TB_UNKNOWN index walks its king-safe list; the child of a move is found arithmetically from the
+ *       parent's digits (the slot on `from` gets the digit of `to`, the side flips; a move that takes the piece of slot j drops
+ *       digit j and indexes sub[j], the table of the signature without that letter, which keeps the slot order) and its value u
+ *       is read; u is settled below d when it is no CZ_TB_UNKNOWN and plies(u) < d.  Some child u < 0 settled below d:
+ *       v = min plies(u) + 2, a win.  Otherwise every child u > 0 settled below d: v = -(max plies(u) + 2), a loss (a child
+ *       that is a draw or unknown prevents it).  Otherwise the index stays CZ_TB_UNKNOWN.
+ *     Values written in pass d have plies == d and a reader of the same launch treats them as not settled, so the result does
+ *     not depend on which stores a reader sees: no synchronisation between workgroups.  *decided (device memory, the caller
+ *     clears it) grows by the number of indices the pass decided.
+ *     STOPPING is the caller's: with S the largest plies in any sub[j] (-1 if none is decided), the build ends after the first
+ *     pass d >= 1 that decides nothing AND has d >= S + 1 — a capture into a sub-table entry lost in 12 plies settles its parent
+ *     at pass 13, whatever passes 1-12 did in this table — and then CZ_TB_UNKNOWN becomes 0.  Sub-tables are finished tables.
+ *   sub is a HOST array of n_slots DEVICE pointers, NULL for the kings' slots — the one host array in this ABI; it is read
+ *     during the call only.  Pass 0 reads no sub-table and takes sub == NULL.
+ *   cz_tb_probe: G boards [G][90] and sides -> value [G] and, when index is not NULL, index [G] (-1 without one).  A board
+ *     whose multiset of pieces is not the signature's answers CZ_TB_MISS and nothing of the table is read; one with a piece
+ *     outside its domain answers CZ_TB_ILLEGAL.  boards at any address: 16-byte aligned boards are staged with 16-byte loads,
+ *     others byte by byte.
+ *   cz_tb_boards: indices int32 [G] -> boards [G][90] (16-byte stores: boards must be 16-byte aligned, CZ_EINVAL otherwise) and
+ *     side [G].  An index whose slots overlap gives an EMPTY board with the index's side; one outside 0 .. entries - 1 an empty
+ *     board and side 0.
+ *   All: CZ_EINVAL for a string that is no signature, a NULL context or array; G == 0 is CZ_OK without a launch.
+ *   cz_tb_entries: host only — the number of entries and slots of a signature. */
+#define CZ_TB_ILLEGAL (-32768)
+#define CZ_TB_UNKNOWN 32767
+#define CZ_TB_MISS 32766
+#define CZ_TB_MAX_SLOTS 10
+int cz_tb_entries(const char *signature, long long *entries, int *n_slots);
+int cz_tb_pass(cz_ctx *, const char *signature, int16_t *table /* [entries] */, const int16_t *const *sub /* host [n_slots] */,
+               int pass, unsigned long long *decided);
+int cz_tb_probe(cz_ctx *, const char *signature, const int16_t *table /* [entries] */, const uint8_t *boards /* [G][90] */,
+                const uint8_t *side, int G, int16_t *value /* [G] */, int32_t *index /* [G] or NULL */);
+int cz_tb_boards(cz_ctx *, const char *signature, const int32_t *index /* [G] */, int G, uint8_t *boards /* [G][90] */,
+                 uint8_t *side);
 /* K3  replaces MCTS_tree.generate_inputs = try_flip + state_to_positions, main.py:531-574.
  *     planes [G][9][10][channels] of dtype CZ_F32 / CZ_BF16.  quirk_q1 = 1 reproduces the
  *     reference bit for bit; 0 gives the transposed encoding its shapes suggest. */

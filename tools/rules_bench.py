@@ -19,7 +19,12 @@ usage: python tools/rules_bench.py [N positions, default 1048576]
            rules.random_positions against the composition it replaces (cz_movegen_kingsafe list -> cz_successors -> the flags-only
            form on every child -> boolean compaction in torch), both in the same run; one JSON line at the end
        python tools/rules_bench.py --mate [N]         Rules.mate ("checks" mode) at plies 5 and 9 on N (default 65 536) positions
-           of rules.random_positions: roots/s and nodes/s; one JSON line at the end"""
+           of rules.random_positions: roots/s and nodes/s; one JSON line at the end
+       python tools/rules_bench.py --tablebase SIG    the retrograde build of one endgame table (Tablebase.build): wall time, passes
+           and entries per second of every pass; then an early pass (the first: every undecided lane is live) and a late one (the
+           last that decides anything: most groups are skipped) as the fused cz_tb_pass against the same pass composed from
+           cz_tb_boards -> cz_movegen_kingsafe -> cz_successors -> Tablebase.probe -> a torch segment reduction, from the same
+           snapshot of the table, alternating in one run; one JSON line at the end"""
 import os
 import sys
 import time
@@ -39,6 +44,13 @@ REPLAY = "--replay" in sys.argv
 REPLAY_NOTATION = "--replay-notation" in sys.argv
 CHECKS = "--checks" in sys.argv
 MATE = "--mate" in sys.argv
+TABLEBASE = None
+if "--tablebase" in sys.argv:
+    _at = sys.argv.index("--tablebase")
+    if _at + 1 >= len(sys.argv):
+        sys.exit("--tablebase needs a signature such as KR-KAABB")
+    TABLEBASE = sys.argv[_at + 1]
+    del sys.argv[_at:_at + 2]
 _args = [a for a in sys.argv[1:] if a not in ("--kingsafe", "--threats", "--successors", "--replay", "--replay-notation", "--checks", "--mate")]
 N = int(_args[0]) if _args else (8192 if REPLAY or REPLAY_NOTATION else 1 << 16 if MATE else 1 << 20)
 ctx = Context(1, 2, 0)
@@ -470,6 +482,103 @@ def notation_leg(max_ply=160, sample=256):
     print(json.dumps(out), flush=True)
 
 
+def tablebase_leg(sig):
+    """The build of one table, pass by pass (host clock around a pass and the read of its counter, which synchronises), then the
+    fused pass against the composed one on two snapshots: device events, one warm-up each, the two forms alternating."""
+    import json
+    from cchess_zero_amd._lib import TB_ILLEGAL, TB_UNKNOWN
+    from cchess_zero_amd.tablebase import Tablebase, closure, entries
+    tb = Tablebase(rules)
+    t0 = time.perf_counter()
+    for s in closure(sig):
+        if s != sig:
+            tb.build_one(s)
+    sub_s = time.perf_counter() - t0
+    n = entries(sig)[0]
+    passes, stamp = [], [0.0, 0]
+
+    def before(_, d, table):
+        stamp[1] = int((table == TB_UNKNOWN).sum())
+        stamp[0] = time.perf_counter()
+
+    def after(_, d, got):
+        ms = (time.perf_counter() - stamp[0]) * 1e3
+        passes.append(dict(d=d, ms=round(ms, 4), undecided=stamp[1], decided=got, entries_per_s=round(n / ms * 1e3)))
+
+    t0 = time.perf_counter()
+    stats = tb.build_one(sig, progress=after, before_pass=before)
+    wall = time.perf_counter() - t0
+    for p in passes:
+        print("pass %3d: %9.3f ms, %10d undecided before it, %9d decided = %.2f G entries/s" % (p["d"], p["ms"], p["undecided"], p["decided"], p["entries_per_s"] / 1e9))
+    early, late = 1, max([p["d"] for p in passes if p["decided"]] or [1])
+    final = tb.tables.pop(sig)
+    snaps = {}
+    tb.build_one(sig, before_pass=lambda _, d, table: snaps.__setitem__(d, table.clone()) if d in (early, late) else None)
+    assert torch.equal(tb.tables[sig], final)
+    subs, _ = tb.sub_tables(sig)
+    work = torch.empty_like(final)
+    counter = torch.zeros(1, dtype=torch.int64, device=final.device)
+    big, CH = 1 << 20, 1 << 20
+
+    def fused(d):
+        ctx.call("cz_tb_pass", sig.encode(), work, subs, d, counter)
+
+    def composed(d):
+        snap = tb.tables[sig]
+        out = snap.clone()
+        unk = (snap == TB_UNKNOWN).nonzero().flatten().to(torch.int32)
+        children = 0
+        for lo in range(0, unk.numel(), CH):
+            idx = unk[lo:lo + CH]
+            b, sd = tb.boards(sig, idx)
+            mv, cnt, _, _ = rules.movegen_kingsafe(b, sd, want_mask=False, pad=False)
+            cb, cs, _, par, _ = rules.successors(b, sd, mv, cnt)
+            children += cb.shape[0]
+            u = tb.probe(cb, cs)[0].to(torch.int64)
+            par, pl = par.to(torch.int64), u.abs() - 1
+            settled = (u != TB_UNKNOWN) & (u != TB_ILLEGAL) & (pl < d)
+            m = idx.numel()
+            lost = torch.full((m,), big, dtype=torch.int64, device=u.device).scatter_reduce_(0, par, torch.where(settled & (u < 0), pl, big), "amin")
+            all_won = torch.ones(m, dtype=torch.int64, device=u.device).scatter_reduce_(0, par, (settled & (u > 0)).to(torch.int64), "amin")
+            won = torch.full((m,), -1, dtype=torch.int64, device=u.device).scatter_reduce_(0, par, torch.where(u > 0, pl, -1), "amax")
+            v = torch.where(lost < big, lost + 2, torch.where(all_won == 1, -(won + 2), torch.full_like(lost, TB_UNKNOWN)))
+            out[idx.to(torch.int64)] = v.to(torch.int16)
+        return out, children
+
+    out = dict(signature=sig, entries=n, sub_tables_s=round(sub_s, 4), build_s=round(wall, 4), passes=stats["passes"], stats=stats, per_pass=passes)
+    for name, d in (("early", early), ("late", late)):
+        snap = snaps[d]
+        tb.tables[sig] = snap
+        work.copy_(snap)
+        fused(d)
+        want, children = composed(d)                      # the warm-up of both, and the check that they compute the same pass
+        assert torch.equal(work, want), "the fused and the composed pass %d differ" % d
+        tf, tc = [], []
+        for _ in range(3):
+            work.copy_(snap)
+            e0, e1, e2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
+            e0.record()
+            fused(d)
+            e1.record()
+            composed(d)
+            e2.record()
+            e2.synchronize()
+            tf.append(e0.elapsed_time(e1))
+            tc.append(e1.elapsed_time(e2))
+        tf.sort(), tc.sort()
+        undecided = int((snap == TB_UNKNOWN).sum())
+        out[name] = dict(d=d, undecided=undecided, children=children, fused_ms=round(tf[1], 4), fused_min_ms=round(tf[0], 4), fused_max_ms=round(tf[2], 4),
+                         composed_ms=round(tc[1], 4), composed_min_ms=round(tc[0], 4), composed_max_ms=round(tc[2], 4), composed_over_fused=round(tc[1] / tf[1], 2),
+                         fused_entries_per_s=round(n / tf[1] * 1e3))
+        print("%s pass %d (%d of %d undecided, %d children): fused %.3f ms (min %.3f, max %.3f), composed %.3f ms (min %.3f, max %.3f) = %.1f x"
+              % (name, d, undecided, n, children, tf[1], tf[0], tf[2], tc[1], tc[0], tc[2], tc[1] / tf[1]))
+    tb.tables[sig] = final
+    print(json.dumps(out), flush=True)
+
+
+if TABLEBASE:
+    tablebase_leg(TABLEBASE)
+    sys.exit(0)
 if REPLAY or REPLAY_NOTATION:
     if REPLAY:
         replay_leg()
