@@ -28,9 +28,13 @@
 //   SC  [2 halves][224][4]   E8M0 scale bytes: dword (h, cell) = the four 32-channel quarters' groups of half h        .. 44,800
 //       entries 192 + (r & 31) of every plane are zero blocks / scale 127: a lane whose tap is off the board reads the alias
 //       of the row it would have read (same banks: conflict-free like the real rows), one address for X, Y and SC
-//   HI  [181][256]           fp16 hi halves, chunk c of a row at c ^ ((byte offset >> 8) & 15); row 180 = zeros           .. 91,136
-//   W   4 x 16 KB            weight ring                                                                              .. 156,672
-//   head weights [3][128] f32                                                                                          .. 158,208
+//   HI  [180][272]           fp16 hi halves: 256 bytes + 16 of padding per row, chunk c of a row at 16 c.  The stride is   .. 93,760
+//       68 dwords = 4 mod 64: the sixteen consecutive-mod-16 rows of a ds_read_b128 lane group fall on sixteen distinct 4-bank
+//       spans without a swizzle, so a row's chunk is an IMMEDIATE of the slab bodies (tests/test_mx_hi_layout_cpu.py walks it)
+//   Z   512 zero bytes       at a multiple of 256 like HI: a lane whose tap is off the board reads at 16 (row & 15) + the     93,952 .. 94,464
+//       same immediate as the real lanes: the banks of the row it would have read
+//   W   4 x 16 KB            weight ring                                                                              .. 160,000
+//   head weights [3][128] f32                                                                                          .. 161,536
 // The last layer's values are written as fp32 (over everything but the head weights) and the head 1x1 convs / the trunk
 // dump read those; the block input of a residual block stays in registers as fp32.
 #pragma once
@@ -48,18 +52,25 @@ struct MXGeo {
     static constexpr int XPLANE = ENT * 16, YPLANE = ENT * 8, SPLANE = ENT * 4;
     static constexpr int X_OFF = 0, Y_OFF = 8 * XPLANE, S_OFF = Y_OFF + 8 * YPLANE;
     static constexpr int HI_OFF = S_OFF + 2 * SPLANE;          // 44,800 = 175 * 256
-    static constexpr int ZERO_OFF = HI_OFF + ROWS * CV_ROWB;   // the zero row of the hi halves
-    static constexpr int W_OFF = ZERO_OFF + CV_ROWB;           // 91,136
+    static constexpr int HI_ROWB = CV_ROWB + 16;               // 272: padded, not swizzled
+    static constexpr int ZERO_BYTES = 512;                     // 16 (row & 15) + 16 (chunk + k-half) <= 496
+    static constexpr int ZERO_OFF = (HI_OFF + ROWS * HI_ROWB + 255) / 256 * 256;   // 93,952: the zero region of the hi halves
+    static constexpr int W_OFF = ZERO_OFF + ZERO_BYTES;        // 94,464
     static constexpr int SLAB_BYTES = 16384;                   // [hi 8192][X 4096][Y 2048][scale dwords 1024][pad 1024]
     static constexpr int SLAB_SHIFT = 14;
     static constexpr int SLABS_PER_LAYER = 36;
     static constexpr int LDS_BYTES = W_OFF + TW_NBUF * SLAB_BYTES;
     static constexpr int PLANES_OFF = W_OFF + 3 * SLAB_BYTES;  // the input planes (32 B per cell) borrow ring buffer 3
     static constexpr int HEADW_OFF = LDS_BYTES;
-    static constexpr int LDS_TOTAL = LDS_BYTES + 3 * 128 * 4;  // 158,208 of the CU's 163,840
+    static constexpr int LDS_TOTAL = LDS_BYTES + 3 * 128 * 4;  // 161,536 of the CU's 163,840
     static constexpr int F32_ROWB = 512;                       // the last layer's fp32 rows (from LDS byte 0)
 };
-static_assert(MXGeo::HI_OFF % 256 == 0 && MXGeo::W_OFF % 16 == 0, "hi rows are swizzled by their absolute 256-byte row");
+static_assert(MXGeo::HI_ROWB % 16 == 0 && (MXGeo::HI_ROWB / 4) % 64 == 4 && MXGeo::HI_OFF % 16 == 0 && MXGeo::W_OFF % 16 == 0,
+              "hi rows: 16-byte chunks, consecutive rows 4 banks apart (conflict-free ds_read_b128 lane groups without a swizzle)");
+static_assert((MXGeo::ZERO_OFF - MXGeo::HI_OFF) % 256 == 0 && MXGeo::ZERO_OFF >= MXGeo::HI_OFF + MXGeo::ROWS * MXGeo::HI_ROWB &&
+              16 * 15 + 16 * 15 + 16 <= MXGeo::ZERO_BYTES,
+              "a masked lane reads ZERO_OFF + 16 (row & 15) + the real lanes' immediate: the banks of the row it would have read");
+static_assert(MXGeo::LDS_TOTAL <= 163840, "one workgroup per CU: 160 KB of LDS");
 static_assert(MXGeo::Y_OFF == 28672 && MXGeo::S_OFF == 43008, "tools/gen_tower_asm.py: MX_Y_OFF / MX_S_OFF");
 static_assert(MXGeo::SLABS_PER_LAYER % 4 == 0 && MXGeo::SLAB_BYTES == 16384 && 3 * MXGeo::SLAB_BYTES + 14336 < 65536,
               "tools/gen_tower_asm.py: slab g of a layer sits in ring slot g & 3 = its quarter, an immediate of the slab bodies (MX_SLAB)");
@@ -106,7 +117,6 @@ __global__ __launch_bounds__(512, 2) void k_trunk_mx_c128(const unsigned char *_
     const int npos = (B - pos0) < Geo::P ? (B - pos0) : Geo::P;
     const int nrows = npos * 90;
     const int nslabs = nlayers * Geo::SLABS_PER_LAYER;
-    auto lds_addr = [](int row_byte_off, int c) { return row_byte_off + ((c ^ ((row_byte_off >> 8) & 15)) << 4); };
     const unsigned voff0 = (unsigned)tid << 4, voff1 = voff0 + (unsigned)Geo::THREADS * 16u;
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);
     auto lds_row_of = [](int natural) {   // natural = p * 90 + y * 10 + x  ->  rank-major row 20 y + 10 p + x
@@ -116,8 +126,8 @@ __global__ __launch_bounds__(512, 2) void k_trunk_mx_c128(const unsigned char *_
 
     trunk_ring_prologue<Geo>(smem, wpk, nslabs, wave_u, voff0, voff1);
     trunk_stage_planes<Geo>(smem, planes, pos0, nrows, tid);
-    // zero row of the hi halves; zero aliases 192 .. 223 of the X / Y planes; scale 127 (= 2^0) in the aliases of SC
-    if (tid < 16) *reinterpret_cast<uint4 *>(smem + Geo::ZERO_OFF + (tid << 4)) = make_uint4(0, 0, 0, 0);
+    // zero region of the hi halves; zero aliases 192 .. 223 of the X / Y planes; scale 127 (= 2^0) in the aliases of SC
+    if (tid < Geo::ZERO_BYTES / 16) *reinterpret_cast<uint4 *>(smem + Geo::ZERO_OFF + (tid << 4)) = make_uint4(0, 0, 0, 0);
     if (tid < 256) *reinterpret_cast<uint4 *>(smem + Geo::X_OFF + (tid >> 5) * Geo::XPLANE + (192 + (tid & 31)) * 16) = make_uint4(0, 0, 0, 0);
     else *reinterpret_cast<uint2 *>(smem + Geo::Y_OFF + ((tid - 256) >> 5) * Geo::YPLANE + (192 + (tid & 31)) * 8) = make_uint2(0, 0);
     if (tid < 64) *reinterpret_cast<uint32_t *>(smem + Geo::S_OFF + (tid >> 5) * Geo::SPLANE + (192 + (tid & 31)) * 4) = 0x7f7f7f7fu;
@@ -147,9 +157,10 @@ __global__ __launch_bounds__(512, 2) void k_trunk_mx_c128(const unsigned char *_
         }
         tapmask[i] = m;
     }
-    // per tap: ab / key = hi row address and swizzle key (cz_trunk_split.h); xr = khalf * XPLANE + 16 * (row or its zero alias):
-    // X block at xr + quarter * 2 XPLANE, Y at Y_OFF + xr / 2 + ..., scale dword at S_OFF + xr / 4
-    auto tap_addr = [&](int tap, int (&ab)[3], int (&key)[3], int (&xr)[3], int (&yr)[3]) {
+    // per tap: ab = the lane's k-half of chunk 0 of its hi row (the bodies add 16 * chunk as an immediate; chunks are even, so
+    // chunk ^ khalf = chunk + khalf); xr = khalf * XPLANE + 16 * (row or its zero alias): X block at xr + quarter * 2 XPLANE, Y at
+    // Y_OFF + xr / 2 + ..., scale dword at S_OFF + sr, sr = xr / 4
+    auto tap_addr = [&](int tap, int (&ab)[3], int (&xr)[3], int (&yr)[3], int (&sr)[3]) {
         const int delta = (tap / 3 - 1) * 20 + (tap - (tap / 3) * 3 - 1);
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
@@ -157,11 +168,10 @@ __global__ __launch_bounds__(512, 2) void k_trunk_mx_c128(const unsigned char *_
             // slot / alias entry collided with the real row lane 12 reads (8.5 % of the LDS cycles in bank conflicts, round 5)
             const int kk = rowk[i] + delta;
             const bool on = (tapmask[i] >> tap) & 1;
-            const int rb = Geo::HI_OFF + kk * CV_ROWB;
-            ab[i] = on ? rb : Geo::ZERO_OFF;
-            key[i] = ((rb >> 8) & 15) ^ khalf;
+            ab[i] = (on ? Geo::HI_OFF + kk * Geo::HI_ROWB : Geo::ZERO_OFF + ((kk & 15) << 4)) + (khalf << 4);
             xr[i] = khalf * Geo::XPLANE + ((on ? kk : 192 + (kk & 31)) << 4);
             yr[i] = xr[i] >> 1;
+            sr[i] = xr[i] >> 2;
         }
     };
     const int vb0 = Geo::W_OFF + khalf * 2048 + ((ct * 32 + l31) << 4);
@@ -227,11 +237,11 @@ __global__ __launch_bounds__(512, 2) void k_trunk_mx_c128(const unsigned char *_
         const u32x6 blk = mx_cvt6(hi, lo, __uint_as_float((uint32_t)byte << 23));
         const bool live = rowk[i] >= 0;
         if (live) {
-            const int rowb = Geo::HI_OFF + rkk[i] * CV_ROWB;
+            const int rowb = Geo::HI_OFF + rkk[i] * Geo::HI_ROWB;
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const int n0 = ct * 32 + 8 * q + 4 * khalf;
-                *reinterpret_cast<uint2 *>(smem + lds_addr(rowb, n0 >> 3) + ((n0 & 4) << 1)) = make_uint2(pk[2 * q], pk[2 * q + 1]);
+                *reinterpret_cast<uint2 *>(smem + rowb + (n0 << 1)) = make_uint2(pk[2 * q], pk[2 * q + 1]);
             }
             const int g = 2 * ct + khalf;
             *reinterpret_cast<uint4 *>(smem + Geo::X_OFF + g * Geo::XPLANE + (rkk[i] << 4)) = make_uint4(blk[0], blk[1], blk[2], blk[3]);
@@ -275,32 +285,32 @@ __global__ __launch_bounds__(512, 2) void k_trunk_mx_c128(const unsigned char *_
         __syncthreads();
     }
 
-#define MX_OPERANDS(NAB, NKEY)                                                                                       \
+#define MX_OPERANDS(NAB)                                                                                             \
             : [c0] "+v"(acc[0]), [c1] "+v"(acc[1]), [c2] "+v"(acc[2]),                                                 \
               [a0h0] "+v"(fa.a[0]), [a0h1] "+v"(fa.a[1]), [a0h2] "+v"(fa.a[2]), [w0] "+v"(fa.w),                      \
               [a1h0] "+v"(fb.a[0]), [a1h1] "+v"(fb.a[1]), [a1h2] "+v"(fb.a[2]), [w1] "+v"(fb.w),                      \
               [sb0] "+v"(sb[0]), [sb1] "+v"(sb[1]), [sb2] "+v"(sb[2]),                                                \
-              [t0] "=&v"(t0), [t1] "=&v"(t1), [t2] "=&v"(t2), [ws] "=&v"(wsr), [keep] "=&s"(keep)                      \
-            : [ab0] "v"(ab[0]), [ab1] "v"(ab[1]), [ab2] "v"(ab[2]), [key0] "v"(key[0]), [key1] "v"(key[1]),            \
-              [key2] "v"(key[2]), [nab0] "v"(NAB[0]), [nab1] "v"(NAB[1]), [nab2] "v"(NAB[2]), [nkey0] "v"(NKEY[0]),     \
-              [nkey1] "v"(NKEY[1]), [nkey2] "v"(NKEY[2]), [xr0] "v"(xr[0]), [xr1] "v"(xr[1]), [xr2] "v"(xr[2]),        \
-              [yr0] "v"(yr[0]), [yr1] "v"(yr[1]), [yr2] "v"(yr[2]), [vb] "v"(vb0), [vy] "v"(vy0), [vs] "v"(vs0),       \
+              [ws] "=&v"(wsr), [keep] "=&s"(keep)                                                                     \
+            : [ab0] "v"(ab[0]), [ab1] "v"(ab[1]), [ab2] "v"(ab[2]), [nab0] "v"(NAB[0]), [nab1] "v"(NAB[1]),            \
+              [nab2] "v"(NAB[2]), [xr0] "v"(xr[0]), [xr1] "v"(xr[1]), [xr2] "v"(xr[2]), [yr0] "v"(yr[0]),              \
+              [yr1] "v"(yr[1]), [yr2] "v"(yr[2]), [sr0] "v"(sr[0]), [sr1] "v"(sr[1]), [sr2] "v"(sr[2]),                \
+              [vb] "v"(vb0), [vy] "v"(vy0), [vs] "v"(vs0),                                                            \
               [voff0] "v"(voff0), [voff1] "v"(voff1), [sbase] "s"(sbase), [ldst] "s"(ldst0)
 #define MX_CLOBBERS "memory", "scc", "v232", "v233", "v234", "v235", "v236", "v237", "v238", "v239", "v240", "v241", "v242", "v243", \
                     "v244", "v245", "v246", "v247", "v248", "v249", "v250", "v251", "v252", "v253", "v254", "v255"
 #define MX_ARGS()   /* slab g sits in ring slot g & 3 = the body's quarter: the bodies carry the slots as immediates, and all that */ \
             const int gn = g + 3 < nslabs ? g + 3 : nslabs - 1;   /* moves from slab to slab is the global source of the DMA (slab g + 3) */ \
             const unsigned char *sbase = wpk + (size_t)gn * Geo::SLAB_BYTES;
-#define MX_RUN(ASMSTR, NAB, NKEY)                                                                                    \
+#define MX_RUN(ASMSTR, NAB)                                                                                          \
         {                                                                                                            \
             MX_ARGS()                                                                                                \
-            asm volatile(ASMSTR MX_OPERANDS(NAB, NKEY) : MX_CLOBBERS);                                               \
+            asm volatile(ASMSTR MX_OPERANDS(NAB) : MX_CLOBBERS);                                                     \
             ++g;                                                                                                     \
         }
-#define MX_RUNV(ASMSTR, NAB, NKEY)   /* the same + the wave-uniform skip mask; clobbers VCC */                        \
+#define MX_RUNV(ASMSTR, NAB)         /* the same + the wave-uniform skip mask; clobbers VCC */                        \
         {                                                                                                            \
             MX_ARGS()                                                                                                \
-            asm volatile(ASMSTR MX_OPERANDS(NAB, NKEY), [skipm] "s"(skipm) : MX_CLOBBERS, "vcc");                    \
+            asm volatile(ASMSTR MX_OPERANDS(NAB), [skipm] "s"(skipm) : MX_CLOBBERS, "vcc");                          \
             ++g;                                                                                                     \
         }
 
@@ -324,16 +334,16 @@ __global__ __launch_bounds__(512, 2) void k_trunk_mx_c128(const unsigned char *_
     for (int layer = 0; layer < nlayers; ++layer) {
         f32x16 acc[3];
         init_acc(acc, nullptr, (layer & 1) != 0);
-        int ab[3], key[3], nab[3], nkey[3], xr[3], yr[3], nxr[3], nyr[3], t0, t1, t2, wsr;
+        int ab[3], nab[3], xr[3], yr[3], sr[3], nxr[3], nyr[3], nsr[3], wsr;
         int sb[3] = {0, 0, 0};
         MxFrag fa, fb;
-        tap_addr(0, ab, key, xr, yr);
+        tap_addr(0, ab, xr, yr, sr);
         {   // the first slab's two fp16 operand sets (waited for by its steps A and B)
             const int vb = vb0;   // a layer starts in ring slot 0
 #pragma unroll
             for (int i = 0; i < 3; ++i) {
-                fa.a[i] = *reinterpret_cast<const bf16x8 *>(smem + ab[i] + ((0 ^ key[i]) << 4));
-                fb.a[i] = *reinterpret_cast<const bf16x8 *>(smem + ab[i] + ((2 ^ key[i]) << 4));
+                fa.a[i] = *reinterpret_cast<const bf16x8 *>(smem + ab[i]);
+                fb.a[i] = *reinterpret_cast<const bf16x8 *>(smem + ab[i] + (2 << 4));
             }
             fa.w = *reinterpret_cast<const bf16x8 *>(smem + vb);
             fb.w = *reinterpret_cast<const bf16x8 *>(smem + vb + 4096);
@@ -343,30 +353,30 @@ __global__ __launch_bounds__(512, 2) void k_trunk_mx_c128(const unsigned char *_
         int tap = 0;
 #pragma unroll 1
         for (; tap < 3; ++tap) {   // dy = -1: cell group 0 branches around the MFMAs of its all-rank-0 row tile
-            MX_RUNV(MX_SKIP0_ASM_Q0, ab, key)
-            MX_RUNV(MX_SKIP0_ASM_Q1, ab, key)
-            MX_RUNV(MX_SKIP0_ASM_Q2, ab, key)
-            tap_addr(tap + 1, nab, nkey, nxr, nyr);
-            MX_RUNV(MX_SKIP0_ASM_Q3, nab, nkey)
+            MX_RUNV(MX_SKIP0_ASM_Q0, ab)
+            MX_RUNV(MX_SKIP0_ASM_Q1, ab)
+            MX_RUNV(MX_SKIP0_ASM_Q2, ab)
+            tap_addr(tap + 1, nab, nxr, nyr, nsr);
+            MX_RUNV(MX_SKIP0_ASM_Q3, nab)
 #pragma unroll
-            for (int i = 0; i < 3; ++i) { ab[i] = nab[i]; key[i] = nkey[i]; xr[i] = nxr[i]; yr[i] = nyr[i]; }
+            for (int i = 0; i < 3; ++i) { ab[i] = nab[i]; xr[i] = nxr[i]; yr[i] = nyr[i]; sr[i] = nsr[i]; }
         }
 #pragma unroll 1
         for (; tap < 8; ++tap) {
-            MX_RUN(MX_SLAB_ASM_Q0, ab, key)
-            MX_RUN(MX_SLAB_ASM_Q1, ab, key)
-            MX_RUN(MX_SLAB_ASM_Q2, ab, key)
-            tap_addr(tap + 1, nab, nkey, nxr, nyr);
-            MX_RUN(MX_SLAB_ASM_Q3, nab, nkey)
+            MX_RUN(MX_SLAB_ASM_Q0, ab)
+            MX_RUN(MX_SLAB_ASM_Q1, ab)
+            MX_RUN(MX_SLAB_ASM_Q2, ab)
+            tap_addr(tap + 1, nab, nxr, nyr, nsr);
+            MX_RUN(MX_SLAB_ASM_Q3, nab)
 #pragma unroll
-            for (int i = 0; i < 3; ++i) { ab[i] = nab[i]; key[i] = nkey[i]; xr[i] = nxr[i]; yr[i] = nyr[i]; }
+            for (int i = 0; i < 3; ++i) { ab[i] = nab[i]; xr[i] = nxr[i]; yr[i] = nyr[i]; sr[i] = nsr[i]; }
         }
-        MX_RUN(MX_SLAB_ASM_Q0, ab, key)      // tap 8; its last slab requests nothing and has waited for every LDS read of the wave in
-        MX_RUN(MX_SLAB_ASM_Q1, ab, key)      // front of its barrier: behind that barrier nobody reads the activation planes any more,
-        MX_RUN(MX_SLAB_ASM_Q2, ab, key)      // and the epilogue may overwrite them in place without a barrier of its own
-        MX_RUN(MX_SLAB_ASM_Q3_LAST, ab, key)
+        MX_RUN(MX_SLAB_ASM_Q0, ab)      // tap 8; its last slab requests nothing and has waited for every LDS read of the wave in
+        MX_RUN(MX_SLAB_ASM_Q1, ab)      // front of its barrier: behind that barrier nobody reads the activation planes any more,
+        MX_RUN(MX_SLAB_ASM_Q2, ab)      // and the epilogue may overwrite them in place without a barrier of its own
+        MX_RUN(MX_SLAB_ASM_Q3_LAST, ab)
         const bool last = layer + 1 == nlayers;
-        if (last) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the fp32 rows reach into the weight ring
+        if (last) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the ring's last pieces (the fp32 rows end below it)
         else load_bias(bias + (layer + 1) * 128);
         asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15" ::: "memory");   // let the MFMAs retire (the compiler does not see them)
         MX_TM(tm_loop)

@@ -122,6 +122,28 @@ MX_Y_OFF, MX_S_OFF = 8 * MX_XPLANE, 8 * MX_XPLANE + 8 * MX_YPLANE
 MX_SLAB = 16384                               # MXGeo::SLAB_BYTES: one slot of the ring of four
 MX_AX = ["v[232:237]", "v[238:243]", "v[244:249]"]   # fp6 activation blocks of the three cell tiles: loaded and consumed inside
 MX_WX = "v[250:255]"                                  # one slab body, so they are hard registers (the body clobbers v232..v255)
+MX_HI_ROWB = 272                              # MXGeo::HI_ROWB: a hi row's 256 bytes + 16 of padding; chunk c at 16 c, no swizzle
+
+
+def mx_hi_chunks(hs):
+    """the 16-byte chunks (lower k-half; the upper reads the next one) of the two fp16 operand sets that body hs requests: the NEXT
+    slab's k-steps 0 and 1, i.e. input channels 32 (hs + 1) .. + 31 of the tap, after the tap's last slab channels 0 .. 31"""
+    ca = ((hs + 1) % 4) * 4
+    return ca, ca + 2
+
+
+def mx_body_bytes(L):
+    """encoded length of a body of slabMX: scalar instructions 4 bytes (8 with a literal: constants outside 0..64), the block-scaled
+    MFMA 16, every other MFMA, LDS read and LDS-DMA 8 (checked once against the assembler's listing of the built kernel)"""
+    n = 0
+    for l in L:
+        op = l.split()[0]
+        if op.startswith("s_"):
+            lit = op == "s_add_u32" and int(l.split()[-1], 16) > 64
+            n += 8 if lit else 4
+        else:
+            n += 16 if op.startswith("v_mfma_scale") else 8
+    return n
 
 
 def slabMX(hs, layer_last=False):
@@ -136,10 +158,14 @@ def slabMX(hs, layer_last=False):
     wave); from slab to slab only the DMA's global source moves (tests/test_mx_slab_plan_cpu.py walks a layer of these bodies).
     layer_last (round 6): the LAST slab of a layer requests no operands (the activations are about to be replaced) and waits
     for all of its LDS reads in front of its barrier — behind it no wave reads the activation planes any more, so the epilogue
-    needs no barrier of its own in front."""
-    nab, nkey = ("nab", "nkey") if hs == 3 else ("ab", "key")
-    ca = ((hs + 1) % 4) * 4
+    needs no barrier of its own in front.
+    The fp16 hi rows sit on a padded stride (MXGeo::HI_ROWB = 272 B = 68 dwords: conflict-free without a swizzle), so a row's chunk is
+    an immediate as well: ab / nab are the lane's row (or its zero alias) + 16 B for the upper k-half, the reads add 16 * chunk.  The
+    tap's scale addresses come in as sr0..2.  A body holds no VALU instruction besides its MFMAs."""
+    nab = "nab" if hs == 3 else "ab"
+    ca, cb = mx_hi_chunks(hs)
     f = lambda i, w, a: "v_mfma_f32_32x32x16_f16 %%[c%d], %%[%s], %%[%s%d], %%[c%d]" % (i, w, a, i, i)
+    hi = lambda s, i, c: "ds_read_b128 %%[a%dh%d], %%[%s%d] offset:%d" % (s, i, nab, i, 16 * c)
     mx = lambda i: ("v_mfma_scale_f32_32x32x64_f8f6f4 %%[c%d], %s, %s, %%[c%d], %%[ws], %%[sb%d] op_sel:[0,%d,0] op_sel_hi:[0,%d,0] cbsz:2 blgp:2"
                     % (i, MX_WX, MX_AX[i], i, i, hs & 1, hs >> 1))
     sub = lambda r, lo, hi: "v[%d:%d]" % (int(r[2:].split(":")[0]) + lo, int(r[2:].split(":")[0]) + hi)
@@ -150,13 +176,11 @@ def slabMX(hs, layer_last=False):
     L += ["s_waitcnt lgkmcnt(4)", f(0, "w0", "a0h")]
     L += ["ds_read_b128 %s, %%[xr0] offset:%d" % (sub(MX_AX[0], 0, 3), xo), "ds_read_b64 %s, %%[yr0] offset:%d" % (sub(MX_AX[0], 4, 5), yo),
           "ds_read_b128 %s, %%[xr1] offset:%d" % (sub(MX_AX[1], 0, 3), xo), "ds_read_b64 %s, %%[yr1] offset:%d" % (sub(MX_AX[1], 4, 5), yo)]
-    if hs == 0:
-        L += ["v_lshrrev_b32 %[t0], 1, %[yr0]", "v_lshrrev_b32 %[t1], 1, %[yr1]", "v_lshrrev_b32 %[t2], 1, %[yr2]"]
     L += [f(1, "w0", "a0h")]
     L += ["ds_read_b128 %s, %%[xr2] offset:%d" % (sub(MX_AX[2], 0, 3), xo), "ds_read_b64 %s, %%[yr2] offset:%d" % (sub(MX_AX[2], 4, 5), yo)]
     nc = 9
     if hs == 0:   # the tap's activation scales: one dword per cell = the four 32-channel quarters' E8M0 bytes of this lane's half
-        L += ["ds_read_b32 %%[sb%d], %%[t%d] offset:%d" % (i, i, MX_S_OFF) for i in range(3)]
+        L += ["ds_read_b32 %%[sb%d], %%[sr%d] offset:%d" % (i, i, MX_S_OFF) for i in range(3)]
         nc = 12
     L += [f(2, "w0", "a0h")]
     L += ["ds_read_b128 %s, %%[vb] offset:%d" % (sub(MX_WX, 0, 3), slot + 8192), "ds_read_b64 %s, %%[vy] offset:%d" % (sub(MX_WX, 4, 5), slot),
@@ -168,12 +192,10 @@ def slabMX(hs, layer_last=False):
     else:
         L += ["s_waitcnt vmcnt(2)", "s_barrier", "s_waitcnt lgkmcnt(%d)" % nc]
         L += [f(0, "w1", "a1h")]
-        L += ["v_xor_b32 %%[t%d], %d, %%[%s%d]" % (i, ca, nkey, i) for i in range(3)]
-        L += ["v_lshl_add_u32 %%[t%d], %%[t%d], 4, %%[%s%d]" % (i, i, nab, i) for i in range(3)]
         L += [f(1, "w1", "a1h")]
-        L += ["ds_read_b128 %[a0h0], %[t0]", "ds_read_b128 %[a0h1], %[t1]"]
+        L += [hi(0, 0, ca), hi(0, 1, ca)]
         L += [f(2, "w1", "a1h")]
-        L += ["ds_read_b128 %[a0h2], %[t2]", "ds_read_b128 %%[w0], %%[vb] offset:%d" % nslot]
+        L += [hi(0, 2, ca), "ds_read_b128 %%[w0], %%[vb] offset:%d" % nslot]
     # step C
     dma1 = ["s_add_u32 m0, %%[ldst], 0x%x" % dslot, "s_nop 0", "global_load_lds_dwordx4 %[voff0], %[sbase]"]
     dma2 = ["s_add_u32 m0, %%[ldst], 0x%x" % (dslot + 0x2000), "s_nop 0", "global_load_lds_dwordx4 %[voff1], %[sbase]"]
@@ -188,19 +210,22 @@ def slabMX(hs, layer_last=False):
     if place == "B0C0":
         L += dma2
     L += [mx(0)]
-    if not layer_last:
-        L += ["v_xor_b32 %%[t%d], %d, %%[%s%d]" % (i, ca + 2, nkey, i) for i in range(3)]
-        L += ["v_lshl_add_u32 %%[t%d], %%[t%d], 4, %%[%s%d]" % (i, i, nab, i) for i in range(3)]
     if place == "C":
         L += dma1
     L += [mx(1)]
-    L += [] if layer_last else ["ds_read_b128 %[a1h0], %[t0]", "ds_read_b128 %[a1h1], %[t1]"]
+    L += [] if layer_last else [hi(1, 0, cb), hi(1, 1, cb)]
     if place == "C":
         L += dma2
     L += [mx(2)]
-    L += [] if layer_last else ["ds_read_b128 %[a1h2], %[t2]", "ds_read_b128 %%[w1], %%[vb] offset:%d" % (nslot + 4096)]
+    L += [] if layer_last else [hi(1, 2, cb), "ds_read_b128 %%[w1], %%[vb] offset:%d" % (nslot + 4096)]
     if place == "Cend":
         L += dma1 + dma2
+    # experiment knob: one s_nop 0 that makes every body a multiple of 8 bytes long ("all"), or only the tap's first body, whose change
+    # against the swizzled layout is 84 bytes where the others' is 72 ("q0").  Both measured slower than no padding, on two boxes
+    # (profiles/mx_hi_stride_ab.txt): -0.6 ... -0.9 % per launch against the parent where the unpadded bodies give -1.2 %
+    pad = os.environ.get("MX_BODY_PAD", "none")
+    if (pad == "all" and (mx_body_bytes(L) + 4) % 8) or (pad == "q0" and hs == 0):
+        L += ["s_nop 0"]
     L += ["s_mov_b32 m0, %[keep]"]
     # timing ablations (tools/experiments/mx_ablate.sh; wrong results): MX_ABLATE = comma list of nolgkmwait, novmwait, nobarrier, bar2 (barrier in
     # every other slab), noc (no fp6 operand reads), nomx (no fp6 MFMAs), nodma, nohi (no fp16 operand reads)
