@@ -25,6 +25,23 @@ extern "C" int cztb_host_parse(const char *sig, int32_t *n, uint32_t *entries, u
     return 0;
 }
 
+// the whole descriptor of sig (without < 0) or of cztb_without(sig's, without): fields [5][CZTB_MAX_SLOTS] = code, dom, radix, ord, mult
+extern "C" int cztb_host_desc(const char *sig, int without, int32_t *n, uint32_t *entries, uint8_t *fields) {
+    CztbDesc d;
+    const int rc = cztb_parse(sig, &d);
+    if (rc) return rc;
+    if (without >= d.n || (without >= 0 && (d.code[without] == 1 || d.code[without] == 8))) return -5;
+    if (without >= 0) d = cztb_without(d, without);
+    *n = d.n;
+    *entries = d.entries;
+    memcpy(fields, d.code, CZTB_MAX_SLOTS);
+    memcpy(fields + CZTB_MAX_SLOTS, d.dom, CZTB_MAX_SLOTS);
+    memcpy(fields + 2 * CZTB_MAX_SLOTS, d.radix, CZTB_MAX_SLOTS);
+    memcpy(fields + 3 * CZTB_MAX_SLOTS, d.ord, CZTB_MAX_SLOTS);
+    memcpy(fields + 4 * CZTB_MAX_SLOTS, d.mult, CZTB_MAX_SLOTS);
+    return 0;
+}
+
 // cz_tb_boards for host arrays: boards [G][90], side [G], overlap [G] (an overlapping index gives an empty board)
 extern "C" int cztb_host_boards(const char *sig, const uint32_t *index, int G, uint8_t *boards, uint8_t *side, uint8_t *overlap) {
     CztbDesc d;

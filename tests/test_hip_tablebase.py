@@ -3,7 +3,7 @@
      tests/test_tablebase_model_cpu.py holds to a fresh run of the model);
   2. independently of the model, Rules.mate(attacker="all") at 5 plies answers a table's wins within 5 plies, and nothing else;
   3. on a five-slot table nobody modelled (KR-KAB) every value is the pass rule applied to its children's FINAL values, the children
-     made by the existing movegen_kingsafe -> successors path;
+     made by the existing movegen_kingsafe -> successors path, and passes, wins, losses and crc32 are the host build's;
   4. probe and boards are inverse to each other, duplicates and foreign boards included;
   5. best / line play the model's principal line.
 All tables are built once per module."""
@@ -13,6 +13,7 @@ import json
 import numpy as np
 import pytest
 
+import tablebase_classes as TC
 import tablebase_model as TM
 
 pytestmark = pytest.mark.gpu
@@ -87,35 +88,22 @@ def test_against_the_mate_search(tb, torch, sig):
 
 def test_fixpoint_on_a_table_nobody_modelled(tb, torch):
     """KR-KAB, 510 300 entries: every legal value is the pass rule on the children's final values; the children come from
-    cz_tb_boards -> movegen_kingsafe -> successors -> probe, none of which the build uses"""
-    from cchess_zero_amd._lib import POS_CAN_TAKE_KING, POS_NO_SAFE_MOVE
+    cz_tb_boards -> movegen_kingsafe -> successors -> probe, none of which the build uses.  And the table is the host build's."""
     sig = "KR-KAB"
     tb.build(sig)
     table = tb.tables[sig]
     assert table.shape == (510300,) and tb.stats[sig]["wins"] > 0 and tb.stats[sig]["losses"] > 0
-    idx, boards, side, v = _legal_positions(tb, torch, sig)
-    mv, cnt, _, pf = tb.rules.movegen_kingsafe(boards, side, want_mask=False, pad=False)
-    assert bool((cnt >= 0).all()) and not bool((pf & POS_CAN_TAKE_KING).any())
-    assert torch.equal(v == -1, (pf & POS_NO_SAFE_MOVE) != 0)                                  # every -1 entry, and no other, has no king-safe move
-    cb, cs, _, par, _ = tb.rules.successors(boards, side, mv, cnt)
-    u, covered = tb.probe(cb, cs)
-    assert bool(covered.all())
-    u, par = u.to(torch.int64), par.to(torch.int64)
-    n, big = boards.shape[0], 1 << 20
-    lost = torch.full((n,), big, dtype=torch.int64, device=u.device).scatter_reduce_(0, par, torch.where(u < 0, -u - 1, big), "amin")
-    all_won = torch.ones(n, dtype=torch.int64, device=u.device).scatter_reduce_(0, par, (u > 0).to(torch.int64), "amin")
-    won = torch.full((n,), -1, dtype=torch.int64, device=u.device).scatter_reduce_(0, par, torch.where(u > 0, u - 1, -1), "amax")
-    want = torch.where(lost < big, lost + 2, torch.where((all_won == 1) & (cnt > 0), -(won + 2), torch.zeros_like(lost)))
-    want = torch.where(cnt == 0, torch.full_like(want, -1), want)
-    bad = (want != v.to(torch.int64)).nonzero().flatten()
-    assert bad.numel() == 0, (int(bad.numel()), idx[bad[:5]], v[bad[:5]], want[bad[:5]])
+    # the arithmetic is tests/tablebase_classes.py's, shared with tests/test_hip_tablebase_classes.py: every -1 entry, and no other, has
+    # no king-safe move; every child is covered; the value is pass_rule of the children's values
+    TC.check_fixpoint(tb, sig, (table != ILLEGAL).nonzero().flatten())
     # the ILLEGAL entries: two slots share a square (an empty board), or the mover can take the king, or the board is refused
-    ill = (table == ILLEGAL).nonzero().flatten().to(torch.int32)
-    ib, is_ = tb.boards(sig, ill)
-    apart = (ib != 0).sum(1) == 5
-    assert bool(((ib != 0).sum(1)[~apart] == 0).all()) and int(apart.sum()) > 0 and int((~apart).sum()) > 0
-    _, icnt, _, ipf = tb.rules.movegen_kingsafe(ib[apart].contiguous(), is_[apart].contiguous(), want_mask=False, want_moves=False)
-    assert bool((((ipf & POS_CAN_TAKE_KING) != 0) | (icnt < 0)).all())
+    apart, overlapping = TC.check_illegal(tb, sig, (table == ILLEGAL).nonzero().flatten())
+    assert apart > 0 and overlapping > 0
+    # a fixpoint cannot see a build that stopped too early (deep wins left as draws are a fixpoint too): the host build's numbers
+    got = TC.table_stats(table, tb.stats[sig]["passes"])
+    print("%s: %s" % (sig, got))
+    for k in ("passes", "wins", "losses", "crc32"):
+        assert got[k] == TC.PINNED[sig][k], (k, got[k], TC.PINNED[sig][k])
 
 
 def test_probe_and_boards(tb, torch):
