@@ -29,12 +29,18 @@ def group_perm(C=128):
     return torch.tensor(order)
 
 
-def q_e2m3(x):
-    """RNE onto the E2M3 grid (step 1/8 below 2, 1/4 below 4, 1/2 below 8), saturating at +-7.5"""
-    ax = x.abs().clamp(max=7.5)
-    e = torch.floor(torch.log2(ax.clamp(min=1.0)))
+def q_e2m3(x, mode="rne", sat=True):
+    """RNE onto the E2M3 grid (step 1/8 below 2, 1/4 below 4, 1/2 below 8), saturating at +-7.5.  mode "rtz" / "half_away" and
+    sat=False are deliberate corruptions (tests/exactnets.py: MUTATIONS), never what the hardware is taken to do"""
+    ax = x.abs()
+    if sat:
+        ax = ax.clamp(max=7.5)
+    e = torch.floor(torch.log2(ax.clamp(min=1.0))).clamp(max=2.0)
     step = torch.exp2(e - 3)
-    return torch.sign(x) * (torch.round(ax / step) * step).clamp(max=7.5)
+    r = ax / step
+    r = torch.round(r) if mode == "rne" else torch.trunc(r) if mode == "rtz" else torch.floor(r + 0.5)
+    r = r * step
+    return torch.sign(x) * (r.clamp(max=7.5) if sat else r)
 
 
 def block_scale(amax):
@@ -44,9 +50,11 @@ def block_scale(amax):
     return torch.exp2((byte - 127).to(amax.dtype)), byte
 
 
-def mxq_pair(p0, p1, cdim, scale_from=None):
+def mxq_pair(p0, p1, cdim, scale_from=None, q=q_e2m3, info=None):
     """p0, p1: the two halves of the blocks (same shape), channels on `cdim` in NATURAL order; one scale per 16-channel
-    group from max(|p0|, |p1|) (or from `scale_from`).  -> dequantised (p0, p1), natural order."""
+    group from max(|p0|, |p1|) (or from `scale_from`).  -> dequantised (p0, p1), natural order.  q: the E2M3 rounding (a
+    corrupted one: tests/exactnets.py); info: a dict that receives what the quantiser saw, in group order [n, groups, 16]:
+    the scaled operands x0, x1, and per group amax and the scale byte"""
     perm = group_perm(p0.shape[cdim]).to(p0.device)
     inv = torch.argsort(perm)
     a = p0.index_select(cdim, perm).movedim(cdim, -1)
@@ -57,10 +65,12 @@ def mxq_pair(p0, p1, cdim, scale_from=None):
         amax = torch.maximum(a.abs().amax(-1), b.abs().amax(-1))
     else:
         amax = scale_from.index_select(cdim, perm).movedim(cdim, -1).reshape(-1, sh[-1] // 16, 16).abs().amax(-1)
-    s, _ = block_scale(amax)
+    s, byte = block_scale(amax)
     s = s.unsqueeze(-1)
-    da = (q_e2m3(a / s) * s).reshape(sh).movedim(-1, cdim).index_select(cdim, inv)
-    db = (q_e2m3(b / s) * s).reshape(sh).movedim(-1, cdim).index_select(cdim, inv)
+    if info is not None:
+        info.update(x0=a / s, x1=b / s, amax=amax, byte=byte)
+    da = (q(a / s) * s).reshape(sh).movedim(-1, cdim).index_select(cdim, inv)
+    db = (q(b / s) * s).reshape(sh).movedim(-1, cdim).index_select(cdim, inv)
     return da, db
 
 

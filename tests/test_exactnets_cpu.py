@@ -2,7 +2,10 @@
 MI355X, "the kernel must equal the float64 reference bit for bit" is a theorem (check_exact: stored values survive their
 format, every partial sum is an exact fp32 number, the net is alive), the reference agrees exactly with the fp32 torch module
 and with the NumPy restatement of the reference graph, and every deliberate corruption of the reference (a swapped tap, channel
-or position, a wrapped border, a missing residual, a dropped lo half, a wrong block scale) changes the expected outputs."""
+or position, a wrapped border, a missing residual, a dropped lo half, a wrong block scale) changes the expected outputs.
+The round families, whose activations are off every engine's storage grid, also show here that the reference's explicit storage
+step meets every rounding, saturation and scale case of its list in every kind of layer, that each corruption of that step
+changes the expected outputs, and that the explicit step leaves every other family's expected outputs bit for bit as they were."""
 import numpy as np
 import pytest
 import torch
@@ -17,7 +20,7 @@ _modules = {}
 
 
 def _module(family, blocks, seed, half=torch.float16):
-    key = (family, blocks, seed, half if family == "lo" else torch.float16)
+    key = (family, blocks, seed, half if family in ("lo", "round", "round_x2") else torch.float16)
     if key not in _modules:
         _modules[key] = E.build(PolicyValueModule(blocks), family, seed, key[3])
     return _modules[key]
@@ -37,6 +40,44 @@ def test_check_exact_holds_for_every_gpu_case(family, blocks, seed, engine):
         print("%s %s x %d seed %d, %s rows: largest activation %.6g, largest sum %.3g of 2^24 granules, %d (layer, channel) pairs alive" %
               (engine, family, blocks, seed, name, r["max_activation"], r["max_sum_over_2^24g"], int(r["channels_alive"].sum())))
     assert alive.shape == (2 * blocks + 1, 128) and bool(alive.all()), "dead (layer, channel) pairs on the GPU's rows: %s" % (~alive).nonzero().tolist()
+
+
+@pytest.mark.parametrize("engine", sorted(E.ROUND_SEEDS))
+def test_round_family_meets_every_storage_case(engine):
+    """counted on the float64 reference alone, over the engine's 1- and 2-block round nets and every batch the GPU test feeds them:
+    at least 32 elements of every case of exactnets.round_cases in EVERY kind of layer that stores (first conv,
+    first and second conv of a block); mx6: 24 distinct activation scale bytes.  Condition (b) holds element by element
+    (check_exact; the largest sum / 2^24 g is printed)"""
+    tally, ratio = {}, 0.0
+    for blocks, seed in zip((1, 2), E.ROUND_SEEDS[engine]):
+        m = _module(E.ROUND_FAMILY[engine], blocks, seed, E.HALF[engine])
+        for name, x in E.gpu_batches(engine).items():
+            E.reference(m, x, engine, tally=tally)
+            ratio = max(ratio, E.check_exact(m, x, engine, liveness=False)["max_sum_over_2^24g"])
+    print("%s: largest sum / 2^24 g %.3g" % (engine, ratio))
+    for case in E.round_cases(engine):
+        per_kind = [tally.get((k, case), 0) for k in E.ROUND_KINDS]
+        print("%s %-18s %s" % (engine, case, "  ".join("%s: %d" % kc for kc in zip(E.ROUND_KINDS, per_kind))))
+        assert min(per_kind) >= 32, (engine, case, per_kind)
+    if engine == "mx6":
+        print("mx6: %d distinct activation scale bytes: %s" % (len(tally["bytes"]), sorted(tally["bytes"])))
+        assert len(tally["bytes"]) >= 24 and 1 in tally["bytes"]
+    assert ratio < 1.0
+
+
+@pytest.mark.parametrize("family,blocks,seed,engine", [c for c in _CASES if c[0] not in E.ROUND_FAMILIES])
+def test_explicit_storage_step_leaves_the_other_families_unchanged(family, blocks, seed, engine):
+    """the storage step the round families go through is the identity on every other case: the expected outputs with the step
+    forced on equal, bit for bit, those of the path without it (the clamp alone, what this reference always computed)"""
+    m = _module(family, blocks, seed, E.HALF[engine])
+    for name, x in E.gpu_batches(engine).items():
+        if name == "dense":
+            continue                               # (its rows are the first five of "live")
+        old, new = E.reference(m, x, engine, storage="identity"), E.reference(m, x, engine, storage="explicit")
+        plain = E.reference(m, x, engine)
+        for k in ("trunk", "z", "logits"):
+            assert torch.equal(old[k], new[k]) and torch.equal(old[k], plain[k]), (name, k)
+        assert all(torch.equal(a, b) for a, b in zip(old["layers"], new["layers"]))
 
 
 def test_dense_family_covers_every_tower_weight_entry():
@@ -115,8 +156,10 @@ def test_every_mutation_changes_the_expected_outputs(family, blocks, seed, engin
     x = torch.cat([E.planes("impulses")[::15], E.planes("dense", 3)])
     ref = E.reference(m, x, engine)
     names = E.applicable_mutations(family, engine, x.shape[0])
-    assert len(names) >= 6 and ("lo_zero" in names) == (family in ("lo", "lo_subnormal", "mx_cross"))
-    assert ("scale_off" in names) == (family == "mx_cross")
+    assert len(names) >= 6 and ("lo_zero" in names) == (family in ("lo", "lo_subnormal", "mx_cross", "round_x2", "round_mx"))
+    assert ("scale_off" in names) == (family in ("mx_cross", "round_mx"))
+    rnd = family in E.ROUND_FAMILIES
+    assert [n for n in E._STORE_MUTATIONS if n in names] == ([n for n, es in E._STORE_MUTATIONS.items() if engine in es] if rnd else [])
     for layer in ([1] if blocks < 3 else [1, 2 * blocks - 3]):
         for name in names:
             if layer > 1 and name in ("lo_zero", "scale_off"):
@@ -125,6 +168,9 @@ def test_every_mutation_changes_the_expected_outputs(family, blocks, seed, engin
             nt, nz = int((mut["trunk"] != ref["trunk"]).sum()), int((mut["z"] != ref["z"]).sum())
             print("%s %s x %d seed %d, layer %d, %s (%s): %d trunk values and %d head conv outputs change" %
                   (engine, family, blocks, seed, layer, name, E.MUTATIONS[name][0], nt, nz))
+            if rnd:        # (its head convs read six channels, of three classes: the trunk output or z must change)
+                assert nt + nz > 0, "%s in layer %d changes nothing: the inputs are too weak" % (name, layer)
+                continue
             assert nt > 0, "%s in layer %d changes nothing: the inputs are too weak" % (name, layer)
             assert nz > 0, "%s in layer %d does not reach the head convs" % (name, layer)
 
@@ -151,10 +197,21 @@ def test_layer_kernel_and_fc_inputs_are_provably_exact():
             w, b = cb.folded()
             for r, relu in ((None, True), (res, True), (res, False), (None, False)):
                 assert not E.conv_layer_check(x, w, b, r, relu)
+    x, res, off = E.conv_layer_rounding_inputs()          # the same kernel where its two roundings are NOT the identity
+    for seed in range(E.DENSE_SEEDS):
+        for cb in _module("dense", 1, seed).blocks[0]:
+            w, b = cb.folded()
+            for r, relu in ((None, True), (res, True), (res, False), (None, False)):
+                assert not E.conv_layer_check(x, w, b + off, r, relu, rounding=True)
     for blocks in (1, 3):
         out = E.tower_reference(_module("sparse", blocks, 0), E.layer_activations(7, 0.25, 3), "layer", check=True)
         assert float((out["trunk"] != 0).double().mean()) > 0.1 and float((out["z"] != 0).double().mean()) > 0.1
         assert all(bool(((v != 0).sum(dim=(0, 2, 3)) > 0).all()) for v in out["layers"])      # every channel of every layer is alive
+    # the round family through the per-layer route (two roundings per residual layer) and through the fused tower (one): exact, and different
+    m = _module("round", 1, E.ROUND_SEEDS["bf16"][0], torch.bfloat16)
+    fused = E.reference(m, E.batch93(), "bf16")
+    out = E.tower_reference(m, fused["layers"][0].permute(0, 2, 3, 1).reshape(93, 90, 128), "layer", check=True)
+    assert int((out["trunk"] != fused["trunk"]).sum()) >= 32
     for B in (5, 129):
         z = E.fc_inputs(B)
         assert not E.fc_check(_module("sparse", 1, 0), z)
@@ -171,6 +228,10 @@ def test_prefix_net_hands_out_layer_2k():
     for k in (1, 2):
         pk = E.reference(E.prefix_module(m, k), x, "fp16")
         assert torch.equal(pk["layers"][-1], ref["layers"][2 * k]) and len(pk["layers"]) == 2 * k + 1
+    for engine in sorted(E.ROUND_SEEDS):                     # ... under every engine's storage step too (round family, 2 blocks)
+        m = _module(E.ROUND_FAMILY[engine], 2, E.ROUND_SEEDS[engine][1], E.HALF[engine])
+        ref, pk = E.reference(m, x, engine), E.reference(E.prefix_module(m, 1), x, engine)
+        assert torch.equal(pk["layers"][-1], ref["layers"][2]) and len(pk["layers"]) == 3
     cells = E.impulse_cells(E.planes("pairs", 5, group=4))
     assert (cells >= 0).tolist() == [True, False, True, False, False] and int(cells[2]) == 14
     assert (E.impulse_cells(E.planes("pairs", 5, group=2)) >= 0).tolist() == [True, False, False, True, True]

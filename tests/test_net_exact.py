@@ -59,6 +59,8 @@ def _first_bad_layer(module, family, seed, engine, x, ref):
     for k in range(1, module.res_block_nums):
         net = _net(E.prefix_module(module, k), engine)
         got = net._hip_net_forward(x.cuda(), trunk=True)
+        if engine == "mx6":      # (a prefix net writes layer 2k as fp32 after a ReLU alone; the full net clamps it at 65504 when it stores it)
+            got = got.clamp(max=65504.0)
         exp = ref["layers"][2 * k].permute(0, 2, 3, 1).reshape(got.shape)
         if E.describe_mismatch(got, exp, "") is not None:
             return "; the first layer that differs is %d or %d (the %d-block prefix net)" % (2 * k - 1, 2 * k, k)
@@ -108,11 +110,21 @@ def test_trunk_kernel_is_bit_exact(engine, family, blocks):
 @pytest.mark.parametrize("engine", sorted(E.CASES))
 def test_trunk_kernel_is_bit_exact_under_the_device_row_count(engine):
     """the compact path (cz_set_batch_count): 11 of the 93 rows are computed, and they are the reference's bits"""
+    _row_count_case(engine, "sparse", 0)
+
+
+@pytest.mark.parametrize("engine", sorted(E.CASES))
+def test_round_trunk_kernel_is_bit_exact_under_the_device_row_count(engine):
+    """the same on the round family (1 block): the storage step of every layer under the device-side row count"""
+    _row_count_case(engine, E.ROUND_FAMILY[engine], E.ROUND_SEEDS[engine][0])
+
+
+def _row_count_case(engine, family, seed):
     from cchess_zero_amd._lib import check, lib
-    module = _module("sparse", 1, 0, E.HALF[engine])
+    module = _module(family, 1, seed, E.HALF[engine])
     net = _net(module, engine)
     x = E.batch93()
-    ref = _reference(module, "sparse", 1, 0, engine, "93", x)
+    ref = _reference(module, family, 1, seed, engine, "93", x)
     n = torch.tensor([11], dtype=torch.int32, device="cuda")
     check(lib().cz_set_batch_count(net._hip_ctx().h, C.c_void_p(n.data_ptr())), "cz_set_batch_count")
     try:
@@ -121,7 +133,7 @@ def test_trunk_kernel_is_bit_exact_under_the_device_row_count(engine):
         torch.cuda.synchronize()
     finally:
         check(lib().cz_set_batch_count(net._hip_ctx().h, None), "cz_set_batch_count")
-    what = "%s sparse x 1, 11 of 93 rows by the device-side row count" % engine
+    what = "%s %s x 1, 11 of 93 rows by the device-side row count" % (engine, family)
     msg = E.describe_mismatch(trunk, ref["trunk"][:11], what + ", trunk output", x[:11], E.GROUP[engine])
     assert msg is None, msg
     msg = E.describe_mismatch(z, ref["z"][:11], what + ", head conv outputs z", x[:11], E.GROUP[engine])
@@ -138,20 +150,38 @@ def test_conv3x3_layer_kernel_is_bit_exact(residual, relu):
     """cz_conv3x3_c128_bf16 on the dense family (every weight entry non-zero in one of its seeds): integer activations fed
     directly, residual on / off, ReLU on / off.  The kernel rounds to bf16 before the residual add: the reference's pre-residual
     sums and results are asserted to be bf16 values, so that rounding is the identity."""
+    _conv3x3_case(residual, relu, False)
+
+
+@pytest.mark.parametrize("residual,relu", [(False, True), (True, True), (True, False), (False, False)])
+def test_conv3x3_layer_kernel_rounds_to_nearest_even(residual, relu):
+    """the same kernel on activations up to 40 and biases with eighths, for which neither its rounding before the residual add nor
+    its final rounding is the identity: the reference states both, and exactnets.conv_layer_check counts at least 32 values
+    rounded down, 32 rounded up and 32 exact ties on each"""
+    _conv3x3_case(residual, relu, True)
+
+
+def _conv3x3_case(residual, relu, rounding):
     from cchess_zero_amd.net import PolicyValueNet
-    x = E.layer_activations(5, 0.3, 3)
-    res = torch.roll(E.layer_activations(6, 0.3, 3), 1, 0) if residual else None
+    if rounding:
+        x, res, off = E.conv_layer_rounding_inputs()
+    else:
+        x, res, off = E.layer_activations(5, 0.3, 3), torch.roll(E.layer_activations(6, 0.3, 3), 1, 0), torch.zeros(128)
+    res = res if residual else None
     for seed in range(E.DENSE_SEEDS):
         module = _module("dense", 1, seed, torch.bfloat16)
         net = PolicyValueNet(1, "cuda:0", torch.bfloat16, module=module, backend="hip-layer")
         for li, cb in enumerate(module.blocks[0]):
             w, b = cb.folded()
-            exp, pre = E.conv_layer_reference(x, w, b, res, relu)
-            assert not E.conv_layer_check(x, w, b, res, relu)
+            b = b.cpu() + off
+            exp = E.conv_layer_reference(x, w, b, res, relu)[0]
+            assert not E.conv_layer_check(x, w, b, res, relu, rounding)
             out = torch.full((x.shape[0], 90, 128), float("nan"), device="cuda", dtype=torch.bfloat16)
-            net._hip_conv(x.cuda().to(torch.bfloat16), net.hip_blocks[0][li], res.cuda().to(torch.bfloat16) if residual else None, out, relu)
+            wp, bp = net.hip_blocks[0][li]
+            assert bp.dtype == torch.float32 and torch.equal(bp.cpu(), cb.folded()[1].cpu())
+            net._hip_conv(x.cuda().to(torch.bfloat16), (wp, b.float().cuda().contiguous()), res.cuda().to(torch.bfloat16) if residual else None, out, relu)
             torch.cuda.synchronize()
-            msg = E.describe_mismatch(out, exp, "cz_conv3x3_c128_bf16 dense seed %d layer %d residual %s relu %s" % (seed, li, residual, relu))
+            msg = E.describe_mismatch(out, exp, "cz_conv3x3_c128_bf16 dense seed %d layer %d residual %s relu %s rounding %s" % (seed, li, residual, relu, rounding))
             assert msg is None, msg + _impulse_note(x, int(msg.split("first at row ")[1].split(" ")[0]))
 
 
@@ -173,6 +203,31 @@ def test_tower_layer_kernels_are_bit_exact(blocks):
                        ("cz_conv3x3_c128_bf16 layer by layer", per_layer, ref["trunk"])):
         msg = E.describe_mismatch(g, e, "%s, sparse x %d" % (name, blocks))
         assert msg is None, msg + _impulse_note(x, int(msg.split("first at row ")[1].split(" ")[0]))
+
+
+def test_tower_layer_kernels_round_to_nearest_even():
+    """the same three routes on the round family (bf16, 1 block), fed the reference's stored first-conv activations of the 93
+    rows: no rounding is the identity here.  cz_tower_c128_bf16 / cz_tower_heads_c128_bf16 add the residual in fp32 and round
+    once (the bf16 engine's reference); cz_conv3x3_c128_bf16 block by block rounds before the residual add and again after it
+    (the "layer" reference, whose conditions of exactness are asserted) — and the two references differ"""
+    from cchess_zero_amd.net import PolicyValueNet
+    seed = E.ROUND_SEEDS["bf16"][0]
+    module = _module("round", 1, seed, torch.bfloat16)
+    net = PolicyValueNet(1, "cuda:0", torch.bfloat16, module=module, backend="hip-layer")
+    fused = _reference(module, "round", 1, seed, "bf16", "93", E.batch93())
+    x = fused["layers"][0].permute(0, 2, 3, 1).reshape(93, 90, 128)
+    assert torch.equal(x.float().to(torch.bfloat16).double(), x)
+    ref = E.tower_reference(module, x, "layer", check=True)
+    assert int((ref["trunk"] != fused["trunk"]).sum()) >= 32
+    h = x.float().cuda().to(torch.bfloat16).reshape(-1, 9, 10, 128).permute(0, 3, 1, 2)
+    got = net._hip_tower_forward(h.clone(memory_format=torch.channels_last)).permute(0, 2, 3, 1).reshape(x.shape)
+    z = net._hip_tower_heads_forward(h.clone(memory_format=torch.channels_last))
+    per_layer = net._hip_blocks_forward(h.clone(memory_format=torch.channels_last)).permute(0, 2, 3, 1).reshape(x.shape)
+    torch.cuda.synchronize()
+    for name, g, e in (("cz_tower_c128_bf16 tower output", got, fused["trunk"]), ("cz_tower_heads_c128_bf16 z", z, fused["z"]),
+                       ("cz_conv3x3_c128_bf16 layer by layer", per_layer, ref["trunk"])):
+        msg = E.describe_mismatch(g, e, "%s, round x 1" % name, E.batch93())
+        assert msg is None, msg
 
 
 @pytest.mark.parametrize("B", [5, 129])
