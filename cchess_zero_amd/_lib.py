@@ -25,6 +25,8 @@ SP_CHASE_STATS = ("chases",)                               # cz_selfplay_chase_s
 MATCH_KING, MATCH_RR60, MATCH_PLY_CAP, MATCH_ABORTED, MATCH_MATE, MATCH_REPETITION, MATCH_PERPETUAL = 1, 2, 3, 4, 5, 6, 7
 MATCH_CHASE = 9   # 8 is not assigned
 MATCH_RESIGN = 10
+MATCH_TABLEBASE = 11   # cz_match_set_tablebase / cz_selfplay_set_tablebase: the position after the move is in a table
+SP_TABLEBASE_STATS = ("tablebase",)   # cz_selfplay_tablebase_stats
 SP_RESIGN_STATS = ("resigned", "playon_games", "playon_would_resign", "playon_false_positives")   # cz_selfplay_resign_stats
 # verdicts of cz_repetition (include/cchess_hip.h: CZ_REP_*)
 REP_NONE, REP_DRAW, REP_RED_LOSES, REP_BLACK_LOSES = 0, 1, 2, 3
@@ -34,6 +36,7 @@ CAUSE_NONE, CAUSE_CHECK, CAUSE_CHASE = 0, 1, 2
 POS_IN_CHECK, POS_CAN_TAKE_KING, POS_NO_SAFE_MOVE = 1, 2, 4
 MATE_NONE = 0x7FFF   # cz_mate_backup (include/cchess_hip.h: CZ_MATE_NONE): no mate proven
 TB_ILLEGAL, TB_UNKNOWN, TB_MISS, TB_MAX_SLOTS = -32768, 32767, 32766, 10   # tablebase values (include/cchess_hip.h: CZ_TB_*)
+TB_SET_MAX = 256   # signatures of one table set (CZ_TB_SET_MAX)
 
 # cz_games_replay (include/cchess_hip.h: CZ_GAME_*): why a game's replay stopped, and the end_flags bits beside POS_*
 GAME_OK, GAME_ILLEGAL, GAME_AFTER_END, GAME_BAD_BOARD, GAME_BAD_LEN, GAME_AMBIGUOUS = 0, 1, 2, 3, 4, 5   # 5: cz_games_read only
@@ -66,6 +69,9 @@ _SIGS = {
     "cz_tb_pass": (C.c_int, [C.c_void_p, C.c_char_p, _vp, C.POINTER(C.c_void_p), C.c_int, _vp]),
     "cz_tb_probe": (C.c_int, [C.c_void_p, C.c_char_p, _vp, _u8p, _u8p, C.c_int, _vp, _i32p]),
     "cz_tb_boards": (C.c_int, [C.c_void_p, C.c_char_p, _i32p, C.c_int, _u8p, _u8p]),
+    "cz_tb_set_create": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "cz_tb_set_destroy": (C.c_int, [C.c_void_p]),
+    "cz_tb_set_probe": (C.c_int, [C.c_void_p, C.c_void_p, _u8p, _u8p, C.c_int, _vp, _i32p]),
     "cz_repetition": (C.c_int, [C.c_void_p, _vp, _u8p, C.c_int, _i32p, _i32p, _u8p, C.c_int, C.c_int, _u8p, _i32p]),
     "cz_threats": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_int, _vp]),
     "cz_repetition_chase": (C.c_int, [C.c_void_p, _vp, _u8p, _vp, C.c_int, _i32p, _i32p, _u8p, C.c_int, C.c_int, _u8p, _i32p, _u8p]),
@@ -125,6 +131,9 @@ _SIGS = {
     "cz_selfplay_chase_stats": (C.c_int, [C.c_void_p, _vp]),
     "cz_selfplay_set_resign": (C.c_int, [C.c_void_p, C.c_float, C.c_int, C.c_double, C.c_ulonglong]),
     "cz_selfplay_resign_stats": (C.c_int, [C.c_void_p, _vp, _vp]),
+    "cz_selfplay_set_tablebase": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "cz_selfplay_tablebase_stats": (C.c_int, [C.c_void_p, _vp]),
+    "cz_match_set_tablebase": (C.c_int, [C.c_void_p, C.c_void_p]),
     "cz_match_set_resign": (C.c_int, [C.c_void_p, C.c_float, C.c_int]),
     "cz_match_create": (C.c_int, [C.c_void_p, C.c_void_p, _u8p, _u8p, _i32p, C.c_int, C.c_longlong, C.c_longlong, C.c_int,
                                   C.POINTER(C.c_void_p)]),

@@ -27,25 +27,30 @@ import time
 import numpy as np
 import torch
 
-from ._lib import (MATCH_ABORTED, MATCH_CHASE, MATCH_KING, MATCH_MATE, MATCH_PERPETUAL, MATCH_PLY_CAP, MATCH_REPETITION, MATCH_RESIGN, MATCH_RR60, NSQ, call,
+from ._lib import (MATCH_ABORTED, MATCH_CHASE, MATCH_KING, MATCH_MATE, MATCH_PERPETUAL, MATCH_PLY_CAP, MATCH_REPETITION, MATCH_RESIGN, MATCH_RR60, MATCH_TABLEBASE, NSQ, call,
                    lib, out_pointers, tables)
 from .engine import SearchEngine, plane_format, pool_nodes
 from .notation import player_to_side, state_to_board
 from .rules import RULES, check_rule_options, root_rules_chase_history, root_rules_history, set_rule_options   # noqa: F401 (RULES: re-exported)
 
 REASONS = {0: "unfinished", MATCH_KING: "king", MATCH_RR60: "rr60", MATCH_PLY_CAP: "ply_cap", MATCH_ABORTED: "aborted", MATCH_MATE: "mate",
-           MATCH_REPETITION: "repetition", MATCH_PERPETUAL: "perpetual", MATCH_CHASE: "chase", MATCH_RESIGN: "resign"}
+           MATCH_REPETITION: "repetition", MATCH_PERPETUAL: "perpetual", MATCH_CHASE: "chase", MATCH_RESIGN: "resign", MATCH_TABLEBASE: "tablebase"}
 
 
-def is_scored(reason, resign=False):
+def is_scored(reason, resign=False, tablebase=False):
     """A finished game that counts: every ending but "aborted" (a mate, rules="xiangqi", is a loss for the mated side; with
     repetition != 0 a repetition is a draw and a perpetual check a loss for the checking side; with chase a perpetual chase is
     a loss for the chasing side).  resign: the match was played with resignation (Match(resign=...)) — then, and only then, a
     game can end as "resign", a loss for the side that resigned, and counts; in a match without it no game carries that reason
-    and the code counts no more than an unassigned one."""
+    and the code counts no more than an unassigned one.  tablebase: the match was played with a table set (Match(tablebase=...))
+    — the same for "tablebase", the table's result of the position a game reached."""
     reason = np.asarray(reason, np.int64)
     scored = ((reason >= MATCH_KING) & (reason <= MATCH_PLY_CAP)) | ((reason >= MATCH_MATE) & (reason <= MATCH_PERPETUAL)) | (reason == MATCH_CHASE)
-    return scored | (reason == MATCH_RESIGN) if resign else scored
+    if resign:
+        scored = scored | (reason == MATCH_RESIGN)
+    if tablebase:
+        scored = scored | (reason == MATCH_TABLEBASE)
+    return scored
 
 
 # ---- openings ------------------------------------------------------------------------------------------------------------
@@ -169,12 +174,12 @@ def elo(score):
     return -400.0 * math.log10(1.0 / score - 1.0)
 
 
-def pentanomial(result, reason, resign=False):
+def pentanomial(result, reason, resign=False, tablebase=False):
     """Counts of the opening pairs' scores for A: index k = points out of 2 times 2 (0, 0.5, 1, 1.5, 2 -> 0..4), over the
-    pairs (games 2p, 2p + 1) whose two games were both scored (an aborted game drops its pair); resign as is_scored's."""
+    pairs (games 2p, 2p + 1) whose two games were both scored (an aborted game drops its pair); resign, tablebase as is_scored's."""
     result = np.asarray(result, np.int64)
     reason = np.asarray(reason, np.int64)
-    scored = is_scored(reason, resign)
+    scored = is_scored(reason, resign, tablebase)
     pair_ok = scored[0::2] & scored[1::2]
     x = (result[0::2] + 1) + (result[1::2] + 1)          # twice A's points of the pair: 0..4
     return np.bincount(x[pair_ok], minlength=5)[:5].astype(np.int64)
@@ -201,9 +206,11 @@ class MatchResult:
     rules ("capture" / "xiangqi") and mates: the games that ended because the mover had no king-safe move; repetition (the
     fold, 0 = no such rule), repetitions: the games drawn by it, perpetuals: the games lost by perpetual check; chase (the
     perpetual-chase rule was on), chases: the games lost by perpetual chase; resign (the threshold the match resigned on, None = games were played
-    out), resigns: the games a mover resigned."""
+    out), resigns: the games a mover resigned; tablebase (the match was played with a table set), tablebases: the games that
+    ended with a table's result."""
 
-    def __init__(self, result, a_red, plies, reason, moves, simulations, seconds, players, rules="capture", repetition=0, chase=False, resign=None):
+    def __init__(self, result, a_red, plies, reason, moves, simulations, seconds, players, rules="capture", repetition=0, chase=False, resign=None,
+                 tablebase=False):
         self.result = np.asarray(result, np.int8)
         self.a_red = np.asarray(a_red, np.uint8)
         self.plies = np.asarray(plies, np.int32)
@@ -212,7 +219,9 @@ class MatchResult:
         self.moves = [[lab[int(x)] for x in row if x != 0xFFFF] for row in moves] if moves is not None else None
         self.games = len(self.result)
         self.resign = None if resign is None else float(resign)
-        scored = is_scored(self.reason, self.resign is not None)
+        self.tablebase = bool(tablebase)
+        self.tablebases = int((self.reason == MATCH_TABLEBASE).sum())
+        scored = is_scored(self.reason, self.resign is not None, self.tablebase)
         self.rules = rules
         self.mates = int((self.reason == MATCH_MATE).sum())
         self.repetition = int(repetition)
@@ -233,7 +242,7 @@ class MatchResult:
         self.by_colour = {"red": wdl(self.a_red == 1), "black": wdl(self.a_red == 0)}
         self.score = (self.wins + 0.5 * self.draws) / self.scored if self.scored else None
         self.elo = elo(self.score)
-        self.pentanomial = pentanomial(self.result, self.reason, self.resign is not None)
+        self.pentanomial = pentanomial(self.result, self.reason, self.resign is not None, self.tablebase)
         iv = pentanomial_interval(self.pentanomial)
         self.elo_95 = None if iv is None else (elo(iv[1]) if iv[1] > 0 else None, elo(iv[2]) if iv[2] < 1 else None)
         self.simulations = int(simulations)
@@ -246,7 +255,7 @@ class MatchResult:
         """The summary (no per-game arrays): what `python -m cchess_zero_amd.arena` prints.  elo None = infinite (every
         scored game won or lost) or no scored game; an interval end None = unbounded on that side."""
         return dict(rules=self.rules, mates=self.mates, repetition=self.repetition, repetitions=self.repetitions, perpetuals=self.perpetuals,
-                    chase=self.chase, chases=self.chases, resign=self.resign, resigns=self.resigns, games=self.games, scored=self.scored, aborted=self.aborted, unfinished=self.unfinished, W=self.wins,
+                    chase=self.chase, chases=self.chases, resign=self.resign, resigns=self.resigns, tablebase=self.tablebase, tablebases=self.tablebases, games=self.games, scored=self.scored, aborted=self.aborted, unfinished=self.unfinished, W=self.wins,
                     D=self.draws, L=self.losses, by_colour=self.by_colour, score=self.score, elo=self.elo,
                     elo_95=None if self.elo_95 is None else list(self.elo_95), pentanomial=self.pentanomial.tolist(),
                     mean_plies=float(self.plies.mean()) if self.games else 0.0,
@@ -324,11 +333,18 @@ class Match:
     perpetually, a side that alone threatened one and the same unprotected piece after every one of its moves of the cycle has
     lost ("chase"; cz_match_set_chase, Rules.threats).
     resign: None — every game is played out; a value — from ply resign_min_ply of a game on, a mover whose root value (the Q of its
-    most visited candidate child, on its own tree) is below it has lost ("resign"; cz_match_set_resign)."""
+    most visited candidate child, on its own tree) is below it has lost ("resign"; cz_match_set_resign).
+    tablebase (rules="xiangqi" only): None — games are played out; a tablebase.Tablebase (all its loaded tables) or a
+    tablebase.DeviceSet — a game whose position after a move is in one of the tables ends there with the table's result
+    ("tablebase"; cz_match_set_tablebase).  An opening that is itself covered plays one ply first."""
 
     def __init__(self, player_a, player_b, openings, slots, max_plies=512, sample_plies=0, seed=0, check_every=8,
-                 nodes_per_tree=None, rules="capture", repetition=0, chase=False, resign=None, resign_min_ply=0):
+                 nodes_per_tree=None, rules="capture", repetition=0, chase=False, resign=None, resign_min_ply=0, tablebase=None):
         check_rule_options("Match", rules, repetition, chase)
+        if tablebase is not None and rules != "xiangqi":
+            raise ValueError("Match: tablebase needs rules='xiangqi' (a table holds values under xiangqi rules)")
+        self.tablebase = tablebase
+        self._tb_set = self._tb_own = None
         if int(resign_min_ply) < 0:
             raise ValueError("Match: resign_min_ply >= 0")
         self.resign = None if resign is None else float(resign)
@@ -363,7 +379,7 @@ class Match:
             local = merge_ranks(local, n_pairs, rank, world)
         return MatchResult(local["result"], local["a_red"], local["plies"], local["reason"], local["moves"], local["simulations"],
                            local["seconds"], [_describe(p) for p in self.players], rules=self.rules, repetition=self.repetition,
-                           chase=self.chase, resign=self.resign)
+                           chase=self.chase, resign=self.resign, tablebase=self.tablebase is not None)
 
     def _play_local(self, op, pair_base, pair_stride):
         self.start(op, pair_base, pair_stride)
@@ -413,6 +429,10 @@ class Match:
         set_rule_options("cz_match", self._h, self.rules, self.repetition, self.chase)
         if self.resign is not None:
             call("cz_match_set_resign", self._h, self.resign, self.resign_min_ply)
+        if self.tablebase is not None:   # a Tablebase: a set over its loaded tables, this match's to close
+            self._tb_set = self.tablebase.device_set() if hasattr(self.tablebase, "device_set") else self.tablebase
+            self._tb_own = self._tb_set if self._tb_set is not self.tablebase else None
+            call("cz_match_set_tablebase", self._h, self._tb_set.h)
         self.masks = [out_pointers("cz_match_active", self._h, 1, player)[0] for player in (0, 1)]
         self.played = torch.empty(G, dtype=torch.int16, device=dev)
 
@@ -470,8 +490,11 @@ class Match:
 
     def close(self):
         if getattr(self, "_h", None):
-            lib().cz_match_destroy(self._h)
+            lib().cz_match_destroy(self._h)   # gives the table set back
             self._h = None
+        if self._tb_own is not None:
+            self._tb_own.close()
+        self._tb_set = self._tb_own = None
 
 
 # ---- command line --------------------------------------------------------------------------------------------------------
@@ -518,11 +541,18 @@ def main(argv=None):
     ap.add_argument("--resign", type=float, default=None,
                     help="a mover whose root value (Q of its most visited move) is below X resigns; default: games are played out")
     ap.add_argument("--resign_min_ply", type=int, default=0, help="with --resign: plies of a game before anybody may resign")
+    ap.add_argument("--tablebase", metavar="DIR", default=None,
+                    help="with --rules xiangqi: a game that reaches a position of a table in DIR (python -m cchess_zero_amd.tablebase --build) "
+                         "ends there with the table's result")
     args = ap.parse_args(argv)
     try:
         check_rule_options("arena", args.rules, args.repetition, args.chase)
     except ValueError as e:
         ap.error(str(e))
+    if args.tablebase and args.rules != "xiangqi":
+        ap.error("--tablebase needs --rules xiangqi (a table holds values under xiangqi rules)")
+    if args.tablebase and not os.path.isdir(args.tablebase):
+        ap.error("--tablebase: %s is no directory" % args.tablebase)
     a = load_player(args.a, args.blocks)
     b = a if args.b == args.a else load_player(args.b, args.blocks)
     if args.all_openings:
@@ -534,9 +564,15 @@ def main(argv=None):
     else:
         pairs = ((256 if args.games is None else args.games) + 1) // 2
         op = random_openings(pairs, args.opening_plies, args.seed)
+    tb = None
+    if args.tablebase:   # under several ranks every rank loads the directory itself
+        from .tablebase import Tablebase
+        tb = Tablebase()
+        if not tb.load(args.tablebase):
+            ap.error("--tablebase: no table in %s" % args.tablebase)
     res = Match((a, args.playout), (b, args.playout_b or args.playout), op, slots=args.slots or 2 * pairs, max_plies=args.max_plies,
                 sample_plies=args.sample_plies, seed=args.seed, rules=args.rules, repetition=args.repetition, chase=args.chase,
-                resign=args.resign, resign_min_ply=args.resign_min_ply).play()
+                resign=args.resign, resign_min_ply=args.resign_min_ply, tablebase=tb).play()
     d = res.to_dict()
     d.update(a=args.a, b=args.b, blocks=args.blocks, opening_plies=args.opening_plies, slots=min(args.slots or 2 * pairs, 2 * pairs),
              seed=args.seed)

@@ -118,6 +118,9 @@ struct CzSelfplay {
     CzRootRules rr;
     long long *xq_stats;         // [3] games ended by mate, by a repetition draw, by perpetual check (cz_selfplay_rules_stats)
     long long *chase_stat;       // [1] games ended by perpetual chase (cz_selfplay_chase_stats)
+    // cz_selfplay_set_tablebase: an allocation of its own (cz_ctx::sp_tb_block).  tb_value NULL: no set is attached, nothing is probed
+    int16_t *tb_value;           // [max_games] the table set's value of every slot's root position after the move (k_tb_probe_set)
+    long long *tb_stat;          // [1] games adjudicated from a table (cz_selfplay_tablebase_stats); NULL before the first attach
     CzSpResign rs;               // cz_selfplay_set_resign
 };
 
@@ -226,6 +229,8 @@ struct cz_ctx {
     int sp_chase;      // cz_selfplay_set_chase: 0 off, 1 on (needs a fold, sp.rr.fold: cz_selfplay_set_repetition)
     void *sp_chase_block;
     void *sp_resign_block;   // cz_selfplay_set_resign: allocated by its first call, sp.rs points into it while resignation is set
+    cz_tb_set *sp_tb;         // cz_selfplay_set_tablebase: the attached table set (not owned), or NULL
+    void *sp_tb_block;        // allocated by the first attach since cz_create: sp.tb_value and sp.tb_stat
     int sp_state;     // 0: no cz_selfplay_begin yet, 1: begun (the setters may be called), 2: a cz_selfplay_choose has run since
     void *ec_block;    // cz_search_set_eval_cache
 };
@@ -308,12 +313,18 @@ __device__ __forceinline__ bool root_cannot_move(const CzTrees &t, int g, int n)
 struct CzGameEnd { int how, loser; };
 // THE PRECEDENCE OF THE ENDINGS, at rule level LEVEL, on slot g after its choose and advance, by one wave64: the verdict of the
 // repetition rule the choose left in rr.rep[g] (with CZ_REP_BY_CHASE: a chase) > a mated mover (rr.mated[g]) > a resignation >
-// an aborted game > check_end (main.py:1380-1392: a king is gone, then 60 plies without a capture) > the driver's ply cap.
+// an aborted game > a table's value of the position after the move (CZ_MATCH_TABLEBASE) > check_end (main.py:1380-1392: a king is
+// gone, then 60 plies without a capture) > the driver's ply cap.
 // The first three were found by the choose on the root it then left untouched, so the side to move (root_side) is the mover that
 // loses a mate or a resignation; `resigned` and `aborted` are the caller's own.  rr is not read below CZ_RULES_KINGSAFE.
+// tb: what the attached table set answers for the root position (k_tb_probe_set), from the side to move's view — CZ_TB_MISS when no
+// set is attached, for a slot that did not just move, and from the bench driver.  A covered value (neither CZ_TB_MISS nor
+// CZ_TB_ILLEGAL) ends the game: tb > 0 the side to move wins, tb < 0 it loses, 0 a draw.  It stands in front of the no-capture
+// counter and the ply cap because a forced mate is a mate whatever they say (the tables' own stance), and behind the endings the
+// choose found because those were found on the root that was then not left: the table judges the position AFTER a move.
 template <int LEVEL>
-__device__ __forceinline__ CzGameEnd wave_game_end(const CzRootRules &rr, int g, bool resigned, bool aborted, const uint8_t *root_board, int root_rr,
-                                                   int root_side, int ply, int max_plies, int lane) {
+__device__ __forceinline__ CzGameEnd wave_game_end(const CzRootRules &rr, int g, bool resigned, bool aborted, int tb, const uint8_t *root_board,
+                                                   int root_rr, int root_side, int ply, int max_plies, int lane) {
     int verdict = CZ_REP_NONE;
     bool by_chase = false;
     if constexpr (LEVEL >= CZ_RULES_REPETITION) verdict = rr.rep[g];
@@ -325,6 +336,7 @@ __device__ __forceinline__ CzGameEnd wave_game_end(const CzRootRules &rr, int g,
     if (LEVEL >= CZ_RULES_KINGSAFE && rr.mated[g]) return {CZ_MATCH_MATE, root_side};
     if (resigned) return {CZ_MATCH_RESIGN, root_side};
     if (aborted) return {CZ_MATCH_ABORTED, -1};
+    if (tb != CZ_TB_MISS && tb != CZ_TB_ILLEGAL) return {CZ_MATCH_TABLEBASE, tb > 0 ? 1 - root_side : (tb < 0 ? root_side : -1)};
     if (Kmiss || kmiss) return {CZ_MATCH_KING, 1 - king_capture_winner(Kmiss)};
     if (restrict_round_draw(root_rr)) return {CZ_MATCH_RR60, -1};
     if (ply >= max_plies) return {CZ_MATCH_PLY_CAP, -1};
@@ -468,6 +480,21 @@ int cz_tree_preorder(cz_ctx *c, int g, CzPreorder &out);   // after a stream syn
 // every tree's evaluation-cache counters (CzTreeRec::ec_*) back to 0, in stream order: cz_search_set_eval_cache (cz_evalcache.hip)
 int cz_search_clear_cache_stats(cz_ctx *c);
 
+// ---- table sets (cz_tablebase.hip, cz_tablebase_set.hip; the consumers are cz_selfplay.hip and cz_match.hip) ----
+struct CztbDesc;
+// the signature -> its descriptor, or CZ_EINVAL with `who` in the text
+int tb_desc(const char *who, const char *signature, CztbDesc *d);
+// One k_tb_probe_set launch: position i < G is the 90 bytes at boards + i * board_stride and the byte side[i * side_stride].
+// board_stride 90: boards at any address (cz_tb_set_probe); otherwise a multiple of 16 with 16-byte aligned boards, each lane
+// reading its own row — the trees' root boards in place (CZD_BOARD_LDS apart, the sides inside the 64-byte tree records).
+// moved [G] or NULL: position i is probed only when moved[i] is a label (< CZ_NLABELS), and answers CZ_TB_MISS otherwise.
+int cz_tb_set_probe_strided(cz_ctx *c, const cz_tb_set *set, const uint8_t *boards, int board_stride, const uint8_t *side, int side_stride,
+                            const uint16_t *moved, int G, int16_t *value, int32_t *which);
+// a consumer takes / gives back its hold on a set: cz_tb_set_destroy refuses a set that is held
+void cz_tb_set_hold(cz_tb_set *set, int delta);
+// what both consumers' setters ask of a set and of their rule level: CZ_EINVAL with api ("cz_selfplay" / "cz_match") in the text
+int cz_tb_set_attachable(const char *api, const char *handle, const cz_ctx *c, const cz_tb_set *set, int rules);
+
 // ---- the rules at the root, host side (cz_rootrules.h; cz_match.hip, cz_selfplay.hip) ----
 // the arrays of G slots inside the carver's allocation: the chase rings (chase_part), or everything else
 inline void carve_root_rules(Carver &k, CzRootRules &rr, size_t G, bool chase_part) {
@@ -498,18 +525,19 @@ inline int czk_root_rules_prepare(cz_ctx *c, const CzRootRules &rr, int G, int l
 }
 
 // The order a consumer's three setters keep — rules before the fold, the fold before the chase rule, off in the reverse order,
-// nothing after the first choose (started) — for the call `what` with argument `value` on a consumer in state (rules, fold,
+// nothing after the first choose (started), no rules 0 under an attached table set (tablebase) — for the call `what` with argument `value` on a consumer in state (rules, fold,
 // chase).  api ("cz_match" / "cz_selfplay") and handle ("match" / "ctx") are the names the error texts speak of, since: where
 // the consumer's history starts.
 enum CzRuleSetter { CZ_SET_RULES, CZ_SET_REPETITION, CZ_SET_CHASE };
 inline int cz_root_rules_order(const char *api, const char *handle, const char *since, int what, int value, int rules, int fold, int chase,
-                               bool started) {
+                               bool started, bool tablebase = false) {
     const std::string a(api), h(handle), late = "before the first " + a + "_choose only (";
     std::string e;
     if (what == CZ_SET_RULES) {
         if (value != 0 && value != 1) e = a + "_set_rules: rules 0 (king capture) or 1 (xiangqi)";
         else if (started) e = a + "_set_rules: " + late + "a game is played under one set of rules)";
         else if (value == 0 && fold != 0) e = a + "_set_rules: the repetition rule needs rules 1: " + a + "_set_repetition(" + h + ", 0) first";
+        else if (value == 0 && tablebase) e = a + "_set_rules: the table set needs rules 1: " + a + "_set_tablebase(" + h + ", NULL) first";
     } else if (what == CZ_SET_REPETITION) {
         if (value != 0 && (value < 2 || value > 8)) e = a + "_set_repetition: fold 0 (off) or 2..8";
         else if (started) e = a + "_set_repetition: " + late + since + ")";

@@ -34,6 +34,7 @@ struct CzMatch {
     uint8_t *reason;              // [n_games] CZ_MATCH_*
     uint16_t *moves;              // [n_games][max_plies] labels played, 0xFFFF past the end
     CzRootRules rr;               // rules = 1: the rules at the root (cz_rootrules.h), of the mover's root positions; NULL before
+    int16_t *tb_value;            // [G] cz_match_set_tablebase: the set's value of the slot's position after the move; NULL while off
 };
 
 struct cz_match {
@@ -46,6 +47,8 @@ struct cz_match {
     bool chosen;                        // a cz_match_choose has run: the repetition rule can no longer be switched on
     int chase;                          // 1: perpetual chase is judged too (cz_match_set_chase; needs a fold)
     void *chase_block;                  // allocated by the first cz_match_set_chase(1): the slots' rings of chase records
+    cz_tb_set *tb;                      // cz_match_set_tablebase: the attached table set (not owned), or NULL
+    void *tb_block;                     // allocated by the first attach: m.tb_value
 };
 
 namespace {
@@ -150,7 +153,8 @@ __global__ __launch_bounds__(64) void k_match_roots_xq(CzTrees ta, CzTrees tb, C
 // plus the match's own endings (ply cap, aborted game), the result, and the slot's next game.  Whether and how the game ended
 // is wave_game_end's answer (cz_internal.h: the one precedence of the endings, in the match's own CZ_MATCH_* codes), the result
 // follows from the side it names as the loser; `aborted` here is a stalled choose, no label played, or a label that is no child
-// of the mover's root.
+// of the mover's root.  cz_match_set_tablebase: m.tb_value[g] is the attached set's value of the position after the move
+// (k_tb_probe_set, the launch in front of this one; CZ_TB_MISS for a slot whose `played` is no label).
 template <int LEVEL>
 __global__ __launch_bounds__(64) void k_match_adjudicate(CzTrees ta, CzTrees tb, CzMatch m, const uint16_t *__restrict__ played) {
     constexpr bool XQ = LEVEL >= CZ_RULES_KINGSAFE, REP = LEVEL >= CZ_RULES_REPETITION;
@@ -162,7 +166,8 @@ __global__ __launch_bounds__(64) void k_match_adjudicate(CzTrees ta, CzTrees tb,
     const CzTrees &mv = ma ? ta : tb, &fo = ma ? tb : ta;   // the mover's tree, the follower's
     const bool aborted = m.stalled[g] != 0 || played[g] >= CZ_NLABELS || (mv.status[g] & CZ_ST_BAD_ADVANCE) != 0;
     const int ply = m.ply[g];
-    const CzGameEnd end = wave_game_end<LEVEL>(m.rr, g, m.resigned[g] != 0, aborted, mv.root_board + (size_t)g * CZD_BOARD_LDS, mv.root_rr[g],
+    const int tbv = m.tb_value ? (int)m.tb_value[g] : CZ_TB_MISS;
+    const CzGameEnd end = wave_game_end<LEVEL>(m.rr, g, m.resigned[g] != 0, aborted, tbv, mv.root_board + (size_t)g * CZD_BOARD_LDS, mv.root_rr[g],
                                                mv.root_side[g], ply, m.max_plies, lane);
     if (lane == 0) fo.status[g] &= ~CZ_ST_BAD_ADVANCE;
     if (!end.how) {
@@ -258,7 +263,8 @@ int cz_match_create(cz_ctx *a, cz_ctx *b, const uint8_t *boards, const uint8_t *
 static int match_order(const cz_match *mh, int what, int value) {
     const char *since = "the history starts at the openings";
     if (!mh) return cz_root_rules_order("cz_match", "match", since, what, -1, 0, 0, 0, false);   // the text of a value out of range
-    return cz_root_rules_order("cz_match", "match", since, what, value, mh->rules, mh->m.rr.fold, mh->chase, what != CZ_SET_RULES && mh->chosen);
+    return cz_root_rules_order("cz_match", "match", since, what, value, mh->rules, mh->m.rr.fold, mh->chase, what != CZ_SET_RULES && mh->chosen,
+                               mh->tb != nullptr);
 }
 
 // one part of m.rr (carve_root_rules) in a zeroed allocation of its own
@@ -310,9 +316,26 @@ int cz_match_set_resign(cz_match *mh, float threshold, int min_ply) {
     return CZ_OK;
 }
 
+int cz_match_set_tablebase(cz_match *mh, cz_tb_set *set) {
+    CZ_REQUIRE(mh, "cz_match_set_tablebase: null match");
+    if (const int rc = cz_tb_set_attachable("cz_match", "match", mh->a, set, mh->rules)) return rc;
+    if (set) {
+        const int rc = carve_alloc(&mh->tb_block, mh->a->stream, false, "cz_match_set_tablebase", [&](Carver &k) { mh->m.tb_value = k.take<int16_t>((size_t)mh->G); });
+        if (rc != CZ_OK) { mh->m.tb_value = nullptr; return rc; }
+    } else {
+        mh->m.tb_value = nullptr;
+    }
+    cz_tb_set_hold(set, 1);
+    cz_tb_set_hold(mh->tb, -1);
+    mh->tb = set;
+    return CZ_OK;
+}
+
 void cz_match_destroy(cz_match *mh) {
     if (!mh) return;
     (void)hipStreamSynchronize(mh->a->stream);
+    cz_tb_set_hold(mh->tb, -1);
+    if (mh->tb_block) (void)hipFree(mh->tb_block);
     (void)hipFree(mh->block);
     if (mh->rules_block) (void)hipFree(mh->rules_block);
     if (mh->chase_block) (void)hipFree(mh->chase_block);
@@ -346,6 +369,12 @@ int cz_match_choose(cz_match *mh, int sample_plies, unsigned long long seed, uin
 int cz_match_adjudicate(cz_match *mh, const uint16_t *played) {
     CZ_REQUIRE(mh && played, "cz_match_adjudicate: null argument");
     CZ_REQUIRE(mh->a->G == mh->G && mh->b->G == mh->G, "cz_match_adjudicate: a context was reset to another number of slots");
+    if (mh->tb && mh->m.tb_value) {   // both trees hold the position after the move (cz_search_advance applies a label to the board of either): A's, in place
+        cz_ctx *a = mh->a;
+        if (const int rc = cz_tb_set_probe_strided(a, mh->tb, a->t.root_board, CZD_BOARD_LDS, &a->t.root_side[0], (int)sizeof(CzTreeRec), played, mh->G,
+                                                   mh->m.tb_value, nullptr))
+            return rc;
+    }
     cz_by_rules_level(cz_rules_level(mh->rules, mh->m.rr.fold, mh->chase), [&](auto L) {
         hipLaunchKernelGGL(k_match_adjudicate<decltype(L)::value>, dim3(mh->G), dim3(64), 0, mh->a->stream, mh->a->t, mh->b->t, mh->m, played);
     });

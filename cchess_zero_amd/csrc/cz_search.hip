@@ -63,7 +63,7 @@ __global__ __launch_bounds__(64) void k_reload_finished(CzTrees t, int G, const 
     if (g >= G || !ready[g]) return;
     // check_end (main.py:1380-1392): a king is gone or 60 plies without a capture; a root without a move to play is over too
     // (aborted).  King-capture rules, nobody resigns, no ply cap.
-    const CzGameEnd end = wave_game_end<CZ_RULES_CAPTURE>(CzRootRules{}, g, false, played[g] == 0xFFFF, t.root_board + (size_t)g * CZD_BOARD_LDS,
+    const CzGameEnd end = wave_game_end<CZ_RULES_CAPTURE>(CzRootRules{}, g, false, played[g] == 0xFFFF, CZ_TB_MISS, t.root_board + (size_t)g * CZD_BOARD_LDS,
                                                           t.root_rr[g], t.root_side[g], 0, 0x7fffffff, lane);
     if (!end.how) return;
     fresh_root(t, g, lane, boards, CZ_NSQ, side, rr, g);

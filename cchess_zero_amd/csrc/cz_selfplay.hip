@@ -183,6 +183,9 @@ __global__ __launch_bounds__(64) void k_sp_choose(CzTrees t, CzSelfplay sp, int 
 // cz_selfplay_set_resign, at every level: a game the last choose resigned is lost by the side to move, z as for a king capture;
 // a play-on game that ends here — however it ends, unless it stalled — goes into the play-on counters and the histogram; the
 // slot's resignation state starts over with its next game.
+// cz_selfplay_set_tablebase: sp.tb_value[g] is what the attached set answers for the position after the move (k_tb_probe_set, the
+// launch in front of this one; CZ_TB_MISS for a slot whose `played` is no label); a covered value ends the game at its place in
+// wave_game_end's precedence, z and the counters as for a king capture, and sp.tb_stat counts it.
 template <int LEVEL>
 __global__ __launch_bounds__(64) void k_sp_adjudicate(CzTrees t, CzSelfplay sp, int G, int reseed, const uint16_t *__restrict__ played,
                                                       int32_t *__restrict__ fin_n) {
@@ -199,7 +202,8 @@ __global__ __launch_bounds__(64) void k_sp_adjudicate(CzTrees t, CzSelfplay sp, 
     }
     const int ply = sp.ply[g];
     const bool aborted = sp.stalled[g] != 0 || (t.status[g] & CZ_ST_BAD_ADVANCE) != 0;
-    const CzGameEnd end = wave_game_end<LEVEL>(sp.rr, g, resigned, aborted, t.root_board + (size_t)g * CZD_BOARD_LDS, t.root_rr[g], t.root_side[g], ply,
+    const int tb = sp.tb_value ? (int)sp.tb_value[g] : CZ_TB_MISS;
+    const CzGameEnd end = wave_game_end<LEVEL>(sp.rr, g, resigned, aborted, tb, t.root_board + (size_t)g * CZD_BOARD_LDS, t.root_rr[g], t.root_side[g], ply,
                                                sp.max_plies, lane);
     if (!end.how) { if (lane == 0) fin_n[g] = 0; return; }
     const bool stalled = end.how == CZ_MATCH_ABORTED, decided = end.loser >= 0;   // neither: a draw
@@ -218,6 +222,7 @@ __global__ __launch_bounds__(64) void k_sp_adjudicate(CzTrees t, CzSelfplay sp, 
         else if (decided) atomicAdd((unsigned long long *)&sp.stats[winner ? CZ_SP_BLACK_WINS : CZ_SP_RED_WINS], 1ull);
         else atomicAdd((unsigned long long *)&sp.stats[CZ_SP_DRAWS], 1ull);
         atomicAdd((unsigned long long *)&sp.stats[CZ_SP_PLIES], (unsigned long long)n);
+        if (end.how == CZ_MATCH_TABLEBASE) atomicAdd((unsigned long long *)sp.tb_stat, 1ull);   // only with a set attached: tb_stat stands
         if constexpr (XQ) {
             if (end.how == CZ_MATCH_CHASE) atomicAdd((unsigned long long *)sp.chase_stat, 1ull);
             else if (end.how == CZ_MATCH_MATE) atomicAdd((unsigned long long *)&sp.xq_stats[0], 1ull);
@@ -299,6 +304,9 @@ int cz_selfplay_begin(cz_ctx *c, int max_plies, const uint8_t *boards, const uin
         sp.max_plies = max_plies;
     }
     c->sp_rules = 0; c->sp.rr.fold = 0; c->sp_chase = 0; c->sp_state = 1;
+    cz_tb_set_hold(c->sp_tb, -1);   // no table set: it needs rules 1; its counter starts with the games
+    c->sp_tb = nullptr; c->sp.tb_value = nullptr;
+    if (c->sp.tb_stat) CZ_HIP(hipMemsetAsync(c->sp.tb_stat, 0, sizeof(long long), c->stream));
     c->sp.rs = CzSpResign{};   // resignation off: no pointer, no kernel looks
     c->sp.rs.threshold = NAN;
     hipLaunchKernelGGL(k_sp_seed, dim3(c->G), dim3(64), 0, c->stream, c->t, c->sp, c->G, boards, side, rr);
@@ -309,7 +317,7 @@ int cz_selfplay_begin(cz_ctx *c, int max_plies, const uint8_t *boards, const uin
 // the setters' order (cz_root_rules_order), in self-play's names
 static int sp_order(const cz_ctx *c, int what, int value) {
     return cz_root_rules_order("cz_selfplay", "ctx", "the history starts at the games' first positions", what, value, c->sp_rules, c->sp.rr.fold,
-                               c->sp_chase, c->sp_state != 1);
+                               c->sp_chase, c->sp_state != 1, c->sp_tb != nullptr);
 }
 
 int cz_selfplay_set_rules(cz_ctx *c, int rules) {
@@ -381,6 +389,25 @@ int cz_selfplay_set_resign(cz_ctx *c, float threshold, int min_ply, double playo
     return CZ_OK;
 }
 
+int cz_selfplay_set_tablebase(cz_ctx *c, cz_tb_set *set) {
+    CZ_REQUIRE(c && c->sp_block && c->sp_state != 0, "cz_selfplay_set_tablebase: call cz_selfplay_begin first");
+    if (const int rc = cz_tb_set_attachable("cz_selfplay", "ctx", c, set, c->sp_rules)) return rc;
+    if (set) {   // the block is made once per context; the counter in it is cz_selfplay_begin's to clear
+        const bool fresh = !c->sp_tb_block;
+        const int rc = carve_alloc(&c->sp_tb_block, c->stream, fresh, "cz_selfplay_set_tablebase", [&](Carver &k) {
+            c->sp.tb_value = k.take<int16_t>((size_t)c->max_games);
+            c->sp.tb_stat = k.take<long long>(1);
+        });
+        if (rc != CZ_OK) { c->sp.tb_value = nullptr; if (!c->sp_tb_block) c->sp.tb_stat = nullptr; return rc; }
+    } else {
+        c->sp.tb_value = nullptr;
+    }
+    cz_tb_set_hold(set, 1);
+    cz_tb_set_hold(c->sp_tb, -1);
+    c->sp_tb = set;
+    return CZ_OK;
+}
+
 int cz_selfplay_active(cz_ctx *c, const uint8_t **active) {
     CZ_REQUIRE(c && c->sp_block && active, "cz_selfplay_active: call cz_selfplay_begin first");
     *active = c->sp.active;
@@ -409,6 +436,11 @@ int cz_selfplay_choose(cz_ctx *c, const float *gamma, const float *u, const uint
 
 int cz_selfplay_adjudicate(cz_ctx *c, int reseed, const uint16_t *played, int32_t *fin_n) {
     CZ_REQUIRE(c && c->sp_block && c->G > 0 && fin_n, "cz_selfplay_adjudicate: call cz_selfplay_begin first / null fin_n");
+    if (c->sp_tb && c->sp.tb_value) {   // the set's value of every root position after the move, read in place: boards 96 bytes apart, sides in the tree records
+        if (const int rc = cz_tb_set_probe_strided(c, c->sp_tb, c->t.root_board, CZD_BOARD_LDS, &c->t.root_side[0], (int)sizeof(CzTreeRec), played, c->G,
+                                                   c->sp.tb_value, nullptr))
+            return rc;
+    }
     cz_by_rules_level(cz_rules_level(c->sp_rules, c->sp.rr.fold, c->sp_chase), [&](auto L) {
         hipLaunchKernelGGL(k_sp_adjudicate<decltype(L)::value>, dim3(c->G), dim3(64), 0, c->stream, c->t, c->sp, c->G, reseed, played, fin_n);
     });
@@ -439,6 +471,13 @@ int cz_selfplay_rules_stats(cz_ctx *c, long long *stats_dev) {
 int cz_selfplay_chase_stats(cz_ctx *c, long long *stats_dev) {
     CZ_REQUIRE(c && c->sp_block && stats_dev, "cz_selfplay_chase_stats: call cz_selfplay_begin first / null argument");
     if (c->sp_chase) CZ_HIP(hipMemcpyAsync(stats_dev, c->sp.chase_stat, sizeof(long long), hipMemcpyDeviceToDevice, c->stream));
+    else CZ_HIP(hipMemsetAsync(stats_dev, 0, sizeof(long long), c->stream));
+    return CZ_OK;
+}
+
+int cz_selfplay_tablebase_stats(cz_ctx *c, long long *stats_dev) {
+    CZ_REQUIRE(c && c->sp_block && stats_dev, "cz_selfplay_tablebase_stats: call cz_selfplay_begin first / null argument");
+    if (c->sp.tb_stat) CZ_HIP(hipMemcpyAsync(stats_dev, c->sp.tb_stat, sizeof(long long), hipMemcpyDeviceToDevice, c->stream));
     else CZ_HIP(hipMemsetAsync(stats_dev, 0, sizeof(long long), c->stream));
     return CZ_OK;
 }

@@ -13,8 +13,10 @@
 // THE CHILD OF A MOVE IS AN INDEX, NOT A BOARD: the slot on `from` takes the digit of `to`, the side flips, and a move that
 // takes the piece of slot j leaves digit j out — Horner over the remaining slots is the index in the table of the signature
 // without that letter, which keeps the slot order.  Two bytes are read per child.
-// Host-compilable like cz_games.h (tests/tablebase_host.cpp): k_tb_pass (cz_tablebase.hip) and the host test program compile
-// this very text.
+// A SET OF TABLES (cz_tablebase_set.hip) is found by MATERIAL KEY: cztb_material_key of a board from the planes cztb_rank reads,
+// cztb_desc_key of a signature, and the sorted directory of keys (cztb_set_sort, cztb_set_find).
+// Host-compilable like cz_games.h (tests/tablebase_host.cpp, tests/tablebase_set_host.cpp): k_tb_pass (cz_tablebase.hip),
+// k_tb_probe_set and the host test programs compile this very text.
 #pragma once
 #include "cz_games.h"
 
@@ -184,20 +186,33 @@ CZM_FN void cztb_words(const CztbDesc &d, const int (&sq)[CZTB_MAX_SLOTS], bool 
 // The index of the position (w, side): among equal pieces the k-th in ascending square order stands on the k-th slot.
 // Returns CZTB_MISS when the board's multiset of pieces is not the signature's (or a byte is no piece code), CZTB_ILLEGAL when
 // a piece stands outside its domain (the position has no index), else 0 and *index.
-CZM_FN int cztb_rank(const CztbDesc &d, const uint32_t (&w)[23], int side, uint32_t *index) {
-    const CzmSet p0 = czm_plane<0>(w), p1 = czm_plane<1>(w), p2 = czm_plane<2>(w), p3 = czm_plane<3>(w);
+// The four bit planes of a board's codes (czm_plane) and the OR of its bytes' high nibbles: what cztb_rank and
+// cztb_material_key read of a position, taken once.
+struct CztbPlanes {
+    CzmSet p0, p1, p2, p3;
+    uint32_t high;   // != 0: some byte is above 15
+};
+CZM_FN CztbPlanes cztb_planes(const uint32_t (&w)[23]) {
     uint32_t high = 0u;
 #pragma unroll
     for (int i = 0; i < 23; ++i) high |= w[i] & 0xF0F0F0F0u;
-    bool miss = high != 0u || czm_popcnt(CzmSet{p0.lo | p1.lo | p2.lo | p3.lo, p0.hi | p1.hi | p2.hi | p3.hi}) != d.n;
+    return CztbPlanes{czm_plane<0>(w), czm_plane<1>(w), czm_plane<2>(w), czm_plane<3>(w), high};
+}
+CZM_FN CzmSet cztb_occupied(const CztbPlanes &P) { return CzmSet{P.p0.lo | P.p1.lo | P.p2.lo | P.p3.lo, P.p0.hi | P.p1.hi | P.p2.hi | P.p3.hi}; }
+// the squares whose byte is c (1 .. 15), given that no byte is above 15
+CZM_FN CzmSet cztb_squares_of(const CztbPlanes &P, int c) {
+    const CzmSet b0 = (c & 1) ? P.p0 : czm_not(P.p0), b1 = (c & 2) ? P.p1 : czm_not(P.p1), b2 = (c & 4) ? P.p2 : czm_not(P.p2), b3 = (c & 8) ? P.p3 : czm_not(P.p3);
+    return czm_and(czm_and(b0, b1), czm_and(b2, b3));
+}
+
+CZM_FN int cztb_rank(const CztbDesc &d, const CztbPlanes &P, int side, uint32_t *index) {
+    bool miss = P.high != 0u || czm_popcnt(cztb_occupied(P)) != d.n;
     bool outside = false;
     uint32_t m = 0u;
 #pragma unroll
     for (int k = 0; k < CZTB_MAX_SLOTS; ++k) {
         if (k < d.n) {
-            const int c = d.code[k];   // wave-uniform: the squares whose byte is c
-            const CzmSet b0 = (c & 1) ? p0 : czm_not(p0), b1 = (c & 2) ? p1 : czm_not(p1), b2 = (c & 4) ? p2 : czm_not(p2), b3 = (c & 8) ? p3 : czm_not(p3);
-            CzmSet s = czm_and(czm_and(b0, b1), czm_and(b2, b3));
+            CzmSet s = cztb_squares_of(P, d.code[k]);   // d.code[k] is wave-uniform: the squares whose byte is that code
             miss |= czm_popcnt(s) != d.mult[k];
 #pragma unroll
             for (int r = 0; r < 4; ++r)
@@ -209,6 +224,71 @@ CZM_FN int cztb_rank(const CztbDesc &d, const uint32_t (&w)[23], int side, uint3
     }
     *index = 2u * m + (uint32_t)(side ? 1 : 0);
     return miss ? CZTB_MISS : outside ? CZTB_ILLEGAL : 0;
+}
+CZM_FN int cztb_rank(const CztbDesc &d, const uint32_t (&w)[23], int side, uint32_t *index) { return cztb_rank(d, cztb_planes(w), side, index); }
+
+// ---- the material key: which table a position belongs to --------------------------------------------------------------------------
+// Sum over the piece codes c = 1 .. 14 of min(count of c, 7) << 3 c, and bit 45 when any byte is no piece code (15 and above):
+// the key Tablebase.signatures_of (cchess_zero_amd/tablebase.py) groups boards by.  Two boards have one key iff they hold the same
+// multiset of pieces (up to six of a kind), so a board whose key is a descriptor's is no CZTB_MISS of cztb_rank under it, and
+// any other is.  A byte above 15 is counted under no code, as in the Python key: its square is taken out of the planes first —
+// the rare path, a branch no board of a game takes.
+#define CZTB_KEY_FOREIGN (1ull << 45)
+CZM_FN uint64_t cztb_material_key(const CztbPlanes &P) {
+    uint64_t key = (P.high != 0u || czm_popcnt(cztb_squares_of(P, 15)) != 0) ? CZTB_KEY_FOREIGN : 0ull;
+#pragma unroll
+    for (int c = 1; c <= 14; ++c) {
+        const int n = czm_popcnt(cztb_squares_of(P, c));
+        key += (uint64_t)(n < 7 ? n : 7) << (3 * c);
+    }
+    return key;
+}
+CZM_FN uint64_t cztb_material_key(const uint32_t (&w)[23]) {
+    CztbPlanes P = cztb_planes(w);
+    if (P.high != 0u) {   // the bytes above 15 become empty squares; the key keeps its bit 45
+        uint32_t c[23];
+#pragma unroll
+        for (int i = 0; i < 23; ++i) {
+            uint32_t h = w[i] & 0xF0F0F0F0u;
+            h |= h >> 1, h |= h >> 2;
+            c[i] = w[i] & ~(((h >> 4) & 0x01010101u) * 0xFFu);
+        }
+        const uint32_t high = P.high;
+        P = cztb_planes(c);
+        P.high = high;
+    }
+    return cztb_material_key(P);
+}
+// the key of every board of the descriptor's signature (host)
+inline uint64_t cztb_desc_key(const CztbDesc &d) {
+    uint64_t key = 0ull;
+    for (int k = 0; k < d.n; ++k) key += 1ull << (3 * d.code[k]);   // at most five of a code: no field runs over
+    return key;
+}
+
+// ---- a set of tables: the directory of keys (cz_tablebase_set.hip) -------------------------------------------------------------------
+#define CZTB_SET_MAX 256   // CZ_TB_SET_MAX: the keys of a set fit 2 KB of LDS, and a closure has at most 2^8 signatures
+// host: the directory order of n keys — order[i] = which of the keys given stands at place i, ascending by key, whatever order
+// they came in.  -> 0; -1: n outside 1 .. CZTB_SET_MAX; 1 + i: the key at place i equals the one before it (a signature given
+// twice: one key, one signature — the letters of a side have a fixed order)
+inline int cztb_set_sort(int n, const uint64_t *keys, int *order) {
+    if (n < 1 || n > CZTB_SET_MAX) return -1;
+    for (int i = 0; i < n; ++i) {   // insertion: n is small
+        int j = i;
+        for (; j > 0 && keys[order[j - 1]] > keys[i]; --j) order[j] = order[j - 1];
+        order[j] = i;
+    }
+    for (int i = 1; i < n; ++i)
+        if (keys[order[i]] == keys[order[i - 1]]) return 1 + i;
+    return 0;
+}
+// the place of `key` among the n sorted keys skeys[0 .. CZTB_SET_MAX) (~0 behind the last), -1 when it is none of them: eight
+// steps, 128 + 64 + .. + 1, that count the keys below it — no step reads past index CZTB_SET_MAX - 2
+CZM_FN int cztb_set_find(const uint64_t *skeys, int n, uint64_t key) {
+    int lo = 0;
+#pragma unroll
+    for (int s = CZTB_SET_MAX / 2; s >= 1; s >>= 1) lo = skeys[lo + s - 1] < key ? lo + s : lo;
+    return (lo < n && skeys[lo] == key) ? lo : -1;
 }
 
 // ---- one index's pass ------------------------------------------------------------------------------------------------------------

@@ -126,7 +126,9 @@ __global__ __launch_bounds__(64) void k_tb_boards(const CztbDesc d, const int32_
     }
 }
 
-// the signature -> its descriptor, or CZ_EINVAL with `who` in the text
+}  // namespace
+
+// the signature -> its descriptor, or CZ_EINVAL with `who` in the text (cz_internal.h: cz_tablebase_set.hip reads signatures too)
 int tb_desc(const char *who, const char *signature, CztbDesc *d) {
     const int rc = cztb_parse(signature, d);
     if (rc == 0) return CZ_OK;
@@ -135,8 +137,6 @@ int tb_desc(const char *who, const char *signature, CztbDesc *d) {
     cz_set_error("%s: bad signature \"%s\": %s", who, signature ? signature : "(null)", why[-rc]);
     return CZ_EINVAL;
 }
-
-}  // namespace
 
 int cz_tb_entries(const char *signature, long long *entries, int *n_slots) {
     CztbDesc d;

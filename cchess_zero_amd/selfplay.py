@@ -27,7 +27,7 @@ import numpy as np
 import torch
 
 from ._lib import (MAXMOVES, NLABELS, NSQ, REC_BYTES, REC_COUNT, REC_FLAGS, REC_LABELS, REC_PLY, REC_SIDE, REC_VISITS, REC_Z,
-                   SP_CHASE_STATS, SP_RESIGN_STATS, SP_RULES_STATS, SP_STATS, out_pointers, tables)
+                   SP_CHASE_STATS, SP_RESIGN_STATS, SP_RULES_STATS, SP_STATS, SP_TABLEBASE_STATS, out_pointers, tables)
 from .rules import RULES, check_rule_options, root_rules_chase_history, root_rules_history, set_rule_options
 
 REC_MAXMOVES = MAXMOVES
@@ -164,12 +164,20 @@ class SelfPlay:
     resign_playon of the games, drawn from `seed` per slot and game, never resigns and is counted instead — stats() says how many
     of them crossed the threshold and how many of those did not lose (the false positives), resign_histogram() what threshold
     a false-positive rate allows (suggest_resign_threshold).
+    tablebase (rules="xiangqi" only): None — games are played out; a tablebase.Tablebase (all its loaded tables) or a
+    tablebase.DeviceSet — a game whose position after a move is in one of the tables ends there with the table's result
+    (cz_selfplay_set_tablebase): z as for a king capture, counted in the wins / draws and in stats()["tablebase"].  A game
+    that starts in a covered position plays one ply first; set_tablebase() attaches or detaches between two plies.
     """
 
     def __init__(self, engine, net, playouts, exploration=True, temperature=1.0, seed=0, max_plies=512, ring_records=None,
                  continuous=True, eval_cache=False, xcache_log2=0, rules="capture", repetition=0, chase=False, resign=None,
-                 resign_min_ply=0, resign_playon=0.1):
+                 resign_min_ply=0, resign_playon=0.1, tablebase=None):
         check_rule_options("SelfPlay", rules, repetition, chase)
+        if tablebase is not None and rules != "xiangqi":
+            raise ValueError("SelfPlay: tablebase needs rules='xiangqi' (a table holds values under xiangqi rules)")
+        self.tablebase = tablebase
+        self._tb_set = self._tb_own = None
         if int(resign_min_ply) < 0 or not 0.0 <= float(resign_playon) <= 1.0:
             raise ValueError("SelfPlay: resign_min_ply >= 0 and 0 <= resign_playon <= 1")
         self.resign = None if resign is None else float(resign)
@@ -212,6 +220,8 @@ class SelfPlay:
         set_rule_options("cz_selfplay", eng.ctx.h, self.rules, self.repetition, self.chase)
         self._resign_on = self.resign is not None
         self._apply_resign()
+        self._tb_on = False   # cz_selfplay_begin detached whatever was attached
+        self.set_tablebase(self.tablebase)
         self._active_ptr, = out_pointers("cz_selfplay_active", eng.ctx.h, 1)
         R = int(self.ring_records or max(65536, 64 * G))
         self.ring = torch.zeros((R, REC_BYTES), dtype=torch.uint8, device=self.dev)
@@ -226,6 +236,7 @@ class SelfPlay:
         self._chase_stats = torch.zeros(len(SP_CHASE_STATS), dtype=torch.int64, device=self.dev)
         self._resign_stats = torch.zeros(len(SP_RESIGN_STATS), dtype=torch.int64, device=self.dev)
         self._resign_hist = torch.zeros(64, dtype=torch.int64, device=self.dev)
+        self._tb_stats = torch.zeros(len(SP_TABLEBASE_STATS), dtype=torch.int64, device=self.dev)
         self.plies = 0
         self.lock_steps = 0
         self._dropped_seen = 0
@@ -235,6 +246,24 @@ class SelfPlay:
         if self._resign_on:
             self.eng.ctx.call("cz_selfplay_set_resign", float("nan") if self.resign is None else self.resign, self.resign_min_ply,
                               self.resign_playon, self.seed)
+
+    def set_tablebase(self, tablebase):
+        """Attaches a Tablebase / DeviceSet to a started loop, or detaches it (None) — between any two plies.  A DeviceSet made
+        here from a Tablebase is closed when it is replaced and by close()."""
+        if tablebase is not None and self.rules != "xiangqi":
+            raise ValueError("SelfPlay: tablebase needs rules='xiangqi' (a table holds values under xiangqi rules)")
+        dset = tablebase.device_set() if hasattr(tablebase, "device_set") else tablebase
+        self.eng.ctx.call("cz_selfplay_set_tablebase", None if dset is None else dset.h)
+        if self._tb_own is not None:
+            self._tb_own.close()
+        self._tb_own = dset if dset is not tablebase else None
+        self.tablebase, self._tb_set = tablebase, dset
+        self._tb_on = self._tb_on or dset is not None
+
+    def close(self):
+        """Detaches the table set (a started loop holds it) and closes the one this loop made itself"""
+        if self._tb_set is not None:
+            self.set_tablebase(None)
 
     def set_resign_threshold(self, threshold):
         """Retunes the resignation threshold of a started loop (None: no ply is judged until the next call): the games in
@@ -385,7 +414,8 @@ class SelfPlay:
         draw, by perpetual check (a win); with chase=True also chases — the games that ended by perpetual chase (a win; not
         among the perpetuals); with resignation on also resigned, playon_games, playon_would_resign, playon_false_positives —
         the games a mover resigned (a win for the other side), the play-on games finished, those in which a side crossed the
-        threshold, and those of them that side won or drew."""
+        threshold, and those of them that side won or drew; with a table set attached at any time since start() also tablebase —
+        the games adjudicated from a table (counted among the wins / draws too)."""
         self.eng.ctx.call("cz_selfplay_stats", self._stats)
         s = self._stats.cpu().numpy()
         d = {k: int(v) for k, v in zip(SP_STATS, s)}
@@ -398,6 +428,9 @@ class SelfPlay:
         if self._resign_on:
             self.eng.ctx.call("cz_selfplay_resign_stats", self._resign_stats, None)
             d.update((k, int(v)) for k, v in zip(SP_RESIGN_STATS, self._resign_stats.cpu().numpy()))
+        if self._tb_on:
+            self.eng.ctx.call("cz_selfplay_tablebase_stats", self._tb_stats)
+            d.update((k, int(v)) for k, v in zip(SP_TABLEBASE_STATS, self._tb_stats.cpu().numpy()))
         d["sims"] += int(self.eng.status()[2].sum().item())   # + the simulations of the searches in progress
         d["plies_played"] = self.plies          # lock-step plies (step_ply)
         d["lock_steps"] = self.lock_steps       # select / net / expand steps of the asynchronous loop (run_async)

@@ -23,7 +23,7 @@ import time
 import numpy as np
 import torch
 
-from ._lib import NSQ, TB_ILLEGAL, TB_MAX_SLOTS, TB_MISS, TB_UNKNOWN, call
+from ._lib import NSQ, TB_ILLEGAL, TB_MAX_SLOTS, TB_MISS, TB_SET_MAX, TB_UNKNOWN, call, lib
 from .notation import fen_to_position, line_text, move_text, position_to_fen
 
 FORMAT_VERSION = 1
@@ -79,6 +79,31 @@ def wdl_of(v):
     if v in (TB_MISS, TB_ILLEGAL, TB_UNKNOWN):
         return None, None
     return ("draw", None) if v == 0 else ("win", v - 1) if v > 0 else ("loss", -v - 1)
+
+
+class DeviceSet:
+    """A cz_tb_set over loaded tables: the handle cz_tb_set_probe, cz_selfplay_set_tablebase and cz_match_set_tablebase take.
+    signatures: the order `which` counts in.  It keeps the tables' tensors alive and is closed explicitly — after every self-play
+    context and match it was attached to has let go of it (cz_tb_set_destroy refuses otherwise: CchessHipError)."""
+
+    def __init__(self, ctx, tables, signatures):
+        self.signatures = tuple(signatures)
+        if not 1 <= len(self.signatures) <= TB_SET_MAX:
+            raise ValueError("a table set holds 1 .. %d signatures, not %d" % (TB_SET_MAX, len(self.signatures)))
+        self.tensors = [tables[s] for s in self.signatures]   # KeyError: a signature that is not loaded
+        names = (C.c_char_p * len(self.signatures))(*[s.encode() for s in self.signatures])
+        ptrs = (C.c_void_p * len(self.signatures))(*[t.data_ptr() for t in self.tensors])
+        self.h = C.c_void_p()
+        ctx.call("cz_tb_set_create", len(self.signatures), names, ptrs, C.byref(self.h))
+
+    def close(self):
+        if getattr(self, "h", None):
+            call("cz_tb_set_destroy", self.h)
+            self.h, self.tensors = None, []
+
+    def __del__(self):   # a set still attached somewhere is left to the process' end rather than torn from under a kernel
+        if getattr(self, "h", None):
+            lib().cz_tb_set_destroy(self.h)
 
 
 class Tablebase:
@@ -221,6 +246,31 @@ class Tablebase:
                     at = (group == k).nonzero().flatten()
                     value[at] = self.probe_one(s, boards[at].contiguous(), side[at].contiguous())
         return value, (value != TB_MISS) & (value != TB_ILLEGAL)
+
+    def device_set(self, signatures=None):
+        """A DeviceSet over the loaded tables (all of them in sorted order, or the signatures given, in that order): one handle
+        for probe_set, SelfPlay(tablebase=) and Match(tablebase=).  The caller closes it."""
+        return DeviceSet(self.ctx, self.tables, sorted(self.tables) if signatures is None else list(signatures))
+
+    def probe_set(self, boards, side, dset=None):
+        """probe() in ONE launch (cz_tb_set_probe), whatever the positions' material and with no grouping on the host ->
+        (value i16 [G], covered bool [G], which i32 [G]: the place of the board's signature in dset.signatures, -1 for TB_MISS).
+        dset: a device_set() to probe; None: one over all loaded tables, made on first use and again when the tables change."""
+        boards = self.ctx.tensor(boards, torch.uint8).reshape(-1, NSQ)
+        side = self.ctx.tensor(side, torch.uint8).reshape(-1)
+        if dset is None:
+            have = tuple(sorted(self.tables))
+            cur = getattr(self, "_set", None)
+            if cur is None or cur.signatures != have or any(a is not self.tables[s] for a, s in zip(cur.tensors, have)):
+                if cur is not None:
+                    cur.close()
+                self._set = self.device_set()
+            dset = self._set
+        G = boards.shape[0]
+        value = torch.empty(G, dtype=torch.int16, device=self.dev)
+        which = torch.empty(G, dtype=torch.int32, device=self.dev)
+        self.ctx.call("cz_tb_set_probe", dset.h, boards, side, G, value, which)
+        return value, (value != TB_MISS) & (value != TB_ILLEGAL), which
 
     def _children(self, boards, side):
         """-> (value [G], child boards, child sides, child labels, child values, parent i64 [T]): the king-safe successors of the

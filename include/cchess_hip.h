@@ -319,6 +319,30 @@ int cz_tb_probe(cz_ctx *, const char *signature, const int16_t *table /* [entrie
                 const uint8_t *side, int G, int16_t *value /* [G] */, int32_t *index /* [G] or NULL */);
 int cz_tb_boards(cz_ctx *, const char *signature, const int32_t *index /* [G] */, int G, uint8_t *boards /* [G][90] */,
                  uint8_t *side);
+/* TABLE SETS: several finished tables behind one handle, probed by ONE launch whatever the positions' material — what a loop
+ *   that must not wait for the host every ply needs (cz_selfplay_set_tablebase, cz_match_set_tablebase).
+ *   THE MATERIAL KEY of a board: the sum over the piece codes c = 1 .. 14 of min(count of c, 7) << 3 c, and bit 45 when any byte
+ *     is no piece code.  Two boards have one key iff they hold the same pieces; a signature's key is that of all its boards.
+ *   cz_tb_set_create: n signatures and their tables (DEVICE pointers, the caller's, which must outlive the set) -> a directory in
+ *     device memory: the keys sorted ascending, beside each its descriptor, its table and its place in the order given.
+ *     1 <= n <= CZ_TB_SET_MAX: the kernel keeps the sorted keys in LDS (2 KB) and finds a board's entry by a binary search of
+ *     eight steps there, and 256 is also the most a closure can hold — a signature has at most eight letters that are no king,
+ *     each present or taken.  CZ_EINVAL: n outside that range, a string that is no signature (cz_tb_entries' text), a
+ *     signature given twice, a table pointer that is NULL or odd.
+ *   cz_tb_set_probe: G boards [G][90] and sides -> value [G], exactly what cz_tb_probe answers under the one signature of the
+ *     set that has the board's pieces — the table's value, or CZ_TB_ILLEGAL for a piece outside its domain — and CZ_TB_MISS when
+ *     no signature of the set has them; which [G] (may be NULL): the place of that signature in cz_tb_set_create's order, -1 for
+ *     a miss.  A board of more than CZ_TB_MAX_SLOTS pieces is a miss before anything is looked up.  boards at any address, as
+ *     for cz_tb_probe; G == 0 is CZ_OK without a launch.
+ *   cz_tb_set_destroy: CZ_EINVAL while a self-play context or a match holds the set (detach it there first, or destroy the
+ *     match); NULL is CZ_OK. */
+#define CZ_TB_SET_MAX 256
+typedef struct cz_tb_set cz_tb_set;
+int cz_tb_set_create(cz_ctx *, int n, const char *const *signatures /* host [n] */, const int16_t *const *tables /* host [n] of device pointers */,
+                     cz_tb_set **out);
+int cz_tb_set_destroy(cz_tb_set *);
+int cz_tb_set_probe(cz_ctx *, const cz_tb_set *, const uint8_t *boards /* [G][90] */, const uint8_t *side, int G, int16_t *value /* [G] */,
+                    int32_t *which /* [G] or NULL */);
 /* K3  replaces MCTS_tree.generate_inputs = try_flip + state_to_positions, main.py:531-574.
  *     planes [G][9][10][channels] of dtype CZ_F32 / CZ_BF16.  quirk_q1 = 1 reproduces the
  *     reference bit for bit; 0 gives the transposed encoding its shapes suggest. */
@@ -676,6 +700,25 @@ int cz_selfplay_chase_stats(cz_ctx *, long long *stats_dev /* [1]: chases */);
  * cz_selfplay_resign_stats: device int64 [4] <- games resigned, play-on games finished, those in which a side crossed the
  *   threshold, those of them that side did not lose; device int64 [64] <- the histogram (may be NULL).  Zeros while off. */
 int cz_selfplay_set_resign(cz_ctx *, float threshold, int min_ply, double playon_fraction, unsigned long long seed);
+/* cz_selfplay_set_tablebase: NULL = no game is adjudicated from a table (the default: everything above, launch for launch and
+ *   byte for byte), a cz_tb_set = cz_selfplay_adjudicate first probes the set on every slot's root position AFTER the move — one
+ *   launch on the trees' boards in place, nothing goes through the host — and a slot that just moved into a position the set
+ *   covers (a value that is neither CZ_TB_MISS nor CZ_TB_ILLEGAL) ends its game there: value > 0 the side to move wins, < 0 it
+ *   loses, 0 a draw; z of every record as for a king capture, fin_n = min(plies played, max_plies), counted in CZ_SP_GAMES,
+ *   RED_WINS / BLACK_WINS / DRAWS, CZ_SP_PLIES and cz_selfplay_tablebase_stats; the slot re-seeds as after any ending.  Place
+ *   among the endings: behind the repetition verdict, the mate, the resignation and the aborted game — found by the choose on
+ *   a root that was then not left —, in front of the king test, the 60-ply rule and the ply cap: a forced mate is a mate
+ *   whatever the no-capture counter says.  Play-on games of the resignation measurement end here like any other game.
+ *   A table holds values under Xiangqi rules, so the set needs cz_selfplay_set_rules(ctx, 1): CZ_EINVAL under rules 0, and
+ *   cz_selfplay_set_rules(ctx, 0) is refused while a set is attached.  Unlike the rule setters it may be called between any two
+ *   plies — it judges positions, it keeps no history.  cz_selfplay_begin detaches the set.  The set must be the context's device's.
+ *   A game whose START position is covered plays one ply first (adjudication follows a move).  A capture that leaves the set
+ *   goes on, and the game is judged again after its next move.  A table draw is a draw even where the repetition or chase
+ *   rules would later have punished a side; nothing is probed inside the search tree.
+ * cz_selfplay_tablebase_stats: device int64 [1] <- games adjudicated from a table since cz_selfplay_begin (0 before a set was
+ *   ever attached). */
+int cz_selfplay_set_tablebase(cz_ctx *, cz_tb_set *set /* NULL = off */);
+int cz_selfplay_tablebase_stats(cz_ctx *, long long *stats_dev /* [1]: games adjudicated */);
 int cz_selfplay_resign_stats(cz_ctx *, long long *stats_dev /* [4]: resigned, playon_games, playon_would_resign, playon_false_positives */,
                              long long *hist_dev /* [64], may be NULL */);
 
@@ -719,6 +762,7 @@ int cz_selfplay_resign_stats(cz_ctx *, long long *stats_dev /* [4]: resigned, pl
 #define CZ_MATCH_CHASE 9        /* cz_match_set_chase: ... neither side checked so, and one side alone chased one piece with every
                                    move of the cycle: that side loses (8 is not assigned) */
 #define CZ_MATCH_RESIGN 10      /* cz_match_set_resign: the mover's root value was below the threshold: it loses */
+#define CZ_MATCH_TABLEBASE 11   /* cz_match_set_tablebase: the position after the move is in a table: its value is the result */
 typedef struct cz_match cz_match;
 int cz_match_create(cz_ctx *a, cz_ctx *b, const uint8_t *open_boards, const uint8_t *open_side, const int32_t *open_rr,
                     int n_openings, long long pair_base, long long pair_stride, int max_plies, cz_match **out);
@@ -761,6 +805,15 @@ int cz_match_set_rules(cz_match *, int rules);
  *   before CZ_MATCH_ABORTED.  There is no play-on fraction: a match measures strength, not the threshold.  May change between
  *   two plies. */
 int cz_match_set_resign(cz_match *, float threshold, int min_ply);
+/* cz_match_set_tablebase: NULL = off (the default: everything above, launch for launch), a cz_tb_set = cz_match_adjudicate first
+ *   probes the set on every slot's position after the move (one launch, on the trees' boards in place) and a slot that just
+ *   moved into a covered position ends its game as CZ_MATCH_TABLEBASE, a scored game: the table's value is from the side to
+ *   move's view, result -1 when the losing side is A's colour in that game, +1 when it is B's, 0 for a table draw; plies = the
+ *   plies played.  Place among the endings, the rule level it needs (cz_match_set_rules(match, 1); CZ_EINVAL otherwise, and
+ *   cz_match_set_rules(match, 0) is refused while a set is attached), the opening that is itself covered (one ply is played
+ *   first), the capture that leaves the set and what is not covered: as cz_selfplay_set_tablebase.  May change between two
+ *   plies.  cz_match_destroy gives the set back. */
+int cz_match_set_tablebase(cz_match *, cz_tb_set *set /* NULL = off */);
 int cz_match_set_repetition(cz_match *, int fold);
 int cz_match_history(cz_match *, const uint64_t **keys, const uint8_t **checks);
 int cz_match_set_chase(cz_match *, int on);

@@ -344,6 +344,8 @@ class cchess_main(object):
         # resignation in the batched self-play games and the evaluation matches (--resign_threshold, --resign_min_ply,
         # --resign_playon, --resign_auto): off unless a threshold or a false-positive target is given
         self.resign_threshold, self.resign_min_ply, self.resign_playon, self.resign_auto = None, 0, 0.1, None
+        # endgame tables (--tablebase DIR, with --rules xiangqi): self-play and evaluation games that reach a table's position end there
+        self.tablebase_dir, self._tablebase = None, None
         # --mirror_augment: every sample a policy update draws is learnt from as it is or as its left-right mirror image, and the
         # mini-batch is built on the GPU from the packed records (cchess_zero_amd/records.py)
         self.mirror_augment = False
@@ -515,7 +517,7 @@ class cchess_main(object):
         sp = getattr(self, "_sp", None)
         if (sp is None or sp.eng.G != G or sp.eng.ctx.cap < cap or sp.playouts != self.playout_counts or sp.net is not net
                 or sp.rules != self.rules or sp.repetition != self.repetition or sp.chase != self.chase
-                or getattr(sp, "resign_options", None) != self._resign_options()):
+                or getattr(sp, "resign_options", None) != self._resign_options() or sp.tablebase is not self._tables()):
             # planes are written by the select kernel straight in the fused net's input format (16 channels of its 16-bit type)
             plane_dtype, channels = plane_format(net)
             eng = SearchEngine(G, cap, torch.cuda.current_device(), plane_dtype=plane_dtype, channels=channels)
@@ -536,7 +538,10 @@ class cchess_main(object):
                           xcache_log2=min(24, max(18, (G * 2048 - 1).bit_length())) if self.playout_counts >= 400 else 0,
                           # a drain interval can end every game of every slot in the worst case: room for ~160 plies per slot
                           ring_records=max(65536, 160 * G), rules=self.rules, repetition=self.repetition, chase=self.chase,
+                          tablebase=self._tables(),
                           **({} if ro is None else dict(resign=ro[0], resign_min_ply=ro[1], resign_playon=ro[2])))
+            if getattr(self, "_sp", None) is not None:
+                self._sp.close()         # the slots that are replaced let go of the table set
             sp.resign_options = ro       # as given: --resign_auto retunes sp.resign, the slots are rebuilt when the options change
             b0 = np.tile(state_to_board(START_STATE), (G, 1))
             sp.start(b0, np.zeros(G, np.uint8), np.zeros(G, np.int32))
@@ -560,12 +565,21 @@ class cchess_main(object):
             st = sp.stats()
             if st["games"] - before["games"] >= target or (max_plies is not None and plies >= max_plies):
                 break
-        self.last_selfplay_stats = {k: (st[k] - before[k] if k in ("games", "red_wins", "black_wins", "draws", "plies", "sims", "lock_steps", "mates", "repetitions", "perpetuals", "chases",
+        self.last_selfplay_stats = {k: (st[k] - before[k] if k in ("games", "red_wins", "black_wins", "draws", "plies", "sims", "lock_steps", "mates", "repetitions", "perpetuals", "chases", "tablebase",
                                                                            "resigned", "playon_games", "playon_would_resign", "playon_false_positives") else st[k])
                                     for k in st}
         self.last_selfplay_sims = self.last_selfplay_stats["sims"]
         rec = torch.cat(chunks, 0) if chunks else sp.ring[:0]
         return parallel.gather_records(rec)
+
+    def _tables(self):
+        """--tablebase DIR: the directory's tables on this rank's GPU, loaded once (every rank loads them itself); None without"""
+        if self.tablebase_dir and self._tablebase is None:
+            from cchess_zero_amd.tablebase import Tablebase
+            self._tablebase = Tablebase()
+            if not self._tablebase.load(self.tablebase_dir):
+                raise ValueError("--tablebase: no table in %s" % self.tablebase_dir)
+        return self._tablebase
 
     def _resign_options(self):
         """What the self-play slots are built with: None = games are played out.  With --resign_auto alone the first threshold is
@@ -609,7 +623,7 @@ class cchess_main(object):
         ro = self._resign_options()      # the matches resign as self-play does now: on the threshold --resign_auto last set
         res = Match((live, self.playout_counts), (opp, self.playout_counts), openings, slots=max(2, min(2 * pairs, self.games)),
                     seed=self.update_seed + self._eval_round, rules=self.rules, repetition=self.repetition, chase=self.chase,
-                    resign=ro and getattr(getattr(self, "_sp", None), "resign", ro[0]), resign_min_ply=ro[1] if ro else 0).play()
+                    resign=ro and getattr(getattr(self, "_sp", None), "resign", ro[0]), resign_min_ply=ro[1] if ro else 0, tablebase=self._tables()).play()
         self.last_evaluation = res
         if opponent is None and res.score is not None and res.score >= 0.55:
             self._eval_snapshot = self._snapshot_net()
@@ -727,6 +741,8 @@ class cchess_main(object):
                           "eval_cache": bool(getattr(self._sp, "eval_cache", False)), "xcache_log2": int(getattr(self._sp, "xcache_log2", 0))}
                 if "chases" in st:
                     timing["chases"] = int(st["chases"])
+                if "tablebase" in st:
+                    timing["tablebase"] = int(st["tablebase"])     # games of the batch that ended with a table's result
                 if "resigned" in st:
                     timing.update((k, int(st[k])) for k in ("resigned", "playon_games", "playon_would_resign", "playon_false_positives"))
                     self._retune_resign()
@@ -816,6 +832,9 @@ if __name__ == '__main__':
     parser.add_argument('--resign_auto', default=None, type=float,
                         help='after every batch set the threshold to what the play-on games allow at this false-positive rate '
                              '(never above 0; without --resign_threshold nobody resigns until enough play-on games have ended)')
+    parser.add_argument('--tablebase', default=None, type=str, metavar='DIR',
+                        help='with --rules xiangqi: batched self-play and evaluation games that reach a position of a table in DIR '
+                             '(python -m cchess_zero_amd.tablebase --build) end there with the table\'s result')
     parser.add_argument('--mirror_augment', action='store_true',
                         help='policy updates learn from every drawn sample as it is or as its left-right mirror image (one coin per '
                              'sample), and build the mini-batch on the GPU from the packed records')
@@ -837,6 +856,10 @@ if __name__ == '__main__':
         parser.error("--repetition is 0 or 2..8 and needs --rules xiangqi")
     if args.chase and not args.repetition:
         parser.error("--chase needs --repetition")
+    if args.tablebase and args.rules != 'xiangqi':
+        parser.error("--tablebase needs --rules xiangqi (a table holds values under xiangqi rules)")
+    if args.tablebase and not os.path.isdir(args.tablebase):
+        parser.error("--tablebase: %s is no directory" % args.tablebase)
     if args.resign_min_ply < 0 or not 0.0 <= args.resign_playon <= 1.0 or not (args.resign_auto is None or 0.0 <= args.resign_auto <= 1.0):
         parser.error("--resign_min_ply >= 0, --resign_playon and --resign_auto in [0, 1]")
 
@@ -867,6 +890,7 @@ if __name__ == '__main__':
         train_main.resign_threshold, train_main.resign_min_ply = args.resign_threshold, args.resign_min_ply
         train_main.resign_playon, train_main.resign_auto = args.resign_playon, args.resign_auto
         train_main.mirror_augment = args.mirror_augment
+        train_main.tablebase_dir = args.tablebase
         if args.pretrain:
             train_main.pretrain(args.pretrain, args.pretrain_steps, args.pretrain_rules, args.pretrain_lr, args.pretrain_notation)
         train_main.run(args.max_batches)

@@ -24,7 +24,12 @@ usage: python tools/rules_bench.py [N positions, default 1048576]
            and entries per second of every pass; then an early pass (the first: every undecided lane is live) and a late one (the
            last that decides anything: most groups are skipped) as the fused cz_tb_pass against the same pass composed from
            cz_tb_boards -> cz_movegen_kingsafe -> cz_successors -> Tablebase.probe -> a torch segment reduction, from the same
-           snapshot of the table, alternating in one run; one JSON line at the end"""
+           snapshot of the table, alternating in one run; one JSON line at the end
+       python tools/rules_bench.py --tablebase-set SIG    the mixed probe: the closure of SIG is built, 65 536 legal positions are
+           drawn evenly from all of its tables and shuffled, and Tablebase.probe (host grouping, one cz_tb_probe per signature) is
+           timed against Tablebase.probe_set (one k_tb_probe_set launch) on them — device events, one warm-up, the two forms
+           alternating three times, the answers compared; then the one launch on 8192 start positions, all misses: what self-play
+           pays per ply with a table set attached; one JSON line at the end"""
 import os
 import sys
 import time
@@ -50,6 +55,13 @@ if "--tablebase" in sys.argv:
     if _at + 1 >= len(sys.argv):
         sys.exit("--tablebase needs a signature such as KR-KAABB")
     TABLEBASE = sys.argv[_at + 1]
+    del sys.argv[_at:_at + 2]
+TABLEBASE_SET = None
+if "--tablebase-set" in sys.argv:
+    _at = sys.argv.index("--tablebase-set")
+    if _at + 1 >= len(sys.argv):
+        sys.exit("--tablebase-set needs a signature such as KR-KAA")
+    TABLEBASE_SET = sys.argv[_at + 1]
     del sys.argv[_at:_at + 2]
 _args = [a for a in sys.argv[1:] if a not in ("--kingsafe", "--threats", "--successors", "--replay", "--replay-notation", "--checks", "--mate")]
 N = int(_args[0]) if _args else (8192 if REPLAY or REPLAY_NOTATION else 1 << 16 if MATE else 1 << 20)
@@ -576,6 +588,59 @@ def tablebase_leg(sig):
     print(json.dumps(out), flush=True)
 
 
+def tablebase_set_leg(sig, n=65536, roots=8192):
+    """Tablebase.probe against Tablebase.probe_set on one mixed batch, and the set's launch on a batch of misses"""
+    import json
+    from cchess_zero_amd._lib import TB_ILLEGAL
+    from cchess_zero_amd.rules import START_BOARD
+    from cchess_zero_amd.tablebase import Tablebase
+    tb = Tablebase(rules)
+    tb.build(sig)
+    sigs = sorted(tb.tables)
+    gen = torch.Generator(device=tb.dev).manual_seed(1)
+    per = (n + len(sigs) - 1) // len(sigs)
+    bs, ss = [], []
+    for s in sigs:
+        legal = (tb.tables[s] != TB_ILLEGAL).nonzero().flatten()
+        idx = legal[torch.randint(0, legal.numel(), (per,), generator=gen, device=tb.dev)].to(torch.int32)
+        b, sd = tb.boards(s, idx)
+        bs.append(b), ss.append(sd)
+    perm = torch.randperm(per * len(sigs), generator=gen, device=tb.dev)[:n]
+    boards, side = torch.cat(bs)[perm].contiguous(), torch.cat(ss)[perm].contiguous()
+
+    def events(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        out = fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1), out
+    _, ref = events(lambda: tb.probe(boards, side))                    # the warm-up of both, and the comparison
+    _, got = events(lambda: tb.probe_set(boards, side))
+    equal = bool(torch.equal(ref[0], got[0]) and torch.equal(ref[1], got[1]))
+    tp, ts = [], []
+    for _ in range(3):
+        tp.append(events(lambda: tb.probe(boards, side))[0])
+        ts.append(events(lambda: tb.probe_set(boards, side))[0])
+    tp.sort(), ts.sort()
+    miss = torch.from_numpy(np.tile(np.asarray(START_BOARD, np.uint8).reshape(1, 90), (roots, 1))).to(tb.dev)
+    mside = torch.zeros(roots, dtype=torch.uint8, device=tb.dev)
+    tb.probe_set(miss, mside)
+    tm = sorted(events(lambda: tb.probe_set(miss, mside))[0] for _ in range(5))
+    all_miss = bool((tb.probe_set(miss, mside)[1] == 0).all())
+    out = dict(signature=sig, tables=len(sigs), positions=n, equal=equal, probe_ms=round(tp[1], 4), probe_min_ms=round(tp[0], 4), probe_max_ms=round(tp[2], 4),
+               probe_set_ms=round(ts[1], 4), probe_set_min_ms=round(ts[0], 4), probe_set_max_ms=round(ts[2], 4), probe_over_probe_set=round(tp[1] / ts[1], 2),
+               roots=roots, roots_all_miss=all_miss, roots_ms=round(tm[2], 4), roots_min_ms=round(tm[0], 4), roots_max_ms=round(tm[4], 4))
+    print("%d positions of %d tables: Tablebase.probe %.3f ms (min %.3f, max %.3f), probe_set %.3f ms (min %.3f, max %.3f) = %.1f x, answers %s"
+          % (n, len(sigs), tp[1], tp[0], tp[2], ts[1], ts[0], ts[2], tp[1] / ts[1], "equal" if equal else "DIFFER"))
+    print("%d start positions, all misses: %.4f ms per launch with its two output tensors (min %.4f, max %.4f)" % (roots, tm[2], tm[0], tm[4]))
+    print(json.dumps(out), flush=True)
+    assert equal and all_miss
+
+
+if TABLEBASE_SET:
+    tablebase_set_leg(TABLEBASE_SET)
+    sys.exit(0)
 if TABLEBASE:
     tablebase_leg(TABLEBASE)
     sys.exit(0)
