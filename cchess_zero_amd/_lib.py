@@ -18,16 +18,17 @@ MASK_WORDS = 66
 F32, BF16, F16 = 0, 1, 2
 # one packed self-play record (include/cchess_hip.h: CZ_REC_*)
 REC_BYTES, REC_SIDE, REC_COUNT, REC_Z, REC_FLAGS, REC_PLY, REC_LABELS, REC_VISITS = 608, 90, 91, 92, 93, 94, 96, 352
+# the self-play counters, getter by getter, in the order of the library's one array (csrc/cz_internal.h: CzSpSlot)
 SP_STATS = ("games", "red_wins", "black_wins", "draws", "plies", "stalled", "dropped", "sims")
 SP_RULES_STATS = ("mates", "repetitions", "perpetuals")   # cz_selfplay_rules_stats
 SP_CHASE_STATS = ("chases",)                               # cz_selfplay_chase_stats
+SP_TABLEBASE_STATS = ("tablebase",)                        # cz_selfplay_tablebase_stats
+SP_RESIGN_STATS = ("resigned", "playon_games", "playon_would_resign", "playon_false_positives")   # cz_selfplay_resign_stats
 # why a match game ended (include/cchess_hip.h: CZ_MATCH_*); 0 = not finished
 MATCH_KING, MATCH_RR60, MATCH_PLY_CAP, MATCH_ABORTED, MATCH_MATE, MATCH_REPETITION, MATCH_PERPETUAL = 1, 2, 3, 4, 5, 6, 7
 MATCH_CHASE = 9   # 8 is not assigned
 MATCH_RESIGN = 10
 MATCH_TABLEBASE = 11   # cz_match_set_tablebase / cz_selfplay_set_tablebase: the position after the move is in a table
-SP_TABLEBASE_STATS = ("tablebase",)   # cz_selfplay_tablebase_stats
-SP_RESIGN_STATS = ("resigned", "playon_games", "playon_would_resign", "playon_false_positives")   # cz_selfplay_resign_stats
 # verdicts of cz_repetition (include/cchess_hip.h: CZ_REP_*)
 REP_NONE, REP_DRAW, REP_RED_LOSES, REP_BLACK_LOSES = 0, 1, 2, 3
 # why cz_repetition_chase gave its verdict (include/cchess_hip.h: CZ_CAUSE_*)

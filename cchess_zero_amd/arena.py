@@ -31,7 +31,8 @@ from ._lib import (MATCH_ABORTED, MATCH_CHASE, MATCH_KING, MATCH_MATE, MATCH_PER
                    lib, out_pointers, tables)
 from .engine import SearchEngine, plane_format, pool_nodes
 from .notation import player_to_side, state_to_board
-from .rules import RULES, check_rule_options, root_rules_chase_history, root_rules_history, set_rule_options   # noqa: F401 (RULES: re-exported)
+from .rules import (RULES, add_rule_flags, check_rule_flags, check_rule_options, root_rules_chase_history, root_rules_history,   # noqa: F401 (RULES: re-exported)
+                    set_rule_options, tablebase_set)
 
 REASONS = {0: "unfinished", MATCH_KING: "king", MATCH_RR60: "rr60", MATCH_PLY_CAP: "ply_cap", MATCH_ABORTED: "aborted", MATCH_MATE: "mate",
            MATCH_REPETITION: "repetition", MATCH_PERPETUAL: "perpetual", MATCH_CHASE: "chase", MATCH_RESIGN: "resign", MATCH_TABLEBASE: "tablebase"}
@@ -340,13 +341,9 @@ class Match:
 
     def __init__(self, player_a, player_b, openings, slots, max_plies=512, sample_plies=0, seed=0, check_every=8,
                  nodes_per_tree=None, rules="capture", repetition=0, chase=False, resign=None, resign_min_ply=0, tablebase=None):
-        check_rule_options("Match", rules, repetition, chase)
-        if tablebase is not None and rules != "xiangqi":
-            raise ValueError("Match: tablebase needs rules='xiangqi' (a table holds values under xiangqi rules)")
+        check_rule_options("Match", rules, repetition, chase, tablebase, resign_min_ply)
         self.tablebase = tablebase
-        self._tb_set = self._tb_own = None
-        if int(resign_min_ply) < 0:
-            raise ValueError("Match: resign_min_ply >= 0")
+        self._tb_own = None
         self.resign = None if resign is None else float(resign)
         self.resign_min_ply = int(resign_min_ply)
         self.rules = rules
@@ -430,9 +427,8 @@ class Match:
         if self.resign is not None:
             call("cz_match_set_resign", self._h, self.resign, self.resign_min_ply)
         if self.tablebase is not None:   # a Tablebase: a set over its loaded tables, this match's to close
-            self._tb_set = self.tablebase.device_set() if hasattr(self.tablebase, "device_set") else self.tablebase
-            self._tb_own = self._tb_set if self._tb_set is not self.tablebase else None
-            call("cz_match_set_tablebase", self._h, self._tb_set.h)
+            dset, self._tb_own = tablebase_set(self.tablebase)
+            call("cz_match_set_tablebase", self._h, dset.h)
         self.masks = [out_pointers("cz_match_active", self._h, 1, player)[0] for player in (0, 1)]
         self.played = torch.empty(G, dtype=torch.int16, device=dev)
 
@@ -494,7 +490,7 @@ class Match:
             self._h = None
         if self._tb_own is not None:
             self._tb_own.close()
-        self._tb_set = self._tb_own = None
+        self._tb_own = None
 
 
 # ---- command line --------------------------------------------------------------------------------------------------------
@@ -531,28 +527,12 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=0, help="openings and sampled plies")
     ap.add_argument("--max_plies", type=int, default=512, help="a game reaching it is a draw")
     ap.add_argument("--sample_plies", type=int, default=0, help="plies sampled from softmax(log N) at the start of a game")
-    ap.add_argument("--rules", choices=sorted(RULES), default="capture",
-                    help="capture: the reference's king-capture games; xiangqi: king-safe moves only, no safe move loses")
-    ap.add_argument("--repetition", type=int, default=0,
-                    help="with --rules xiangqi: a game ends when its position occurs for the N-th time (3 is the usual value): a draw, "
-                         "or a loss for the side that checked perpetually; 0 = no repetition rule")
-    ap.add_argument("--chase", action="store_true",
-                    help="with --repetition: a side that alone chased one unprotected piece with every move of the cycle loses")
+    add_rule_flags(ap, "the match")
     ap.add_argument("--resign", type=float, default=None,
                     help="a mover whose root value (Q of its most visited move) is below X resigns; default: games are played out")
     ap.add_argument("--resign_min_ply", type=int, default=0, help="with --resign: plies of a game before anybody may resign")
-    ap.add_argument("--tablebase", metavar="DIR", default=None,
-                    help="with --rules xiangqi: a game that reaches a position of a table in DIR (python -m cchess_zero_amd.tablebase --build) "
-                         "ends there with the table's result")
     args = ap.parse_args(argv)
-    try:
-        check_rule_options("arena", args.rules, args.repetition, args.chase)
-    except ValueError as e:
-        ap.error(str(e))
-    if args.tablebase and args.rules != "xiangqi":
-        ap.error("--tablebase needs --rules xiangqi (a table holds values under xiangqi rules)")
-    if args.tablebase and not os.path.isdir(args.tablebase):
-        ap.error("--tablebase: %s is no directory" % args.tablebase)
+    load_tables = check_rule_flags(ap, args, "arena")
     a = load_player(args.a, args.blocks)
     b = a if args.b == args.a else load_player(args.b, args.blocks)
     if args.all_openings:
@@ -564,12 +544,10 @@ def main(argv=None):
     else:
         pairs = ((256 if args.games is None else args.games) + 1) // 2
         op = random_openings(pairs, args.opening_plies, args.seed)
-    tb = None
-    if args.tablebase:   # under several ranks every rank loads the directory itself
-        from .tablebase import Tablebase
-        tb = Tablebase()
-        if not tb.load(args.tablebase):
-            ap.error("--tablebase: no table in %s" % args.tablebase)
+    try:
+        tb = load_tables()   # under several ranks every rank loads the directory itself
+    except ValueError as e:
+        ap.error(str(e))
     res = Match((a, args.playout), (b, args.playout_b or args.playout), op, slots=args.slots or 2 * pairs, max_plies=args.max_plies,
                 sample_plies=args.sample_plies, seed=args.seed, rules=args.rules, repetition=args.repetition, chase=args.chase,
                 resign=args.resign, resign_min_ply=args.resign_min_ply, tablebase=tb).play()

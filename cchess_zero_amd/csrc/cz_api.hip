@@ -162,10 +162,8 @@ void cz_destroy(cz_ctx *c) {
     if (c->tree_block) (void)hipFree(c->tree_block);
     if (c->pool_block) (void)hipFree(c->pool_block);
     if (c->sp_block) (void)hipFree(c->sp_block);
-    if (c->sp_chase_block) (void)hipFree(c->sp_chase_block);
     if (c->sp_resign_block) (void)hipFree(c->sp_resign_block);
-    cz_tb_set_hold(c->sp_tb, -1);   // the set is the caller's: only the hold on it goes
-    if (c->sp_tb_block) (void)hipFree(c->sp_tb_block);
+    cz_root_free(c->sp_root);
     if (c->ec_block) (void)hipFree(c->ec_block);
 #if defined(CZ_EXPERIMENT_MX2) || defined(CZ_EXPERIMENT_MX12)
     if (c->mx_xbuf) (void)hipFree(c->mx_xbuf);

@@ -82,7 +82,8 @@ struct CzPool {
     uint16_t *sd;   // src | dst << 8 of `move` (k_select applies the move without the label -> (src, dst) table round trip)
 };
 
-// cz_selfplay_set_resign: what resignation keeps per slot, and its counters — an allocation of its own (cz_ctx::sp_resign_block).
+// cz_selfplay_set_resign: what resignation keeps per slot — an allocation of its own (cz_ctx::sp_resign_block); its counters are
+// slots of CzSelfplay::stats.
 // game_no == NULL: the setter has not run since cz_selfplay_begin, and no kernel does anything for it.
 struct CzSpResign {
     float threshold;             // a mover whose root value (wave_root_value) is below it resigns; NaN: no ply is judged
@@ -94,12 +95,21 @@ struct CzSpResign {
     float *minq;                 // [max_games][2] lowest judged root value of red / black in the game in progress; 2.0: none yet
     uint8_t *would;              // [max_games] play-on game: 0, or 1 + the side that first crossed the threshold
     uint8_t *resigned;           // [max_games] the last choose resigned the game (k_sp_adjudicate ends it)
-    long long *stats;            // [4] resigned, playon_games, playon_would_resign, playon_false_positives
-    long long *hist;             // [64] lowest root values of the sides that did not lose a play-on game, bins of 1/32 over [-1, 1)
 };
 __device__ __forceinline__ bool sp_plays_on(const CzSpResign &rs, int g, uint32_t game_no) {
     return uniform53(splitmix64(rs.seed ^ splitmix64(((unsigned long long)g << 32) | (unsigned long long)game_no))) < rs.playon_fraction;
 }
+
+// Every counter of self-play is a slot of CzSelfplay::stats, cleared by cz_selfplay_begin: the public CZ_SP_NSTATS
+// (cz_selfplay_stats), then what the other four getters copy out, each a slice in its own order
+enum CzSpSlot {
+    CZ_SP_MATES = CZ_SP_NSTATS, CZ_SP_REPETITIONS, CZ_SP_PERPETUALS,              // cz_selfplay_rules_stats
+    CZ_SP_CHASES,                                                                   // cz_selfplay_chase_stats
+    CZ_SP_TABLEBASE,                                                                // cz_selfplay_tablebase_stats
+    CZ_SP_RESIGNED, CZ_SP_PLAYON_GAMES, CZ_SP_PLAYON_WOULD, CZ_SP_PLAYON_FALSE,   // cz_selfplay_resign_stats
+    CZ_SP_RESIGN_HIST,   // its 64 bins: lowest root values of the sides that did not lose a play-on game, 1/32 each over [-1, 1)
+    CZ_SP_NSLOTS = CZ_SP_RESIGN_HIST + 64
+};
 
 // cz_selfplay_*: per game slot, the (s, pi, z) records of the game in progress (cchess_main.selfplay keeps
 // states / mcts_probs / current_players lists, main.py:1496-1518) and the counters of finished games
@@ -112,17 +122,17 @@ struct CzSelfplay {
     uint8_t *start_board;        // [max_games][96] position every new game of the slot starts from
     uint8_t *start_side;         // [max_games]
     int32_t *start_rr;           // [max_games]
-    long long *stats;            // [CZ_SP_NSTATS]
+    long long *stats;            // [CZ_SP_NSLOTS] (CzSpSlot)
     // cz_selfplay_set_rules(1): what the rules at the root keep beside the games (cz_rootrules.h); the chase part is an allocation
-    // of its own, chase_stat behind it, NULL while cz_selfplay_set_chase is off
+    // of its own (CzRootHost), NULL while cz_selfplay_set_chase is off
     CzRootRules rr;
-    long long *xq_stats;         // [3] games ended by mate, by a repetition draw, by perpetual check (cz_selfplay_rules_stats)
-    long long *chase_stat;       // [1] games ended by perpetual chase (cz_selfplay_chase_stats)
-    // cz_selfplay_set_tablebase: an allocation of its own (cz_ctx::sp_tb_block).  tb_value NULL: no set is attached, nothing is probed
+    // cz_selfplay_set_tablebase: an allocation of its own (CzRootHost).  tb_value NULL: no set is attached, nothing is probed
     int16_t *tb_value;           // [max_games] the table set's value of every slot's root position after the move (k_tb_probe_set)
-    long long *tb_stat;          // [1] games adjudicated from a table (cz_selfplay_tablebase_stats); NULL before the first attach
     CzSpResign rs;               // cz_selfplay_set_resign
 };
+__device__ __forceinline__ void sp_count(const CzSelfplay &sp, int slot, unsigned long long n = 1ull) {
+    atomicAdd((unsigned long long *)&sp.stats[slot], n);
+}
 
 // Per-tree scalars: ONE 64-byte record per tree instead of sixteen arrays.  A wave owns a tree, so what it reads at entry
 // (root, counters, status) and leaves behind (the pending leaf) is one cache line, and the kernels hold one base pointer
@@ -193,6 +203,28 @@ struct CzTrees {
     unsigned long long *evtotal;      // [2] rows evaluated, steps: running totals for the flop accounting
 };
 
+// The rules at the root and the table set of one consumer, host side: the match embeds one (cz_match), self-play one (cz_ctx).  The
+// device view — rr (the fold is rr->fold) and tb_value — stays inside the consumer's kernel-argument struct; the functions on
+// this one (cz_root_*, below) are the bodies of both consumers' setters and getters.
+struct cz_ctx;
+struct CzRootHost {
+    // the consumer's contract (cz_root_begin): the names its error texts speak of, and where the two consumers differ
+    const char *api, *handle, *since;   // "cz_match" / "cz_selfplay", "match" / "ctx", where the consumer's history starts
+    bool rules_between_plies;   // the match: the rules may change between two plies, the first choose freezes only the fold and the chase rule
+    bool owns_rules_part;       // the match: rr's arrays other than the chase part are a zeroed allocation of the first set_rules(1);
+                                // self-play's live in sp_block and are k_sp_seed's to initialise
+    bool rezero_chase;          // self-play: the chase rings are cleared at every switching on; the match's once, when they are made
+    cz_ctx *c;                  // whose stream and device
+    int G;                      // slots the arrays are carved for
+    CzRootRules *rr;
+    int16_t **tb_value;
+    // the state
+    int rules, chase;           // 0 king capture / 1 xiangqi; 1: perpetual chase is judged too (needs a fold)
+    bool chosen;                // a choose has run
+    cz_tb_set *tb;              // the attached table set (not owned; held), or NULL
+    void *rules_block, *chase_block, *tb_block;   // rr's two parts and tb_value, made at the first switching on, kept until cz_root_free
+};
+
 struct cz_ctx {
     int device;
     hipStream_t stream;
@@ -224,14 +256,9 @@ struct cz_ctx {
     unsigned long long *clock_probe;  // cz_set_clock_probe: [clock_probe_wgs][4] stamps written by the trunk kernels, or NULL
     int clock_probe_wgs, clock_probe_last_grid;
     CzSelfplay sp;     // cz_selfplay_begin
-    void *sp_block;
-    int sp_rules;      // cz_selfplay_set_rules: 0 king capture, 1 xiangqi
-    int sp_chase;      // cz_selfplay_set_chase: 0 off, 1 on (needs a fold, sp.rr.fold: cz_selfplay_set_repetition)
-    void *sp_chase_block;
+    void *sp_block;    // NULL: no cz_selfplay_begin yet
+    CzRootHost sp_root;      // the rules at the root of self-play and its table set, over sp.rr and sp.tb_value
     void *sp_resign_block;   // cz_selfplay_set_resign: allocated by its first call, sp.rs points into it while resignation is set
-    cz_tb_set *sp_tb;         // cz_selfplay_set_tablebase: the attached table set (not owned), or NULL
-    void *sp_tb_block;        // allocated by the first attach since cz_create: sp.tb_value and sp.tb_stat
-    int sp_state;     // 0: no cz_selfplay_begin yet, 1: begun (the setters may be called), 2: a cz_selfplay_choose has run since
     void *ec_block;    // cz_search_set_eval_cache
 };
 
@@ -551,4 +578,108 @@ inline int cz_root_rules_order(const char *api, const char *handle, const char *
     if (e.empty()) return CZ_OK;
     cz_set_error("%s", e.c_str());
     return CZ_EINVAL;
+}
+
+// ---- one consumer's rules at the root and table set (CzRootHost): what the public setters and getters of both call ----
+// A consumer starts (cz_match_create, cz_selfplay_begin): its contract — the first ten fields of `contract` —, rules, fold and
+// chase off, nothing chosen, no set attached; the blocks it has stay for the next switching on.
+inline void cz_root_begin(CzRootHost &h, CzRootHost contract) {
+    cz_tb_set_hold(h.tb, -1);
+    contract.rules_block = h.rules_block; contract.chase_block = h.chase_block; contract.tb_block = h.tb_block;
+    h = contract;
+    h.rr->fold = 0;
+    *h.tb_value = nullptr;
+}
+inline int cz_root_order(const CzRootHost &h, int what, int value) {
+    return cz_root_rules_order(h.api, h.handle, h.since, what, value, h.rules, h.rr->fold, h.chase,
+                               h.chosen && !(what == CZ_SET_RULES && h.rules_between_plies), h.tb != nullptr);
+}
+// one part of rr (carve_root_rules) in a zeroed allocation of its own, for the setter `_set_<what>`
+inline int cz_root_carve(CzRootHost &h, void **block, bool chase_part, const char *what) {
+    return carve_alloc(block, h.c->stream, true, (std::string(h.api) + "_set_" + what).c_str(),
+                       [&](Carver &k) { carve_root_rules(k, *h.rr, (size_t)h.G, chase_part); });
+}
+inline int cz_root_set_rules(CzRootHost &h, int rules) {
+    if (const int rc = cz_root_order(h, CZ_SET_RULES, rules)) return rc;
+    if (rules == 1 && h.owns_rules_part && !h.rules_block) {
+        if (const int rc = cz_root_carve(h, &h.rules_block, false, "rules")) return rc;
+    }
+    h.rules = rules;
+    return CZ_OK;
+}
+inline int cz_root_set_repetition(CzRootHost &h, int fold) {
+    if (const int rc = cz_root_order(h, CZ_SET_REPETITION, fold)) return rc;
+    h.rr->fold = fold;
+    return CZ_OK;
+}
+inline int cz_root_set_chase(CzRootHost &h, int on) {
+    if (const int rc = cz_root_order(h, CZ_SET_CHASE, on)) return rc;
+    if (on && (h.rezero_chase || !h.chase_block)) {
+        if (const int rc = cz_root_carve(h, &h.chase_block, true, "chase")) return rc;
+    }
+    h.chase = on;
+    return CZ_OK;
+}
+// the device pointers of the rings, owned by the consumer; CZ_EINVAL while the rule is off
+inline int cz_root_history(const CzRootHost &h, const uint64_t **keys, const uint8_t **checks) {
+    if (h.rr->fold == 0) { cz_set_error("%s_history: %s_set_repetition first", h.api, h.api); return CZ_EINVAL; }
+    if (keys) *keys = h.rr->ring_key;
+    if (checks) *checks = h.rr->ring_check;
+    return CZ_OK;
+}
+inline int cz_root_chase_history(const CzRootHost &h, const uint64_t **chase) {
+    if (h.chase == 0) { cz_set_error("%s_chase_history: %s_set_chase first", h.api, h.api); return CZ_EINVAL; }
+    if (chase) *chase = h.rr->ring_chase;
+    return CZ_OK;
+}
+// attaches `set` (NULL: detaches): what cz_tb_set_attachable asks, tb_value [G] in an allocation made once, the holds
+inline int cz_root_set_tablebase(CzRootHost &h, cz_tb_set *set) {
+    if (const int rc = cz_tb_set_attachable(h.api, h.handle, h.c, set, h.rules)) return rc;
+    *h.tb_value = nullptr;
+    if (set) {
+        const int rc = carve_alloc(&h.tb_block, h.c->stream, false, (std::string(h.api) + "_set_tablebase").c_str(),
+                                   [&](Carver &k) { *h.tb_value = k.take<int16_t>((size_t)h.G); });
+        if (rc != CZ_OK) { *h.tb_value = nullptr; return rc; }
+    }
+    cz_tb_set_hold(set, 1);
+    cz_tb_set_hold(h.tb, -1);
+    h.tb = set;
+    return CZ_OK;
+}
+// In front of an adjudicate kernel: the attached set's value of the G root positions of h.c's trees after the move, read in
+// place — boards 96 bytes apart, sides in the tree records — into tb_value.  Nothing without a set.
+inline int cz_root_probe(const CzRootHost &h, const uint16_t *played, int G) {
+    if (!h.tb || !*h.tb_value) return CZ_OK;
+    const CzTrees &t = h.c->t;
+    return cz_tb_set_probe_strided(h.c, h.tb, t.root_board, CZD_BOARD_LDS, &t.root_side[0], (int)sizeof(CzTreeRec), played, G, *h.tb_value, nullptr);
+}
+inline int cz_root_level(const CzRootHost &h) { return cz_rules_level(h.rules, h.rr->fold, h.chase); }
+// A consumer's choose over G slots.  From CZ_RULES_KINGSAFE: gather(), its launch of the kernel that copies every slot's root
+// position out (wave_gather_root), then what the rules need of them; then choose(L), its launch of the choose kernel at level L.
+template <typename Gather, typename Choose>
+inline int cz_root_choose(CzRootHost &h, int G, Gather gather, Choose choose) {
+    h.chosen = true;
+    const int level = cz_root_level(h);
+    if (level >= CZ_RULES_KINGSAFE) {
+        gather();
+        CZ_HIP(hipGetLastError());
+        if (const int rc = czk_root_rules_prepare(h.c, *h.rr, G, level)) return rc;
+    }
+    cz_by_rules_level(level, choose);
+    CZ_HIP(hipGetLastError());
+    return CZ_OK;
+}
+// A consumer's adjudicate: the probe, then adjudicate(L), its launch of the adjudicate kernel at level L
+template <typename Adjudicate>
+inline int cz_root_adjudicate(const CzRootHost &h, const uint16_t *played, int G, Adjudicate adjudicate) {
+    if (const int rc = cz_root_probe(h, played, G)) return rc;
+    cz_by_rules_level(cz_root_level(h), adjudicate);
+    CZ_HIP(hipGetLastError());
+    return CZ_OK;
+}
+// the hold on the set and the blocks (the set itself is the caller's)
+inline void cz_root_free(CzRootHost &h) {
+    cz_tb_set_hold(h.tb, -1);
+    for (void *b : {h.rules_block, h.chase_block, h.tb_block})
+        if (b) (void)hipFree(b);
 }

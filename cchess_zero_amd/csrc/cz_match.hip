@@ -40,15 +40,9 @@ struct CzMatch {
 struct cz_match {
     cz_ctx *a, *b;
     int G, n_games;
-    CzMatch m;                          // the arrays inside block; m.rr inside rules_block and chase_block (m.rr.fold: cz_match_set_repetition)
+    CzMatch m;                          // the arrays inside block; m.rr and m.tb_value inside root's blocks
     void *block;
-    int rules;                          // 0: king capture (the reference's games), 1: xiangqi (cz_match_set_rules)
-    void *rules_block;                  // allocated by the first cz_match_set_rules(1): the king-safe and repetition arrays
-    bool chosen;                        // a cz_match_choose has run: the repetition rule can no longer be switched on
-    int chase;                          // 1: perpetual chase is judged too (cz_match_set_chase; needs a fold)
-    void *chase_block;                  // allocated by the first cz_match_set_chase(1): the slots' rings of chase records
-    cz_tb_set *tb;                      // cz_match_set_tablebase: the attached table set (not owned), or NULL
-    void *tb_block;                     // allocated by the first attach: m.tb_value
+    CzRootHost root;                    // the rules at the root and the table set (cz_internal.h), over m.rr and m.tb_value
 };
 
 namespace {
@@ -232,6 +226,8 @@ int cz_match_create(cz_ctx *a, cz_ctx *b, const uint8_t *boards, const uint8_t *
     CzMatch &m = mh->m;
     m.G = mh->G; m.n_games = mh->n_games; m.max_plies = max_plies; m.pair_base = pair_base; m.pair_stride = pair_stride;
     m.resign_threshold = NAN; m.resign_min_ply = 0;
+    // the rules may change between two plies; m.rr's arrays are all the root's own, zeroed once when they are made
+    cz_root_begin(mh->root, CzRootHost{"cz_match", "match", "the history starts at the openings", true, true, false, a, mh->G, &m.rr, &m.tb_value});
     const size_t np = (size_t)n_openings;
     int rc = carve_alloc(&mh->block, a->stream, true, "cz_match_create", [&](Carver &k) { carve(k, m, (size_t)mh->G, (size_t)mh->n_games); });
     auto fail = [&](hipError_t e, const char *what) {
@@ -259,54 +255,23 @@ int cz_match_create(cz_ctx *a, cz_ctx *b, const uint8_t *boards, const uint8_t *
     return CZ_OK;
 }
 
-// the setters' order (cz_root_rules_order), in the match's names; the rules themselves may change between two plies
-static int match_order(const cz_match *mh, int what, int value) {
-    const char *since = "the history starts at the openings";
-    if (!mh) return cz_root_rules_order("cz_match", "match", since, what, -1, 0, 0, 0, false);   // the text of a value out of range
-    return cz_root_rules_order("cz_match", "match", since, what, value, mh->rules, mh->m.rr.fold, mh->chase, what != CZ_SET_RULES && mh->chosen,
-                               mh->tb != nullptr);
-}
+// a setter of the rules on no match: refused with the text of a value out of range
+static int no_match(int what) { return cz_root_rules_order("cz_match", "match", "", what, -1, 0, 0, 0, false); }
 
-// one part of m.rr (carve_root_rules) in a zeroed allocation of its own
-static int alloc_root_rules(cz_match *mh, void **block, bool chase_part, const char *who) {
-    return carve_alloc(block, mh->a->stream, true, who, [&](Carver &k) { carve_root_rules(k, mh->m.rr, (size_t)mh->G, chase_part); });
-}
+int cz_match_set_rules(cz_match *mh, int rules) { return mh ? cz_root_set_rules(mh->root, rules) : no_match(CZ_SET_RULES); }
 
-int cz_match_set_rules(cz_match *mh, int rules) {
-    if (const int rc = match_order(mh, CZ_SET_RULES, rules)) return rc;
-    if (rules == 1 && !mh->rules_block) {
-        if (const int rc = alloc_root_rules(mh, &mh->rules_block, false, "cz_match_set_rules")) return rc;
-    }
-    mh->rules = rules;
-    return CZ_OK;
-}
-
-int cz_match_set_repetition(cz_match *mh, int fold) {
-    if (const int rc = match_order(mh, CZ_SET_REPETITION, fold)) return rc;
-    mh->m.rr.fold = fold;
-    return CZ_OK;
-}
+int cz_match_set_repetition(cz_match *mh, int fold) { return mh ? cz_root_set_repetition(mh->root, fold) : no_match(CZ_SET_REPETITION); }
 
 int cz_match_history(cz_match *mh, const uint64_t **keys, const uint8_t **checks) {
-    CZ_REQUIRE(mh && mh->m.rr.fold != 0, "cz_match_history: cz_match_set_repetition first");
-    if (keys) *keys = mh->m.rr.ring_key;
-    if (checks) *checks = mh->m.rr.ring_check;
-    return CZ_OK;
+    CZ_REQUIRE(mh, "cz_match_history: cz_match_set_repetition first");
+    return cz_root_history(mh->root, keys, checks);
 }
 
-int cz_match_set_chase(cz_match *mh, int on) {
-    if (const int rc = match_order(mh, CZ_SET_CHASE, on)) return rc;
-    if (on && !mh->chase_block) {
-        if (const int rc = alloc_root_rules(mh, &mh->chase_block, true, "cz_match_set_chase")) return rc;
-    }
-    mh->chase = on;
-    return CZ_OK;
-}
+int cz_match_set_chase(cz_match *mh, int on) { return mh ? cz_root_set_chase(mh->root, on) : no_match(CZ_SET_CHASE); }
 
 int cz_match_chase_history(cz_match *mh, const uint64_t **chase) {
-    CZ_REQUIRE(mh && mh->chase != 0, "cz_match_chase_history: cz_match_set_chase first");
-    if (chase) *chase = mh->m.rr.ring_chase;
-    return CZ_OK;
+    CZ_REQUIRE(mh, "cz_match_chase_history: cz_match_set_chase first");
+    return cz_root_chase_history(mh->root, chase);
 }
 
 int cz_match_set_resign(cz_match *mh, float threshold, int min_ply) {
@@ -318,27 +283,14 @@ int cz_match_set_resign(cz_match *mh, float threshold, int min_ply) {
 
 int cz_match_set_tablebase(cz_match *mh, cz_tb_set *set) {
     CZ_REQUIRE(mh, "cz_match_set_tablebase: null match");
-    if (const int rc = cz_tb_set_attachable("cz_match", "match", mh->a, set, mh->rules)) return rc;
-    if (set) {
-        const int rc = carve_alloc(&mh->tb_block, mh->a->stream, false, "cz_match_set_tablebase", [&](Carver &k) { mh->m.tb_value = k.take<int16_t>((size_t)mh->G); });
-        if (rc != CZ_OK) { mh->m.tb_value = nullptr; return rc; }
-    } else {
-        mh->m.tb_value = nullptr;
-    }
-    cz_tb_set_hold(set, 1);
-    cz_tb_set_hold(mh->tb, -1);
-    mh->tb = set;
-    return CZ_OK;
+    return cz_root_set_tablebase(mh->root, set);
 }
 
 void cz_match_destroy(cz_match *mh) {
     if (!mh) return;
     (void)hipStreamSynchronize(mh->a->stream);
-    cz_tb_set_hold(mh->tb, -1);
-    if (mh->tb_block) (void)hipFree(mh->tb_block);
+    cz_root_free(mh->root);
     (void)hipFree(mh->block);
-    if (mh->rules_block) (void)hipFree(mh->rules_block);
-    if (mh->chase_block) (void)hipFree(mh->chase_block);
     delete mh;
 }
 
@@ -352,34 +304,21 @@ int cz_match_active(cz_match *mh, int player, const uint8_t **mask) {
 int cz_match_choose(cz_match *mh, int sample_plies, unsigned long long seed, uint16_t *played) {
     CZ_REQUIRE(mh && played && sample_plies >= 0, "cz_match_choose: null argument / sample_plies < 0");
     CZ_REQUIRE(mh->a->G == mh->G && mh->b->G == mh->G, "cz_match_choose: a context was reset to another number of slots");
-    mh->chosen = true;
-    const int level = cz_rules_level(mh->rules, mh->m.rr.fold, mh->chase);
-    if (level >= CZ_RULES_KINGSAFE) {   // what the rules need of every slot's root position, then the choice
-        hipLaunchKernelGGL(k_match_roots_xq, dim3(mh->G), dim3(64), 0, mh->a->stream, mh->a->t, mh->b->t, mh->m);
-        CZ_HIP(hipGetLastError());
-        if (const int rc = czk_root_rules_prepare(mh->a, mh->m.rr, mh->G, level)) return rc;
-    }
-    cz_by_rules_level(level, [&](auto L) {
-        hipLaunchKernelGGL(k_match_choose<decltype(L)::value>, dim3(mh->G), dim3(64), 0, mh->a->stream, mh->a->t, mh->b->t, mh->m, sample_plies, seed, played);
-    });
-    CZ_HIP(hipGetLastError());
-    return CZ_OK;
+    return cz_root_choose(
+        mh->root, mh->G, [&] { hipLaunchKernelGGL(k_match_roots_xq, dim3(mh->G), dim3(64), 0, mh->a->stream, mh->a->t, mh->b->t, mh->m); },
+        [&](auto L) {
+            hipLaunchKernelGGL(k_match_choose<decltype(L)::value>, dim3(mh->G), dim3(64), 0, mh->a->stream, mh->a->t, mh->b->t, mh->m, sample_plies, seed,
+                               played);
+        });
 }
 
 int cz_match_adjudicate(cz_match *mh, const uint16_t *played) {
     CZ_REQUIRE(mh && played, "cz_match_adjudicate: null argument");
     CZ_REQUIRE(mh->a->G == mh->G && mh->b->G == mh->G, "cz_match_adjudicate: a context was reset to another number of slots");
-    if (mh->tb && mh->m.tb_value) {   // both trees hold the position after the move (cz_search_advance applies a label to the board of either): A's, in place
-        cz_ctx *a = mh->a;
-        if (const int rc = cz_tb_set_probe_strided(a, mh->tb, a->t.root_board, CZD_BOARD_LDS, &a->t.root_side[0], (int)sizeof(CzTreeRec), played, mh->G,
-                                                   mh->m.tb_value, nullptr))
-            return rc;
-    }
-    cz_by_rules_level(cz_rules_level(mh->rules, mh->m.rr.fold, mh->chase), [&](auto L) {
+    // both trees hold the position after the move (cz_search_advance applies a label to the board of either): the set is probed on A's
+    return cz_root_adjudicate(mh->root, played, mh->G, [&](auto L) {
         hipLaunchKernelGGL(k_match_adjudicate<decltype(L)::value>, dim3(mh->G), dim3(64), 0, mh->a->stream, mh->a->t, mh->b->t, mh->m, played);
     });
-    CZ_HIP(hipGetLastError());
-    return CZ_OK;
 }
 
 int cz_match_results(cz_match *mh, const int8_t **result, const uint8_t **a_red, const int32_t **plies, const uint8_t **reason,

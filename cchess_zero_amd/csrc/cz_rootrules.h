@@ -2,7 +2,7 @@
 // (cz_selfplay.hip): the king-safe set of the root position, the slot's rings of position keys, check flags and chase records,
 // and the repetition / perpetual-check / perpetual-chase verdict on them; and wave_choose_prologue, the steps both choose kernels
 // take at a root before they choose.  The search below the root is untouched.  How a game then ends is wave_game_end's
-// (cz_internal.h), for these two and the bench driver.  The host side (carve_root_rules, czk_root_rules_prepare, cz_root_rules_order) is in cz_internal.h.
+// (cz_internal.h), for these two and the bench driver.  The host side (CzRootHost and its cz_root_* functions) is in cz_internal.h.
 #pragma once
 #include <type_traits>
 

@@ -39,11 +39,9 @@ __global__ __launch_bounds__(64) void k_sp_seed(CzTrees t, CzSelfplay sp, int G,
         sp.start_rr[g] = boards ? (rr ? rr[g] : 0) : t.root_rr[g];
         sp.ply[g] = 0; sp.stalled[g] = 0; sp.active[g] = 1;
         sp.rr.mated[g] = 0; sp.rr.rep[g] = CZ_REP_NONE;
-        if (g == 0) {
-            for (int k = 0; k < CZ_SP_NSTATS; ++k) sp.stats[k] = 0;
-            for (int k = 0; k < 3; ++k) sp.xq_stats[k] = 0;
-        }
     }
+    if (g == 0)   // every counter starts with the games
+        for (int k = lane; k < CZ_SP_NSLOTS; k += 64) sp.stats[k] = 0;
     sp.rr.ring_key[(size_t)g * 64 + lane] = 0ull;
     sp.rr.ring_check[(size_t)g * 64 + lane] = 0;
 }
@@ -91,7 +89,7 @@ __global__ __launch_bounds__(64) void k_sp_choose(CzTrees t, CzSelfplay sp, int 
         if (lane == 0) played[g] = 0xFFFF;
         return;
     }
-    if (lane == 0) atomicAdd((unsigned long long *)&sp.stats[CZ_SP_SIMS], (unsigned long long)t.sims[g]);
+    if (lane == 0) sp_count(sp, CZ_SP_SIMS, (unsigned long long)t.sims[g]);
     if (XQ && lane == 0) { sp.rr.mated[g] = 0; sp.rr.rep[g] = CZ_REP_NONE; }
     const TreeView v = view_of(t, g);
     const int ply = sp.ply[g];
@@ -179,13 +177,13 @@ __global__ __launch_bounds__(64) void k_sp_choose(CzTrees t, CzSelfplay sp, int 
 // stalled choose or a played label that is no root child, and such a game is dropped with no record.  From CZ_RULES_KINGSAFE the
 // endings the last choose found on the root it left untouched come first — a repetition verdict (a draw, or a loss for the side
 // that checked perpetually), then a mated mover (the side to move loses); z as for a king capture.  At CZ_RULES_CHASE the verdict
-// may be a chase — a loss for the side that chased, z as for perpetual check, counted in chase_stat and not among the perpetuals.
+// may be a chase — a loss for the side that chased, z as for perpetual check, counted in CZ_SP_CHASES and not among the perpetuals.
 // cz_selfplay_set_resign, at every level: a game the last choose resigned is lost by the side to move, z as for a king capture;
 // a play-on game that ends here — however it ends, unless it stalled — goes into the play-on counters and the histogram; the
 // slot's resignation state starts over with its next game.
 // cz_selfplay_set_tablebase: sp.tb_value[g] is what the attached set answers for the position after the move (k_tb_probe_set, the
 // launch in front of this one; CZ_TB_MISS for a slot whose `played` is no label); a covered value ends the game at its place in
-// wave_game_end's precedence, z and the counters as for a king capture, and sp.tb_stat counts it.
+// wave_game_end's precedence, z and the counters as for a king capture, and CZ_SP_TABLEBASE counts it.
 template <int LEVEL>
 __global__ __launch_bounds__(64) void k_sp_adjudicate(CzTrees t, CzSelfplay sp, int G, int reseed, const uint16_t *__restrict__ played,
                                                       int32_t *__restrict__ fin_n) {
@@ -217,31 +215,28 @@ __global__ __launch_bounds__(64) void k_sp_adjudicate(CzTrees t, CzSelfplay sp, 
     }
     if (lane == 0) {
         fin_n[g] = n;
-        atomicAdd((unsigned long long *)&sp.stats[CZ_SP_GAMES], 1ull);
-        if (stalled) atomicAdd((unsigned long long *)&sp.stats[CZ_SP_STALLED], 1ull);
-        else if (decided) atomicAdd((unsigned long long *)&sp.stats[winner ? CZ_SP_BLACK_WINS : CZ_SP_RED_WINS], 1ull);
-        else atomicAdd((unsigned long long *)&sp.stats[CZ_SP_DRAWS], 1ull);
-        atomicAdd((unsigned long long *)&sp.stats[CZ_SP_PLIES], (unsigned long long)n);
-        if (end.how == CZ_MATCH_TABLEBASE) atomicAdd((unsigned long long *)sp.tb_stat, 1ull);   // only with a set attached: tb_stat stands
+        sp_count(sp, CZ_SP_GAMES);
+        sp_count(sp, stalled ? CZ_SP_STALLED : decided ? (winner ? CZ_SP_BLACK_WINS : CZ_SP_RED_WINS) : CZ_SP_DRAWS);
+        sp_count(sp, CZ_SP_PLIES, (unsigned long long)n);
+        if (end.how == CZ_MATCH_TABLEBASE) sp_count(sp, CZ_SP_TABLEBASE);
         if constexpr (XQ) {
-            if (end.how == CZ_MATCH_CHASE) atomicAdd((unsigned long long *)sp.chase_stat, 1ull);
-            else if (end.how == CZ_MATCH_MATE) atomicAdd((unsigned long long *)&sp.xq_stats[0], 1ull);
-            else if (end.how == CZ_MATCH_REPETITION || end.how == CZ_MATCH_PERPETUAL) atomicAdd((unsigned long long *)&sp.xq_stats[end.how == CZ_MATCH_REPETITION ? 1 : 2], 1ull);
+            if (end.how == CZ_MATCH_CHASE) sp_count(sp, CZ_SP_CHASES);
+            else if (end.how == CZ_MATCH_MATE) sp_count(sp, CZ_SP_MATES);
+            else if (end.how == CZ_MATCH_REPETITION || end.how == CZ_MATCH_PERPETUAL) sp_count(sp, end.how == CZ_MATCH_REPETITION ? CZ_SP_REPETITIONS : CZ_SP_PERPETUALS);
             sp.rr.mated[g] = 0; sp.rr.rep[g] = CZ_REP_NONE;
         }
         if (sp.rs.game_no) {
-            unsigned long long *rstat = (unsigned long long *)sp.rs.stats, *rhist = (unsigned long long *)sp.rs.hist;
-            if (end.how == CZ_MATCH_RESIGN) atomicAdd(&rstat[0], 1ull);
+            if (end.how == CZ_MATCH_RESIGN) sp_count(sp, CZ_SP_RESIGNED);
             if (sp.rs.playon[g] && !stalled) {   // what the game would have done had it not played on, against how it ended
                 const int loser = end.loser, would = sp.rs.would[g];
-                atomicAdd(&rstat[1], 1ull);
+                sp_count(sp, CZ_SP_PLAYON_GAMES);
                 if (would) {
-                    atomicAdd(&rstat[2], 1ull);
-                    if (loser != would - 1) atomicAdd(&rstat[3], 1ull);   // the side that would have resigned won or drew
+                    sp_count(sp, CZ_SP_PLAYON_WOULD);
+                    if (loser != would - 1) sp_count(sp, CZ_SP_PLAYON_FALSE);   // the side that would have resigned won or drew
                 }
                 for (int s = 0; s < 2; ++s) {
                     const float q = sp.rs.minq[2 * g + s];
-                    if (loser != s && q < 2.0f) atomicAdd(&rhist[min(max((int)floorf((q + 1.0f) * 32.0f), 0), 63)], 1ull);
+                    if (loser != s && q < 2.0f) sp_count(sp, CZ_SP_RESIGN_HIST + min(max((int)floorf((q + 1.0f) * 32.0f), 0), 63));
                 }
             }
             // the slot's next game (reseed), or a parked slot with nothing left over
@@ -264,7 +259,7 @@ __global__ __launch_bounds__(64) void k_sp_flush(CzSelfplay sp, int G, const int
     if (n <= 0) return;
     const long long off = offset[g];
     if (read_cursor && off + n - *read_cursor > ring_records) {   // would overwrite records nobody has read yet
-        if (lane == 0) atomicAdd((unsigned long long *)&sp.stats[CZ_SP_DROPPED], (unsigned long long)n);
+        if (lane == 0) sp_count(sp, CZ_SP_DROPPED, (unsigned long long)n);
         return;
     }
     for (int j = 0; j < n; ++j) {
@@ -277,7 +272,8 @@ __global__ __launch_bounds__(64) void k_sp_flush(CzSelfplay sp, int G, const int
 }  // namespace
 
 // ---- the entry points, in cz_match.hip's order: create, setters, getters, choose, adjudicate ------------------------
-// The state lives in cz_ctx (sp, sp_rules, sp_chase, sp_state and the three blocks): cz_destroy frees the blocks.
+// The state lives in cz_ctx: sp in sp_block, sp.rs in sp_resign_block, and sp_root (CzRootHost, cz_internal.h) with the chase
+// part of sp.rr and sp.tb_value in its own two blocks.  cz_destroy frees all four.
 
 int cz_selfplay_begin(cz_ctx *c, int max_plies, const uint8_t *boards, const uint8_t *side, const int32_t *rr) {
     CZ_REQUIRE(c && c->G > 0, "cz_selfplay_begin: call cz_search_reset first");
@@ -296,17 +292,16 @@ int cz_selfplay_begin(cz_ctx *c, int max_plies, const uint8_t *boards, const uin
             sp.start_board = k.take<uint8_t>(G * CZD_BOARD_LDS);
             sp.start_side = k.take<uint8_t>(G);
             sp.start_rr = k.take<int32_t>(G);
-            sp.stats = k.take<long long>(CZ_SP_NSTATS);
-            sp.xq_stats = k.take<long long>(3);
+            sp.stats = k.take<long long>(CZ_SP_NSLOTS);
             carve_root_rules(k, sp.rr, G, false);
         });
         if (rc != CZ_OK) return rc;
         sp.max_plies = max_plies;
     }
-    c->sp_rules = 0; c->sp.rr.fold = 0; c->sp_chase = 0; c->sp_state = 1;
-    cz_tb_set_hold(c->sp_tb, -1);   // no table set: it needs rules 1; its counter starts with the games
-    c->sp_tb = nullptr; c->sp.tb_value = nullptr;
-    if (c->sp.tb_stat) CZ_HIP(hipMemsetAsync(c->sp.tb_stat, 0, sizeof(long long), c->stream));
+    // rules, fold and chase off, no table set (it needs rules 1).  Nothing may change after the first choose; sp.rr's arrays
+    // other than the chase part are sp_block's; the chase rings are cleared whenever the rule is switched on
+    cz_root_begin(c->sp_root, CzRootHost{"cz_selfplay", "ctx", "the history starts at the games' first positions", false, false, true, c,
+                                         c->max_games, &c->sp.rr, &c->sp.tb_value});
     c->sp.rs = CzSpResign{};   // resignation off: no pointer, no kernel looks
     c->sp.rs.threshold = NAN;
     hipLaunchKernelGGL(k_sp_seed, dim3(c->G), dim3(64), 0, c->stream, c->t, c->sp, c->G, boards, side, rr);
@@ -314,55 +309,33 @@ int cz_selfplay_begin(cz_ctx *c, int max_plies, const uint8_t *boards, const uin
     return CZ_OK;
 }
 
-// the setters' order (cz_root_rules_order), in self-play's names
-static int sp_order(const cz_ctx *c, int what, int value) {
-    return cz_root_rules_order("cz_selfplay", "ctx", "the history starts at the games' first positions", what, value, c->sp_rules, c->sp.rr.fold,
-                               c->sp_chase, c->sp_state != 1, c->sp_tb != nullptr);
-}
-
 int cz_selfplay_set_rules(cz_ctx *c, int rules) {
-    CZ_REQUIRE(c && c->sp_block && c->sp_state != 0, "cz_selfplay_set_rules: call cz_selfplay_begin first");
-    if (const int rc = sp_order(c, CZ_SET_RULES, rules)) return rc;
-    c->sp_rules = rules;
-    return CZ_OK;
+    CZ_REQUIRE(c && c->sp_block, "cz_selfplay_set_rules: call cz_selfplay_begin first");
+    return cz_root_set_rules(c->sp_root, rules);
 }
 
 int cz_selfplay_set_repetition(cz_ctx *c, int fold) {
-    CZ_REQUIRE(c && c->sp_block && c->sp_state != 0, "cz_selfplay_set_repetition: call cz_selfplay_begin first");
-    if (const int rc = sp_order(c, CZ_SET_REPETITION, fold)) return rc;
-    c->sp.rr.fold = fold;
-    return CZ_OK;
+    CZ_REQUIRE(c && c->sp_block, "cz_selfplay_set_repetition: call cz_selfplay_begin first");
+    return cz_root_set_repetition(c->sp_root, fold);
 }
 
 int cz_selfplay_history(cz_ctx *c, const uint64_t **keys, const uint8_t **checks) {
-    CZ_REQUIRE(c && c->sp_block && c->sp.rr.fold != 0, "cz_selfplay_history: cz_selfplay_set_repetition first");
-    if (keys) *keys = c->sp.rr.ring_key;
-    if (checks) *checks = c->sp.rr.ring_check;
-    return CZ_OK;
+    CZ_REQUIRE(c && c->sp_block, "cz_selfplay_history: cz_selfplay_set_repetition first");
+    return cz_root_history(c->sp_root, keys, checks);
 }
 
 int cz_selfplay_set_chase(cz_ctx *c, int on) {
-    CZ_REQUIRE(c && c->sp_block && c->sp_state != 0, "cz_selfplay_set_chase: call cz_selfplay_begin first");
-    if (const int rc = sp_order(c, CZ_SET_CHASE, on)) return rc;
-    if (on) {   // zeroed at every switching on: the counter starts with the games, as cz_selfplay_begin's
-        const int rc = carve_alloc(&c->sp_chase_block, c->stream, true, "cz_selfplay_set_chase", [&](Carver &k) {
-            carve_root_rules(k, c->sp.rr, (size_t)c->max_games, true);
-            c->sp.chase_stat = k.take<long long>(1);
-        });
-        if (rc != CZ_OK) return rc;
-    }
-    c->sp_chase = on;
-    return CZ_OK;
+    CZ_REQUIRE(c && c->sp_block, "cz_selfplay_set_chase: call cz_selfplay_begin first");
+    return cz_root_set_chase(c->sp_root, on);
 }
 
 int cz_selfplay_chase_history(cz_ctx *c, const uint64_t **chase) {
-    CZ_REQUIRE(c && c->sp_block && c->sp_chase != 0, "cz_selfplay_chase_history: cz_selfplay_set_chase first");
-    if (chase) *chase = c->sp.rr.ring_chase;
-    return CZ_OK;
+    CZ_REQUIRE(c && c->sp_block, "cz_selfplay_chase_history: cz_selfplay_set_chase first");
+    return cz_root_chase_history(c->sp_root, chase);
 }
 
 int cz_selfplay_set_resign(cz_ctx *c, float threshold, int min_ply, double playon_fraction, unsigned long long seed) {
-    CZ_REQUIRE(c && c->sp_block && c->sp_state != 0, "cz_selfplay_set_resign: call cz_selfplay_begin first");
+    CZ_REQUIRE(c && c->sp_block, "cz_selfplay_set_resign: call cz_selfplay_begin first");
     CZ_REQUIRE(min_ply >= 0 && playon_fraction >= 0.0 && playon_fraction <= 1.0, "cz_selfplay_set_resign: min_ply >= 0 and 0 <= playon_fraction <= 1 required");
     CzSpResign &rs = c->sp.rs;
     if (rs.game_no) {   // a later call retunes: the per-game state, the counters and the seed stay
@@ -373,14 +346,12 @@ int cz_selfplay_set_resign(cz_ctx *c, float threshold, int min_ply, double playo
     const size_t G = (size_t)c->max_games;
     CzSpResign r{};   // c->sp.rs stays "off" until the block stands
     r.threshold = threshold; r.min_ply = min_ply; r.playon_fraction = playon_fraction; r.seed = seed;
-    const int rc = carve_alloc(&c->sp_resign_block, c->stream, true, "cz_selfplay_set_resign", [&](Carver &k) {   // the counters start with the games
+    const int rc = carve_alloc(&c->sp_resign_block, c->stream, true, "cz_selfplay_set_resign", [&](Carver &k) {
         r.game_no = k.take<uint32_t>(G);
         r.playon = k.take<uint8_t>(G);
         r.minq = k.take<float>(G * 2);
         r.would = k.take<uint8_t>(G);
         r.resigned = k.take<uint8_t>(G);
-        r.stats = k.take<long long>(4);
-        r.hist = k.take<long long>(64);
     });
     if (rc != CZ_OK) return rc;
     rs = r;
@@ -390,22 +361,8 @@ int cz_selfplay_set_resign(cz_ctx *c, float threshold, int min_ply, double playo
 }
 
 int cz_selfplay_set_tablebase(cz_ctx *c, cz_tb_set *set) {
-    CZ_REQUIRE(c && c->sp_block && c->sp_state != 0, "cz_selfplay_set_tablebase: call cz_selfplay_begin first");
-    if (const int rc = cz_tb_set_attachable("cz_selfplay", "ctx", c, set, c->sp_rules)) return rc;
-    if (set) {   // the block is made once per context; the counter in it is cz_selfplay_begin's to clear
-        const bool fresh = !c->sp_tb_block;
-        const int rc = carve_alloc(&c->sp_tb_block, c->stream, fresh, "cz_selfplay_set_tablebase", [&](Carver &k) {
-            c->sp.tb_value = k.take<int16_t>((size_t)c->max_games);
-            c->sp.tb_stat = k.take<long long>(1);
-        });
-        if (rc != CZ_OK) { c->sp.tb_value = nullptr; if (!c->sp_tb_block) c->sp.tb_stat = nullptr; return rc; }
-    } else {
-        c->sp.tb_value = nullptr;
-    }
-    cz_tb_set_hold(set, 1);
-    cz_tb_set_hold(c->sp_tb, -1);
-    c->sp_tb = set;
-    return CZ_OK;
+    CZ_REQUIRE(c && c->sp_block, "cz_selfplay_set_tablebase: call cz_selfplay_begin first");
+    return cz_root_set_tablebase(c->sp_root, set);
 }
 
 int cz_selfplay_active(cz_ctx *c, const uint8_t **active) {
@@ -419,33 +376,19 @@ int cz_selfplay_choose(cz_ctx *c, const float *gamma, const float *u, const uint
     CZ_REQUIRE(u && played, "cz_selfplay_choose: u and played required");
     CZ_REQUIRE(temperature > 0.0 && eps >= 0.f && eps <= 1.f, "cz_selfplay_choose: temperature > 0 and 0 <= noise_eps <= 1 required");
     CZ_REQUIRE(min_sims >= 0, "cz_selfplay_choose: min_sims >= 0 required");
-    c->sp_state = 2;
-    const int level = cz_rules_level(c->sp_rules, c->sp.rr.fold, c->sp_chase);
-    if (level >= CZ_RULES_KINGSAFE) {   // what the rules need of every slot's root position, then the choice
-        hipLaunchKernelGGL(k_sp_roots_xq, dim3(c->G), dim3(64), 0, c->stream, c->t, c->sp, c->G);
-        CZ_HIP(hipGetLastError());
-        if (const int rc = czk_root_rules_prepare(c, c->sp.rr, c->G, level)) return rc;
-    }
-    cz_by_rules_level(level, [&](auto L) {
-        hipLaunchKernelGGL(k_sp_choose<decltype(L)::value>, dim3(c->G), dim3(64), 0, c->stream, c->t, c->sp, c->G, gamma, u, forced, 1.0 / temperature, eps,
-                           min_sims, played);
-    });
-    CZ_HIP(hipGetLastError());
-    return CZ_OK;
+    return cz_root_choose(
+        c->sp_root, c->G, [&] { hipLaunchKernelGGL(k_sp_roots_xq, dim3(c->G), dim3(64), 0, c->stream, c->t, c->sp, c->G); },
+        [&](auto L) {
+            hipLaunchKernelGGL(k_sp_choose<decltype(L)::value>, dim3(c->G), dim3(64), 0, c->stream, c->t, c->sp, c->G, gamma, u, forced, 1.0 / temperature,
+                               eps, min_sims, played);
+        });
 }
 
 int cz_selfplay_adjudicate(cz_ctx *c, int reseed, const uint16_t *played, int32_t *fin_n) {
     CZ_REQUIRE(c && c->sp_block && c->G > 0 && fin_n, "cz_selfplay_adjudicate: call cz_selfplay_begin first / null fin_n");
-    if (c->sp_tb && c->sp.tb_value) {   // the set's value of every root position after the move, read in place: boards 96 bytes apart, sides in the tree records
-        if (const int rc = cz_tb_set_probe_strided(c, c->sp_tb, c->t.root_board, CZD_BOARD_LDS, &c->t.root_side[0], (int)sizeof(CzTreeRec), played, c->G,
-                                                   c->sp.tb_value, nullptr))
-            return rc;
-    }
-    cz_by_rules_level(cz_rules_level(c->sp_rules, c->sp.rr.fold, c->sp_chase), [&](auto L) {
+    return cz_root_adjudicate(c->sp_root, played, c->G, [&](auto L) {
         hipLaunchKernelGGL(k_sp_adjudicate<decltype(L)::value>, dim3(c->G), dim3(64), 0, c->stream, c->t, c->sp, c->G, reseed, played, fin_n);
     });
-    CZ_HIP(hipGetLastError());
-    return CZ_OK;
 }
 
 int cz_selfplay_flush(cz_ctx *c, const int32_t *fin_n, const long long *offset, uint8_t *ring, long long ring_records, const long long *read_cursor) {
@@ -456,41 +399,18 @@ int cz_selfplay_flush(cz_ctx *c, const int32_t *fin_n, const long long *offset, 
     return CZ_OK;
 }
 
-int cz_selfplay_stats(cz_ctx *c, long long *stats_dev) {
-    CZ_REQUIRE(c && c->sp_block && stats_dev, "cz_selfplay_stats: call cz_selfplay_begin first / null argument");
-    CZ_HIP(hipMemcpyAsync(stats_dev, c->sp.stats, sizeof(long long) * CZ_SP_NSTATS, hipMemcpyDeviceToDevice, c->stream));
+// The five getters: slots first .. first + n - 1 of sp.stats (CzSpSlot), device to device.  A rule that is off reads the zeros
+// cz_selfplay_begin left: its slots are counted only while it is on, and it is switched on after a begin.
+static int sp_stats_slice(cz_ctx *c, const char *who, long long *dst, int first, int n) {
+    if (!(c && c->sp_block && dst)) { cz_set_error("%s: call cz_selfplay_begin first / null argument", who); return CZ_EINVAL; }
+    CZ_HIP(hipMemcpyAsync(dst, c->sp.stats + first, sizeof(long long) * n, hipMemcpyDeviceToDevice, c->stream));
     return CZ_OK;
 }
-
-int cz_selfplay_rules_stats(cz_ctx *c, long long *stats_dev) {
-    CZ_REQUIRE(c && c->sp_block && stats_dev, "cz_selfplay_rules_stats: call cz_selfplay_begin first / null argument");
-    CZ_HIP(hipMemcpyAsync(stats_dev, c->sp.xq_stats, sizeof(long long) * 3, hipMemcpyDeviceToDevice, c->stream));
-    return CZ_OK;
-}
-
-int cz_selfplay_chase_stats(cz_ctx *c, long long *stats_dev) {
-    CZ_REQUIRE(c && c->sp_block && stats_dev, "cz_selfplay_chase_stats: call cz_selfplay_begin first / null argument");
-    if (c->sp_chase) CZ_HIP(hipMemcpyAsync(stats_dev, c->sp.chase_stat, sizeof(long long), hipMemcpyDeviceToDevice, c->stream));
-    else CZ_HIP(hipMemsetAsync(stats_dev, 0, sizeof(long long), c->stream));
-    return CZ_OK;
-}
-
-int cz_selfplay_tablebase_stats(cz_ctx *c, long long *stats_dev) {
-    CZ_REQUIRE(c && c->sp_block && stats_dev, "cz_selfplay_tablebase_stats: call cz_selfplay_begin first / null argument");
-    if (c->sp.tb_stat) CZ_HIP(hipMemcpyAsync(stats_dev, c->sp.tb_stat, sizeof(long long), hipMemcpyDeviceToDevice, c->stream));
-    else CZ_HIP(hipMemsetAsync(stats_dev, 0, sizeof(long long), c->stream));
-    return CZ_OK;
-}
-
+int cz_selfplay_stats(cz_ctx *c, long long *stats_dev) { return sp_stats_slice(c, "cz_selfplay_stats", stats_dev, 0, CZ_SP_NSTATS); }
+int cz_selfplay_rules_stats(cz_ctx *c, long long *stats_dev) { return sp_stats_slice(c, "cz_selfplay_rules_stats", stats_dev, CZ_SP_MATES, 3); }
+int cz_selfplay_chase_stats(cz_ctx *c, long long *stats_dev) { return sp_stats_slice(c, "cz_selfplay_chase_stats", stats_dev, CZ_SP_CHASES, 1); }
+int cz_selfplay_tablebase_stats(cz_ctx *c, long long *stats_dev) { return sp_stats_slice(c, "cz_selfplay_tablebase_stats", stats_dev, CZ_SP_TABLEBASE, 1); }
 int cz_selfplay_resign_stats(cz_ctx *c, long long *stats_dev, long long *hist_dev) {
-    CZ_REQUIRE(c && c->sp_block && stats_dev, "cz_selfplay_resign_stats: call cz_selfplay_begin first / null argument");
-    const CzSpResign &rs = c->sp.rs;
-    if (rs.game_no) {
-        CZ_HIP(hipMemcpyAsync(stats_dev, rs.stats, sizeof(long long) * 4, hipMemcpyDeviceToDevice, c->stream));
-        if (hist_dev) CZ_HIP(hipMemcpyAsync(hist_dev, rs.hist, sizeof(long long) * 64, hipMemcpyDeviceToDevice, c->stream));
-    } else {
-        CZ_HIP(hipMemsetAsync(stats_dev, 0, sizeof(long long) * 4, c->stream));
-        if (hist_dev) CZ_HIP(hipMemsetAsync(hist_dev, 0, sizeof(long long) * 64, c->stream));
-    }
-    return CZ_OK;
+    if (const int rc = sp_stats_slice(c, "cz_selfplay_resign_stats", stats_dev, CZ_SP_RESIGNED, 4)) return rc;
+    return hist_dev ? sp_stats_slice(c, "cz_selfplay_resign_stats", hist_dev, CZ_SP_RESIGN_HIST, 64) : CZ_OK;
 }

@@ -1,4 +1,6 @@
 """Batched rules ops K1-K3 over device tensors (host side of cz_movegen / cz_apply_move / cz_encode_planes)."""
+import os
+
 import numpy as np
 import torch
 
@@ -10,9 +12,10 @@ from .engine import Context
 RULES = {"capture": 0, "xiangqi": 1}   # cz_match_set_rules / cz_selfplay_set_rules
 
 
-def check_rule_options(who, rules, repetition, chase):
-    """The rule options of arena.Match and selfplay.SelfPlay (`who` names the caller in the text): rules before a repetition
-    fold, a fold before the chase rule.  Raises ValueError."""
+def check_rule_options(who, rules, repetition, chase, tablebase=None, resign_min_ply=0, resign_playon=None):
+    """The options of arena.Match and selfplay.SelfPlay on how a game ends (`who` names the caller in the text): rules before a
+    repetition fold, a fold before the chase rule, rules before a table set (anything but None), and the resignation ranges
+    (resign_playon: SelfPlay's alone).  Raises ValueError."""
     if rules not in RULES:
         raise ValueError("%s: rules is 'capture' or 'xiangqi', not %r" % (who, rules))
     if isinstance(repetition, bool) or not isinstance(repetition, (int, np.integer)) or not (repetition == 0 or 2 <= repetition <= 8):
@@ -21,6 +24,54 @@ def check_rule_options(who, rules, repetition, chase):
         raise ValueError("%s: repetition needs rules='xiangqi' (the check flags come from the king-safe moves)" % who)
     if chase and not repetition:
         raise ValueError("%s: chase needs a repetition fold (a chase is judged on a repeated position)" % who)
+    if tablebase is not None and rules != "xiangqi":
+        raise ValueError("%s: tablebase needs rules='xiangqi' (a table holds values under xiangqi rules)" % who)
+    if int(resign_min_ply) < 0 or not (resign_playon is None or 0.0 <= float(resign_playon) <= 1.0):
+        raise ValueError("%s: resign_min_ply >= 0%s" % (who, "" if resign_playon is None else " and 0 <= resign_playon <= 1"))
+
+
+def tablebase_set(tablebase):
+    """A tablebase option (a tablebase.Tablebase, a tablebase.DeviceSet or None) -> (the DeviceSet to attach, the one made here
+    from a Tablebase's loaded tables — the caller's to close — or None)."""
+    dset = tablebase.device_set() if hasattr(tablebase, "device_set") else tablebase
+    return dset, (dset if dset is not tablebase else None)
+
+
+def add_rule_flags(parser, games):
+    """--rules, --repetition, --chase and --tablebase DIR on an argparse parser; games: whose games they rule, for the help"""
+    parser.add_argument("--rules", choices=sorted(RULES), default="capture",
+                        help="%s: capture = the reference's games (a king is taken); xiangqi = king-safe moves only, a side without one "
+                             "is mated" % games)
+    parser.add_argument("--repetition", type=int, default=0,
+                        help="with --rules xiangqi: a game ends when its position occurs for the N-th time (3 is the usual value): a draw, "
+                             "or a loss for the side that checked perpetually; 0 = no repetition rule")
+    parser.add_argument("--chase", action="store_true",
+                        help="with --repetition: a side that alone chased one unprotected piece with every move of the cycle loses")
+    parser.add_argument("--tablebase", metavar="DIR", default=None,
+                        help="with --rules xiangqi: a game that reaches a position of a table in DIR (python -m cchess_zero_amd.tablebase "
+                             "--build) ends there with the table's result")
+
+
+def check_rule_flags(parser, args, who):
+    """The cross-checks of add_rule_flags' arguments: parser.error on a failure -> load(), which reads the tables of --tablebase
+    DIR onto the current device (None without the flag; ValueError for a directory without a table) — called once the
+    caller's device stands, by every rank itself."""
+    try:
+        check_rule_options(who, args.rules, args.repetition, args.chase, args.tablebase)
+    except ValueError as e:
+        parser.error(str(e))
+    if args.tablebase and not os.path.isdir(args.tablebase):
+        parser.error("--tablebase: %s is no directory" % args.tablebase)
+
+    def load():
+        if not args.tablebase:
+            return None
+        from .tablebase import Tablebase
+        tb = Tablebase()
+        if not tb.load(args.tablebase):
+            raise ValueError("--tablebase: no table in %s" % args.tablebase)
+        return tb
+    return load
 
 
 def set_rule_options(prefix, handle, rules, repetition, chase):

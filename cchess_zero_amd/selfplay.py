@@ -28,9 +28,15 @@ import torch
 
 from ._lib import (MAXMOVES, NLABELS, NSQ, REC_BYTES, REC_COUNT, REC_FLAGS, REC_LABELS, REC_PLY, REC_SIDE, REC_VISITS, REC_Z,
                    SP_CHASE_STATS, SP_RESIGN_STATS, SP_RULES_STATS, SP_STATS, SP_TABLEBASE_STATS, out_pointers, tables)
-from .rules import RULES, check_rule_options, root_rules_chase_history, root_rules_history, set_rule_options
+from .rules import RULES, check_rule_options, root_rules_chase_history, root_rules_history, set_rule_options, tablebase_set
 
 REC_MAXMOVES = MAXMOVES
+# SelfPlay.stats(): (getter, the names of what it copies out, whether the loop reports them, the getter's further arguments)
+STATS_GETTERS = (("cz_selfplay_stats", SP_STATS, lambda sp: True, ()),
+                 ("cz_selfplay_rules_stats", SP_RULES_STATS, lambda sp: RULES[sp.rules] != 0, ()),
+                 ("cz_selfplay_chase_stats", SP_CHASE_STATS, lambda sp: sp.chase, ()),
+                 ("cz_selfplay_resign_stats", SP_RESIGN_STATS, lambda sp: sp._resign_on, (None,)),
+                 ("cz_selfplay_tablebase_stats", SP_TABLEBASE_STATS, lambda sp: sp._tb_on, ()))
 
 
 def pack_records(boards, side, labels, visits, counts, z, ply=None):
@@ -173,13 +179,9 @@ class SelfPlay:
     def __init__(self, engine, net, playouts, exploration=True, temperature=1.0, seed=0, max_plies=512, ring_records=None,
                  continuous=True, eval_cache=False, xcache_log2=0, rules="capture", repetition=0, chase=False, resign=None,
                  resign_min_ply=0, resign_playon=0.1, tablebase=None):
-        check_rule_options("SelfPlay", rules, repetition, chase)
-        if tablebase is not None and rules != "xiangqi":
-            raise ValueError("SelfPlay: tablebase needs rules='xiangqi' (a table holds values under xiangqi rules)")
+        check_rule_options("SelfPlay", rules, repetition, chase, tablebase, resign_min_ply, resign_playon)
         self.tablebase = tablebase
         self._tb_set = self._tb_own = None
-        if int(resign_min_ply) < 0 or not 0.0 <= float(resign_playon) <= 1.0:
-            raise ValueError("SelfPlay: resign_min_ply >= 0 and 0 <= resign_playon <= 1")
         self.resign = None if resign is None else float(resign)
         self.resign_min_ply = int(resign_min_ply)
         self.resign_playon = float(resign_playon)
@@ -231,12 +233,8 @@ class SelfPlay:
         self.played = torch.empty(G, dtype=torch.int16, device=self.dev)
         self.fin_n = torch.zeros(G, dtype=torch.int32, device=self.dev)
         self._alpha = torch.full((G, MAXMOVES), 0.3, dtype=torch.float32, device=self.dev)
-        self._stats = torch.zeros(len(SP_STATS), dtype=torch.int64, device=self.dev)
-        self._rules_stats = torch.zeros(len(SP_RULES_STATS), dtype=torch.int64, device=self.dev)
-        self._chase_stats = torch.zeros(len(SP_CHASE_STATS), dtype=torch.int64, device=self.dev)
-        self._resign_stats = torch.zeros(len(SP_RESIGN_STATS), dtype=torch.int64, device=self.dev)
-        self._resign_hist = torch.zeros(64, dtype=torch.int64, device=self.dev)
-        self._tb_stats = torch.zeros(len(SP_TABLEBASE_STATS), dtype=torch.int64, device=self.dev)
+        # what the getters copy out: cz_selfplay_stats' at the front (drain_device), the others' behind as stats() asks, then the histogram
+        self._stats = torch.zeros(sum(len(names) for _, names, _, _ in STATS_GETTERS) + 64, dtype=torch.int64, device=self.dev)
         self.plies = 0
         self.lock_steps = 0
         self._dropped_seen = 0
@@ -250,14 +248,12 @@ class SelfPlay:
     def set_tablebase(self, tablebase):
         """Attaches a Tablebase / DeviceSet to a started loop, or detaches it (None) — between any two plies.  A DeviceSet made
         here from a Tablebase is closed when it is replaced and by close()."""
-        if tablebase is not None and self.rules != "xiangqi":
-            raise ValueError("SelfPlay: tablebase needs rules='xiangqi' (a table holds values under xiangqi rules)")
-        dset = tablebase.device_set() if hasattr(tablebase, "device_set") else tablebase
+        check_rule_options("SelfPlay", self.rules, self.repetition, self.chase, tablebase)
+        dset, own = tablebase_set(tablebase)
         self.eng.ctx.call("cz_selfplay_set_tablebase", None if dset is None else dset.h)
         if self._tb_own is not None:
             self._tb_own.close()
-        self._tb_own = dset if dset is not tablebase else None
-        self.tablebase, self._tb_set = tablebase, dset
+        self.tablebase, self._tb_set, self._tb_own = tablebase, dset, own
         self._tb_on = self._tb_on or dset is not None
 
     def close(self):
@@ -416,21 +412,12 @@ class SelfPlay:
         the games a mover resigned (a win for the other side), the play-on games finished, those in which a side crossed the
         threshold, and those of them that side won or drew; with a table set attached at any time since start() also tablebase —
         the games adjudicated from a table (counted among the wins / draws too)."""
-        self.eng.ctx.call("cz_selfplay_stats", self._stats)
-        s = self._stats.cpu().numpy()
-        d = {k: int(v) for k, v in zip(SP_STATS, s)}
-        if RULES[self.rules]:
-            self.eng.ctx.call("cz_selfplay_rules_stats", self._rules_stats)
-            d.update((k, int(v)) for k, v in zip(SP_RULES_STATS, self._rules_stats.cpu().numpy()))
-        if self.chase:
-            self.eng.ctx.call("cz_selfplay_chase_stats", self._chase_stats)
-            d.update((k, int(v)) for k, v in zip(SP_CHASE_STATS, self._chase_stats.cpu().numpy()))
-        if self._resign_on:
-            self.eng.ctx.call("cz_selfplay_resign_stats", self._resign_stats, None)
-            d.update((k, int(v)) for k, v in zip(SP_RESIGN_STATS, self._resign_stats.cpu().numpy()))
-        if self._tb_on:
-            self.eng.ctx.call("cz_selfplay_tablebase_stats", self._tb_stats)
-            d.update((k, int(v)) for k, v in zip(SP_TABLEBASE_STATS, self._tb_stats.cpu().numpy()))
+        keys = []
+        for getter, names, on, extra in STATS_GETTERS:
+            if on(self):
+                self.eng.ctx.call(getter, self._stats[len(keys):], *extra)
+                keys += names
+        d = {k: int(v) for k, v in zip(keys, self._stats.cpu().numpy())}
         d["sims"] += int(self.eng.status()[2].sum().item())   # + the simulations of the searches in progress
         d["plies_played"] = self.plies          # lock-step plies (step_ply)
         d["lock_steps"] = self.lock_steps       # select / net / expand steps of the asynchronous loop (run_async)
@@ -439,5 +426,5 @@ class SelfPlay:
     def resign_histogram(self):
         """int64 [64] on the host: the lowest root value of every side that did not lose its play-on game, in bins of 1 / 32 over
         [-1, 1) (cz_selfplay_resign_stats; all zero without resignation) — the input of suggest_resign_threshold."""
-        self.eng.ctx.call("cz_selfplay_resign_stats", self._resign_stats, self._resign_hist)
-        return self._resign_hist.cpu().numpy().copy()
+        self.eng.ctx.call("cz_selfplay_resign_stats", self._stats[-64 - len(SP_RESIGN_STATS):], self._stats[-64:])
+        return self._stats[-64:].cpu().numpy().copy()

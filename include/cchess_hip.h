@@ -667,8 +667,8 @@ int cz_selfplay_stats(cz_ctx *, long long *stats_dev);
  *   side that alone chased one piece with every move of the cycle — z as for perpetual check.  Such a game counts in
  *   cz_selfplay_chase_stats and NOT among cz_selfplay_rules_stats' perpetuals (whose signature and meaning stay).
  * cz_selfplay_chase_history: the device pointer of the third ring; CZ_EINVAL while the rule is off.
- * cz_selfplay_chase_stats: device int64 [1] <- games ended by perpetual chase since cz_selfplay_set_chase(ctx, 1) (0 while
- *   the rule is off). */
+ * cz_selfplay_chase_stats: device int64 [1] <- games ended by perpetual chase since cz_selfplay_begin (0 while the rule is
+ *   off). */
 int cz_selfplay_set_rules(cz_ctx *, int rules);
 int cz_selfplay_set_repetition(cz_ctx *, int fold);
 int cz_selfplay_history(cz_ctx *, const uint64_t **keys, const uint8_t **checks);
@@ -693,8 +693,8 @@ int cz_selfplay_chase_stats(cz_ctx *, long long *stats_dev /* [1]: chases */);
  *   + 1, and if that side then won or drew, playon_false_positives + 1; and for each side that did not lose and was judged at all,
  *   its lowest value q goes into the histogram at bin clamp((int)floorf((q + 1.0f) * 32.0f), 0, 63): 64 bins of 1/32 over [-1, 1)
  *   — the values a threshold must stay below to spare those sides.
- *   The first call after cz_selfplay_begin (which switches resignation off) allocates and zeroes the state and the counters, draws
- *   every slot's game 0 and may come at any time; seed is taken then.  A later call only changes threshold, min_ply and
+ *   The first call after cz_selfplay_begin (which switches resignation off and zeroes the counters) allocates and zeroes the state,
+ *   draws every slot's game 0 and may come at any time; seed is taken then.  A later call only changes threshold, min_ply and
  *   playon_fraction — the game numbers, the games' state and the counters stay, so a threshold can be retuned between batches; with
  *   NaN no ply is judged until the next call.  playon_fraction applies from the slots' next games.
  * cz_selfplay_resign_stats: device int64 [4] <- games resigned, play-on games finished, those in which a side crossed the

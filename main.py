@@ -345,7 +345,7 @@ class cchess_main(object):
         # --resign_playon, --resign_auto): off unless a threshold or a false-positive target is given
         self.resign_threshold, self.resign_min_ply, self.resign_playon, self.resign_auto = None, 0, 0.1, None
         # endgame tables (--tablebase DIR, with --rules xiangqi): self-play and evaluation games that reach a table's position end there
-        self.tablebase_dir, self._tablebase = None, None
+        self.load_tables, self._tablebase = None, None   # rules.check_rule_flags' loader of the directory
         # --mirror_augment: every sample a policy update draws is learnt from as it is or as its left-right mirror image, and the
         # mini-batch is built on the GPU from the packed records (cchess_zero_amd/records.py)
         self.mirror_augment = False
@@ -574,11 +574,8 @@ class cchess_main(object):
 
     def _tables(self):
         """--tablebase DIR: the directory's tables on this rank's GPU, loaded once (every rank loads them itself); None without"""
-        if self.tablebase_dir and self._tablebase is None:
-            from cchess_zero_amd.tablebase import Tablebase
-            self._tablebase = Tablebase()
-            if not self._tablebase.load(self.tablebase_dir):
-                raise ValueError("--tablebase: no table in %s" % self.tablebase_dir)
+        if self.load_tables and self._tablebase is None:
+            self._tablebase = self.load_tables()
         return self._tablebase
 
     def _resign_options(self):
@@ -815,14 +812,8 @@ if __name__ == '__main__':
     parser.add_argument('--eval_every', default=0, type=int,
                         help='every this many batches, a match of the live net against a frozen snapshot (policy_evaluate); 0 = off')
     parser.add_argument('--eval_games', default=256, type=int, help='games of each evaluation match')
-    parser.add_argument('--rules', default='capture', choices=['capture', 'xiangqi'], type=str,
-                        help='batched self-play and evaluation matches: capture = the reference\'s games (a king is taken); xiangqi = '
-                             'king-safe moves only, a side without one is mated')
-    parser.add_argument('--repetition', default=0, type=int,
-                        help='with --rules xiangqi: a game ends when its position occurs for the N-th time (3 is the usual value): a draw, '
-                             'or a loss for the side that checked perpetually; 0 = no repetition rule')
-    parser.add_argument('--chase', action='store_true',
-                        help='with --repetition: a side that alone chased one unprotected piece with every move of the cycle loses')
+    from cchess_zero_amd.rules import add_rule_flags, check_rule_flags
+    add_rule_flags(parser, 'batched self-play and evaluation matches')
     parser.add_argument('--resign_threshold', default=None, type=float,
                         help='batched self-play and evaluation matches: a mover whose root value (Q of its most visited move) is below X '
                              'resigns; default: every game is played out')
@@ -832,9 +823,6 @@ if __name__ == '__main__':
     parser.add_argument('--resign_auto', default=None, type=float,
                         help='after every batch set the threshold to what the play-on games allow at this false-positive rate '
                              '(never above 0; without --resign_threshold nobody resigns until enough play-on games have ended)')
-    parser.add_argument('--tablebase', default=None, type=str, metavar='DIR',
-                        help='with --rules xiangqi: batched self-play and evaluation games that reach a position of a table in DIR '
-                             '(python -m cchess_zero_amd.tablebase --build) end there with the table\'s result')
     parser.add_argument('--mirror_augment', action='store_true',
                         help='policy updates learn from every drawn sample as it is or as its left-right mirror image (one coin per '
                              'sample), and build the mini-batch on the GPU from the packed records')
@@ -852,14 +840,7 @@ if __name__ == '__main__':
                              'fp32 graph on 64 positions with the LIVE weights after every weight change, falling over mx6 -> fp16x2 -> '
                              'fp32 otherwise (mx6: ~4e-5 of the largest logit; fp16x2: ~6e-6); fp16 = 2x faster, ~1e-3 of the largest logit')
     args = parser.parse_args()
-    if not (args.repetition == 0 or 2 <= args.repetition <= 8) or (args.repetition and args.rules != 'xiangqi'):
-        parser.error("--repetition is 0 or 2..8 and needs --rules xiangqi")
-    if args.chase and not args.repetition:
-        parser.error("--chase needs --repetition")
-    if args.tablebase and args.rules != 'xiangqi':
-        parser.error("--tablebase needs --rules xiangqi (a table holds values under xiangqi rules)")
-    if args.tablebase and not os.path.isdir(args.tablebase):
-        parser.error("--tablebase: %s is no directory" % args.tablebase)
+    load_tables = check_rule_flags(parser, args, 'main')
     if args.resign_min_ply < 0 or not 0.0 <= args.resign_playon <= 1.0 or not (args.resign_auto is None or 0.0 <= args.resign_auto <= 1.0):
         parser.error("--resign_min_ply >= 0, --resign_playon and --resign_auto in [0, 1]")
 
@@ -890,7 +871,7 @@ if __name__ == '__main__':
         train_main.resign_threshold, train_main.resign_min_ply = args.resign_threshold, args.resign_min_ply
         train_main.resign_playon, train_main.resign_auto = args.resign_playon, args.resign_auto
         train_main.mirror_augment = args.mirror_augment
-        train_main.tablebase_dir = args.tablebase
+        train_main.load_tables = load_tables
         if args.pretrain:
             train_main.pretrain(args.pretrain, args.pretrain_steps, args.pretrain_rules, args.pretrain_lr, args.pretrain_notation)
         train_main.run(args.max_batches)
