@@ -165,9 +165,6 @@ void cz_destroy(cz_ctx *c) {
     if (c->sp_resign_block) (void)hipFree(c->sp_resign_block);
     cz_root_free(c->sp_root);
     if (c->ec_block) (void)hipFree(c->ec_block);
-#if defined(CZ_EXPERIMENT_MX2) || defined(CZ_EXPERIMENT_MX12)
-    if (c->mx_xbuf) (void)hipFree(c->mx_xbuf);
-#endif
     delete c;
 }
 

@@ -1,27 +1,31 @@
-// cz_conv.hip — C-ABI wrapper of the fused MFMA conv3x3 kernel (device code: cz_conv_kernel.h).
+// cz_conv.hip — the C-ABI entry points of the MFMA conv kernels (device code: cz_conv_kernel.h, cz_trunk_split.h, cz_trunk_mx.h).
+// The six one-launch trunk entries are a TrunkEntry each and one call of launch_trunk.  The variants that were measured and not
+// adopted are not launched from here: tools/experiments/patches/mx_variants_hook.patch adds their hook to the
+// copy of the sources that tools/experiments/mx_ablate.sh builds.
 #include "cz_internal.h"
 #include "cz_conv_kernel.h"
 #include "cz_trunk_split.h"
 #include "cz_trunk_mx.h"
 #include <initializer_list>
-#ifdef CZ_EXPERIMENT_MX2   /* tools/experiments/mx_ablate.sh: the 3 x 2-tile / K-split variant of round 6 (measured, not adopted: DESIGN.md 4.2) */
-#include "cz_trunk_mx2.h"
-#include <cstdlib>
-#endif
-#ifdef CZ_EXPERIMENT_MX12  /* the same arithmetic with twelve waves per workgroup, two cell tiles per wave */
-#include "cz_trunk_mx12.h"
-#include <cstdlib>
-#endif
+#include <type_traits>
+
+#define CZ_KERNEL(...) reinterpret_cast<const void *>(__VA_ARGS__)
+
+// the dynamic-LDS opt-in of a kernel family (both dtypes together; NULL: no second kernel), on its first launch in this context
+static int lds_opt_in(cz_ctx *c, int family, int lds_bytes, const void *k0, const void *k1 = nullptr) {
+    if (c->lds_opt_in[family]) return CZ_OK;
+    for (const void *k : {k0, k1})
+        if (k) CZ_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
+    c->lds_opt_in[family] = true;
+    return CZ_OK;
+}
 
 extern "C" int cz_conv3x3_c128_bf16(cz_ctx *c, const void *in, const void *wpk, const float *bias, const void *residual,
                                     void *out, int B, int relu) {
     using namespace czconv;
     CZ_REQUIRE(c && in && wpk && bias && out && B >= 0, "cz_conv3x3_c128_bf16: null argument");
     if (B == 0) return CZ_OK;
-    if (!c->conv_attr_set) {
-        CZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_conv3x3_c128), hipFuncAttributeMaxDynamicSharedMemorySize, CV_LDS_BYTES));
-        c->conv_attr_set = true;
-    }
+    if (const int rc = lds_opt_in(c, CZ_LDS_CONV, CV_LDS_BYTES, CZ_KERNEL(k_conv3x3_c128))) return rc;
     const int grid = (B + CV_P - 1) / CV_P;
     hipLaunchKernelGGL(k_conv3x3_c128, dim3(grid), dim3(CV_THREADS), CV_LDS_BYTES, c->stream, (const uint16_t *)in,
                        (const uint16_t *)wpk, bias, (const uint16_t *)residual, (uint16_t *)out, B, relu);
@@ -47,125 +51,89 @@ static int trunk_grid(const char *who, const float *head_w, const void *wpk16, i
     return CZ_OK;
 }
 
-// the dynamic-LDS opt-in of an entry point's kernels (both dtypes together), on its first launch in this context
-static int trunk_lds_opt_in(bool &done, int lds_bytes, std::initializer_list<const void *> kernels) {
-    if (done) return CZ_OK;
-    for (const void *k : kernels) CZ_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
-    done = true;
-    return CZ_OK;
-}
+// What differs between the one-launch trunk entry points.  K: the kernels' type — their leading parameters, then
+// (B, layers, the device row count, the clock probe)
+template <typename K>
+struct TrunkEntry {
+    const char *name;         // in the argument errors
+    const char *align_name;   // in the alignment errors
+    K kernel[2];              // what `which` chooses between (one kernel: the second is NULL); opted in together
+    int lds_bytes, threads, P, family;   // dynamic LDS, workgroup size, positions per workgroup, the CzLdsFamily of the opt-in
+    bool wpk16;               // the weights are fetched by 16-byte DMA from their first byte
+};
 
-#define CZ_KERNEL(...) reinterpret_cast<const void *>(__VA_ARGS__)
-
-static int launch_tower(cz_ctx *c, const void *in, const void *wpk, const float *bias, void *out, const float *head_w,
-                        const float *head_b, float *head_out, int B, int nblocks, const void *planes = nullptr,
-                        const void *w0 = nullptr, const float *b0 = nullptr, bool f16 = false) {
-    using namespace czconv;
+// One trunk launch, whole: the argument checks in their order, the grid (B == 0: CZ_OK, nothing is launched or opted in), the
+// opt-in, the launch of kernel[which] with (lead..., B, 2 * nblocks, row count, clock probe).  given: the entry's own pointers
+// and counts are there; which < 0: cz_net_trunk_split's halves_dtype names neither kernel.
+template <typename K, typename... L>
+static int launch_trunk(cz_ctx *c, const TrunkEntry<K> &e, int which, bool given, const void *wpk, const float *head_w, const float *head_b,
+                        const float *head_out, int B, int nblocks, L... lead) {
+    static_assert(std::is_same_v<K, void (*)(L..., int, int, const int32_t *, unsigned long long *)>, "the launch arguments are the kernel's parameters, type by type");
+    if (!given) { cz_set_error("%s: null argument / nblocks < 1", e.name); return CZ_EINVAL; }
+    if (head_out && !(head_w && head_b)) { cz_set_error("%s: head_out needs head_w and head_b", e.name); return CZ_EINVAL; }
+    if (which < 0) { cz_set_error("%s: halves_dtype must be CZ_F16 or CZ_BF16", e.name); return CZ_EINVAL; }
     int grid;
-    if (const int rc = trunk_grid("cz_net_trunk", head_w, nullptr, B, T8_P, &grid); rc != CZ_OK || grid == 0) return rc;
-    if (const int rc = trunk_lds_opt_in(c->tower_attr_set, T8_LDS_BYTES, {CZ_KERNEL(k_tower8_c128<false, 4>), CZ_KERNEL(k_tower8_c128<true, 4>)})) return rc;
-    const auto kernel = f16 ? k_tower8_c128<true, 4> : k_tower8_c128<false, 4>;
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(T8_THREADS), T8_LDS_BYTES, c->stream, (const uint16_t *)in, (const uint16_t *)wpk, bias,
-                       (uint16_t *)out, head_w, head_b, head_out, (const uint16_t *)planes, (const uint16_t *)w0, b0, B, 2 * nblocks,
-                       c->batch_count, clock_probe(c, grid));
+    if (const int rc = trunk_grid(e.align_name, head_w, e.wpk16 ? wpk : nullptr, B, e.P, &grid); rc != CZ_OK || grid == 0) return rc;
+    if (const int rc = lds_opt_in(c, e.family, e.lds_bytes, CZ_KERNEL(e.kernel[0]), CZ_KERNEL(e.kernel[1]))) return rc;
+    hipLaunchKernelGGL(e.kernel[which], dim3(grid), dim3(e.threads), e.lds_bytes, c->stream, lead..., B, 2 * nblocks, c->batch_count,
+                       clock_probe(c, grid));
     CZ_HIP(hipGetLastError());
     return CZ_OK;
 }
 
+// the three entry points of k_tower8_c128 (their alignment errors share one name); f16: the fp16 instantiation
+static int launch_tower(cz_ctx *c, const char *name, bool given, bool f16, const void *in, const void *wpk, const float *bias, void *out,
+                        const float *head_w, const float *head_b, float *head_out, int B, int nblocks, const void *planes = nullptr,
+                        const void *w0 = nullptr, const float *b0 = nullptr) {
+    using namespace czconv;
+    const TrunkEntry<decltype(&k_tower8_c128<false, 4>)> e = {name, "cz_net_trunk", {k_tower8_c128<false, 4>, k_tower8_c128<true, 4>},
+                                                              T8_LDS_BYTES, T8_THREADS, T8_P, CZ_LDS_TOWER, false};
+    return launch_trunk(c, e, f16 ? 1 : 0, given, wpk, head_w, head_b, head_out, B, nblocks, (const uint16_t *)in, (const uint16_t *)wpk, bias,
+                        (uint16_t *)out, head_w, head_b, head_out, (const uint16_t *)planes, (const uint16_t *)w0, b0);
+}
+
 extern "C" int cz_tower_c128_bf16(cz_ctx *c, const void *in, const void *wpk, const float *bias, void *out, int B, int nblocks) {
-    CZ_REQUIRE(c && in && wpk && bias && out && B >= 0 && nblocks >= 1, "cz_tower_c128_bf16: null argument / nblocks < 1");
-    return launch_tower(c, in, wpk, bias, out, nullptr, nullptr, nullptr, B, nblocks);
+    return launch_tower(c, "cz_tower_c128_bf16", c && in && wpk && bias && out && B >= 0 && nblocks >= 1, false, in, wpk, bias, out, nullptr,
+                        nullptr, nullptr, B, nblocks);
 }
 
 extern "C" int cz_tower_heads_c128_bf16(cz_ctx *c, const void *in, const void *wpk, const float *bias, void *trunk_out,
                                         const float *head_w, const float *head_b, float *head_out, int B, int nblocks) {
-    CZ_REQUIRE(c && in && wpk && bias && head_w && head_b && head_out && B >= 0 && nblocks >= 1,
-               "cz_tower_heads_c128_bf16: null argument / nblocks < 1");
-    return launch_tower(c, in, wpk, bias, trunk_out, head_w, head_b, head_out, B, nblocks);
+    return launch_tower(c, "cz_tower_heads_c128_bf16", c && in && wpk && bias && head_w && head_b && head_out && B >= 0 && nblocks >= 1, false,
+                        in, wpk, bias, trunk_out, head_w, head_b, head_out, B, nblocks);
 }
+
+// what the four whole-net entry points ask of their arguments, under the names all four give them
+#define CZ_NET_GIVEN (c && planes16 && w0 && b0 && wpk && bias && B >= 0 && nblocks >= 1 && (trunk_out || head_out))
 
 extern "C" int cz_net_trunk_bf16(cz_ctx *c, const void *planes16, const void *w0, const float *b0, const void *wpk,
                                  const float *bias, void *trunk_out, const float *head_w, const float *head_b,
                                  float *head_out, int B, int nblocks) {
-    CZ_REQUIRE(c && planes16 && w0 && b0 && wpk && bias && B >= 0 && nblocks >= 1 && (trunk_out || head_out),
-               "cz_net_trunk_bf16: null argument / nblocks < 1");
-    CZ_REQUIRE(!head_out || (head_w && head_b), "cz_net_trunk_bf16: head_out needs head_w and head_b");
-    return launch_tower(c, nullptr, wpk, bias, trunk_out, head_w, head_b, head_out, B, nblocks, planes16, w0, b0);
+    return launch_tower(c, "cz_net_trunk_bf16", CZ_NET_GIVEN, false, nullptr, wpk, bias, trunk_out, head_w, head_b, head_out, B, nblocks, planes16, w0, b0);
 }
 
 extern "C" int cz_net_trunk_f16(cz_ctx *c, const void *planes16, const void *w0, const float *b0, const void *wpk,
                                 const float *bias, void *trunk_out, const float *head_w, const float *head_b,
                                 float *head_out, int B, int nblocks) {
-    CZ_REQUIRE(c && planes16 && w0 && b0 && wpk && bias && B >= 0 && nblocks >= 1 && (trunk_out || head_out),
-               "cz_net_trunk_f16: null argument / nblocks < 1");
-    CZ_REQUIRE(!head_out || (head_w && head_b), "cz_net_trunk_f16: head_out needs head_w and head_b");
-    return launch_tower(c, nullptr, wpk, bias, trunk_out, head_w, head_b, head_out, B, nblocks, planes16, w0, b0, true);
+    return launch_tower(c, "cz_net_trunk_f16", CZ_NET_GIVEN, true, nullptr, wpk, bias, trunk_out, head_w, head_b, head_out, B, nblocks, planes16, w0, b0);
 }
 
 extern "C" int cz_net_trunk_split(cz_ctx *c, const void *planes16, const void *w0, const float *b0, const void *wpk,
                                   const float *bias, float *trunk_out, const float *head_w, const float *head_b,
                                   float *head_out, int B, int nblocks, int halves_dtype) {
     using namespace czconv;
-    CZ_REQUIRE(c && planes16 && w0 && b0 && wpk && bias && B >= 0 && nblocks >= 1 && (trunk_out || head_out),
-               "cz_net_trunk_split: null argument / nblocks < 1");
-    CZ_REQUIRE(!head_out || (head_w && head_b), "cz_net_trunk_split: head_out needs head_w and head_b");
-    CZ_REQUIRE(halves_dtype == CZ_F16 || halves_dtype == CZ_BF16, "cz_net_trunk_split: halves_dtype must be CZ_F16 or CZ_BF16");
-    int grid;
-    if (const int rc = trunk_grid("cz_net_trunk_split", head_w, nullptr, B, XS_P, &grid); rc != CZ_OK || grid == 0) return rc;
-    if (const int rc = trunk_lds_opt_in(c->split_attr_set, XS_LDS_BYTES, {CZ_KERNEL(k_trunk_split_c128<false>), CZ_KERNEL(k_trunk_split_c128<true>)})) return rc;
-    const auto kernel = halves_dtype == CZ_F16 ? k_trunk_split_c128<true> : k_trunk_split_c128<false>;
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(XS_THREADS), XS_LDS_BYTES, c->stream, (const uint16_t *)wpk, bias, trunk_out, head_w,
-                       head_b, head_out, (const uint16_t *)planes16, (const uint16_t *)w0, b0, B, 2 * nblocks, c->batch_count,
-                       clock_probe(c, grid));
-    CZ_HIP(hipGetLastError());
-    return CZ_OK;
+    static const TrunkEntry<decltype(&k_trunk_split_c128<false>)> e = {"cz_net_trunk_split", "cz_net_trunk_split", {k_trunk_split_c128<false>, k_trunk_split_c128<true>},
+                                                                       XS_LDS_BYTES, XS_THREADS, XS_P, CZ_LDS_SPLIT, false};
+    return launch_trunk(c, e, halves_dtype == CZ_F16 ? 1 : halves_dtype == CZ_BF16 ? 0 : -1, CZ_NET_GIVEN, wpk, head_w, head_b, head_out, B, nblocks,
+                        (const uint16_t *)wpk, bias, trunk_out, head_w, head_b, head_out, (const uint16_t *)planes16, (const uint16_t *)w0, b0);
 }
 
 extern "C" int cz_net_trunk_mx(cz_ctx *c, const void *planes16, const void *w0, const float *b0, const void *wpk, const float *bias,
                                float *trunk_out, const float *head_w, const float *head_b, float *head_out, int B, int nblocks) {
     using namespace czconv;
-    CZ_REQUIRE(c && planes16 && w0 && b0 && wpk && bias && B >= 0 && nblocks >= 1 && (trunk_out || head_out),
-               "cz_net_trunk_mx: null argument / nblocks < 1");
-    CZ_REQUIRE(!head_out || (head_w && head_b), "cz_net_trunk_mx: head_out needs head_w and head_b");
-    int grid;
-    if (const int rc = trunk_grid("cz_net_trunk_mx", head_w, wpk, B, MX_P, &grid); rc != CZ_OK || grid == 0) return rc;
-    auto kernel = k_trunk_mx_c128;   // experiment builds: the variants with the same parameters replace it
-    int threads = MX_THREADS;
-    bool *attr_set = &c->mx_attr_set;
-#ifdef CZ_EXPERIMENT_MX12
-    {
-        const char *e = getenv("CCHESS_MX_KERNEL");
-        if (e && e[0] == '1' && e[1] == '2') { kernel = k_trunk_mx12_c128; threads = 768; attr_set = &c->mx2_attr_set; }
-    }
-#endif
-#ifdef CZ_EXPERIMENT_MX2
-    if (!c->mx_kernel) {   // experiment builds only: CCHESS_MX_KERNEL=2 selects k_trunk_mx2_c128
-        const char *e = getenv("CCHESS_MX_KERNEL");
-        c->mx_kernel = (e && e[0] == '2') ? 2 : 1;
-    }
-    if (c->mx_kernel == 2) {
-        if (const int rc = trunk_lds_opt_in(c->mx2_attr_set, MX_LDS_BYTES, {CZ_KERNEL(k_trunk_mx2_c128)})) return rc;
-        const size_t need = (size_t)grid * MX2_XBUF_FLOATS_PER_WG * sizeof(float);
-        if (need > c->mx_xbuf_bytes) {   // grown outside any capture: the first launch of a batch size allocates (as torch's allocator would)
-            CZ_HIP(hipStreamSynchronize(c->stream));
-            if (c->mx_xbuf) (void)hipFree(c->mx_xbuf);
-            c->mx_xbuf = nullptr; c->mx_xbuf_bytes = 0;
-            if (hipMalloc(&c->mx_xbuf, need) != hipSuccess) { c->mx_xbuf = nullptr; cz_set_error("cz_net_trunk_mx: hipMalloc(%zu B) for the block-input scratch failed", need); return CZ_ENOMEM; }
-            c->mx_xbuf_bytes = need;
-        }
-        hipLaunchKernelGGL(k_trunk_mx2_c128, dim3(grid), dim3(MX_THREADS), MX_LDS_BYTES, c->stream, (const unsigned char *)wpk, bias, trunk_out,
-                           head_w, head_b, head_out, (const uint16_t *)planes16, (const uint16_t *)w0, b0, B, 2 * nblocks, c->batch_count,
-                           clock_probe(c, grid), (float *)c->mx_xbuf);
-        CZ_HIP(hipGetLastError());
-        return CZ_OK;
-    }
-#endif
-    if (const int rc = trunk_lds_opt_in(*attr_set, MX_LDS_BYTES, {CZ_KERNEL(kernel)})) return rc;
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), MX_LDS_BYTES, c->stream, (const unsigned char *)wpk, bias, trunk_out, head_w,
-                       head_b, head_out, (const uint16_t *)planes16, (const uint16_t *)w0, b0, B, 2 * nblocks, c->batch_count,
-                       clock_probe(c, grid));
-    CZ_HIP(hipGetLastError());
-    return CZ_OK;
+    static const TrunkEntry<decltype(&k_trunk_mx_c128)> e = {"cz_net_trunk_mx", "cz_net_trunk_mx", {k_trunk_mx_c128, nullptr}, MX_LDS_BYTES, MX_THREADS, MX_P, CZ_LDS_MX, true};
+    return launch_trunk(c, e, 0, CZ_NET_GIVEN, wpk, head_w, head_b, head_out, B, nblocks, (const unsigned char *)wpk, bias, trunk_out, head_w,
+                        head_b, head_out, (const uint16_t *)planes16, (const uint16_t *)w0, b0);
 }
 
 extern "C" int cz_set_clock_probe(cz_ctx *c, unsigned long long *buf_dev, int max_workgroups) {

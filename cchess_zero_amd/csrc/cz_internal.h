@@ -225,6 +225,9 @@ struct CzRootHost {
     void *rules_block, *chase_block, *tb_block;   // rr's two parts and tb_value, made at the first switching on, kept until cz_root_free
 };
 
+// the kernel families of cz_conv.hip that opt in to dynamic LDS once per context, both dtypes of a family together
+enum CzLdsFamily { CZ_LDS_CONV, CZ_LDS_TOWER, CZ_LDS_SPLIT, CZ_LDS_MX, CZ_LDS_NFAMILIES };
+
 struct cz_ctx {
     int device;
     hipStream_t stream;
@@ -237,13 +240,7 @@ struct cz_ctx {
     void *pool_block;
     bool adv_attr_set;   // dynamic-LDS opt-in of k_advance_lds done
     bool adv_force_global;   // cz_search_debug_advance_in_global_memory (tests): take the path of pools whose bitmap exceeds LDS
-    bool conv_attr_set, tower_attr_set, split_attr_set, mx_attr_set;  // dynamic-LDS opt-in of the MFMA kernels done for this device
-#if defined(CZ_EXPERIMENT_MX2) || defined(CZ_EXPERIMENT_MX12)   // experiment builds only (tools/experiments/mx_ablate.sh)
-    bool mx2_attr_set;
-    int mx_kernel;       // cz_net_trunk_mx: 0 = not chosen yet, 1 = k_trunk_mx_c128, 2 = k_trunk_mx2_c128 (CCHESS_MX_KERNEL=2 selects the latter)
-    void *mx_xbuf;       // k_trunk_mx2_c128's block-input scratch (98,304 B per workgroup), grown on demand
-    size_t mx_xbuf_bytes;
-#endif
+    bool lds_opt_in[CZ_LDS_NFAMILIES];   // dynamic-LDS opt-in of an MFMA kernel family done for this device (cz_conv.hip)
     int width;         // simulations in flight per tree the pending arrays are sized for (cz_search_set_width)
     void *pend_block;  // separate allocation of the pending arrays when width > 1
     int terminal_extra;   // cz_search_set_terminal_extra: terminal simulations a tree may complete inside one select launch
