@@ -73,6 +73,10 @@ _SIGS = {
     "cz_tb_set_create": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "cz_tb_set_destroy": (C.c_int, [C.c_void_p]),
     "cz_tb_set_probe": (C.c_int, [C.c_void_p, C.c_void_p, _u8p, _u8p, C.c_int, _vp, _i32p]),
+    "cz_book_keys": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_int, _vp, _u8p]),
+    "cz_book_entries": (C.c_int, [C.c_void_p, _u8p, C.c_int, C.c_int, _vp, _u16p, _u8p]),
+    "cz_book_probe": (C.c_int, [C.c_void_p, C.c_int, _vp, _u8p, _u8p, C.c_int, _i32p, _i32p, _u8p]),
+    "cz_book_choose": (C.c_int, [C.c_void_p, C.c_int, _vp, _u16p, _vp, _u8p, _u8p, _vp, C.c_int, C.c_int, C.c_int, _vp, _u16p, _i32p]),
     "cz_repetition": (C.c_int, [C.c_void_p, _vp, _u8p, C.c_int, _i32p, _i32p, _u8p, C.c_int, C.c_int, _u8p, _i32p]),
     "cz_threats": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_int, _vp]),
     "cz_repetition_chase": (C.c_int, [C.c_void_p, _vp, _u8p, _vp, C.c_int, _i32p, _i32p, _u8p, C.c_int, C.c_int, _u8p, _i32p, _u8p]),

@@ -1,6 +1,6 @@
 """Analysis of N positions at once: best move, score and principal variations per position.
 
-    python -m cchess_zero_amd.analysis --fen "<fen>" [--fen "<fen>" ...] [--fen-file F] --model M.pt --blocks 7 --playout 400 --lines 3
+    python -m cchess_zero_amd.analysis --fen "<fen>" [--fen "<fen>" ...] [--fen-file F] --model M.pt --blocks 7 --playout 400 --lines 3 [--book B.npz]
 
 prints one JSON object per position.  Positions are searched in chunks of `games` trees through one SearchEngine; per chunk:
 reset, one Rules.movegen_kingsafe launch for the root masks, `playouts` simulations, one cz_search_lines launch.
@@ -97,7 +97,7 @@ class Analyzer:
             out.append(rows)
         return out
 
-    def analyse(self, positions, n_lines=1, max_len=16, ban=None, notation="iccs", mate_plies=0, tablebase=None):
+    def analyse(self, positions, n_lines=1, max_len=16, ban=None, notation="iccs", mate_plies=0, tablebase=None, book=None):
         """positions: FEN strings or (board uint8[90], side, restrict round) tuples, any number; ban: None or, per position, the
         moves no line may start with.  -> per position dict(bestmove, score, lines=[dict(pv=[move text ...], visits, q)], sims,
         flags): lines in rank order (more visits first), visits / q those of the line's first move, bestmove = lines[0].pv[0],
@@ -110,7 +110,9 @@ class Analyzer:
         and everything it reports are unchanged.
         tablebase = a cchess_zero_amd.tablebase.Tablebase (default None: nothing changes): every position's dict gains tablebase =
         dict(wdl, plies, pv=[move text ...]) — the exact value from the mover's view and the table's principal line — or
-        tablebase = None for a position no loaded table covers; the search and everything it reports are unchanged."""
+        tablebase = None for a position no loaded table covers; the search and everything it reports are unchanged.
+        book = a cchess_zero_amd.book.Book (default None: nothing changes): every position's dict gains book = Book.probe's list of
+        the position (empty when the book does not hold it); the search and everything it reports are unchanged."""
         from .notation import line_text
         pos = [fen_to_position(p) if isinstance(p, str) else p for p in positions]
         if ban is not None and len(ban) != len(pos):
@@ -146,6 +148,10 @@ class Analyzer:
             for r, p in zip(out, pos):
                 d = tablebase.describe(p[0], 1 if p[1] else 0, notation)
                 r["tablebase"] = None if d is None else dict(wdl=d["wdl"], plies=d["plies"], pv=d["pv"])
+        if book is not None and pos:
+            rows = book.probe(np.stack([np.asarray(p[0], np.uint8).reshape(90) for p in pos]), np.array([1 if p[1] else 0 for p in pos], np.uint8))
+            for r, b in zip(out, rows):
+                r["book"] = b
         return out
 
 
@@ -161,6 +167,8 @@ def main(argv=None):
     ap.add_argument("--notation", choices=("iccs", "wxf", "chinese"), default="iccs", help="how the moves of the output are written (default: ICCS)")
     ap.add_argument("--tablebase", metavar="DIR", default=None, help="a directory of endgame tables (python -m cchess_zero_amd.tablebase --build): "
                     "every position also reports its exact value and line from them")
+    ap.add_argument("--book", metavar="B.npz", default=None, help="an opening book (python -m cchess_zero_amd.book --build): every position also reports "
+                    "its book moves")
     args = ap.parse_args(argv)
     fens = list(args.fen)
     if args.fen_file:
@@ -179,7 +187,11 @@ def main(argv=None):
         from .tablebase import Tablebase
         tb = Tablebase(an.rule_kernels)
         tb.load(args.tablebase)
-    res = an.analyse(pos, args.lines, notation=args.notation, tablebase=tb)
+    bk = None
+    if args.book:
+        from .book import Book
+        bk = Book(an.engine.ctx).load(args.book)
+    res = an.analyse(pos, args.lines, notation=args.notation, tablebase=tb, book=bk)
     for f, r in zip(fens, res):
         print(json.dumps(dict(fen=f, **r), ensure_ascii=args.notation != "chinese"), flush=True)
     return res

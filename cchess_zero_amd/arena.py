@@ -134,6 +134,37 @@ def random_openings(n, plies, seed, device=None):
     return Openings(np.stack(out_b), out_s, out_r, out_m, np.array(out_k, np.uint64))
 
 
+def book_openings(book, n, plies, seed, min_games=2):
+    """n distinct positions (distinct by Zobrist key, side to move included) `plies` plies into an opening book
+    (cchess_zero_amd.book.Book): Book.playout — every move drawn in proportion to its games among the entries of at least min_games —
+    over-drawn and de-duplicated, as random_openings does; a line that leaves the book before `plies` is dropped.  The same seed
+    gives the same set, in the same order.  ValueError with the count found if the book does not hold n of them."""
+    from .rules import Rules
+    n, plies = int(n), int(plies)
+    gen = torch.Generator(device=book.ctx.device).manual_seed(int(seed))
+    rules = Rules(ctx=book.ctx)
+    out_b, out_s, out_r, out_m, out_k, seen = [], [], [], [], [], set()
+    for _ in range(8):
+        if len(out_k) >= n:
+            break
+        found = len(out_k)
+        po = book.playout(max(256, 4 * (n - found)), plies, gen, min_games, book.rules)
+        keys = rules.hash(po.boards, po.side).cpu().numpy().view(np.uint64)
+        for i in np.nonzero(po.lens == plies)[0]:
+            k = int(keys[i])
+            if k in seen:
+                continue
+            seen.add(k)
+            out_b.append(po.boards[i]); out_s.append(po.side[i]); out_r.append(po.rr[i]); out_m.append(po.labels[i]); out_k.append(k)
+            if len(out_k) >= n:
+                break
+        if len(out_k) == found:   # a whole over-drawn round without a new position: the book holds no more
+            break
+    if len(out_k) < n:
+        raise ValueError("book_openings: only %d distinct positions found %d plies into the book (asked for %d)" % (len(out_k), plies, n))
+    return Openings(np.stack(out_b), out_s, out_r, out_m, np.array(out_k, np.uint64))
+
+
 def exhaustive_openings(plies, device=None):
     """EVERY distinct position (distinct by Zobrist key, side to move included; the first occurrence in generation order)
     after `plies` king-safe plies from the start position, on the GPU (movegen_kingsafe -> successors, ply by ply, -> hash).
@@ -523,6 +554,8 @@ def main(argv=None):
     ap.add_argument("--opening_plies", type=int, default=4, help="random plies of the openings")
     ap.add_argument("--all_openings", action="store_true",
                     help="every distinct position after --opening_plies king-safe plies (exhaustive_openings) instead of a random sample")
+    ap.add_argument("--book", metavar="B.npz", default=None,
+                    help="openings --opening_plies plies into this opening book (book_openings; python -m cchess_zero_amd.book --build) instead of random ones")
     ap.add_argument("--slots", type=int, default=None, help="concurrent games (default: all)")
     ap.add_argument("--seed", type=int, default=0, help="openings and sampled plies")
     ap.add_argument("--max_plies", type=int, default=512, help="a game reaching it is a draw")
@@ -533,6 +566,8 @@ def main(argv=None):
     ap.add_argument("--resign_min_ply", type=int, default=0, help="with --resign: plies of a game before anybody may resign")
     args = ap.parse_args(argv)
     load_tables = check_rule_flags(ap, args, "arena")
+    if args.all_openings and args.book:
+        ap.error("--all_openings and --book: one source of openings")
     a = load_player(args.a, args.blocks)
     b = a if args.b == args.a else load_player(args.b, args.blocks)
     if args.all_openings:
@@ -541,6 +576,13 @@ def main(argv=None):
         if pairs > len(op):
             ap.error("--all_openings: %d plies give %d openings, --games %d asks for %d" % (args.opening_plies, len(op), args.games, pairs))
         op = op.subset(np.arange(pairs))
+    elif args.book:
+        from .book import Book
+        pairs = ((256 if args.games is None else args.games) + 1) // 2
+        try:
+            op = book_openings(Book().load(args.book), pairs, args.opening_plies, args.seed)
+        except (OSError, ValueError) as e:
+            ap.error("--book: %s" % e)
     else:
         pairs = ((256 if args.games is None else args.games) + 1) // 2
         op = random_openings(pairs, args.opening_plies, args.seed)

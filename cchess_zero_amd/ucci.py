@@ -2,7 +2,7 @@
 
     python -m cchess_zero_amd.ucci --model M.pt --blocks 7 [--playout 400] [--search_threads 16]
 
-Commands: ucci, isready, setoption <name> <value> (Playouts, MultiPV, Notation, MateSearch, Tablebase), position {startpos | fen <fen>} [moves m1 m2 ...],
+Commands: ucci, isready, setoption <name> <value> (Playouts, MultiPV, Notation, MateSearch, Tablebase, Book, BookMinGames, BookSample), position {startpos | fen <fen>} [moves m1 m2 ...],
 banmoves m1 ..., go [nodes N | time T | depth D], stop, quit.  Moves are ICCS coordinates ("h2e2": files a-i, ranks 0-9 with
 red at rank 0), positions standard Xiangqi FEN (notation.fen_to_position).  After each go: one `info depth <len> [multipv k]
 score <round(1000 q)> nodes <sims> time <ms> pv m1 m2 ...` per line, then `bestmove m1 [ponder m2]`, or `nobestmove` when the
@@ -20,6 +20,14 @@ covered position is answered at once, as MateSearch answers a mate: `info depth 
 `bestmove` — s is 30000 - plies for a win, -30000 + plies for a loss and 0 for a draw, the pv the table's principal line.  When
 banmoves bans the table's best move, or no table covers the position, the engine goes on as without the option.
 
+`setoption Book <file>` (default: unset, and nothing changes; `setoption Book none` unsets it): every go asks the searcher for a
+move from that opening book (python -m cchess_zero_amd.book --build) AFTER the tablebase and the mate solver and before the
+search, among the king-safe moves that are not banned and have at least `setoption BookMinGames N` games (default 2): the most
+played one, or with `setoption BookSample true` (default false) one drawn in proportion to the games.  A book move is answered
+at once: `info string book games G wins W draws D losses L`, `info depth 1 score <round(1000 (2 score - 1))> nodes 0 time <ms> pv
+<move>` — score = (wins + draws / 2) / games from the mover's view — and `bestmove`.  A position whose only book moves are banned,
+or that is not in the book, is searched as without the option.
+
 The search is the one analysis.py describes: the reference's king-capture search with the Xiangqi rules applied at the root.
 Out of scope: the engine does not judge repetition itself (GUIs send banmoves), it does not ponder (`ponder m2` is only the
 line's second move), and it does not reuse the tree between position commands — every go starts from a fresh root.
@@ -34,6 +42,8 @@ UcciEngine(searcher, inp, out) is the protocol loop; `searcher` is what it needs
     tablebase(directory) -> (value, [labels]) or None: the position's value in the endgame tables of the directory (int16 as
         include/cchess_hip.h defines it, from the mover's view) and the table's line; None when no table covers the position
         (only called after setoption Tablebase)
+    book(file, allowed uint32 [66], min_games, sample) -> (label, dict(games, wins, draws, losses, score)) or None: a move of
+        the position from the opening book in that file, among `allowed` (only called after setoption Book)
 AnalyzerSearcher provides it on one device tree; the tests fake it on the C oracle.
 """
 import argparse
@@ -61,6 +71,7 @@ class UcciEngine:
         self.mate_plies = 0         # setoption MateSearch: the horizon of the mate solver in front of every go, 0 = off
         self.pv_notation = "iccs"   # setoption Notation: how the info lines write their pv
         self.tablebase_dir = None   # setoption Tablebase: the directory of the endgame tables asked in front of every go, None = off
+        self.book_file, self.book_min_games, self.book_sample = None, 2, False   # setoption Book / BookMinGames / BookSample
         t = _lib.tables()
         self.labels, self.label2i, self.srcdst = t["labels"], t["label2i"], t["srcdst"]
         self.pos = fen_to_position(START_FEN)
@@ -147,6 +158,15 @@ class UcciEngine:
             value = " ".join(args[1:])
             self.tablebase_dir = None if value.lower() == "none" else value
             return
+        if name == "book":
+            value = " ".join(args[1:])
+            self.book_file = None if value.lower() == "none" else value
+            return
+        if name == "booksample":
+            if args[1].lower() not in ("true", "false"):
+                return self.say("info string setoption BookSample: %r is not true or false" % args[1])
+            self.book_sample = args[1].lower() == "true"
+            return
         try:
             value = int(args[1])
         except ValueError:
@@ -159,6 +179,8 @@ class UcciEngine:
             if value != 0 and (value < 1 or value > MAX_MATE_PLIES or value % 2 == 0):
                 return self.say("info string setoption MateSearch: %d is not 0 (off) or an odd number of plies up to %d" % (value, MAX_MATE_PLIES))
             self.mate_plies = value
+        elif name == "bookmingames":
+            self.book_min_games = max(0, value)
 
     def _legal(self, pos, text):
         """Is `text` a king-safe move of pos?  (The searcher is left on pos.)"""
@@ -242,6 +264,15 @@ class UcciEngine:
                 self.say("info depth %d score %d nodes %d time %d pv %s" % (dist, MATE_SCORE - dist, nodes, ms,
                                                                            " ".join(line_text(self.pos[0], self.pos[1], pv, self.pv_notation))))
                 return self.say("bestmove %s%s" % (self.labels[pv[0]], " ponder %s" % self.labels[pv[1]] if len(pv) > 1 else ""))
+        if self.book_file:
+            found = s.book(self.book_file, allowed, self.book_min_games, self.book_sample)
+            if found is not None:
+                label, n = found
+                ms = int(round((self.clock() - start) * 1000.0))
+                self.say("info string book games %d wins %d draws %d losses %d" % (n["games"], n["wins"], n["draws"], n["losses"]))
+                self.say("info depth 1 score %d nodes 0 time %d pv %s" % (int(round(1000.0 * (2.0 * n["score"] - 1.0))), ms,
+                                                                          " ".join(line_text(self.pos[0], self.pos[1], [label], self.pv_notation))))
+                return self.say("bestmove %s" % self.labels[label])
         chunk = CHUNK_STEPS * max(1, int(getattr(s, "width", 1)))
         budget = amount if mode in ("playouts", "nodes") else self.options["playouts"] if mode == "depth" else None
         sims = 0
@@ -280,6 +311,8 @@ class AnalyzerSearcher:
         self.width = analyzer.engine.width
         self.pos, self._rooted = None, False
         self._tb = {}   # directory -> its loaded Tablebase
+        self._books = {}   # file -> its loaded Book
+        self._book_seed = 0
 
     def set_position(self, board, side, rr):
         self.pos = (np.asarray(board, np.uint8).reshape(1, 90), np.array([1 if side else 0], np.uint8), np.array([int(rr)], np.int32))
@@ -306,6 +339,20 @@ class AnalyzerSearcher:
             return None
         v = int(value[0])
         return v, tb.line(self.pos[0][0], int(self.pos[1][0]), abs(v) - 1 if v else PV_LEN)
+
+    def book(self, file, allowed, min_games, sample):
+        if file not in self._books:
+            from .book import Book
+            self._books[file] = Book(self.a.engine.ctx).load(file)
+        bk = self._books[file]
+        self._book_seed += 1   # another draw at every go
+        mask = np.ascontiguousarray(allowed, np.uint32).reshape(1, -1)
+        played, index = bk.choose(self.pos[0], self.pos[1], mask, min_games, "sample" if sample else "most", seed=self._book_seed)
+        i = int(index[0])
+        if i < 0:
+            return None
+        n, w, d = int(bk.games[i]), int(bk.wins[i]), int(bk.draws[i])
+        return int(played[0]) & 0xFFFF, dict(games=n, wins=w, draws=d, losses=n - w - d, score=(w + d / 2.0) / n)
 
     def _sims(self):
         return int(self.a.engine.status()[2].cpu().numpy()[0])

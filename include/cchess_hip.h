@@ -343,6 +343,43 @@ int cz_tb_set_create(cz_ctx *, int n, const char *const *signatures /* host [n] 
 int cz_tb_set_destroy(cz_tb_set *);
 int cz_tb_set_probe(cz_ctx *, const cz_tb_set *, const uint8_t *boards /* [G][90] */, const uint8_t *side, int G, int16_t *value /* [G] */,
                     int32_t *which /* [G] or NULL */);
+/* BOOK: an opening book from recorded games.  No reference function: the reference has no book.  A book is a table of entries
+ *   (key, label) -> games, wins, draws in the CALLER'S device arrays bkey u64 [E], blabel u16 [E], bgames u32 [E] (wins and draws
+ *   never reach a kernel), ascending by key as unsigned 64-bit, then by label, one entry per pair.  There is no handle.
+ *   THE CANONICAL KEY of a position: k = cz_hash(board, side), k' = cz_hash of the board with its files reversed (cell (r, f)
+ *     from (r, 8 - f)), same side; key = min(k, k') as unsigned.  The position is MIRRORED when k' < k and SELF-MIRROR when
+ *     k' == k (the opening position is).  `mirrored` bytes: 0 as it is, 1 mirrored, 2 self-mirror.  A byte above 14 hashes as
+ *     an empty square, as in cz_hash.
+ *   THE CANONICAL LABEL of a move played there: cz_mirror_table[label] in a mirrored position, min(label, mirror[label]) in a
+ *     self-mirror one (h2e2 and b2e2 from the opening position are one entry), the label itself otherwise.
+ *   cz_book_keys: G boards [G][90] and sides -> key [G] and, unless NULL, mirrored [G].  boards at any address, as cz_tb_probe.
+ *   cz_book_entries: n packed CZ_REC_* records (16-byte aligned) -> per record its canonical key, the canonical label of the
+ *     move played — the label at the FIRST maximum of the first `count` visits (count above 128 is taken as 128) — and
+ *     outcome 0 / 1 / 2: the mover won (z > 0) / drew (z == 0) / lost.  A record with ply >= max_ply (max_ply > 0; 0: no bound)
+ *     or count == 0 is SKIPPED: outcome 255, label 0xFFFF; its key is written all the same.
+ *   cz_book_probe: per position the canonical key and an unsigned binary search of bkey: first [G] the first entry of that key
+ *     and count [G] how many follow it (the position's entries are first .. first + count - 1), or first -1 / count 0.
+ *     E == 0 is a legal, empty book (bkey may be NULL).
+ *   cz_book_choose: probe and pick in one launch.  An entry is ELIGIBLE when games >= max(min_games, 1) and its label, translated
+ *     to the position's OWN orientation (mirror[label] for a mirrored position, the label itself otherwise), is set in
+ *     allowed [G][66] (bit l & 31 of word l >> 5, as cz_movegen's mask; NULL: every label).  mode 0: the eligible entry with the
+ *     most games, the first of equals in entry order.  mode 1: in proportion to games, in integers: T the sum over the eligible
+ *     entries (the caller keeps the sum of games over one position below 2^32), t = ((uint64) rnd[g] * T) >> 32, the first
+ *     eligible entry whose running sum exceeds t.  played [G]: the move in the position's own orientation, 0xFFFF when nothing
+ *     is eligible; index [G] (may be NULL): the chosen entry, or -1.  A stored label >= 2086 is never eligible.
+ *   All: G == 0 / n == 0 is CZ_OK without a launch.  CZ_EINVAL: a NULL context or required array, negative G / n / E / max_ply
+ *     / min_games, mode outside 0 .. 1, mode 1 without rnd, a u64 array not 8-byte, a u32 / i32 array not 4-byte, a u16 array
+ *     not 2-byte aligned, records not 16-byte aligned. */
+int cz_book_keys(cz_ctx *, const uint8_t *boards /* [G][90] */, const uint8_t *side, int G, uint64_t *key /* [G] */,
+                 uint8_t *mirrored /* [G] or NULL */);
+int cz_book_entries(cz_ctx *, const uint8_t *records /* [n][CZ_REC_BYTES] */, int n, int max_ply, uint64_t *key /* [n] */,
+                    uint16_t *label /* [n] */, uint8_t *outcome /* [n] */);
+int cz_book_probe(cz_ctx *, int E, const uint64_t *bkey /* [E] */, const uint8_t *boards /* [G][90] */, const uint8_t *side, int G,
+                  int32_t *first /* [G] */, int32_t *count /* [G] */, uint8_t *mirrored /* [G] */);
+int cz_book_choose(cz_ctx *, int E, const uint64_t *bkey /* [E] */, const uint16_t *blabel /* [E] */, const uint32_t *bgames /* [E] */,
+                   const uint8_t *boards /* [G][90] */, const uint8_t *side, const uint32_t *allowed /* [G][66] or NULL */, int G,
+                   int min_games, int mode, const uint32_t *rnd /* [G], mode 1 */, uint16_t *played /* [G] */,
+                   int32_t *index /* [G] or NULL */);
 /* K3  replaces MCTS_tree.generate_inputs = try_flip + state_to_positions, main.py:531-574.
  *     planes [G][9][10][channels] of dtype CZ_F32 / CZ_BF16.  quirk_q1 = 1 reproduces the
  *     reference bit for bit; 0 gives the transposed encoding its shapes suggest. */

@@ -29,7 +29,12 @@ usage: python tools/rules_bench.py [N positions, default 1048576]
            drawn evenly from all of its tables and shuffled, and Tablebase.probe (host grouping, one cz_tb_probe per signature) is
            timed against Tablebase.probe_set (one k_tb_probe_set launch) on them — device events, one warm-up, the two forms
            alternating three times, the answers compared; then the one launch on 8192 start positions, all misses: what self-play
-           pays per ply with a table set attached; one JSON line at the end"""
+           pays per ply with a table set attached; one JSON line at the end
+       python tools/rules_bench.py --book             the opening book's kernels (csrc/cz_book.hip): cz_book_keys on 1 M positions
+           against the composed path (the boards flipped in torch, two cz_hash launches, torch.minimum on the flipped-sign keys),
+           cz_book_probe on 65 536 positions against a book of about 1 M entries against the composed keys followed by
+           torch.searchsorted — device events, one warm-up call, the two forms alternating, the answers compared — and Book.build
+           on the records of 65 536 random games, end to end (host clock); one JSON line at the end"""
 import os
 import sys
 import time
@@ -48,6 +53,7 @@ SUCCESSORS = "--successors" in sys.argv
 REPLAY = "--replay" in sys.argv
 REPLAY_NOTATION = "--replay-notation" in sys.argv
 CHECKS = "--checks" in sys.argv
+BOOK = "--book" in sys.argv
 MATE = "--mate" in sys.argv
 TABLEBASE = None
 if "--tablebase" in sys.argv:
@@ -63,7 +69,7 @@ if "--tablebase-set" in sys.argv:
         sys.exit("--tablebase-set needs a signature such as KR-KAA")
     TABLEBASE_SET = sys.argv[_at + 1]
     del sys.argv[_at:_at + 2]
-_args = [a for a in sys.argv[1:] if a not in ("--kingsafe", "--threats", "--successors", "--replay", "--replay-notation", "--checks", "--mate")]
+_args = [a for a in sys.argv[1:] if a not in ("--kingsafe", "--threats", "--successors", "--replay", "--replay-notation", "--checks", "--mate", "--book")]
 N = int(_args[0]) if _args else (8192 if REPLAY or REPLAY_NOTATION else 1 << 16 if MATE else 1 << 20)
 ctx = Context(1, 2, 0)
 rules = Rules(ctx)
@@ -638,6 +644,103 @@ def tablebase_set_leg(sig, n=65536, roots=8192):
     assert equal and all_miss
 
 
+def book_leg(n_keys=1 << 20, n_probe=1 << 16, n_games=1 << 16, launches=20):
+    """the book's fused kernels against their compositions, alternating in one run, and Book.build end to end"""
+    import json
+    from cchess_zero_amd import games as GA
+    from cchess_zero_amd.book import Book
+    from cchess_zero_amd.rules import random_positions
+    SIGN = -(1 << 63)
+    boards, side, _ = random_positions(rules, n_keys, seed=17)
+    bk = Book(ctx)
+
+    def fused_keys(b, s):
+        key = torch.empty(b.shape[0], dtype=torch.int64, device=b.device)
+        mir = torch.empty(b.shape[0], dtype=torch.uint8, device=b.device)
+        ctx.call("cz_book_keys", b, s, b.shape[0], key, mir)
+        return key, mir
+
+    def composed_keys(b, s):
+        k = rules.hash(b, s) ^ SIGN
+        km = rules.hash(b.view(-1, 10, 9).flip(2).reshape(-1, 90).contiguous(), s) ^ SIGN
+        return torch.minimum(k, km) ^ SIGN, (km < k).to(torch.uint8) + 2 * (km == k).to(torch.uint8)
+
+    def alternate(a, b):
+        """(median, min, max) ms of each form over `launches` alternating calls, after one warm-up call of each"""
+        a(), b()
+        torch.cuda.synchronize()
+        ta, tb = [], []
+        for _ in range(launches):
+            for fn, ts in ((a, ta), (b, tb)):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                fn()
+                e1.record()
+                e1.synchronize()
+                ts.append(e0.elapsed_time(e1))
+        ta.sort(), tb.sort()
+        return (ta[len(ta) // 2], ta[0], ta[-1]), (tb[len(tb) // 2], tb[0], tb[-1])
+    out = dict(key_positions=n_keys)
+    fk, ck = fused_keys(boards, side), composed_keys(boards, side)
+    out["keys_equal"] = bool(torch.equal(fk[0], ck[0]) and torch.equal(fk[1], ck[1]))
+    f, c = alternate(lambda: fused_keys(boards, side), lambda: composed_keys(boards, side))
+    out.update(keys_fused_ms=[round(x, 4) for x in f], keys_composed_ms=[round(x, 4) for x in c], keys_composed_over_fused=round(c[0] / f[0], 2))
+    print("cz_book_keys, %d positions: fused %.3f ms (min %.3f, max %.3f) = %.2f G positions/s; composed %.3f ms (min %.3f, max %.3f) = %.2f x; answers %s"
+          % (n_keys, f[0], f[1], f[2], n_keys / f[0] / 1e6, c[0], c[1], c[2], c[0] / f[0], "equal" if out["keys_equal"] else "DIFFER"))
+    # a book of the distinct keys of the 1 M positions; the probed positions: half of them from it, half from another seed
+    skey = torch.unique(fk[0] ^ SIGN)          # sorted as unsigned
+    bkey = (skey ^ SIGN).contiguous()
+    E = int(bkey.numel())
+    ob, os_, _ = random_positions(rules, n_probe // 2, seed=18)
+    pb, ps = torch.cat([boards[:n_probe // 2], ob]).contiguous(), torch.cat([side[:n_probe // 2], os_]).contiguous()
+
+    def fused_probe():
+        first = torch.empty(n_probe, dtype=torch.int32, device=pb.device)
+        count = torch.empty(n_probe, dtype=torch.int32, device=pb.device)
+        mir = torch.empty(n_probe, dtype=torch.uint8, device=pb.device)
+        ctx.call("cz_book_probe", E, bkey, pb, ps, n_probe, first, count, mir)
+        return first, count, mir
+
+    def composed_probe():
+        key, mir = composed_keys(pb, ps)
+        lo = torch.searchsorted(skey, key ^ SIGN, right=False)
+        count = (torch.searchsorted(skey, key ^ SIGN, right=True) - lo).to(torch.int32)
+        return torch.where(count > 0, lo.to(torch.int32), torch.full_like(count, -1)), count, mir
+    fp, cp = fused_probe(), composed_probe()
+    out.update(book_entries=E, probe_positions=n_probe, probe_hits=int((fp[0] >= 0).sum()), probe_equal=bool(all(torch.equal(x, y) for x, y in zip(fp, cp))))
+    f, c = alternate(fused_probe, composed_probe)
+    out.update(probe_fused_ms=[round(x, 4) for x in f], probe_composed_ms=[round(x, 4) for x in c], probe_composed_over_fused=round(c[0] / f[0], 2))
+    print("cz_book_probe, %d positions (%d hits) against %d entries: fused %.3f ms (min %.3f, max %.3f); composed %.3f ms (min %.3f, max %.3f) = %.2f x; answers %s"
+          % (n_probe, out["probe_hits"], E, f[0], f[1], f[2], c[0], c[1], c[2], c[0] / f[0], "equal" if out["probe_equal"] else "DIFFER"))
+    # Book.build, end to end, on the records of random games
+    rg = GA.random_games("xiangqi", n_games, 3, 40, engine_rules=rules)
+    gs = GA.games_from_labels(rg["moves"], rg["lens"], np.random.default_rng(3).integers(-1, 2, n_games))
+    rec = GA.GameReplayer(ctx).replay(gs, rules="xiangqi").records
+    bk.build(rec, 40)
+    torch.cuda.synchronize()
+    tb, te = [], []
+    for _ in range(3):
+        t0 = time.perf_counter()
+        bk.build(rec, 40)
+        tb.append((time.perf_counter() - t0) * 1e3)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        bk.entries(rec, 40)
+        e1.record()
+        e1.synchronize()
+        te.append(e0.elapsed_time(e1))
+    tb.sort(), te.sort()
+    out.update(build_games=n_games, build_records=int(rec.shape[0]), build_entries=len(bk), build_ms=[round(x, 2) for x in (tb[1], tb[0], tb[2])],
+               entries_launch_ms=[round(x, 4) for x in (te[1], te[0], te[2])])
+    print("Book.build, %d games = %d records -> %d entries: %.1f ms end to end (min %.1f, max %.1f), of which the cz_book_entries launch %.3f ms (min %.3f, max %.3f)"
+          % (n_games, rec.shape[0], len(bk), tb[1], tb[0], tb[2], te[1], te[0], te[2]))
+    print(json.dumps(out), flush=True)
+    assert out["keys_equal"] and out["probe_equal"]
+
+
+if BOOK:
+    book_leg()
+    sys.exit(0)
 if TABLEBASE_SET:
     tablebase_set_leg(TABLEBASE_SET)
     sys.exit(0)
