@@ -22,6 +22,7 @@ REC_BYTES, REC_SIDE, REC_COUNT, REC_Z, REC_FLAGS, REC_PLY, REC_LABELS, REC_VISIT
 SP_STATS = ("games", "red_wins", "black_wins", "draws", "plies", "stalled", "dropped", "sims")
 SP_RULES_STATS = ("mates", "repetitions", "perpetuals")   # cz_selfplay_rules_stats
 SP_CHASE_STATS = ("chases",)                               # cz_selfplay_chase_stats
+SP_AVOID_STATS = ("avoided", "forced_repetitions")         # cz_selfplay_avoid_stats
 SP_TABLEBASE_STATS = ("tablebase",)                        # cz_selfplay_tablebase_stats
 SP_RESIGN_STATS = ("resigned", "playon_games", "playon_would_resign", "playon_false_positives")   # cz_selfplay_resign_stats
 # why a match game ended (include/cchess_hip.h: CZ_MATCH_*); 0 = not finished
@@ -33,6 +34,8 @@ MATCH_TABLEBASE = 11   # cz_match_set_tablebase / cz_selfplay_set_tablebase: the
 REP_NONE, REP_DRAW, REP_RED_LOSES, REP_BLACK_LOSES = 0, 1, 2, 3
 # why cz_repetition_chase gave its verdict (include/cchess_hip.h: CZ_CAUSE_*)
 CAUSE_NONE, CAUSE_CHECK, CAUSE_CHASE = 0, 1, 2
+# summary bits of cz_repetition_moves (include/cchess_hip.h: CZ_REPMOVES_*)
+REPMOVES_REMOVED, REPMOVES_FORCED, REPMOVES_OPP_LOSES = 1, 2, 4
 # position flags of cz_movegen_kingsafe (include/cchess_hip.h: CZ_POS_*)
 POS_IN_CHECK, POS_CAN_TAKE_KING, POS_NO_SAFE_MOVE = 1, 2, 4
 MATE_NONE = 0x7FFF   # cz_mate_backup (include/cchess_hip.h: CZ_MATE_NONE): no mate proven
@@ -80,6 +83,8 @@ _SIGS = {
     "cz_repetition": (C.c_int, [C.c_void_p, _vp, _u8p, C.c_int, _i32p, _i32p, _u8p, C.c_int, C.c_int, _u8p, _i32p]),
     "cz_threats": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_int, _vp]),
     "cz_repetition_chase": (C.c_int, [C.c_void_p, _vp, _u8p, _vp, C.c_int, _i32p, _i32p, _u8p, C.c_int, C.c_int, _u8p, _i32p, _u8p]),
+    "cz_repetition_moves": (C.c_int, [C.c_void_p, _u8p, _u8p, _vp, _u8p, _vp, C.c_int, _i32p, _i32p, C.c_int, C.c_int, _u16p, _u16p, _u8p, _u16p, _u8p,
+                                     _vp, _u8p]),
     "cz_apply_move": (C.c_int, [C.c_void_p, _u8p, _u8p, _u16p, C.c_int, _vp, _u8p, _vp]),
     "cz_successors": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_int, _u16p, _i32p, C.c_int, _u8p, _u8p, _u8p, _i32p, _u16p]),
     "cz_hash": (C.c_int, [C.c_void_p, _u8p, _u8p, C.c_int, _vp]),
@@ -147,6 +152,10 @@ _SIGS = {
     "cz_match_set_repetition": (C.c_int, [C.c_void_p, C.c_int]),
     "cz_match_history": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "cz_match_set_chase": (C.c_int, [C.c_void_p, C.c_int]),
+    "cz_match_set_avoid": (C.c_int, [C.c_void_p, C.c_int]),
+    "cz_match_avoid_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "cz_selfplay_set_avoid": (C.c_int, [C.c_void_p, C.c_int]),
+    "cz_selfplay_avoid_stats": (C.c_int, [C.c_void_p, _vp]),
     "cz_match_chase_history": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "cz_match_active": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
     "cz_match_choose": (C.c_int, [C.c_void_p, C.c_int, C.c_ulonglong, _u16p]),

@@ -97,7 +97,61 @@ class Analyzer:
             out.append(rows)
         return out
 
-    def analyse(self, positions, n_lines=1, max_len=16, ban=None, notation="iccs", mate_plies=0, tablebase=None, book=None):
+    def repetition(self, positions, history, fold=3, chase=False, notation="iccs"):
+        """What the repetition rule says about the moves of positions whose games are known: history[i] = the positions of
+        game i BEFORE positions[i], the first one first (tuples as analyse() takes them), or None -> per position None, or
+        dict(fold, chase, banned=[dict(move, verdict, cause, reply)], forced, wins=[dict(move, cause)]): `banned` the moves that
+        lose by the rule (Rules.repetition_moves: verdict "loss" = the move itself completes the fold-th occurrence with the
+        mover as the side that checked / chased perpetually, "reply" = the opponent's `reply` does), `forced` = every move
+        loses, `wins` the moves after which the opponent has lost.  One batch of hash / in_check / threats over all the games'
+        positions, then one cz_repetition_moves launch."""
+        from .notation import line_text
+        tup = lambda p: fen_to_position(p) if isinstance(p, str) else p
+        games = [(i, [tup(q) for q in h] + [tup(p)]) for i, (p, h) in enumerate(zip(positions, history)) if h is not None]
+        out = [None] * len(positions)
+        if not games:
+            return out
+        rk = self.rule_kernels
+        boards = np.stack([np.asarray(q[0], np.uint8).reshape(90) for _, g in games for q in g])
+        side = np.array([1 if q[1] else 0 for _, g in games for q in g], np.uint8)
+        keys, checks = rk.hash(boards, side).cpu().numpy(), (rk.in_check(boards, side) & _lib.POS_IN_CHECK).cpu().numpy()
+        recs = rk.threats(boards, side).cpu().numpy() if chase else None
+        G, stride = len(games), max(len(g) for _, g in games)
+        K, C, R = np.zeros((G, stride), np.int64), np.zeros((G, stride), np.uint8), np.zeros((G, stride, 4), np.int64)
+        length, window, at = np.zeros(G, np.int32), np.zeros(G, np.int32), 0
+        for k, (_, g) in enumerate(games):
+            n = len(g)
+            K[k, :n], C[k, :n], length[k] = keys[at:at + n], checks[at:at + n], n
+            if chase:
+                R[k, :n] = recs[at:at + n]
+            window[k] = int(g[-1][2]) if len(g[-1]) > 2 else n - 1     # the restrict round: plies since the last capture
+            at += n
+        last = np.cumsum(length) - 1
+        r = rk.repetition_moves(boards[last], side[last], K, C, R if chase else None, length, window, int(fold))
+        r = {k: v.cpu().numpy() for k, v in r.items()}
+        cause = {_lib.CAUSE_CHECK: "check", _lib.CAUSE_CHASE: "chase"}
+        for k, (i, g) in enumerate(games):
+            b, sd = boards[last[k]], int(side[last[k]])
+            text = lambda l: line_text(b, sd, [int(l) & 0xFFFF], notation)[0]
+            loss_m, loss_o = (_lib.REP_BLACK_LOSES, _lib.REP_RED_LOSES) if sd else (_lib.REP_RED_LOSES, _lib.REP_BLACK_LOSES)
+            banned, wins = [], []
+            for j in range(int(r["count"][k])):
+                v, rv, mv = int(r["verdict"][k, j]), int(r["reply_verdict"][k, j]), int(r["moves"][k, j]) & 0xFFFF
+                if v & 15 == loss_m:
+                    banned.append(dict(move=text(mv), verdict="loss", cause=cause[v >> 4], reply=None))
+                elif v & 15 == _lib.REP_NONE and rv:
+                    nb = np.array(b, np.uint8, copy=True)
+                    src, dst = int(_lib.tables()["srcdst"][mv]) & 0xFF, int(_lib.tables()["srcdst"][mv]) >> 8
+                    nb[dst], nb[src] = nb[src], 0
+                    banned.append(dict(move=text(mv), verdict="reply", cause=cause[rv >> 4],
+                                       reply=line_text(nb, 1 - sd, [int(r["reply"][k, j]) & 0xFFFF], notation)[0]))
+                elif v & 15 == loss_o:
+                    wins.append(dict(move=text(mv), cause=cause[v >> 4]))
+            out[i] = dict(fold=int(fold), chase=bool(chase), banned=banned, forced=bool(int(r["summary"][k]) & _lib.REPMOVES_FORCED), wins=wins)
+        return out
+
+    def analyse(self, positions, n_lines=1, max_len=16, ban=None, notation="iccs", mate_plies=0, tablebase=None, book=None, history=None,
+                repetition=3, chase=False):
         """positions: FEN strings or (board uint8[90], side, restrict round) tuples, any number; ban: None or, per position, the
         moves no line may start with.  -> per position dict(bestmove, score, lines=[dict(pv=[move text ...], visits, q)], sims,
         flags): lines in rank order (more visits first), visits / q those of the line's first move, bestmove = lines[0].pv[0],
@@ -112,7 +166,10 @@ class Analyzer:
         dict(wdl, plies, pv=[move text ...]) — the exact value from the mover's view and the table's principal line — or
         tablebase = None for a position no loaded table covers; the search and everything it reports are unchanged.
         book = a cchess_zero_amd.book.Book (default None: nothing changes): every position's dict gains book = Book.probe's list of
-        the position (empty when the book does not hold it); the search and everything it reports are unchanged."""
+        the position (empty when the book does not hold it); the search and everything it reports are unchanged.
+        history = per position the earlier positions of its game or None (default None: nothing changes): every position's dict
+        gains repetition = Analyzer.repetition's answer under the fold `repetition` (and the chase rule with `chase`) — the moves
+        the repetition rule bans, with their verdicts — or None; the search and everything it reports are unchanged."""
         from .notation import line_text
         pos = [fen_to_position(p) if isinstance(p, str) else p for p in positions]
         if ban is not None and len(ban) != len(pos):
@@ -152,6 +209,29 @@ class Analyzer:
             rows = book.probe(np.stack([np.asarray(p[0], np.uint8).reshape(90) for p in pos]), np.array([1 if p[1] else 0 for p in pos], np.uint8))
             for r, b in zip(out, rows):
                 r["book"] = b
+        if history is not None:
+            if len(history) != len(pos):
+                raise ValueError("history has one entry per position")
+            for r, h in zip(out, self.repetition(pos, history, repetition, chase, notation)):
+                r["repetition"] = h
+        return out
+
+    def play(self, position, moves):
+        """position (a tuple as analyse() takes it) and ICCS moves -> every position of the line, the first one first; ValueError
+        on a move that is not king-safe where it is played."""
+        t = _lib.tables()
+        out = [(np.asarray(position[0], np.uint8).reshape(90), 1 if position[1] else 0, int(position[2]) if len(position) > 2 else 0)]
+        for m in moves:
+            b, sd, rr = out[-1]
+            l = label_of(m)
+            allowed, _ = self.root_masks(b[None], np.array([sd], np.uint8))
+            if allowed is not None and not (int(allowed[0, l >> 5]) >> (l & 31)) & 1:
+                raise ValueError("illegal move %s" % m)
+            src, dst = int(t["srcdst"][l]) & 0xFF, int(t["srcdst"][l]) >> 8
+            nb = b.copy()
+            capture = nb[dst] != 0
+            nb[dst], nb[src] = nb[src], 0
+            out.append((nb, 1 - sd, 0 if capture else rr + 1))
         return out
 
 
@@ -169,7 +249,13 @@ def main(argv=None):
                     "every position also reports its exact value and line from them")
     ap.add_argument("--book", metavar="B.npz", default=None, help="an opening book (python -m cchess_zero_amd.book --build): every position also reports "
                     "its book moves")
+    ap.add_argument("--moves", metavar="\"<iccs ...>\"", default=None, help="moves played from every --fen: the position after them is analysed, and "
+                    "its output gains \"repetition\": the moves the repetition rule bans in it, given that game")
+    ap.add_argument("--repetition", type=int, default=3, help="with --moves: the fold of the repetition rule (2..8, default 3)")
+    ap.add_argument("--chase", action="store_true", help="with --moves: the perpetual-chase rule too")
     args = ap.parse_args(argv)
+    if args.moves is not None and not 2 <= args.repetition <= 8:
+        ap.error("--repetition is 2..8, not %d" % args.repetition)
     fens = list(args.fen)
     if args.fen_file:
         fens += [l.strip() for l in open(args.fen_file) if l.strip()]
@@ -191,7 +277,14 @@ def main(argv=None):
     if args.book:
         from .book import Book
         bk = Book(an.engine.ctx).load(args.book)
-    res = an.analyse(pos, args.lines, notation=args.notation, tablebase=tb, book=bk)
+    history = None
+    if args.moves is not None:
+        try:
+            games = [an.play(p, args.moves.split()) for p in pos]
+        except ValueError as e:
+            ap.error(str(e))
+        pos, history = [g[-1] for g in games], [g[:-1] for g in games]
+    res = an.analyse(pos, args.lines, notation=args.notation, tablebase=tb, book=bk, history=history, repetition=args.repetition, chase=args.chase)
     for f, r in zip(fens, res):
         print(json.dumps(dict(fen=f, **r), ensure_ascii=args.notation != "chinese"), flush=True)
     return res

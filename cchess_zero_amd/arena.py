@@ -242,7 +242,7 @@ class MatchResult:
     ended with a table's result."""
 
     def __init__(self, result, a_red, plies, reason, moves, simulations, seconds, players, rules="capture", repetition=0, chase=False, resign=None,
-                 tablebase=False):
+                 tablebase=False, avoid=False, avoided=0, forced_repetitions=0):
         self.result = np.asarray(result, np.int8)
         self.a_red = np.asarray(a_red, np.uint8)
         self.plies = np.asarray(plies, np.int32)
@@ -261,6 +261,8 @@ class MatchResult:
         self.perpetuals = int((self.reason == MATCH_PERPETUAL).sum())
         self.chase = bool(chase)
         self.chases = int((self.reason == MATCH_CHASE).sum())
+        # avoid_repetition: the plies at which a move that loses by repetition was taken from the choice / at which every move lost
+        self.avoid, self.avoided, self.forced_repetitions = bool(avoid), int(avoided), int(forced_repetitions)
         self.resigns = int((self.reason == MATCH_RESIGN).sum())
         self.aborted = int((self.reason == MATCH_ABORTED).sum())
         self.unfinished = int((self.reason == 0).sum())
@@ -286,7 +288,8 @@ class MatchResult:
     def to_dict(self):
         """The summary (no per-game arrays): what `python -m cchess_zero_amd.arena` prints.  elo None = infinite (every
         scored game won or lost) or no scored game; an interval end None = unbounded on that side."""
-        return dict(rules=self.rules, mates=self.mates, repetition=self.repetition, repetitions=self.repetitions, perpetuals=self.perpetuals,
+        avoid = dict(avoid_repetition=True, avoided=self.avoided, forced_repetitions=self.forced_repetitions) if self.avoid else {}
+        return dict(**avoid, rules=self.rules, mates=self.mates, repetition=self.repetition, repetitions=self.repetitions, perpetuals=self.perpetuals,
                     chase=self.chase, chases=self.chases, resign=self.resign, resigns=self.resigns, tablebase=self.tablebase, tablebases=self.tablebases, games=self.games, scored=self.scored, aborted=self.aborted, unfinished=self.unfinished, W=self.wins,
                     D=self.draws, L=self.losses, by_colour=self.by_colour, score=self.score, elo=self.elo,
                     elo_95=None if self.elo_95 is None else list(self.elo_95), pentanomial=self.pentanomial.tolist(),
@@ -371,8 +374,10 @@ class Match:
     ("tablebase"; cz_match_set_tablebase).  An opening that is itself covered plays one ply first."""
 
     def __init__(self, player_a, player_b, openings, slots, max_plies=512, sample_plies=0, seed=0, check_every=8,
-                 nodes_per_tree=None, rules="capture", repetition=0, chase=False, resign=None, resign_min_ply=0, tablebase=None):
-        check_rule_options("Match", rules, repetition, chase, tablebase, resign_min_ply)
+                 nodes_per_tree=None, rules="capture", repetition=0, chase=False, resign=None, resign_min_ply=0, tablebase=None,
+                 avoid_repetition=False):
+        check_rule_options("Match", rules, repetition, chase, tablebase, resign_min_ply, avoid=avoid_repetition)
+        self.avoid = bool(avoid_repetition)
         self.tablebase = tablebase
         self._tb_own = None
         self.resign = None if resign is None else float(resign)
@@ -402,12 +407,19 @@ class Match:
             local = self._play_local(self.openings.subset(mine), rank, world)
         else:
             local = dict(result=np.zeros(0, np.int8), a_red=np.zeros(0, np.uint8), plies=np.zeros(0, np.int32),
-                         reason=np.zeros(0, np.uint8), moves=np.zeros((0, self.max_plies), np.uint16), simulations=0, seconds=0.0)
+                         reason=np.zeros(0, np.uint8), moves=np.zeros((0, self.max_plies), np.uint16), simulations=0, seconds=0.0,
+                         avoided=(0, 0))
+        avoided = local.pop("avoided")
         if multi:
             local = merge_ranks(local, n_pairs, rank, world)
+            if self.avoid:
+                t = torch.tensor(avoided, dtype=torch.int64, device="cuda" if dist.get_backend() == "nccl" else "cpu")
+                dist.all_reduce(t)
+                avoided = tuple(int(x) for x in t.tolist())
         return MatchResult(local["result"], local["a_red"], local["plies"], local["reason"], local["moves"], local["simulations"],
                            local["seconds"], [_describe(p) for p in self.players], rules=self.rules, repetition=self.repetition,
-                           chase=self.chase, resign=self.resign, tablebase=self.tablebase is not None)
+                           chase=self.chase, resign=self.resign, tablebase=self.tablebase is not None, avoid=self.avoid, avoided=avoided[0],
+                           forced_repetitions=avoided[1])
 
     def _play_local(self, op, pair_base, pair_stride):
         self.start(op, pair_base, pair_stride)
@@ -430,6 +442,7 @@ class Match:
             out = self.results()
             out["simulations"] = self.finished()[1]
             out["seconds"] = seconds
+            out["avoided"] = self.avoid_stats()
             return out
         finally:
             self.close()
@@ -454,7 +467,7 @@ class Match:
         eb.ctx.bind_stream()
         self._h = C.c_void_p()
         call("cz_match_create", ea.ctx.h, eb.ctx.h, *self._op_dev, len(op), int(pair_base), int(pair_stride), self.max_plies, C.byref(self._h))
-        set_rule_options("cz_match", self._h, self.rules, self.repetition, self.chase)
+        set_rule_options("cz_match", self._h, self.rules, self.repetition, self.chase, self.avoid)
         if self.resign is not None:
             call("cz_match_set_resign", self._h, self.resign, self.resign_min_ply)
         if self.tablebase is not None:   # a Tablebase: a set over its loaded tables, this match's to close
@@ -493,6 +506,12 @@ class Match:
         fin, sims = C.c_int32(0), C.c_ulonglong(0)
         call("cz_match_finished", self._h, C.byref(fin), C.byref(sims))
         return int(fin.value), int(sims.value)
+
+    def avoid_stats(self):
+        """(plies at which a losing move was taken from the choice, plies at which every move lost) so far — synchronises."""
+        a, f = C.c_int32(0), C.c_int32(0)
+        call("cz_match_avoid_stats", self._h, C.byref(a), C.byref(f))
+        return int(a.value), int(f.value)
 
     def active(self):
         """(mask of A, mask of B, game of each slot) as host arrays."""
@@ -591,7 +610,7 @@ def main(argv=None):
     except ValueError as e:
         ap.error(str(e))
     res = Match((a, args.playout), (b, args.playout_b or args.playout), op, slots=args.slots or 2 * pairs, max_plies=args.max_plies,
-                sample_plies=args.sample_plies, seed=args.seed, rules=args.rules, repetition=args.repetition, chase=args.chase,
+                sample_plies=args.sample_plies, seed=args.seed, rules=args.rules, repetition=args.repetition, chase=args.chase, avoid_repetition=args.avoid_repetition,
                 resign=args.resign, resign_min_ply=args.resign_min_ply, tablebase=tb).play()
     d = res.to_dict()
     d.update(a=args.a, b=args.b, blocks=args.blocks, opening_plies=args.opening_plies, slots=min(args.slots or 2 * pairs, 2 * pairs),

@@ -108,7 +108,8 @@ enum CzSpSlot {
     CZ_SP_TABLEBASE,                                                                // cz_selfplay_tablebase_stats
     CZ_SP_RESIGNED, CZ_SP_PLAYON_GAMES, CZ_SP_PLAYON_WOULD, CZ_SP_PLAYON_FALSE,   // cz_selfplay_resign_stats
     CZ_SP_RESIGN_HIST,   // its 64 bins: lowest root values of the sides that did not lose a play-on game, 1/32 each over [-1, 1)
-    CZ_SP_NSLOTS = CZ_SP_RESIGN_HIST + 64
+    CZ_SP_AVOIDED = CZ_SP_RESIGN_HIST + 64, CZ_SP_FORCED_REPETITIONS,               // cz_selfplay_avoid_stats
+    CZ_SP_NSLOTS
 };
 
 // cz_selfplay_*: per game slot, the (s, pi, z) records of the game in progress (cchess_main.selfplay keeps
@@ -219,7 +220,7 @@ struct CzRootHost {
     CzRootRules *rr;
     int16_t **tb_value;
     // the state
-    int rules, chase;           // 0 king capture / 1 xiangqi; 1: perpetual chase is judged too (needs a fold)
+    int rules, chase;           // 0 king capture / 1 xiangqi; 1: perpetual chase is judged too (needs a fold); the avoid switch is rr->avoid
     bool chosen;                // a choose has run
     cz_tb_set *tb;              // the attached table set (not owned; held), or NULL
     void *rules_block, *chase_block, *tb_block;   // rr's two parts and tb_value, made at the first switching on, kept until cz_root_free
@@ -536,6 +537,9 @@ inline void carve_root_rules(Carver &k, CzRootRules &rr, size_t G, bool chase_pa
     rr.rep = k.take<uint8_t>(G);
     rr.flags = k.take<uint8_t>(G);
     rr.root_key = k.take<uint64_t>(G);
+    rr.slot_ply = k.take<int32_t>(G);
+    rr.slot_rr = k.take<int32_t>(G);
+    rr.avoid_sum = k.take<uint8_t>(G);
 }
 
 // Between a consumer's root gather (wave_gather_root) and its choose kernel, level >= CZ_RULES_KINGSAFE: the king-safe sets of
@@ -552,9 +556,9 @@ inline int czk_root_rules_prepare(cz_ctx *c, const CzRootRules &rr, int G, int l
 // nothing after the first choose (started), no rules 0 under an attached table set (tablebase) — for the call `what` with argument `value` on a consumer in state (rules, fold,
 // chase).  api ("cz_match" / "cz_selfplay") and handle ("match" / "ctx") are the names the error texts speak of, since: where
 // the consumer's history starts.
-enum CzRuleSetter { CZ_SET_RULES, CZ_SET_REPETITION, CZ_SET_CHASE };
+enum CzRuleSetter { CZ_SET_RULES, CZ_SET_REPETITION, CZ_SET_CHASE, CZ_SET_AVOID };
 inline int cz_root_rules_order(const char *api, const char *handle, const char *since, int what, int value, int rules, int fold, int chase,
-                               bool started, bool tablebase = false) {
+                               bool started, bool tablebase = false, int avoid = 0) {
     const std::string a(api), h(handle), late = "before the first " + a + "_choose only (";
     std::string e;
     if (what == CZ_SET_RULES) {
@@ -567,6 +571,11 @@ inline int cz_root_rules_order(const char *api, const char *handle, const char *
         else if (started) e = a + "_set_repetition: " + late + since + ")";
         else if (value != 0 && rules != 1) e = a + "_set_repetition: " + a + "_set_rules(" + h + ", 1) first (the check flags are the king-safe pass's)";
         else if (value == 0 && chase != 0) e = a + "_set_repetition: the chase rule needs a fold: " + a + "_set_chase(" + h + ", 0) first";
+        else if (value == 0 && avoid != 0) e = a + "_set_repetition: the avoid step needs a fold: " + a + "_set_avoid(" + h + ", 0) first";
+    } else if (what == CZ_SET_AVOID) {
+        if (value != 0 && value != 1) e = a + "_set_avoid: on 0 or 1";
+        else if (started) e = a + "_set_avoid: " + late + since + ")";
+        else if (value != 0 && fold == 0) e = a + "_set_avoid: " + a + "_set_repetition(" + h + ", fold) first (a move is judged by the repetition rule)";
     } else {
         if (value != 0 && value != 1) e = a + "_set_chase: on 0 or 1";
         else if (started) e = a + "_set_chase: " + late + since + ")";
@@ -585,11 +594,12 @@ inline void cz_root_begin(CzRootHost &h, CzRootHost contract) {
     contract.rules_block = h.rules_block; contract.chase_block = h.chase_block; contract.tb_block = h.tb_block;
     h = contract;
     h.rr->fold = 0;
+    h.rr->avoid = 0;
     *h.tb_value = nullptr;
 }
 inline int cz_root_order(const CzRootHost &h, int what, int value) {
     return cz_root_rules_order(h.api, h.handle, h.since, what, value, h.rules, h.rr->fold, h.chase,
-                               h.chosen && !(what == CZ_SET_RULES && h.rules_between_plies), h.tb != nullptr);
+                               h.chosen && !(what == CZ_SET_RULES && h.rules_between_plies), h.tb != nullptr, h.rr->avoid);
 }
 // one part of rr (carve_root_rules) in a zeroed allocation of its own, for the setter `_set_<what>`
 inline int cz_root_carve(CzRootHost &h, void **block, bool chase_part, const char *what) {
@@ -617,6 +627,14 @@ inline int cz_root_set_chase(CzRootHost &h, int on) {
     h.chase = on;
     return CZ_OK;
 }
+inline int cz_root_set_avoid(CzRootHost &h, int on) {
+    if (const int rc = cz_root_order(h, CZ_SET_AVOID, on)) return rc;
+    h.rr->avoid = on;
+    return CZ_OK;
+}
+// The avoid step (cz_repmoves.hip): one launch of wave_repetition_moves over the G slots' rings, between the root pass and
+// the choose kernel; rr.safe becomes the set without the moves that lose by repetition, rr.avoid_sum what happened.
+int czv_root_avoid(cz_ctx *c, const CzRootRules &rr, int G, int chase);
 // the device pointers of the rings, owned by the consumer; CZ_EINVAL while the rule is off
 inline int cz_root_history(const CzRootHost &h, const uint64_t **keys, const uint8_t **checks) {
     if (h.rr->fold == 0) { cz_set_error("%s_history: %s_set_repetition first", h.api, h.api); return CZ_EINVAL; }
@@ -661,6 +679,8 @@ inline int cz_root_choose(CzRootHost &h, int G, Gather gather, Choose choose) {
         gather();
         CZ_HIP(hipGetLastError());
         if (const int rc = czk_root_rules_prepare(h.c, *h.rr, G, level)) return rc;
+        if (h.rr->avoid && level >= CZ_RULES_REPETITION)
+            if (const int rc = czv_root_avoid(h.c, *h.rr, G, h.chase)) return rc;
     }
     cz_by_rules_level(level, choose);
     CZ_HIP(hipGetLastError());

@@ -18,7 +18,7 @@ struct CzMatch {
     const uint8_t *open_board;    // [n_games / 2][90]
     const uint8_t *open_side;     // [n_games / 2]
     const int32_t *open_rr;       // [n_games / 2]
-    int32_t *queue;               // [2] next game to hand out, games finished
+    int32_t *queue;               // [4] next game to hand out, games finished; cz_match_set_avoid: plies with a move removed, plies at which every move loses
     unsigned long long *sims;     // [1] simulations of the searches whose move was chosen
     int32_t *game;                // [G] game of the slot, -1 = parked
     int32_t *ply;                 // [G] plies played in the slot's game
@@ -79,7 +79,7 @@ __device__ __forceinline__ void take_game(const CzTrees &ta, const CzTrees &tb, 
 __global__ __launch_bounds__(64) void k_match_start(CzTrees ta, CzTrees tb, CzMatch m) {
     const int g = blockIdx.x, lane = threadIdx.x;
     if (g >= m.G) return;
-    if (g == 0 && lane == 0) { m.queue[0] = min(m.G, m.n_games); m.queue[1] = 0; *m.sims = 0ull; }
+    if (g == 0 && lane == 0) { m.queue[0] = min(m.G, m.n_games); m.queue[1] = 0; m.queue[2] = 0; m.queue[3] = 0; *m.sims = 0ull; }
     take_game(ta, tb, m, g, g, lane);
 }
 
@@ -118,6 +118,7 @@ __global__ __launch_bounds__(64) void k_match_choose(CzTrees ta, CzTrees tb, CzM
             return;
         }
     }
+    if (LEVEL >= CZ_RULES_REPETITION && lane == 0) root_count_avoid(m.rr, g, [&](int k) { atomicAdd(&m.queue[2 + k], 1); });
     int pick;
     if (ply < sample_plies) {
         double pi[2];
@@ -139,7 +140,7 @@ __global__ __launch_bounds__(64) void k_match_choose(CzTrees ta, CzTrees tb, CzM
 __global__ __launch_bounds__(64) void k_match_roots_xq(CzTrees ta, CzTrees tb, CzMatch m) {
     const int g = blockIdx.x, lane = threadIdx.x;
     if (g >= m.G) return;
-    wave_gather_root(m.rr, m.mover_a[g] ? ta : tb, g, m.game[g] >= 0, lane);
+    wave_gather_root(m.rr, m.mover_a[g] ? ta : tb, g, m.game[g] >= 0, m.ply[g], lane);
 }
 
 // After cz_search_advance(played) on both contexts: the follower's failed advance (its root was never expanded, so it has no
@@ -194,7 +195,7 @@ static void carve(Carver &k, CzMatch &m, size_t G, size_t n) {
     m.open_board = k.take<uint8_t>(np * CZ_NSQ);
     m.open_side = k.take<uint8_t>(np);
     m.open_rr = k.take<int32_t>(np);
-    m.queue = k.take<int32_t>(2);
+    m.queue = k.take<int32_t>(4);
     m.sims = k.take<unsigned long long>(1);
     m.game = k.take<int32_t>(G);
     m.ply = k.take<int32_t>(G);
@@ -272,6 +273,18 @@ int cz_match_set_chase(cz_match *mh, int on) { return mh ? cz_root_set_chase(mh-
 int cz_match_chase_history(cz_match *mh, const uint64_t **chase) {
     CZ_REQUIRE(mh, "cz_match_chase_history: cz_match_set_chase first");
     return cz_root_chase_history(mh->root, chase);
+}
+
+int cz_match_set_avoid(cz_match *mh, int on) { return mh ? cz_root_set_avoid(mh->root, on) : no_match(CZ_SET_AVOID); }
+
+int cz_match_avoid_stats(cz_match *mh, int32_t *avoided, int32_t *forced) {
+    CZ_REQUIRE(mh, "cz_match_avoid_stats: null match");
+    int32_t q[4] = {0, 0, 0, 0};
+    CZ_HIP(hipMemcpyAsync(q, mh->m.queue, sizeof(q), hipMemcpyDeviceToHost, mh->a->stream));
+    CZ_HIP(hipStreamSynchronize(mh->a->stream));
+    if (avoided) *avoided = q[2];
+    if (forced) *forced = q[3];
+    return CZ_OK;
 }
 
 int cz_match_set_resign(cz_match *mh, float threshold, int min_ply) {

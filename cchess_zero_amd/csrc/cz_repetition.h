@@ -16,9 +16,11 @@
 // position of the cycle with side 1 - X to move (at least one) is a check.  -> CZ_REP_*, wave-uniform; first = -1 without a verdict.
 // wave_repetition_ex also says which sides checked perpetually (red / black), which CZ_REP_DRAW folds together: the chase
 // verdict below runs only when neither did.
-__device__ __forceinline__ int wave_repetition_ex(const uint64_t *__restrict__ keys, const uint8_t *__restrict__ in_check, int imask,
-                                                  int n, int w, uint64_t key_n, bool chk_n, int side_n, int fold, int lane, int &first,
-                                                  bool &red, bool &black) {
+// The _at forms take the history through accessors: key_at(i) / chk_at(i) answer position i < n wherever it is kept (a ring,
+// a record, or — cz_repmoves.h — a record with one or two positions behind it that exist in registers only).
+template <typename KeyAt, typename ChkAt>
+__device__ __forceinline__ int wave_repetition_at(KeyAt key_at, ChkAt chk_at, int n, int w, uint64_t key_n, bool chk_n, int side_n,
+                                                  int fold, int lane, int &first, bool &red, bool &black) {
     red = black = false;
     first = -1;
     int need = fold - 1;
@@ -29,8 +31,8 @@ __device__ __forceinline__ int wave_repetition_ex(const uint64_t *__restrict__ k
     for (int base = 0; base < w; base += 64) {   // the match never takes a second chunk (w <= 63)
         const int l = base + lane, i = n - 1 - l;
         const bool valid = l < w;
-        const uint64_t k = valid ? keys[i & imask] : 0ull;
-        const bool c = valid && in_check[i & imask] != 0;
+        const uint64_t k = valid ? key_at(i) : 0ull;
+        const bool c = valid && chk_at(i);
         unsigned long long eq = __ballot(valid && k == key_n);
         const int cnt = __popcll(eq);
         int upto = 64;                           // the lanes below it are inside the cycle
@@ -52,6 +54,12 @@ __device__ __forceinline__ int wave_repetition_ex(const uint64_t *__restrict__ k
     red = seen[1] && !quiet[1]; black = seen[0] && !quiet[0];   // red checked with every move / black did
     return red == black ? CZ_REP_DRAW : (red ? CZ_REP_RED_LOSES : CZ_REP_BLACK_LOSES);
 }
+__device__ __forceinline__ int wave_repetition_ex(const uint64_t *__restrict__ keys, const uint8_t *__restrict__ in_check, int imask,
+                                                  int n, int w, uint64_t key_n, bool chk_n, int side_n, int fold, int lane, int &first,
+                                                  bool &red, bool &black) {
+    return wave_repetition_at([=](int i) { return keys[i & imask]; }, [=](int i) { return in_check[i & imask] != 0; }, n, w, key_n, chk_n,
+                              side_n, fold, lane, first, red, black);
+}
 __device__ __forceinline__ int wave_repetition(const uint64_t *__restrict__ keys, const uint8_t *__restrict__ in_check, int imask,
                                                int n, int w, uint64_t key_n, bool chk_n, int side_n, int fold, int lane, int &first) {
     bool red, black;
@@ -68,8 +76,9 @@ __device__ __forceinline__ int wave_repetition(const uint64_t *__restrict__ keys
 // The walk is serial and wave-uniform: a chunk of 64 positions is loaded one per lane (ascending: lane l holds position
 // j + 1 + base + l) and read back lane by lane with __shfl; it stops when neither side has a candidate left.
 struct CzChaseSet { uint64_t lo, hi; };
-__device__ __forceinline__ int wave_chase(const uint64_t *__restrict__ chase, int imask, int n, int j, const uint64_t (&rec_n)[4],
-                                          int side_n, int lane) {
+// rec_at(i, r0, r1, r2, r3): the record of position i < n, as the accessors of wave_repetition_at
+template <typename RecAt>
+__device__ __forceinline__ int wave_chase_at(RecAt rec_at, int n, int j, const uint64_t (&rec_n)[4], int side_n, int lane) {
     // state per victim side v (the side TO MOVE in the positions walked); the loop over v is unrolled: no array is indexed at run time
     CzChaseSet C[2] = {{0ull, 0ull}, {0ull, 0ull}}, prev[2] = {{0ull, 0ull}, {0ull, 0ull}};
     bool started[2] = {false, false}, dead[2] = {false, false};
@@ -80,8 +89,7 @@ __device__ __forceinline__ int wave_chase(const uint64_t *__restrict__ chase, in
         const int i = j + 1 + base + lane;
         uint64_t r0 = 0ull, r1 = 0ull, r2 = 0ull, r3 = 0ull;
         if (i < n) {
-            const uint64_t *p = chase + (size_t)(i & imask) * 4;
-            r0 = p[0]; r1 = p[1]; r2 = p[2]; r3 = p[3];
+            rec_at(i, r0, r1, r2, r3);
         } else if (i == n) {
             r0 = rec_n[0]; r1 = rec_n[1]; r2 = rec_n[2]; r3 = rec_n[3];
         }
@@ -114,21 +122,39 @@ __device__ __forceinline__ int wave_chase(const uint64_t *__restrict__ chase, in
     return ((started[1] && !dead[1]) ? 1 : 0) | ((started[0] && !dead[0]) ? 2 : 0);
 }
 
+__device__ __forceinline__ int wave_chase(const uint64_t *__restrict__ chase, int imask, int n, int j, const uint64_t (&rec_n)[4],
+                                          int side_n, int lane) {
+    return wave_chase_at([=](int i, uint64_t &r0, uint64_t &r1, uint64_t &r2, uint64_t &r3) {
+        const uint64_t *p = chase + (size_t)(i & imask) * 4;
+        r0 = p[0]; r1 = p[1]; r2 = p[2]; r3 = p[3];
+    }, n, j, rec_n, side_n, lane);
+}
+
 // The repetition rule with the chase verdict behind it: wave_repetition's code and first; *cause = CZ_CAUSE_*.  Exactly one
 // side checked perpetually: as wave_repetition, cause check (it outranks a chase by the other side).  Both: a draw.  Neither:
 // exactly one side chases perpetually -> that side loses, cause chase; else a draw.
-__device__ __forceinline__ int wave_repetition_chase(const uint64_t *__restrict__ keys, const uint8_t *__restrict__ in_check,
-                                                     const uint64_t *__restrict__ chase, int imask, int n, int w, uint64_t key_n,
-                                                     bool chk_n, const uint64_t (&rec_n)[4], int side_n, int fold, int lane, int &first,
-                                                     int &cause) {
+template <typename KeyAt, typename ChkAt, typename RecAt>
+__device__ __forceinline__ int wave_repetition_chase_at(KeyAt key_at, ChkAt chk_at, RecAt rec_at, int n, int w, uint64_t key_n, bool chk_n,
+                                                        const uint64_t (&rec_n)[4], int side_n, int fold, int lane, int &first, int &cause) {
     bool red, black;
-    const int v = wave_repetition_ex(keys, in_check, imask, n, w, key_n, chk_n, side_n, fold, lane, first, red, black);
+    const int v = wave_repetition_at(key_at, chk_at, n, w, key_n, chk_n, side_n, fold, lane, first, red, black);
     cause = CZ_CAUSE_NONE;
     if (v == CZ_REP_NONE) return v;
     if (v != CZ_REP_DRAW) { cause = CZ_CAUSE_CHECK; return v; }
     if (red) return v;   // both checked
-    const int ch = wave_chase(chase, imask, n, first, rec_n, side_n, lane);
+    const int ch = wave_chase_at(rec_at, n, first, rec_n, side_n, lane);
     if (ch == 0 || ch == 3) return CZ_REP_DRAW;
     cause = CZ_CAUSE_CHASE;
     return ch == 1 ? CZ_REP_RED_LOSES : CZ_REP_BLACK_LOSES;
+}
+__device__ __forceinline__ int wave_repetition_chase(const uint64_t *__restrict__ keys, const uint8_t *__restrict__ in_check,
+                                                     const uint64_t *__restrict__ chase, int imask, int n, int w, uint64_t key_n,
+                                                     bool chk_n, const uint64_t (&rec_n)[4], int side_n, int fold, int lane, int &first,
+                                                     int &cause) {
+    return wave_repetition_chase_at([=](int i) { return keys[i & imask]; }, [=](int i) { return in_check[i & imask] != 0; },
+                                    [=](int i, uint64_t &r0, uint64_t &r1, uint64_t &r2, uint64_t &r3) {
+                                        const uint64_t *p = chase + (size_t)(i & imask) * 4;
+                                        r0 = p[0]; r1 = p[1]; r2 = p[2]; r3 = p[3];
+                                    },
+                                    n, w, key_n, chk_n, rec_n, side_n, fold, lane, first, cause);
 }

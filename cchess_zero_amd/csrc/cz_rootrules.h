@@ -24,6 +24,12 @@ struct CzRootRules {
     uint64_t *ring_chase;   // [G][64][4] the chase record (cz_threats) of position i of the slot's game at [i & 63]
     uint64_t *root_chase;   // [G][4] the record of the root position
     int fold;               // 0: no repetition rule, 2..8: a fold-th occurrence ends the game
+    // the avoid step (cz_match_set_avoid / cz_selfplay_set_avoid; czv_root_avoid, cz_repmoves.hip): between the root pass and the
+    // choose kernel `safe` loses the moves that lose by repetition (cz_repmoves.h), and avoid_sum says what happened
+    int avoid;              // 0: off
+    int32_t *slot_ply;      // [G] the ply of the slot's game at the last gather, -1 for a parked slot
+    int32_t *slot_rr;       // [G] root_rr of the position gathered
+    uint8_t *avoid_sum;     // [G] CZ_REPMOVES_* of the last avoid step
 };
 #define CZ_REP_BY_CHASE 0x10   /* in CzRootRules::rep beside the CZ_REP_* verdict: the loss is a chase, not a perpetual check */
 
@@ -51,9 +57,21 @@ inline void cz_by_rules_level(int level, F &&f) {
 
 // Before the choice: slot g's root position of tree set t (CzTrees), for cz_movegen_kingsafe / cz_hash / cz_threats, by one wave64
 template <typename Trees>
-__device__ __forceinline__ void wave_gather_root(const CzRootRules &rr, const Trees &t, int g, bool live, int lane) {
+__device__ __forceinline__ void wave_gather_root(const CzRootRules &rr, const Trees &t, int g, bool live, int ply, int lane) {
     for (int j = lane; j < CZ_NSQ; j += 64) rr.board[(size_t)g * CZ_NSQ + j] = live ? t.root_board[(size_t)g * CZD_BOARD_LDS + j] : (uint8_t)0;
-    if (lane == 0) rr.side[g] = live ? t.root_side[g] : (uint8_t)0;
+    if (lane == 0) {
+        rr.side[g] = live ? t.root_side[g] : (uint8_t)0;
+        rr.slot_ply[g] = live ? ply : -1;
+        rr.slot_rr[g] = t.root_rr[g];
+    }
+}
+// the avoid step's counters at a ply whose mover chooses among candidates: a move was removed / every move loses
+template <typename Count>
+__device__ __forceinline__ void root_count_avoid(const CzRootRules &rr, int g, Count count) {
+    if (!rr.avoid) return;
+    const int s = rr.avoid_sum[g];
+    if (s & CZ_REPMOVES_REMOVED) count(0);
+    if (s & CZ_REPMOVES_FORCED) count(1);
 }
 
 // The root position of slot g's game goes into the slot's rings at the game's ply, and a fold-th occurrence inside the last

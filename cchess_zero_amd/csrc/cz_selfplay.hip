@@ -64,7 +64,7 @@ __global__ __launch_bounds__(64) void k_sp_resign_init(CzSpResign rs, int G) {
 __global__ __launch_bounds__(64) void k_sp_roots_xq(CzTrees t, CzSelfplay sp, int G) {
     const int g = blockIdx.x, lane = threadIdx.x;
     if (g >= G) return;
-    wave_gather_root(sp.rr, t, g, sp.active[g] != 0, lane);
+    wave_gather_root(sp.rr, t, g, sp.active[g] != 0, sp.ply[g], lane);
 }
 
 // get_action (main.py:1337-1351) + the record append of selfplay (:1504-1518) for every active game, at rule level LEVEL
@@ -126,6 +126,8 @@ __global__ __launch_bounds__(64) void k_sp_choose(CzTrees t, CzSelfplay sp, int 
             if (quits) return;
         }
     }
+    if (LEVEL >= CZ_RULES_REPETITION && lane == 0)
+        root_count_avoid(sp.rr, g, [&](int k) { sp_count(sp, k ? CZ_SP_FORCED_REPETITIONS : CZ_SP_AVOIDED); });
     wave_visit_policy(N, n, inv_temp, lane, pi);
     double gm[2] = {0.0, 0.0};
     if (gamma && eps > 0.f) {
@@ -334,6 +336,11 @@ int cz_selfplay_chase_history(cz_ctx *c, const uint64_t **chase) {
     return cz_root_chase_history(c->sp_root, chase);
 }
 
+int cz_selfplay_set_avoid(cz_ctx *c, int on) {
+    CZ_REQUIRE(c && c->sp_block, "cz_selfplay_set_avoid: call cz_selfplay_begin first");
+    return cz_root_set_avoid(c->sp_root, on);
+}
+
 int cz_selfplay_set_resign(cz_ctx *c, float threshold, int min_ply, double playon_fraction, unsigned long long seed) {
     CZ_REQUIRE(c && c->sp_block, "cz_selfplay_set_resign: call cz_selfplay_begin first");
     CZ_REQUIRE(min_ply >= 0 && playon_fraction >= 0.0 && playon_fraction <= 1.0, "cz_selfplay_set_resign: min_ply >= 0 and 0 <= playon_fraction <= 1 required");
@@ -410,6 +417,7 @@ int cz_selfplay_stats(cz_ctx *c, long long *stats_dev) { return sp_stats_slice(c
 int cz_selfplay_rules_stats(cz_ctx *c, long long *stats_dev) { return sp_stats_slice(c, "cz_selfplay_rules_stats", stats_dev, CZ_SP_MATES, 3); }
 int cz_selfplay_chase_stats(cz_ctx *c, long long *stats_dev) { return sp_stats_slice(c, "cz_selfplay_chase_stats", stats_dev, CZ_SP_CHASES, 1); }
 int cz_selfplay_tablebase_stats(cz_ctx *c, long long *stats_dev) { return sp_stats_slice(c, "cz_selfplay_tablebase_stats", stats_dev, CZ_SP_TABLEBASE, 1); }
+int cz_selfplay_avoid_stats(cz_ctx *c, long long *stats_dev) { return sp_stats_slice(c, "cz_selfplay_avoid_stats", stats_dev, CZ_SP_AVOIDED, 2); }
 int cz_selfplay_resign_stats(cz_ctx *c, long long *stats_dev, long long *hist_dev) {
     if (const int rc = sp_stats_slice(c, "cz_selfplay_resign_stats", stats_dev, CZ_SP_RESIGNED, 4)) return rc;
     return hist_dev ? sp_stats_slice(c, "cz_selfplay_resign_stats", hist_dev, CZ_SP_RESIGN_HIST, 64) : CZ_OK;

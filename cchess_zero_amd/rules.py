@@ -12,7 +12,7 @@ from .engine import Context
 RULES = {"capture": 0, "xiangqi": 1}   # cz_match_set_rules / cz_selfplay_set_rules
 
 
-def check_rule_options(who, rules, repetition, chase, tablebase=None, resign_min_ply=0, resign_playon=None):
+def check_rule_options(who, rules, repetition, chase, tablebase=None, resign_min_ply=0, resign_playon=None, avoid=False):
     """The options of arena.Match and selfplay.SelfPlay on how a game ends (`who` names the caller in the text): rules before a
     repetition fold, a fold before the chase rule, rules before a table set (anything but None), and the resignation ranges
     (resign_playon: SelfPlay's alone).  Raises ValueError."""
@@ -24,6 +24,8 @@ def check_rule_options(who, rules, repetition, chase, tablebase=None, resign_min
         raise ValueError("%s: repetition needs rules='xiangqi' (the check flags come from the king-safe moves)" % who)
     if chase and not repetition:
         raise ValueError("%s: chase needs a repetition fold (a chase is judged on a repeated position)" % who)
+    if avoid and not repetition:
+        raise ValueError("%s: avoid_repetition needs a repetition fold (a move is judged by the repetition rule)" % who)
     if tablebase is not None and rules != "xiangqi":
         raise ValueError("%s: tablebase needs rules='xiangqi' (a table holds values under xiangqi rules)" % who)
     if int(resign_min_ply) < 0 or not (resign_playon is None or 0.0 <= float(resign_playon) <= 1.0):
@@ -47,6 +49,10 @@ def add_rule_flags(parser, games):
                              "or a loss for the side that checked perpetually; 0 = no repetition rule")
     parser.add_argument("--chase", action="store_true",
                         help="with --repetition: a side that alone chased one unprotected piece with every move of the cycle loses")
+    parser.add_argument("--avoid_repetition", action="store_true",
+                        help="with --repetition: the mover does not choose a move that loses by that rule (and by --chase) — it completes "
+                             "the N-th occurrence with the mover as the perpetual checker / chaser, or a reply to it does — unless every move "
+                             "does; one more launch per ply, over all slots (1.65 ms per ply on 8 192 slots, where a ply searches for seconds)")
     parser.add_argument("--tablebase", metavar="DIR", default=None,
                         help="with --rules xiangqi: a game that reaches a position of a table in DIR (python -m cchess_zero_amd.tablebase "
                              "--build) ends there with the table's result")
@@ -57,7 +63,7 @@ def check_rule_flags(parser, args, who):
     DIR onto the current device (None without the flag; ValueError for a directory without a table) — called once the
     caller's device stands, by every rank itself."""
     try:
-        check_rule_options(who, args.rules, args.repetition, args.chase, args.tablebase)
+        check_rule_options(who, args.rules, args.repetition, args.chase, args.tablebase, avoid=getattr(args, "avoid_repetition", False))
     except ValueError as e:
         parser.error(str(e))
     if args.tablebase and not os.path.isdir(args.tablebase):
@@ -74,10 +80,10 @@ def check_rule_flags(parser, args, who):
     return load
 
 
-def set_rule_options(prefix, handle, rules, repetition, chase):
-    """<prefix>_set_rules / _set_repetition / _set_chase on a match or a self-play context, in the order the library asks for;
-    an option that is off is left alone."""
-    for name, value in (("rules", RULES[rules]), ("repetition", int(repetition)), ("chase", int(bool(chase)))):
+def set_rule_options(prefix, handle, rules, repetition, chase, avoid=False):
+    """<prefix>_set_rules / _set_repetition / _set_chase / _set_avoid on a match or a self-play context, in the order the library
+    asks for; an option that is off is left alone."""
+    for name, value in (("rules", RULES[rules]), ("repetition", int(repetition)), ("chase", int(bool(chase))), ("avoid", int(bool(avoid)))):
         if value:
             call("%s_set_%s" % (prefix, name), handle, value)
 
@@ -241,6 +247,34 @@ class Rules:
         cause = torch.empty(G, dtype=torch.uint8, device=self.dev)
         self.ctx.call("cz_repetition_chase", keys, in_check, chase, stride, length, window, side, G, int(fold), verdict, first, cause)
         return verdict, first, cause
+
+    def repetition_moves(self, boards, side, keys, in_check, chase=None, length=None, window=None, fold=3):
+        """What repetition_chase() would answer after every king-safe move of G positions and after every king-safe reply to
+        it (cz_repetition_moves, one launch): boards [G, 90], side [G] the current positions; keys, in_check, chase, length,
+        window, fold the games' records as repetition_chase() takes them, the current position being the record's last one
+        (chase None: no chase rule, as repetition()) -> a dict of device tensors: `moves` [G, 128] i16(u16 bits) and `count`
+        [G] i16 as movegen_kingsafe; `verdict` [G, 128] u8, REP_* | CAUSE_* << 4 of the position after move j; `reply`
+        [G, 128] i16(u16 bits) and `reply_verdict` [G, 128] u8, the first reply whose verdict is a loss for the mover (-1 / 0:
+        none); `allowed` [G, 66] i32, the king-safe set without the moves that lose — by their own verdict, or, their own
+        being REP_NONE, by a reply — or the whole set when every move loses; `summary` [G] u8 of REPMOVES_REMOVED / _FORCED /
+        _OPP_LOSES."""
+        boards = self._dev(boards, torch.uint8).reshape(-1, NSQ)
+        G = boards.shape[0]
+        side = self._dev(side, torch.uint8).reshape(G)
+        keys = self._dev(keys, torch.int64).reshape(G, -1)
+        stride = keys.shape[1]
+        in_check = self._dev(in_check, torch.uint8).reshape(G, stride)
+        chase = None if chase is None else self._dev(chase, torch.int64).reshape(G, stride, 4)
+        length = torch.full((G,), stride, dtype=torch.int32, device=self.dev) if length is None else self._dev(length, torch.int32).reshape(G)
+        window = None if window is None else self._dev(window, torch.int32).reshape(G)
+        out = dict(moves=torch.empty((G, MAXMOVES), dtype=torch.int16, device=self.dev), count=torch.empty(G, dtype=torch.int16, device=self.dev),
+                   verdict=torch.empty((G, MAXMOVES), dtype=torch.uint8, device=self.dev),
+                   reply=torch.empty((G, MAXMOVES), dtype=torch.int16, device=self.dev),
+                   reply_verdict=torch.empty((G, MAXMOVES), dtype=torch.uint8, device=self.dev),
+                   allowed=torch.empty((G, MASK_WORDS), dtype=torch.int32, device=self.dev), summary=torch.empty(G, dtype=torch.uint8, device=self.dev))
+        self.ctx.call("cz_repetition_moves", boards, side, keys, in_check, chase, stride, length, window, G, int(fold), out["moves"], out["count"],
+                      out["verdict"], out["reply"], out["reply_verdict"], out["allowed"], out["summary"])
+        return out
 
     @staticmethod
     def check_counts(count):

@@ -27,7 +27,7 @@ import numpy as np
 import torch
 
 from ._lib import (MAXMOVES, NLABELS, NSQ, REC_BYTES, REC_COUNT, REC_FLAGS, REC_LABELS, REC_PLY, REC_SIDE, REC_VISITS, REC_Z,
-                   SP_CHASE_STATS, SP_RESIGN_STATS, SP_RULES_STATS, SP_STATS, SP_TABLEBASE_STATS, out_pointers, tables)
+                   SP_AVOID_STATS, SP_CHASE_STATS, SP_RESIGN_STATS, SP_RULES_STATS, SP_STATS, SP_TABLEBASE_STATS, out_pointers, tables)
 from .rules import RULES, check_rule_options, root_rules_chase_history, root_rules_history, set_rule_options, tablebase_set
 
 REC_MAXMOVES = MAXMOVES
@@ -35,6 +35,7 @@ REC_MAXMOVES = MAXMOVES
 STATS_GETTERS = (("cz_selfplay_stats", SP_STATS, lambda sp: True, ()),
                  ("cz_selfplay_rules_stats", SP_RULES_STATS, lambda sp: RULES[sp.rules] != 0, ()),
                  ("cz_selfplay_chase_stats", SP_CHASE_STATS, lambda sp: sp.chase, ()),
+                 ("cz_selfplay_avoid_stats", SP_AVOID_STATS, lambda sp: sp.avoid, ()),
                  ("cz_selfplay_resign_stats", SP_RESIGN_STATS, lambda sp: sp._resign_on, (None,)),
                  ("cz_selfplay_tablebase_stats", SP_TABLEBASE_STATS, lambda sp: sp._tb_on, ()))
 
@@ -178,8 +179,9 @@ class SelfPlay:
 
     def __init__(self, engine, net, playouts, exploration=True, temperature=1.0, seed=0, max_plies=512, ring_records=None,
                  continuous=True, eval_cache=False, xcache_log2=0, rules="capture", repetition=0, chase=False, resign=None,
-                 resign_min_ply=0, resign_playon=0.1, tablebase=None):
-        check_rule_options("SelfPlay", rules, repetition, chase, tablebase, resign_min_ply, resign_playon)
+                 resign_min_ply=0, resign_playon=0.1, tablebase=None, avoid_repetition=False):
+        check_rule_options("SelfPlay", rules, repetition, chase, tablebase, resign_min_ply, resign_playon, avoid=avoid_repetition)
+        self.avoid = bool(avoid_repetition)   # the mover does not choose a move that loses by repetition (cz_selfplay_set_avoid)
         self.tablebase = tablebase
         self._tb_set = self._tb_own = None
         self.resign = None if resign is None else float(resign)
@@ -219,7 +221,7 @@ class SelfPlay:
         eng.compact = not self.continuous   # parked games drop out of the net's batch; a full batch needs no compaction
         G = eng.G
         eng.ctx.call("cz_selfplay_begin", self.max_plies, None, None, None)
-        set_rule_options("cz_selfplay", eng.ctx.h, self.rules, self.repetition, self.chase)
+        set_rule_options("cz_selfplay", eng.ctx.h, self.rules, self.repetition, self.chase, self.avoid)
         self._resign_on = self.resign is not None
         self._apply_resign()
         self._tb_on = False   # cz_selfplay_begin detached whatever was attached

@@ -2,7 +2,8 @@
 
     python -m cchess_zero_amd.ucci --model M.pt --blocks 7 [--playout 400] [--search_threads 16]
 
-Commands: ucci, isready, setoption <name> <value> (Playouts, MultiPV, Notation, MateSearch, Tablebase, Book, BookMinGames, BookSample), position {startpos | fen <fen>} [moves m1 m2 ...],
+Commands: ucci, isready, setoption <name> <value> (Playouts, MultiPV, Notation, MateSearch, Tablebase, Book, BookMinGames, BookSample,
+Repetition, Chase), position {startpos | fen <fen>} [moves m1 m2 ...],
 banmoves m1 ..., go [nodes N | time T | depth D], stop, quit.  Moves are ICCS coordinates ("h2e2": files a-i, ranks 0-9 with
 red at rank 0), positions standard Xiangqi FEN (notation.fen_to_position).  After each go: one `info depth <len> [multipv k]
 score <round(1000 q)> nodes <sims> time <ms> pv m1 m2 ...` per line, then `bestmove m1 [ponder m2]`, or `nobestmove` when the
@@ -28,9 +29,23 @@ at once: `info string book games G wins W draws D losses L`, `info depth 1 score
 <move>` — score = (wins + draws / 2) / games from the mover's view — and `bestmove`.  A position whose only book moves are banned,
 or that is not in the book, is searched as without the option.
 
+`setoption Repetition N` (N = 2 .. 8, 3 is the usual rule; default 0 = off, and nothing changes) and `setoption Chase true`
+(default false): the engine keeps every position of the `position` command — from its start position on, the FEN's halfmove
+clock and the captures saying how far back a repetition can reach — and every go first asks the searcher what the repetition
+rule (with Chase: and the perpetual-chase rule) would answer after each king-safe move and after each reply to it
+(Rules.repetition_moves, one launch).  A move that loses — it completes the N-th occurrence with the mover as the side that
+checked or chased perpetually, or some reply to it does — is banned like a GUI's banmoves: `info string repetition: banned <moves>`.
+A move after which the OPPONENT has lost by that rule is played at once, before the tablebase, the mate solver and the book:
+`info string repetition: <move> ends the game, the opponent <checked|chased> perpetually`, `info depth 1 score 29999 nodes 0 time
+<ms> pv <move>`, `bestmove`.  When every move loses the engine says `info string repetition: every move loses` and searches as
+without the option — also when the moves that do not lose are all banned by the GUI.  The tablebase, mate and book answers
+respect the ban.
+
 The search is the one analysis.py describes: the reference's king-capture search with the Xiangqi rules applied at the root.
-Out of scope: the engine does not judge repetition itself (GUIs send banmoves), it does not ponder (`ponder m2` is only the
-line's second move), and it does not reuse the tree between position commands — every go starts from a fresh root.
+Out of scope: verdicts inside the tree (the search below the root does not know the repetition rule), forced sequences longer
+than a move and its reply, preferring or avoiding DRAWS by repetition (Rules.repetition_moves reports them; the engine does not
+act on them); the engine does not ponder (`ponder m2` is only the line's second move), and it does not reuse the tree between
+position commands — every go starts from a fresh root.
 
 UcciEngine(searcher, inp, out) is the protocol loop; `searcher` is what it needs from a search:
     set_position(board uint8[90], side, restrict round)
@@ -44,6 +59,9 @@ UcciEngine(searcher, inp, out) is the protocol loop; `searcher` is what it needs
         (only called after setoption Tablebase)
     book(file, allowed uint32 [66], min_games, sample) -> (label, dict(games, wins, draws, losses, score)) or None: a move of
         the position from the opening book in that file, among `allowed` (only called after setoption Book)
+    repetition_moves(boards uint8 [n, 90], sides [n], window, fold, chase) -> dict(moves, verdict, reply, reply_verdict: one
+        entry per king-safe move of the LAST position, allowed uint32 [66], summary) as Rules.repetition_moves answers on the
+        game whose positions these are, the last one's window being `window` (only called with Repetition > 0)
 AnalyzerSearcher provides it on one device tree; the tests fake it on the C oracle.
 """
 import argparse
@@ -72,9 +90,11 @@ class UcciEngine:
         self.pv_notation = "iccs"   # setoption Notation: how the info lines write their pv
         self.tablebase_dir = None   # setoption Tablebase: the directory of the endgame tables asked in front of every go, None = off
         self.book_file, self.book_min_games, self.book_sample = None, 2, False   # setoption Book / BookMinGames / BookSample
+        self.repetition, self.chase = 0, False   # setoption Repetition / Chase: the fold of the repetition rule (0 = off), the chase rule
         t = _lib.tables()
         self.labels, self.label2i, self.srcdst = t["labels"], t["label2i"], t["srcdst"]
         self.pos = fen_to_position(START_FEN)
+        self.history = [self.pos]   # every position of the last position command, the start first; history[-1] is pos
         self.ban = []
         self.searcher.set_position(*self.pos)
         self._lines = queue.Queue()
@@ -167,6 +187,11 @@ class UcciEngine:
                 return self.say("info string setoption BookSample: %r is not true or false" % args[1])
             self.book_sample = args[1].lower() == "true"
             return
+        if name == "chase":
+            if args[1].lower() not in ("true", "false"):
+                return self.say("info string setoption Chase: %r is not true or false" % args[1])
+            self.chase = args[1].lower() == "true"
+            return
         try:
             value = int(args[1])
         except ValueError:
@@ -181,6 +206,10 @@ class UcciEngine:
             self.mate_plies = value
         elif name == "bookmingames":
             self.book_min_games = max(0, value)
+        elif name == "repetition":
+            if value != 0 and (value < 2 or value > 8):
+                return self.say("info string setoption Repetition: %d is not 0 (off) or 2..8" % value)
+            self.repetition = value
 
     def _legal(self, pos, text):
         """Is `text` a king-safe move of pos?  (The searcher is left on pos.)"""
@@ -202,7 +231,7 @@ class UcciEngine:
 
     def position(self, args):
         """position {startpos | fen <fen>} [moves ...]: on a malformed FEN or an illegal move one `info string` line, and the
-        previous position (and its banmoves) stays."""
+        previous position (with its history and its banmoves) stays."""
         moves = args[args.index("moves") + 1:] if "moves" in args else []
         head = args[:args.index("moves")] if "moves" in args else args
         try:
@@ -212,15 +241,17 @@ class UcciEngine:
                 pos = fen_to_position(" ".join(head[1:]))
             else:
                 raise ValueError("position startpos | position fen <fen>")
+            history = [pos]
             for m in moves:
                 label = self._legal(pos, m)
                 if label is None:
                     raise ValueError("illegal move %s in %s" % (m, " ".join(args)))
                 pos = self.apply(pos, label)
+                history.append(pos)
         except ValueError as e:
             self.searcher.set_position(*self.pos)
             return self.say("info string %s" % e)
-        self.pos, self.ban = pos, []
+        self.pos, self.history, self.ban = pos, history, []
         self.searcher.set_position(*pos)
 
     def banmoves(self, args):
@@ -229,6 +260,32 @@ class UcciEngine:
                 self.ban.append(self.label2i[m])
             else:
                 self.say("info string banmoves: no such move %s" % m)
+
+    def _repetition(self, s, allowed, ban):
+        """In front of a go with Repetition > 0: takes the moves that lose by the repetition rule out of `allowed` and into
+        `ban`, says so -> the label of an allowed move after which the opponent has lost by it, or None."""
+        boards = np.stack([np.asarray(p[0], np.uint8) for p in self.history])
+        sides = np.array([p[1] for p in self.history], np.uint8)
+        r = s.repetition_moves(boards, sides, int(self.pos[2]), self.repetition, self.chase)
+        moves, verdict = [int(m) for m in r["moves"]], [int(v) for v in r["verdict"]]
+        if int(r["summary"]) & _lib.REPMOVES_FORCED:
+            self.say("info string repetition: every move loses")
+        else:
+            kept = np.asarray(r["allowed"], np.uint32)
+            lost = [m for m in moves if not (int(kept[m >> 5]) >> (m & 31)) & 1]
+            if lost and not (allowed & kept).any():   # the GUI has banned every move that does not lose: a losing move is still a move
+                self.say("info string repetition: every move loses")
+            elif lost:
+                ban.extend(lost)
+                allowed &= kept
+                self.say("info string repetition: banned %s" % " ".join(self.labels[m] for m in lost))
+        opponent = _lib.REP_RED_LOSES if self.pos[1] else _lib.REP_BLACK_LOSES
+        for m, v in zip(moves, verdict):
+            if v & 15 == opponent and (int(allowed[m >> 5]) >> (m & 31)) & 1:
+                self.say("info string repetition: %s ends the game, the opponent %s perpetually"
+                         % (self.labels[m], "chased" if v >> 4 == _lib.CAUSE_CHASE else "checked"))
+                return m
+        return None
 
     def go(self, args):
         mode, amount = "playouts", self.options["playouts"]
@@ -247,9 +304,16 @@ class UcciEngine:
             allowed[label >> 5] &= ~(np.uint32(1) << np.uint32(label & 31))
         if not allowed.any():
             return self.say("nobestmove")
+        ban = list(self.ban)
+        if self.repetition:
+            won = self._repetition(s, allowed, ban)
+            if won is not None:
+                ms = int(round((self.clock() - start) * 1000.0))
+                self.say("info depth 1 score %d nodes 0 time %d pv %s" % (MATE_SCORE - 1, ms, " ".join(line_text(self.pos[0], self.pos[1], [won], self.pv_notation))))
+                return self.say("bestmove %s" % self.labels[won])
         if self.tablebase_dir:
             found = s.tablebase(self.tablebase_dir)
-            if found is not None and found[1] and found[1][0] not in self.ban:
+            if found is not None and found[1] and found[1][0] not in ban:
                 value, pv = found
                 plies = abs(int(value)) - 1
                 score = 0 if value == 0 else MATE_SCORE - plies if value > 0 else plies - MATE_SCORE
@@ -258,7 +322,7 @@ class UcciEngine:
                 return self.say("bestmove %s%s" % (self.labels[pv[0]], " ponder %s" % self.labels[pv[1]] if len(pv) > 1 else ""))
         if self.mate_plies:
             found = s.mate(self.mate_plies)
-            if found is not None and found[1] and found[1][0] not in self.ban:
+            if found is not None and found[1] and found[1][0] not in ban:
                 dist, pv, nodes = found
                 ms = int(round((self.clock() - start) * 1000.0))
                 self.say("info depth %d score %d nodes %d time %d pv %s" % (dist, MATE_SCORE - dist, nodes, ms,
@@ -353,6 +417,19 @@ class AnalyzerSearcher:
             return None
         n, w, d = int(bk.games[i]), int(bk.wins[i]), int(bk.draws[i])
         return int(played[0]) & 0xFFFF, dict(games=n, wins=w, draws=d, losses=n - w - d, score=(w + d / 2.0) / n)
+
+    def repetition_moves(self, boards, sides, window, fold, chase):
+        """The history's keys, check flags and chase records in one batch each, then the fused call on the last position"""
+        rk = self.a.rule_kernels
+        n = len(boards)
+        keys = rk.hash(boards, sides).reshape(1, n)
+        checks = (rk.in_check(boards, sides) & _lib.POS_IN_CHECK).reshape(1, n)
+        recs = rk.threats(boards, sides).reshape(1, n, 4) if chase else None
+        r = rk.repetition_moves(boards[-1:], sides[-1:], keys, checks, recs, None, np.array([window], np.int32), fold)
+        count = int(r["count"][0])
+        row = lambda k, dt: r[k][0].cpu().numpy().view(dt)
+        return dict(moves=row("moves", np.uint16)[:count], verdict=row("verdict", np.uint8)[:count], reply=row("reply", np.uint16)[:count],
+                    reply_verdict=row("reply_verdict", np.uint8)[:count], allowed=row("allowed", np.uint32), summary=int(r["summary"][0]))
 
     def _sims(self):
         return int(self.a.engine.status()[2].cpu().numpy()[0])

@@ -220,6 +220,36 @@ int cz_threats(cz_ctx *, const uint8_t *boards, const uint8_t *side, int G, uint
 #define CZ_CAUSE_CHASE 2
 int cz_repetition_chase(cz_ctx *, const uint64_t *keys, const uint8_t *in_check, const uint64_t *chase, int stride, const int32_t *len,
                         const int32_t *window, const uint8_t *side, int G, int fold, uint8_t *verdict, int32_t *first, uint8_t *cause);
+/* K1m REPETITION VERDICTS ON MOVES: what cz_repetition_chase WOULD answer after every king-safe move of G positions, and after
+ *     every king-safe reply to it — the lookahead of a mover who does not want to lose by repetition.  No new rule: every
+ *     verdict is that call's on the record extended by the new position's cz_hash, CZ_POS_IN_CHECK flag and cz_threats record.
+ *     boards [G][90], side [G]: the current positions.  keys, in_check, chase, stride, len, window, fold: the games' records
+ *     exactly as cz_repetition_chase takes them, the current position being position len[g] - 1 OF THE RECORD (its key, flag
+ *     and chase record are read there, not computed); chase == NULL: no chase rule, as cz_repetition (a loss then has cause
+ *     CZ_CAUSE_CHECK).  window[g] (NULL: every earlier position) is the current position's window w.
+ *       CANDIDATE j is the j-th king-safe move of the current position, in cz_movegen_kingsafe's order; it makes position len.
+ *         Its window is 0 after a capture, else min(w + 1, len).
+ *       A REPLY is a king-safe move of the position after the candidate; it makes position len + 1, its window by the same step.
+ *       A candidate is LOSING when its own verdict is a loss for the mover, or its own verdict is CZ_REP_NONE and some reply's
+ *         verdict is a loss for the mover.
+ *     Outputs, each NULL or (not all NULL):
+ *       moves uint16 [G][128] (16-byte aligned, CZ_EINVAL otherwise), count uint16 [G]: the king-safe list as
+ *         cz_movegen_kingsafe writes it (0xFFFF padding);
+ *       verdict uint8 [G][128]: CZ_REP_* | CZ_CAUSE_* << 4 of the position after candidate j (0 behind the list);
+ *       reply uint16 [G][128], reply_verdict uint8 [G][128]: the first king-safe reply to candidate j, in generation order,
+ *         whose verdict is a loss for the mover, and that verdict; 0xFFFF / 0 when there is none;
+ *       allowed uint32 [G][66]: the king-safe set without the losing candidates — or the whole king-safe set when every
+ *         candidate is losing: a forced loss is still a move;
+ *       summary uint8 [G]: CZ_REPMOVES_* below.
+ *     A board cz_movegen_kingsafe refuses answers count 0xFFFF and zeros in every other row.  A length outside 1 .. stride
+ *     reads nothing of the record: the list and the whole set, no verdict.  G == 0: CZ_OK, no launch.  One launch, one wave
+ *     per game, a pure function of the input; no position it makes is written to memory. */
+#define CZ_REPMOVES_REMOVED 1      /* some candidate is losing and was taken out of allowed */
+#define CZ_REPMOVES_FORCED 2       /* every candidate is losing (at least one): allowed is the king-safe set */
+#define CZ_REPMOVES_OPP_LOSES 4    /* some candidate's own verdict is a loss for the opponent */
+int cz_repetition_moves(cz_ctx *, const uint8_t *boards, const uint8_t *side, const uint64_t *keys, const uint8_t *in_check,
+                        const uint64_t *chase, int stride, const int32_t *len, const int32_t *window, int G, int fold, uint16_t *moves,
+                        uint16_t *count, uint8_t *verdict, uint16_t *reply, uint8_t *reply_verdict, uint32_t *allowed, uint8_t *summary);
 /* K2  replaces GameBoard.sim_do_action (main.py:647-702), is_kill_move (:226) and the king test
  *     (:409-413).  Updates boards/side in place.  hash: in/out incremental Zobrist (may be NULL);
  *     captured [G] = captured piece code or 0; terminal [G]: bit0 'K' missing, bit1 'k' missing.
@@ -854,6 +884,19 @@ int cz_match_set_tablebase(cz_match *, cz_tb_set *set /* NULL = off */);
 int cz_match_set_repetition(cz_match *, int fold);
 int cz_match_history(cz_match *, const uint64_t **keys, const uint8_t **checks);
 int cz_match_set_chase(cz_match *, int on);
+/* THE AVOID STEP (off by default: the launches and outputs are those without it).  cz_match_set_avoid(match, 1) — after
+ *   cz_match_set_repetition, before the first cz_match_choose, off again before the fold goes — makes cz_match_choose run one more
+ *   launch between the root pass and the choice: cz_repetition_moves' kernel over the slots' rings (windows as the rule's own,
+ *   min(root_rr, ply, 63), never past 63; with cz_match_set_chase the chase rule too), and the candidates of the choice are its
+ *   `allowed`: the king-safe root children without the moves that lose by repetition, themselves or by a reply.  A mover whose
+ *   every move loses chooses among all king-safe moves; "mated" still means no king-safe move.  cz_match_avoid_stats: the plies at
+ *   which a move was removed and the plies at which every move lost, over the moves chosen so far (synchronises).
+ *   cz_selfplay_set_avoid / cz_selfplay_avoid_stats (long long [2], device): the same for self-play, where pi, the noise and the
+ *   record of a ply run over the candidates that are left. */
+int cz_match_set_avoid(cz_match *, int on);
+int cz_match_avoid_stats(cz_match *, int32_t *avoided, int32_t *forced);
+int cz_selfplay_set_avoid(cz_ctx *, int on);
+int cz_selfplay_avoid_stats(cz_ctx *, long long *stats_dev /* [2] */);
 int cz_match_chase_history(cz_match *, const uint64_t **chase);
 int cz_match_active(cz_match *, int player, const uint8_t **mask_dev);
 int cz_match_choose(cz_match *, int sample_plies, unsigned long long seed, uint16_t *played);

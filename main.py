@@ -341,6 +341,7 @@ class cchess_main(object):
         self.last_evaluation = None
         self.rules, self.repetition = "capture", 0   # the batched self-play games and the evaluation matches (--rules, --repetition)
         self.chase = False                            # ... and whether they judge perpetual chase (--chase)
+        self.avoid_repetition = False                 # ... and whether a mover avoids the moves that lose by it (--avoid_repetition)
         # resignation in the batched self-play games and the evaluation matches (--resign_threshold, --resign_min_ply,
         # --resign_playon, --resign_auto): off unless a threshold or a false-positive target is given
         self.resign_threshold, self.resign_min_ply, self.resign_playon, self.resign_auto = None, 0, 0.1, None
@@ -516,7 +517,7 @@ class cchess_main(object):
         net = self.policy_value_netowrk.net
         sp = getattr(self, "_sp", None)
         if (sp is None or sp.eng.G != G or sp.eng.ctx.cap < cap or sp.playouts != self.playout_counts or sp.net is not net
-                or sp.rules != self.rules or sp.repetition != self.repetition or sp.chase != self.chase
+                or sp.rules != self.rules or sp.repetition != self.repetition or sp.chase != self.chase or sp.avoid != self.avoid_repetition
                 or getattr(sp, "resign_options", None) != self._resign_options() or sp.tablebase is not self._tables()):
             # planes are written by the select kernel straight in the fused net's input format (16 channels of its 16-bit type)
             plane_dtype, channels = plane_format(net)
@@ -538,7 +539,7 @@ class cchess_main(object):
                           xcache_log2=min(24, max(18, (G * 2048 - 1).bit_length())) if self.playout_counts >= 400 else 0,
                           # a drain interval can end every game of every slot in the worst case: room for ~160 plies per slot
                           ring_records=max(65536, 160 * G), rules=self.rules, repetition=self.repetition, chase=self.chase,
-                          tablebase=self._tables(),
+                          avoid_repetition=self.avoid_repetition, tablebase=self._tables(),
                           **({} if ro is None else dict(resign=ro[0], resign_min_ply=ro[1], resign_playon=ro[2])))
             if getattr(self, "_sp", None) is not None:
                 self._sp.close()         # the slots that are replaced let go of the table set
@@ -565,7 +566,7 @@ class cchess_main(object):
             st = sp.stats()
             if st["games"] - before["games"] >= target or (max_plies is not None and plies >= max_plies):
                 break
-        self.last_selfplay_stats = {k: (st[k] - before[k] if k in ("games", "red_wins", "black_wins", "draws", "plies", "sims", "lock_steps", "mates", "repetitions", "perpetuals", "chases", "tablebase",
+        self.last_selfplay_stats = {k: (st[k] - before[k] if k in ("games", "red_wins", "black_wins", "draws", "plies", "sims", "lock_steps", "mates", "repetitions", "perpetuals", "chases", "avoided", "forced_repetitions", "tablebase",
                                                                            "resigned", "playon_games", "playon_would_resign", "playon_false_positives") else st[k])
                                     for k in st}
         self.last_selfplay_sims = self.last_selfplay_stats["sims"]
@@ -619,7 +620,7 @@ class cchess_main(object):
         openings = random_openings(pairs, 4, seed=self.update_seed + self._eval_round)
         ro = self._resign_options()      # the matches resign as self-play does now: on the threshold --resign_auto last set
         res = Match((live, self.playout_counts), (opp, self.playout_counts), openings, slots=max(2, min(2 * pairs, self.games)),
-                    seed=self.update_seed + self._eval_round, rules=self.rules, repetition=self.repetition, chase=self.chase,
+                    seed=self.update_seed + self._eval_round, rules=self.rules, repetition=self.repetition, chase=self.chase, avoid_repetition=self.avoid_repetition,
                     resign=ro and getattr(getattr(self, "_sp", None), "resign", ro[0]), resign_min_ply=ro[1] if ro else 0, tablebase=self._tables()).play()
         self.last_evaluation = res
         if opponent is None and res.score is not None and res.score >= 0.55:
@@ -738,6 +739,8 @@ class cchess_main(object):
                           "eval_cache": bool(getattr(self._sp, "eval_cache", False)), "xcache_log2": int(getattr(self._sp, "xcache_log2", 0))}
                 if "chases" in st:
                     timing["chases"] = int(st["chases"])
+                if "avoided" in st:
+                    timing["avoided"], timing["forced_repetitions"] = int(st["avoided"]), int(st["forced_repetitions"])
                 if "tablebase" in st:
                     timing["tablebase"] = int(st["tablebase"])     # games of the batch that ended with a table's result
                 if "resigned" in st:
@@ -868,6 +871,7 @@ if __name__ == '__main__':
                                  args.res_block_nums, args.human_color, games=args.games)
         train_main.eval_every, train_main.eval_games = args.eval_every, args.eval_games
         train_main.rules, train_main.repetition, train_main.chase = args.rules, args.repetition, args.chase
+        train_main.avoid_repetition = args.avoid_repetition
         train_main.resign_threshold, train_main.resign_min_ply = args.resign_threshold, args.resign_min_ply
         train_main.resign_playon, train_main.resign_auto = args.resign_playon, args.resign_auto
         train_main.mirror_augment = args.mirror_augment

@@ -34,7 +34,16 @@ usage: python tools/rules_bench.py [N positions, default 1048576]
            against the composed path (the boards flipped in torch, two cz_hash launches, torch.minimum on the flipped-sign keys),
            cz_book_probe on 65 536 positions against a book of about 1 M entries against the composed keys followed by
            torch.searchsorted — device events, one warm-up call, the two forms alternating, the answers compared — and Book.build
-           on the records of 65 536 random games, end to end (host clock); one JSON line at the end"""
+           on the records of 65 536 random games, end to end (host clock); one JSON line at the end
+       python tools/rules_bench.py --repetition-moves [N]   cz_repetition_moves (fold 3, chase records given) on N (default 4096)
+           mid-game positions of random king-safe games with the 40 plies before them as their records, against the same answer
+           composed from the public calls (king-safe lists -> cz_successors -> king-safe lists of the children -> cz_successors
+           -> cz_hash / flags / cz_threats of every child and grandchild -> extended records -> cz_repetition_chase -> a torch
+           reduction) on the first min(N, 1024) of them — the host clock around a synchronise for both forms (and device events
+           around the fused call), one warm-up each, the two forms alternating, the answers compared; one JSON line.  Then the same
+           on games whose last 16 plies shuffle (each side takes its last move back when it may): positions that repeat, the hit
+           path; one JSON line.  Then the avoid step: a match on 8192 slots (random openings, a constant net, 8 playouts), 24 plies
+           with cz_match_set_avoid on and 24 with it off, device events around every cz_match_choose; one JSON line at the end"""
 import os
 import sys
 import time
@@ -55,6 +64,7 @@ REPLAY_NOTATION = "--replay-notation" in sys.argv
 CHECKS = "--checks" in sys.argv
 BOOK = "--book" in sys.argv
 MATE = "--mate" in sys.argv
+REPMOVES = "--repetition-moves" in sys.argv
 TABLEBASE = None
 if "--tablebase" in sys.argv:
     _at = sys.argv.index("--tablebase")
@@ -69,8 +79,8 @@ if "--tablebase-set" in sys.argv:
         sys.exit("--tablebase-set needs a signature such as KR-KAA")
     TABLEBASE_SET = sys.argv[_at + 1]
     del sys.argv[_at:_at + 2]
-_args = [a for a in sys.argv[1:] if a not in ("--kingsafe", "--threats", "--successors", "--replay", "--replay-notation", "--checks", "--mate", "--book")]
-N = int(_args[0]) if _args else (8192 if REPLAY or REPLAY_NOTATION else 1 << 16 if MATE else 1 << 20)
+_args = [a for a in sys.argv[1:] if a not in ("--kingsafe", "--threats", "--successors", "--replay", "--replay-notation", "--checks", "--mate", "--book", "--repetition-moves")]
+N = int(_args[0]) if _args else (8192 if REPLAY or REPLAY_NOTATION else 1 << 16 if MATE else 4096 if REPMOVES else 1 << 20)
 ctx = Context(1, 2, 0)
 rules = Rules(ctx)
 
@@ -738,6 +748,152 @@ def book_leg(n_keys=1 << 20, n_probe=1 << 16, n_games=1 << 16, launches=20):
     assert out["keys_equal"] and out["probe_equal"]
 
 
+def repetition_moves_leg(plies_before=24, record=41, fold=3, shuffle=0):
+    """N games of uniform random king-safe moves from the start position (a side without one stands still): the position after
+    plies_before + record - 1 plies with the record - 1 positions before it as its record.  shuffle: in the last `shuffle` plies a
+    side takes back its last move whenever that is king-safe, so that positions repeat."""
+    import json
+    from cchess_zero_amd._lib import REP_BLACK_LOSES, REP_NONE, REP_RED_LOSES, tables
+    from cchess_zero_amd.rules import START_BOARD
+    dev = rules.dev
+    gen = torch.Generator(device=dev).manual_seed(29)
+    t = tables()
+    sd = t["srcdst"].astype(np.int64)
+    back = torch.from_numpy(t["lut"][sd >> 8, sd & 0xFF].astype(np.int16)).to(dev)        # the label of the move back
+    last = [torch.full((N,), -1, dtype=torch.int16, device=dev) for _ in range(2)]       # the moves of the last two plies
+    b = torch.from_numpy(np.tile(START_BOARD, (N, 1))).to(dev)
+    s = torch.zeros(N, dtype=torch.uint8, device=dev)
+    rr = torch.zeros(N, dtype=torch.int32, device=dev)
+    hist_b, hist_s = [], []
+    for ply in range(plies_before + record):
+        if ply >= plies_before:
+            hist_b.append(b.clone()); hist_s.append(s.clone())
+        if ply == plies_before + record - 1:
+            break
+        mv, cnt, _, _ = rules.movegen_kingsafe(b, s, want_mask=False)
+        c = cnt.to(torch.int64).clamp(min=0)
+        pick = mv.gather(1, (torch.rand(N, generator=gen, device=dev) * c.clamp(min=1)).to(torch.int64).clamp(max=127).unsqueeze(1)).squeeze(1)
+        if ply >= plies_before + record - 1 - shuffle:
+            undo = torch.where(last[0] >= 0, back[last[0].to(torch.int64).clamp(min=0)], torch.full_like(pick, -1))
+            can = (undo >= 0) & ((mv == undo.unsqueeze(1)) & (torch.arange(128, device=dev).unsqueeze(0) < c.unsqueeze(1))).any(1)
+            pick = torch.where(can, undo, pick)
+        last = [last[1], torch.where(c > 0, pick, torch.full_like(pick, -1))]
+        cap, _ = rules.apply_move(b, s, torch.where(c > 0, pick, torch.full_like(pick, -1)))
+        rr = torch.where(c > 0, torch.where(cap != 0, torch.zeros_like(rr), rr + 1), rr)
+    hb, hs = torch.stack(hist_b, 1).contiguous(), torch.stack(hist_s, 1).contiguous()          # [N, record, 90], [N, record]
+    keys = rules.hash(hb.reshape(-1, 90), hs.reshape(-1)).reshape(N, record)
+    chk = (rules.in_check(hb.reshape(-1, 90), hs.reshape(-1)) & 1).reshape(N, record)
+    rec = rules.threats(hb.reshape(-1, 90), hs.reshape(-1)).reshape(N, record, 4)
+    window = rr.clamp(max=record - 1)
+    length = torch.full((N,), record, dtype=torch.int32, device=dev)
+
+    def fused(n):
+        return rules.repetition_moves(b[:n], s[:n], keys[:n], chk[:n], rec[:n], length[:n], window[:n], fold)
+
+    def composed(n):
+        """-> (verdict, reply_verdict != 0, losing) per child in list order, and the numbers of children and grandchildren"""
+        def level(pb, ps, pk, pc, pr, plen, pwin):
+            mv, cnt, _, _ = rules.movegen_kingsafe(pb, ps, want_mask=False, pad=False)
+            cb, cs, cap, par, _ = rules.successors(pb, ps, mv, cnt)
+            par = par.to(torch.int64)
+            T = cb.shape[0]
+            at = plen[par].to(torch.int64).unsqueeze(1)
+            k = torch.cat([pk[par], torch.zeros((T, 1), dtype=torch.int64, device=dev)], 1).scatter_(1, at, rules.hash(cb, cs).unsqueeze(1))
+            f = torch.cat([pc[par], torch.zeros((T, 1), dtype=torch.uint8, device=dev)], 1).scatter_(1, at, (rules.in_check(cb, cs) & 1).unsqueeze(1))
+            r = torch.cat([pr[par], torch.zeros((T, 1, 4), dtype=torch.int64, device=dev)], 1).scatter_(1, at.unsqueeze(2).expand(T, 1, 4), rules.threats(cb, cs).unsqueeze(1))
+            w = torch.where(cap != 0, torch.zeros_like(plen[par]), torch.minimum(pwin[par] + 1, plen[par]))
+            v, _, cause = rules.repetition_chase(k, f, r, cs, plen[par] + 1, w, fold)
+            return cb, cs, k, f, r, plen[par] + 1, w, v | (cause << 4), par
+        cb, cs, k1, f1, r1, l1, w1, own, par1 = level(b[:n], s[:n], keys[:n], chk[:n], rec[:n], length[:n], window[:n])
+        _, _, _, _, _, _, _, rep, par2 = level(cb, cs, k1, f1, r1, l1, w1)
+        loss = torch.where(s[:n][par1] != 0, REP_BLACK_LOSES, REP_RED_LOSES).to(torch.uint8)
+        hit = torch.zeros(own.shape[0], dtype=torch.int32, device=dev).index_put_((par2,), ((rep & 15) == loss[par2]).to(torch.int32), accumulate=True) > 0
+        return own, hit, ((own & 15) == loss) | (((own & 15) == REP_NONE) & hit), own.shape[0], rep.shape[0]
+
+    M = min(N, 1024)
+    own, hit, losing, children, grandchildren = composed(M)
+    got = fused(M)
+    cnt = got["count"][:M].to(torch.int64)
+    live = torch.arange(128, device=dev).unsqueeze(0) < cnt.unsqueeze(1)
+    equal = bool(torch.equal(got["verdict"][:M][live], own) and torch.equal((got["reply_verdict"][:M] != 0)[live], hit))
+    full = fused(N)
+    torch.cuda.synchronize()
+    flagged = int((((full["verdict"] & 15) != 0) | (full["reply_verdict"] != 0)).any(1).sum().item())
+    removed = int((full["summary"] & 1 != 0).sum().item())
+    tf, tfm, tc, tfh = [], [], [], []
+    for _ in range(5):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fused(M)
+        torch.cuda.synchronize()
+        tfh.append((time.perf_counter() - t0) * 1e3)
+        for n, ts in ((N, tf), (M, tfm)):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fused(n)
+            e1.record()
+            e1.synchronize()
+            ts.append(e0.elapsed_time(e1))
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        composed(M)
+        torch.cuda.synchronize()
+        tc.append((time.perf_counter() - t0) * 1e3)
+    med = lambda ts: sorted(ts)[len(ts) // 2]
+    out = dict(positions=N, record=record, fold=fold, shuffled_plies=shuffle, positions_with_a_verdict=flagged, positions_with_a_move_removed=removed,
+               fused_ms=round(med(tf), 4), fused_positions_per_s=round(N / med(tf) * 1e3), composed_positions=M, composed_children=children,
+               composed_grandchildren=grandchildren, composed_ms=round(med(tc), 3), fused_ms_on_the_composed_positions=round(med(tfm), 4),
+               fused_host_clock_ms_on_the_composed_positions=round(med(tfh), 4), fused_vs_composed=round(med(tc) / med(tfh), 1), answers_equal=equal)
+    print("cz_repetition_moves: %d positions with %d-position records in %.3f ms (%.0f positions/s); %d with a verdict, %d with a move removed"
+          % (N, record, med(tf), N / med(tf) * 1e3, flagged, removed))
+    print("the composed path on %d of them (%d children, %d grandchildren): %.2f ms; the fused call on the same: %.4f ms by the same host clock "
+          "(%.4f ms by device events) = %.0f x; answers equal: %s" % (M, children, grandchildren, med(tc), med(tfh), med(tfm), med(tc) / med(tfh), equal))
+    print(json.dumps(out), flush=True)
+    assert equal
+
+
+def avoid_step_leg(G=8192, plies=24):
+    """cz_match_choose on G slots with the avoid step on against off: the same openings, a constant net and 8 playouts per move, so
+    that the choose step is what the plies differ in; device events around every choose, the first two plies left out."""
+    import json
+    from cchess_zero_amd.arena import Match, random_openings
+
+    def forward(planes):
+        B = planes.shape[0]
+        return torch.ones((B, 2086), dtype=torch.float32, device=planes.device), torch.zeros((B, 1), dtype=torch.float32, device=planes.device)
+    op = random_openings(G // 2, 8, seed=3)
+    out = dict(slots=G, plies=plies)
+    for name, avoid in (("off", False), ("on", True)):
+        m = Match((forward, 8), (forward, 8), op, slots=G, max_plies=200, seed=1, rules="xiangqi", repetition=3, chase=True, avoid_repetition=avoid)
+        m.start()
+        ts = []
+        for ply in range(plies):
+            m.search(0)
+            m.search(1)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            m.choose()
+            e1.record()
+            e1.synchronize()
+            ts.append(e0.elapsed_time(e1))
+            m.follow()
+            m.adjudicate()
+        ts = sorted(ts[2:])
+        out["choose_ms_" + name] = round(ts[len(ts) // 2], 4)
+        if avoid:
+            out["avoided"], out["forced_repetitions"] = m.avoid_stats()
+        m.close()
+    out["avoid_step_ms"] = round(out["choose_ms_on"] - out["choose_ms_off"], 4)
+    print("cz_match_choose on %d slots, rules xiangqi, fold 3, chase: %.3f ms per ply with the avoid step, %.3f ms without (median of %d plies)"
+          % (G, out["choose_ms_on"], out["choose_ms_off"], plies - 2))
+    print(json.dumps(out), flush=True)
+
+
+if REPMOVES:
+    repetition_moves_leg()
+    repetition_moves_leg(shuffle=16)
+    avoid_step_leg()
+    sys.exit(0)
 if BOOK:
     book_leg()
     sys.exit(0)
